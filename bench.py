@@ -2,6 +2,7 @@
 """Headline benchmark: queries/s @ top-10 over a 1M x 384-d corpus (+ docs embedded/s).
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line on rank 0.
+``--dump-outputs DIR`` also writes the search outputs of the last timed step to ``DIR/*.npy`` (see dump_outputs).
 For N > 1 the driver launches it under ``python -m torch.distributed.run`` (one rank per GPU over
 RCCL); started from a bare shell without ``RANK`` in the environment it starts that launcher itself
 as a CHILD process - before anything touches the GPU - and exits with the child's return code.
@@ -39,6 +40,7 @@ DIM = 384
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured copy)
 MFMA_F32_PEAK_TF = 157.3   # fp32-input MFMA peak (= vector rate)
 MFMA_BF16_PEAK_TF = 2500.0  # dense bf16 MFMA peak
+DUMP_BYTES = 60_000_000     # --dump-outputs: array bytes kept under 64 MB in all, .npy headers included
 
 
 class HipEvents:
@@ -441,6 +443,24 @@ def bench_search_locality(pkg, lib, dev, n, nq, ev, steps: int = 5):
     return out
 
 
+def dump_outputs(out_dir, scores: np.ndarray, ids: np.ndarray) -> Path:
+    """``--dump-outputs DIR``: what the timed search returned in its last step, for comparing two builds output for
+    output.  ``search_scores.npy`` (float32 [q, k]), ``search_ids.npy`` (the int64 global ids as float64, exact below
+    2**53) and ``search_query_rows.npy`` (float64: the query row of each output row).  Outputs above DUMP_BYTES keep a
+    fixed, seeded sample of query rows, the same rows for the same --queries."""
+    nq, k = scores.shape
+    per_row = k * (4 + 8) + 8
+    rows = np.arange(nq)
+    if nq * per_row > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_BYTES // per_row, replace=False))
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "search_scores.npy", np.ascontiguousarray(scores[rows], dtype=np.float32))
+    np.save(out / "search_ids.npy", np.ascontiguousarray(ids[rows], dtype=np.float64))
+    np.save(out / "search_query_rows.npy", rows.astype(np.float64))
+    return out
+
+
 def self_launch(args) -> int:
     """``bench.py --gpus N`` from a bare shell: start the torch.distributed launcher as a child
     (never exec: this process must not have touched the GPU, and it has not) and return its code."""
@@ -476,8 +496,13 @@ def main() -> None:
                     help="rendezvous + one all-gather over gloo on CPU, no GPU work: tests the N > 1 launch plumbing")
     ap.add_argument("--no-hostile", action="store_true", help="skip the anisotropic / near-duplicate search leg")
     ap.add_argument("--no-cfg3", action="store_true", help="skip the BASELINE cfg-3 legs (8 841 823 rows: one shard + whole corpus)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the scores and ids of the last timed search step to DIR/*.npy "
+                         "(bench_outputs/ is git-ignored)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_child:
         cpu_baselines_child()
         return
@@ -612,6 +637,9 @@ def main() -> None:
     dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     qps = nq * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, res[0].cpu().numpy(), res[1].cpu().numpy())
+        print(f"bench.py: last timed step's search outputs written to {dumped}", file=sys.stderr, flush=True)
 
     parity = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:

@@ -17,10 +17,12 @@ source files / engines are absent here, so fixtures come from:
             oracle restatement (oracle/encoder.py) is asserted equal to it here, and the
             embeddings are stored.  Weights are NOT stored: tests regenerate them from the recipe.
 
-Usage:  python tests/golden/make_golden.py
+Usage:  SSKD_REFERENCE=<checkout of the reference project> python tests/golden/make_golden.py
+        (SSKD_REFERENCE is read only by the fixtures that run the reference's own code)
 """
 from __future__ import annotations
 
+import os
 import sys
 from pathlib import Path
 
@@ -30,6 +32,16 @@ import torch
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent.parent
 sys.path.insert(0, str(REPO))
+
+
+def _reference() -> str:
+    """The reference checkout named by SSKD_REFERENCE, put on sys.path."""
+    ref = os.environ.get("SSKD_REFERENCE", "")
+    if not (ref and Path(ref, "src").is_dir()):
+        raise SystemExit("set SSKD_REFERENCE to a checkout of the reference project (the directory holding src/)")
+    if ref not in sys.path:
+        sys.path.insert(0, ref)
+    return ref
 
 from oracle import encoder as enc_oracle  # noqa: E402
 from oracle import search as oracle  # noqa: E402
@@ -69,8 +81,7 @@ def _register_reference_stubs():
     model classes are type annotations in the modules driven below, never called."""
     import types
 
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
+    _reference()
     stub = types.ModuleType("loguru")
 
     class _Silent:
@@ -145,7 +156,7 @@ def _reference_topk(q, c, k_values, relevant):
     import importlib.util
 
     _register_reference_stubs()
-    spec = importlib.util.spec_from_file_location("ref_simple_eval", "/root/reference/scripts/simple_eval.py")
+    spec = importlib.util.spec_from_file_location("ref_simple_eval", Path(_reference(), "scripts", "simple_eval.py"))
     simple_eval = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(simple_eval)
     from src.kd.eval import KDEvaluator
@@ -541,14 +552,14 @@ def make_xlmr_spread():
 
 def make_kd_loss():
     """Losses and autograd gradients from the REFERENCE'S OWN code (src/kd/losses.py), imported from
-    /root/reference in this container only.  Its one missing dependency is a logging package used
+    the SSKD_REFERENCE checkout.  Its one missing dependency is a logging package used
     for ``logger.info`` lines; an in-process no-op stand-in is registered for it (it takes no part
     in the arithmetic).  The oracle restatement is asserted equal here."""
     import types
 
     from oracle import kd_losses as kd_oracle
 
-    sys.path.insert(0, "/root/reference")
+    _reference()
     stub = types.ModuleType("loguru")
 
     class _Silent:
@@ -620,7 +631,7 @@ def make_api_schemas():
     here as is): the boundary the drop-in must keep."""
     import json
 
-    sys.path.insert(0, "/root/reference")
+    _reference()
     from src.serve import schemas as ref
 
     out = {name: contract_of(getattr(ref, name)) for name in API_MODELS}

@@ -202,6 +202,37 @@ def test_bench_self_launches_ranks_from_a_bare_shell():
     assert bad.returncode != 0
 
 
+def test_bench_dump_outputs_and_steps_check(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs DIR`` writes the last timed step's search outputs as float32 / float64 .npy files,
+    exactly, and above its size cap a fixed, seeded sample of query rows; ``--steps`` below 1 is refused."""
+    import subprocess
+    import sys
+
+    import bench
+    from conftest import REPO
+
+    rng = np.random.default_rng(5)
+    scores = rng.standard_normal((300, 10)).astype(np.float32)
+    ids = rng.integers(0, 1 << 40, (300, 10), dtype=np.int64)
+    bench.dump_outputs(tmp_path / "all", scores, ids)
+    got_s, got_i, rows = (np.load(tmp_path / "all" / f"search_{n}.npy") for n in ("scores", "ids", "query_rows"))
+    assert got_s.dtype == np.float32 and got_i.dtype == np.float64 and rows.dtype == np.float64
+    assert np.array_equal(got_s, scores) and np.array_equal(got_i.astype(np.int64), ids)
+    assert np.array_equal(rows, np.arange(300))
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * (10 * 12 + 8))
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, scores, ids)
+    rows = np.load(tmp_path / "a" / "search_query_rows.npy").astype(np.int64)
+    assert rows.shape == (100,) and np.array_equal(rows, np.load(tmp_path / "b" / "search_query_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "search_scores.npy"), scores[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "search_ids.npy").astype(np.int64), ids[rows])
+
+    zero = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "0", "--launch-check"],
+                          capture_output=True, text=True, timeout=300)
+    assert zero.returncode != 0 and "--steps" in zero.stderr
+
+
 def test_native_wordpiece_equals_tokenizers_library():
     """The C++ host tokenizer (sskd_tokenizer_*) reproduces the `tokenizers` library - the engine
     behind the reference's SentenceTransformer.encode - id for id on ASCII text, and FLAGS every text
