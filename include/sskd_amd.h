@@ -178,6 +178,44 @@ int sskd_index_search_onepass(const float* d_tiled, int64_t n_rows, const float*
                               int* d_inexact, void* d_workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Filtered search: a row allow-mask honoured by every search path
+ *   (faiss: SearchParameters(sel=IDSelector...) and, through a mask the caller keeps, remove_ids)
+ * Format: a DEVICE uint32 array of sskd_row_mask_words(n_rows) = ceil(n_rows / 32) words; bit (r & 31) of
+ * word (r >> 5) set means LOCAL row r may be returned.  Bits at or past n_rows are ignored.  One mask serves
+ * every query of a call.
+ * The _filtered entry points take the arguments of their unfiltered counterparts plus d_row_mask; a masked row
+ * never appears in an output, and the results are bit for bit those of the same search over an index that holds
+ * the allowed rows only (ids mapped back).  When fewer than k rows are allowed (none included) the tail is padded
+ * exactly as when n_rows < k: (-FLT_MAX, -1).  A NULL d_row_mask means "all rows" and runs the unfiltered kernels.
+ * Workspace: the existing *_workspace_bytes queries (and plans) size the filtered calls too - the mask changes
+ * neither.  The one-pass proof and the screened path's in-call exact fallback hold as without a mask.
+ * ------------------------------------------------------------------------- */
+int64_t sskd_row_mask_words(int64_t n_rows);
+/* d_flags: one byte per row (uint8 / bool, non-zero = allowed) -> d_mask (every word written) */
+int sskd_row_mask_pack(const uint8_t* d_flags, int64_t n_rows, uint32_t* d_mask, void* stream);
+/* set (allow != 0) or clear the bits of the n_ids local rows d_rows (int64) with atomic or / and.  Rows outside
+ * [0, n_rows) are skipped and counted: *d_bad (device int, zeroed by the call) = how many there were. */
+int sskd_row_mask_update(uint32_t* d_mask, int64_t n_rows, const int64_t* d_rows, int64_t n_ids, int allow,
+                         int* d_bad, void* stream);
+/* d_out = d_a AND d_b (d_out may alias either input) */
+int sskd_row_mask_and(const uint32_t* d_a, const uint32_t* d_b, int64_t n_rows, uint32_t* d_out, void* stream);
+/* *d_count (device int64) = number of allowed rows among the first n_rows (no pre-zeroing needed) */
+int sskd_row_mask_count(const uint32_t* d_mask, int64_t n_rows, int64_t* d_count, void* stream);
+
+int sskd_index_search_filtered(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq, int k,
+                               int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                               int64_t* d_out_ids, void* d_workspace, size_t workspace_bytes, void* stream,
+                               const sskd_search_tuning* tuning, void* ev_scan_begin, void* ev_scan_end);
+int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16, int64_t n_rows, const float* d_queries,
+                                        int nq, int k, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                                        int64_t* d_out_ids, int* d_status, void* d_workspace, size_t workspace_bytes,
+                                        void* stream, void* ev_scan_begin, void* ev_scan_end);
+int sskd_index_search_onepass_filtered(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
+                                       int k, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                                       int64_t* d_out_ids, int* d_inexact, void* d_workspace,
+                                       size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

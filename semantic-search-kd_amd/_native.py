@@ -129,6 +129,18 @@ SIGNATURES = {
     "sskd_index_search_screened": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "sskd_index_search_onepass_workspace_bytes": (_sz, [_i64, _i, _i]),
     "sskd_index_search_onepass": (_i, [_vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sskd_row_mask_words": (_i64, [_i64]),
+    "sskd_row_mask_pack": (_i, [_vp, _i64, _vp, _vp]),
+    "sskd_row_mask_update": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp]),
+    "sskd_row_mask_and": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "sskd_row_mask_count": (_i, [_vp, _i64, _vp, _vp]),
+    "sskd_index_search_filtered": (
+        _i, [_vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(SearchTuning), _vp, _vp]
+    ),
+    "sskd_index_search_screened_filtered": (
+        _i, [_vp, _vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]
+    ),
+    "sskd_index_search_onepass_filtered": (_i, [_vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

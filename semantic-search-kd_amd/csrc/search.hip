@@ -135,6 +135,7 @@ struct ScanParams {
   int tiles_per_slice;
   int lists_per_query;
   const int* nq_dev;       // optional: the number of queries actually present (<= nq) lives on the device
+  const uint32_t* row_mask;  // MASKED kernels only: ceil(n_rows / 32) allow words (row r = bit r & 31 of word r >> 5)
 };
 
 // number of queries to serve: the host bound, or the device-side count when one is given (the
@@ -242,6 +243,30 @@ struct LaneList {
   }
 };
 
+// Row allow-mask (sskd_amd.h): one 32-bit word per 32-row tile, so the word of tile t is wave-uniform - one scalar
+// load per tile.  In the D layout of both 32x32 MFMAs accumulator register r of lane l holds tile row
+// (r & 3) + 8 (r >> 2) + 4 (l >> 5), so lane l tests bit (r & 3) + 8 (r >> 2) of word >> 4 (l >> 5).  A masked row's score
+// becomes -inf at the same place as a padding row's past n_rows, before any list insertion, pool offer or append: from
+// there on the kernels treat it exactly like padding, which no list, pool, bound or run ever holds.
+// (read through the constant address space: nothing writes the mask during a search, and that lets the compiler issue an
+// s_load instead of a vector load + v_readfirstlane)
+typedef const __attribute__((address_space(4))) uint32_t const_u32;
+__device__ inline uint32_t tile_mask_word(const uint32_t* __restrict__ row_mask, int t) {
+  return ((const_u32*)row_mask)[t];
+}
+template <int QB>
+__device__ inline void apply_tile_mask(f32x16 (&acc)[QB], uint32_t word, int h) {
+  if (word == 0xFFFFFFFFu) return;   // (wave-uniform) every row of the tile is allowed
+  const uint32_t lw = word >> (4 * h);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const bool off = ((lw >> ((r & 3) + 8 * (r >> 2))) & 1u) == 0u;
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq)
+      if (off) acc[qq][r] = -INFINITY;
+  }
+}
+
 __device__ inline void load_group(float4 (&buf)[GROUP], const float* __restrict__ base) {
 #pragma unroll
   for (int s = 0; s < GROUP; ++s)
@@ -272,7 +297,10 @@ __device__ inline void compute_group(const float4 (&a)[GROUP], const float4* __r
 // POOLS = false: plain per-lane lists, no shared bound - then the ONLY reason a row is missing from
 // a query's candidates is that its own list was full of better rows, which is what the one-pass
 // search for k > K relies on (sskd_index_search_onepass).
-template <int K, int QB, int WAVES, bool HAS_UB, bool POOLS = true>
+// MASKED: rows whose bit in p.row_mask is clear score -inf (tile_mask_word above).  A list, pool or bucket only ever
+// takes scores above -inf, so every full list / pool still holds K distinct ALLOWED rows: the shared bounds, the
+// chained passes' upper bound and the one-pass proof hold for the allowed rows as they do for the whole shard.
+template <int K, int QB, int WAVES, bool HAS_UB, bool POOLS = true, bool MASKED = false>
 __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
   extern __shared__ float4 qs[];  // [QB][96 chunks][32 queries]
   const int tid = threadIdx.x;
@@ -335,6 +363,8 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
   int tiles_done = 0;
   for (; t < t_end; t += WAVES, ++tiles_done) {
     const float* tile = lane_base + (int64_t)t * TILE_FLOATS;
+    uint32_t mword = 0xFFFFFFFFu;
+    if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
     // the workgroup's bound every tile (one LDS word), the global one every few tiles: an atomic
     // executes at the memory side, so it both publishes ours and returns a fresh value
     const bool exchange = tiles_done < TAU_REFRESH_TILES ? (tiles_done & (tiles_done - 1)) == 0
@@ -381,6 +411,7 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
         for (int r = 0; r < 16; ++r)
           if (rowbase + (r & 3) + 8 * (r >> 2) >= p.n_rows) acc[qq][r] = -INFINITY;
     }
+    if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
 #pragma unroll
     for (int qq = 0; qq < QB; ++qq) {
       float m = acc[qq][0];
@@ -688,6 +719,64 @@ __global__ __launch_bounds__(256) void fill_int_kernel(int* p, int n, int v) {
 __global__ __launch_bounds__(256) void fill_empty_kernel(float* s, int64_t* ids, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) { s[i] = -FLT_MAX; ids[i] = -1; }
+}
+
+// ------------------------------------------------------------------------- //
+// row allow-masks (sskd_amd.h): small bandwidth-bound helpers
+// ------------------------------------------------------------------------- //
+
+// one byte per row -> words: lane l of a wave tests row 64 w + l, one ballot is two words
+__global__ __launch_bounds__(256) void row_mask_pack_kernel(const uint8_t* __restrict__ flags, int64_t n_rows,
+                                                            uint32_t* __restrict__ mask, int64_t n_words) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = w * 64 + lane;
+  const unsigned long long b = __ballot(row < n_rows && flags[row] != 0);
+  if (lane < 2 && 2 * w + lane < n_words) mask[2 * w + lane] = (uint32_t)(b >> (32 * lane));
+}
+
+// set (allow != 0) or clear the bits of a list of rows; rows outside [0, n_rows) are skipped and counted in *bad
+__global__ __launch_bounds__(256) void row_mask_update_kernel(uint32_t* __restrict__ mask, int64_t n_rows,
+                                                              const int64_t* __restrict__ rows, int64_t n_ids, int allow,
+                                                              int* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_ids) return;
+  const int64_t r = rows[i];
+  if (r < 0 || r >= n_rows) {
+    atomicAdd(bad, 1);
+    return;
+  }
+  const uint32_t bit = 1u << (r & 31);
+  if (allow) atomicOr(mask + (r >> 5), bit);
+  else atomicAnd(mask + (r >> 5), ~bit);
+}
+
+__global__ __launch_bounds__(256) void row_mask_and_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                           uint32_t* __restrict__ out, int64_t n_words) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_words) out[i] = a[i] & b[i];
+}
+
+// one workgroup: popcount of the first n_rows bits (the bits at or past n_rows are ignored); no pre-zeroed output
+__global__ __launch_bounds__(1024) void row_mask_count_kernel(const uint32_t* __restrict__ mask, int64_t n_rows,
+                                                              int64_t* __restrict__ count) {
+  __shared__ unsigned long long part[16];
+  const int64_t n_words = (n_rows + 31) >> 5;
+  unsigned long long c = 0;
+  for (int64_t i = threadIdx.x; i < n_words; i += 1024) {
+    uint32_t v = mask[i];
+    if (i == n_words - 1 && (n_rows & 31)) v &= (1u << (n_rows & 31)) - 1u;
+    c += __popc(v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long s = 0;
+    for (int i = 0; i < 16; ++i) s += part[i];
+    *count = (int64_t)s;
+  }
 }
 
 // ------------------------------------------------------------------------- //
@@ -1005,6 +1094,7 @@ struct ScreenAppendParams {
   int lists_per_query;
   int pre_tiles;            // the sample: the shard's first tiles, pre_tps of them per slice (0: no sample phase)
   int pre_tps;
+  const uint32_t* row_mask; // MASKED kernels only (as ScanParams::row_mask)
 };
 
 // out of line: the cold path must not cost the screening loop registers
@@ -1019,7 +1109,15 @@ __device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* 
 
 // One phase of the screening kernel: the tiles [t_begin, t_end) of this workgroup, one tile per wave at a time.
 // BOUND_ONLY: nothing is appended and nothing exchanged - one pool offer per lane and tile (the sample phase).
-template <int K, int QB, int WAVES, bool BOUND_ONLY, bool LIGHT, int BG, int RG>
+// MASKED: the row allow-mask (tile_mask_word).  Why the proof survives it: a masked row scores -inf right after the MFMAs,
+// and gthr starts at -FLT_MAX, so it never passes "x >= gthr" (no append), and every pool offer is either a row that passed
+// that test or the lane's best row m of a tile only when m >= gthr (the sample phase, LIGHT) or when some row was taken
+// (first tile): never -inf.  So a slot of a pool or bucket that is not INT_MIN is always the finite score of an allowed
+// row, the pool is "full" (its minimum above INT_MIN) only with K scores of DISTINCT allowed rows, and every bound is a
+// lower bound of the k-th best screen score among the ALLOWED rows - the band the finalize kernel needs.  With fewer than
+// k allowed rows no pool ever fills, nothing is pruned, and the finalize kernel takes every appended row (tau = -inf).
+// The in-call exact fallback scans with the same mask.
+template <int K, int QB, int WAVES, bool BOUND_ONLY, bool LIGHT, int BG, int RG, bool MASKED = false>
 __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_begin, int t_end, int wave, int j, int h, int q0,
                                              const sbf16x8* __restrict__ lane_base, const sbf16x8* __restrict__ qlane,
                                              int* __restrict__ pool, int* __restrict__ wthr, uint2* run0, int64_t run_stride,
@@ -1035,6 +1133,8 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
   int tiles_done = 0;
   for (; t < t_end; t += WAVES, ++tiles_done) {
     const sbf16x8* tile = lane_base + (int64_t)t * BTILE_VEC;
+    uint32_t mword = 0xFFFFFFFFu;
+    if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
     // bounds are exchanged with global memory at tile 0 (the sample phases' bounds), tile 16 and every 64th: an exchange is
     // ten dependent agent-scope loads + an atomic per sub-block (~3 us of stall); at tiles 0, 1, 2, 4, 8, 16, ... and
     // every 8th it cost 5 % of the kernel at 1 M rows and 10 % on a 125 k-row shard.  The sample phase never reads them.
@@ -1069,6 +1169,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
         for (int r = 0; r < 16; ++r)
           if (rowbase + (r & 3) + 8 * (r >> 2) >= p.n_rows) acc[qq][r] = -INFINITY;
     }
+    if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
 #ifdef SSKD_SCREEN_ABL_NOLIST  // timing ablation: no candidate / pool maintenance (accumulators kept alive)
 #pragma unroll
     for (int qq = 0; qq < QB; ++qq)
@@ -1157,7 +1258,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 
 }
 
-template <int K, int QB, int WAVES, bool LIGHT, int BG, int RG>
+template <int K, int QB, int WAVES, bool LIGHT, int BG, int RG, bool MASKED = false>
 __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendParams p) {
   extern __shared__ float4 qs_raw[];
   sbf16x8* const qs = reinterpret_cast<sbf16x8*>(qs_raw);  // [QB][24 steps][64 lanes]
@@ -1226,7 +1327,7 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   if (p.pre_tps > 0) {
     const int s_begin = slice * p.pre_tps;
     const int s_end = min(s_begin + p.pre_tps, p.pre_tiles);
-    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG>(p, s_begin, s_end, wave, j, h, q0, lane_base, qlane,
+    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, wave, j, h, q0, lane_base, qlane,
                                              pool, wthr, run0, run_stride, ragged, gthr, band, cnt, real);
     // what this workgroup learned from its share of the sample; everybody's offers are in before phase 1
 #pragma unroll
@@ -1246,7 +1347,7 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
       __syncthreads();
     }
   }
-  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG>(p, t_begin, t_end, wave, j, h, q0, lane_base,
+  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, wave, j, h, q0, lane_base,
                                             qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt, real);
 
 #pragma unroll
@@ -1582,28 +1683,34 @@ Plan make_plan(int64_t n_rows, int nq, int k, const sskd_search_tuning* tn = nul
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-template <int K, int QB, bool HAS_UB, bool POOLS = true>
+template <int K, int QB, bool HAS_UB, bool POOLS = true, bool MASKED = false>
 void launch_scan(const Plan& pl, const ScanParams& sp, hipStream_t st) {
   constexpr int WAVES = 8;
   const size_t lds = (size_t)QB * 32 * CHUNKS * sizeof(float4) + (size_t)QB * 32 * (K + 1) * sizeof(int);
-  auto kern = scan_topk_kernel<K, QB, WAVES, HAS_UB, POOLS>;
+  auto kern = scan_topk_kernel<K, QB, WAVES, HAS_UB, POOLS, MASKED>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kern, dim3(pl.n_qblocks * pl.n_slices), dim3(WAVES * 64), lds, st, sp);
 }
 
-template <bool HAS_UB>
-int dispatch_scan(const Plan& pl, const ScanParams& sp, hipStream_t st) {
+template <bool HAS_UB, bool MASKED>
+int dispatch_scan_as(const Plan& pl, const ScanParams& sp, hipStream_t st) {
   const bool few = !pl.pools;
-  if (pl.K == 10 && pl.QB == 1 && few) launch_scan<10, 1, HAS_UB, false>(pl, sp, st);
-  else if (pl.K == 10 && pl.QB == 2 && few) launch_scan<10, 2, HAS_UB, false>(pl, sp, st);
-  else if (pl.K == 10 && pl.QB == 1) launch_scan<10, 1, HAS_UB>(pl, sp, st);
-  else if (pl.K == 10 && pl.QB == 2) launch_scan<10, 2, HAS_UB>(pl, sp, st);
-  else if (pl.K == 16 && pl.QB == 1) launch_scan<16, 1, HAS_UB>(pl, sp, st);
-  else if (pl.K == 16 && pl.QB == 2) launch_scan<16, 2, HAS_UB>(pl, sp, st);
-  else if (pl.K == 32 && pl.QB == 1) launch_scan<32, 1, HAS_UB>(pl, sp, st);
+  if (pl.K == 10 && pl.QB == 1 && few) launch_scan<10, 1, HAS_UB, false, MASKED>(pl, sp, st);
+  else if (pl.K == 10 && pl.QB == 2 && few) launch_scan<10, 2, HAS_UB, false, MASKED>(pl, sp, st);
+  else if (pl.K == 10 && pl.QB == 1) launch_scan<10, 1, HAS_UB, true, MASKED>(pl, sp, st);
+  else if (pl.K == 10 && pl.QB == 2) launch_scan<10, 2, HAS_UB, true, MASKED>(pl, sp, st);
+  else if (pl.K == 16 && pl.QB == 1) launch_scan<16, 1, HAS_UB, true, MASKED>(pl, sp, st);
+  else if (pl.K == 16 && pl.QB == 2) launch_scan<16, 2, HAS_UB, true, MASKED>(pl, sp, st);
+  else if (pl.K == 32 && pl.QB == 1) launch_scan<32, 1, HAS_UB, true, MASKED>(pl, sp, st);
   else return sskd::fail(SSKD_ERR_UNSUPPORTED, "no scan kernel for K=%d QB=%d", pl.K, pl.QB);
   return sskd::check_launch("scan_topk_kernel");
+}
+
+// a NULL row mask takes the unmasked instantiation
+template <bool HAS_UB>
+int dispatch_scan(const Plan& pl, const ScanParams& sp, hipStream_t st) {
+  return sp.row_mask ? dispatch_scan_as<HAS_UB, true>(pl, sp, st) : dispatch_scan_as<HAS_UB, false>(pl, sp, st);
 }
 
 }  // namespace
@@ -1616,7 +1723,7 @@ static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* 
                              int k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
                              void* d_workspace, size_t workspace_bytes, void* stream,
                              const sskd_search_tuning* tuning, void* ev_scan_begin, void* ev_scan_end,
-                             const int* nq_dev);
+                             const int* nq_dev, const uint32_t* row_mask);
 
 extern "C" {
 
@@ -1721,17 +1828,68 @@ int sskd_index_search_ex(const float* d_tiled, int64_t n_rows, const float* d_qu
                          void* d_workspace, size_t workspace_bytes, void* stream,
                          const sskd_search_tuning* tuning, void* ev_scan_begin, void* ev_scan_end) {
   return exact_search_impl(d_tiled, n_rows, d_queries, nq, k, id_offset, d_out_scores, d_out_ids, d_workspace,
-                           workspace_bytes, stream, tuning, ev_scan_begin, ev_scan_end, nullptr);
+                           workspace_bytes, stream, tuning, ev_scan_begin, ev_scan_end, nullptr, nullptr);
+}
+
+int sskd_index_search_filtered(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq, int k,
+                               int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                               int64_t* d_out_ids, void* d_workspace, size_t workspace_bytes, void* stream,
+                               const sskd_search_tuning* tuning, void* ev_scan_begin, void* ev_scan_end) {
+  return exact_search_impl(d_tiled, n_rows, d_queries, nq, k, id_offset, d_out_scores, d_out_ids, d_workspace,
+                           workspace_bytes, stream, tuning, ev_scan_begin, ev_scan_end, nullptr, d_row_mask);
+}
+
+int64_t sskd_row_mask_words(int64_t n_rows) { return n_rows <= 0 ? 0 : sskd::ceil_div(n_rows, 32); }
+
+int sskd_row_mask_pack(const uint8_t* d_flags, int64_t n_rows, uint32_t* d_mask, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "row_mask_pack: n_rows < 0");
+  if (n_rows == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_flags && d_mask, "row_mask_pack: null pointer");
+  const int64_t words = sskd_row_mask_words(n_rows);
+  hipLaunchKernelGGL(row_mask_pack_kernel, dim3((unsigned)sskd::ceil_div(sskd::ceil_div(words, 2), 4)), dim3(256), 0,
+                     sskd::as_stream(stream), d_flags, n_rows, d_mask, words);
+  return sskd::check_launch("row_mask_pack_kernel");
+}
+
+int sskd_row_mask_update(uint32_t* d_mask, int64_t n_rows, const int64_t* d_rows, int64_t n_ids, int allow,
+                         int* d_bad, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0 && n_ids >= 0, "row_mask_update: bad shape");
+  SSKD_REQUIRE(d_bad, "row_mask_update: null d_bad");
+  hipStream_t st = sskd::as_stream(stream);
+  if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return sskd::fail(SSKD_ERR_HIP, "row_mask_update: memset failed");
+  if (n_ids == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_mask && d_rows, "row_mask_update: null pointer");
+  hipLaunchKernelGGL(row_mask_update_kernel, dim3((unsigned)sskd::ceil_div(n_ids, 256)), dim3(256), 0, st, d_mask, n_rows,
+                     d_rows, n_ids, allow, d_bad);
+  return sskd::check_launch("row_mask_update_kernel");
+}
+
+int sskd_row_mask_and(const uint32_t* d_a, const uint32_t* d_b, int64_t n_rows, uint32_t* d_out, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "row_mask_and: n_rows < 0");
+  if (n_rows == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_a && d_b && d_out, "row_mask_and: null pointer");
+  const int64_t words = sskd_row_mask_words(n_rows);
+  hipLaunchKernelGGL(row_mask_and_kernel, dim3((unsigned)sskd::ceil_div(words, 256)), dim3(256), 0,
+                     sskd::as_stream(stream), d_a, d_b, d_out, words);
+  return sskd::check_launch("row_mask_and_kernel");
+}
+
+int sskd_row_mask_count(const uint32_t* d_mask, int64_t n_rows, int64_t* d_count, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "row_mask_count: n_rows < 0");
+  SSKD_REQUIRE(d_count && (d_mask || n_rows == 0), "row_mask_count: null pointer");
+  hipLaunchKernelGGL(row_mask_count_kernel, dim3(1), dim3(1024), 0, sskd::as_stream(stream), d_mask, n_rows, d_count);
+  return sskd::check_launch("row_mask_count_kernel");
 }
 
 }  // extern "C"
 
-// the exact search proper; nq_dev (optional) = device-side count of the queries present (<= nq)
+// the exact search proper; nq_dev (optional) = device-side count of the queries present (<= nq);
+// row_mask (optional) = the allow-mask: NULL takes the unmasked kernels
 static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
                              int k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
                              void* d_workspace, size_t workspace_bytes, void* stream,
                              const sskd_search_tuning* tuning, void* ev_scan_begin, void* ev_scan_end,
-                             const int* nq_dev) {
+                             const int* nq_dev, const uint32_t* row_mask) {
   SSKD_REQUIRE(n_rows >= 0, "index_search: n_rows < 0");
   SSKD_REQUIRE(nq >= 0, "index_search: nq < 0");
   SSKD_REQUIRE(k >= 1 && k <= SSKD_K_MAX, "index_search: k=%d outside [1, %d]", k, SSKD_K_MAX);
@@ -1787,6 +1945,7 @@ static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* 
   sp.tiles_per_slice = pl.tiles_per_slice;
   sp.lists_per_query = pl.lists_per_query;
   sp.nq_dev = nq_dev;
+  sp.row_mask = row_mask;
 
   for (int pass = 0; pass < pl.passes; ++pass) {
     hipLaunchKernelGGL(fill_int_kernel, dim3((unsigned)sskd::ceil_div(nq * (1 + pl.K), 256)), dim3(256),
@@ -1873,6 +2032,14 @@ int sskd_index_search_onepass(const float* d_tiled, int64_t n_rows, const float*
                               int k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
                               int* d_inexact, void* d_workspace, size_t workspace_bytes,
                               void* stream) {
+  return sskd_index_search_onepass_filtered(d_tiled, n_rows, d_queries, nq, k, id_offset, nullptr, d_out_scores,
+                                            d_out_ids, d_inexact, d_workspace, workspace_bytes, stream);
+}
+
+int sskd_index_search_onepass_filtered(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
+                                       int k, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                                       int64_t* d_out_ids, int* d_inexact, void* d_workspace,
+                                       size_t workspace_bytes, void* stream) {
   SSKD_REQUIRE(n_rows >= 1, "index_search_onepass: empty index");
   SSKD_REQUIRE(nq >= 1 && nq <= ONEPASS_MAX_NQ, "index_search_onepass: nq=%d outside [1, %d]", nq,
                ONEPASS_MAX_NQ);
@@ -1921,8 +2088,14 @@ int sskd_index_search_onepass(const float* d_tiled, int64_t n_rows, const float*
   sp.n_slices = pl.n_slices;
   sp.tiles_per_slice = pl.tiles_per_slice;
   sp.lists_per_query = pl.lists_per_query;
-  if (pl.QB == 1) launch_scan<10, 1, false, false>(pl, sp, st);
-  else launch_scan<10, 2, false, false>(pl, sp, st);
+  sp.row_mask = d_row_mask;
+  if (d_row_mask) {
+    if (pl.QB == 1) launch_scan<10, 1, false, false, true>(pl, sp, st);
+    else launch_scan<10, 2, false, false, true>(pl, sp, st);
+  } else {
+    if (pl.QB == 1) launch_scan<10, 1, false, false>(pl, sp, st);
+    else launch_scan<10, 2, false, false>(pl, sp, st);
+  }
   int rc = sskd::check_launch("scan_topk_kernel (no pools)");
   if (rc != SSKD_OK) return rc;
 
@@ -2212,6 +2385,15 @@ int sskd_index_search_screened(const float* d_tiled, const void* d_bf16, int64_t
                                int nq, int k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
                                int* d_status, void* d_workspace, size_t workspace_bytes, void* stream,
                                void* ev_scan_begin, void* ev_scan_end) {
+  return sskd_index_search_screened_filtered(d_tiled, d_bf16, n_rows, d_queries, nq, k, id_offset, nullptr, d_out_scores,
+                                             d_out_ids, d_status, d_workspace, workspace_bytes, stream, ev_scan_begin,
+                                             ev_scan_end);
+}
+
+int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16, int64_t n_rows, const float* d_queries,
+                                        int nq, int k, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                                        int64_t* d_out_ids, int* d_status, void* d_workspace, size_t workspace_bytes,
+                                        void* stream, void* ev_scan_begin, void* ev_scan_end) {
   ScreenPlan pl{};
   if (!screen_plan(n_rows, nq, k, &pl))
     return sskd::fail(SSKD_ERR_UNSUPPORTED,
@@ -2243,18 +2425,22 @@ int sskd_index_search_screened(const float* d_tiled, const void* d_bf16, int64_t
   sp.n_rows = n_rows;
   sp.nq = nq;
   sp.lists_per_query = pl.lists_per_query;
+  sp.row_mask = d_row_mask;
   const size_t lds = (size_t)pl.QB * BSTEPS * 64 * 16 + (size_t)pl.QB * 32 * 11 * sizeof(int);
   const void* kern = nullptr;
   switch (pl.QB) {
-#define SSKD_SCREEN_CASE(qb, bg, rg)                                                                      \
-  case qb:                                                                                                \
-    kern = pl.light ? reinterpret_cast<const void*>(screen_append_kernel<10, qb, SCREEN_WAVES, true, bg, rg>)   \
-                    : reinterpret_cast<const void*>(screen_append_kernel<10, qb, SCREEN_WAVES, false, bg, rg>); \
+#define SSKD_SCREEN_KERN(qb, light, bg, rg)                                                                           \
+  (d_row_mask ? reinterpret_cast<const void*>(screen_append_kernel<10, qb, SCREEN_WAVES, light, bg, rg, true>)       \
+              : reinterpret_cast<const void*>(screen_append_kernel<10, qb, SCREEN_WAVES, light, bg, rg>))
+#define SSKD_SCREEN_CASE(qb, bg, rg)                                                                                  \
+  case qb:                                                                                                            \
+    kern = pl.light ? SSKD_SCREEN_KERN(qb, true, bg, rg) : SSKD_SCREEN_KERN(qb, false, bg, rg);                       \
     break;
     SSKD_SCREEN_CASE(2, BGROUP, SCREEN_RING)
     SSKD_SCREEN_CASE(4, BGROUP, SCREEN_RING)
     SSKD_SCREEN_CASE(5, BGROUP_Q5, SCREEN_RING_Q5)
 #undef SSKD_SCREEN_CASE
+#undef SSKD_SCREEN_KERN
     default:
       return sskd::fail(SSKD_ERR_UNSUPPORTED, "index_search_screened: no screening kernel for %d queries per workgroup", 32 * pl.QB);
   }
@@ -2298,12 +2484,12 @@ int sskd_index_search_screened(const float* d_tiled, const void* d_bf16, int64_t
   const int tier1 = nq < SCREEN_FALLBACK_TIER1 ? nq : SCREEN_FALLBACK_TIER1;
   hipLaunchKernelGGL(screen_fallback_tiers_kernel, dim3(1), dim3(1), 0, st, w.fb_count, tier1);
   rc = exact_search_impl(d_tiled, n_rows, w.fb_queries, tier1, k, id_offset, w.fb_scores, w.fb_ids,
-                         w.exact_ws, w.exact_bytes, stream, nullptr, nullptr, nullptr, w.fb_count + 1);
+                         w.exact_ws, w.exact_bytes, stream, nullptr, nullptr, nullptr, w.fb_count + 1, d_row_mask);
   if (rc != SSKD_OK) return rc;
   if (nq > tier1) {
     rc = exact_search_impl(d_tiled, n_rows, w.fb_queries + (size_t)tier1 * DIM, nq - tier1, k, id_offset,
                            w.fb_scores + (size_t)tier1 * k, w.fb_ids + (size_t)tier1 * k, w.exact_ws2, w.exact_bytes2, stream,
-                           nullptr, nullptr, nullptr, w.fb_count + 2);
+                           nullptr, nullptr, nullptr, w.fb_count + 2, d_row_mask);
     if (rc != SSKD_OK) return rc;
   }
   hipLaunchKernelGGL(screen_scatter_kernel, dim3(64), dim3(256), 0, st, w.fb_count, w.fb_qid, w.fb_scores, w.fb_ids, k,

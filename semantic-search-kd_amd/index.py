@@ -34,11 +34,47 @@ _FAISS_DUMMY = 1 << 20
 _METRIC_INNER_PRODUCT = 0
 
 
+class RowFilter:
+    """A prepared per-call filter: the device allow-mask of ``n_rows`` rows (``include/sskd_amd.h``: int32 words,
+    bit ``r & 31`` of word ``r >> 5`` set = local row ``r`` may be returned).  Made by ``FAISSIndexBuilder.row_filter``;
+    reusable, and ``search_device`` with it makes no host synchronisation (safe under graph capture)."""
+
+    def __init__(self, words: torch.Tensor, n_rows: int):
+        self.words = words
+        self.n_rows = int(n_rows)
+
+
+def mask_words(allow, n_rows: int) -> np.ndarray:
+    """Host-side normalisation of a filter: a bool array over ``n_rows`` rows, or an integer array of allowed local
+    rows -> the little-endian uint32 mask words (``np.packbits(..., bitorder="little")``, padded to whole words)."""
+    a = np.asarray(allow)
+    if a.dtype == np.bool_:
+        if a.shape != (n_rows,):
+            raise ValueError(f"a boolean filter needs one entry per row: shape {a.shape}, index has {n_rows} rows")
+        flags = a
+    elif a.dtype.kind in "iu" or a.size == 0:
+        rows = a.astype(np.int64).ravel()
+        if rows.size and (rows.min() < 0 or rows.max() >= n_rows):
+            raise ValueError(f"filter rows outside [0, {n_rows})")
+        flags = np.zeros(n_rows, dtype=np.bool_)
+        flags[rows] = True
+    else:
+        raise TypeError(f"a filter is a bool array or an integer id array, got dtype {a.dtype}")
+    n_words = -(-n_rows // 32)
+    packed = np.zeros(4 * n_words, dtype=np.uint8)
+    bits = np.packbits(flags, bitorder="little")
+    packed[: bits.size] = bits
+    return packed.view("<u4")
+
+
 class IndexHandle:
     """What ``build_from_parquet`` returns: the reference only reads ``.ntotal`` (build_faiss_index.py:72)."""
 
     def __init__(self, owner: "FAISSIndexBuilder"):
         self._owner = owner
+
+    def remove_ids(self, ids) -> int:
+        return self._owner.remove_ids(ids)
 
     @property
     def ntotal(self) -> int:
@@ -98,11 +134,27 @@ class FAISSIndexBuilder:
         # exact fallback (a cost diagnostic; nothing to act on)
         self.last_status: Optional[torch.Tensor] = None
         self.index: Optional[IndexHandle] = None
+        # tombstones (remove_ids): the device allow-mask of the LIVE rows (made on the first removal; bits past ntotal
+        # stay set, so rows added later are live) and how many rows it clears
+        self._live: Optional[torch.Tensor] = None
+        self._n_removed = 0
+        self._mask_scratch: Optional[torch.Tensor] = None   # allow AND live of a filtered call
 
     # ------------------------------------------------------------------ storage
     @property
     def ntotal(self) -> int:
+        """Stored rows, removed ones included (their row numbers stay valid: ``doc_ids[row]``)."""
         return self._n
+
+    @property
+    def n_removed(self) -> int:
+        """Rows taken out by ``remove_ids`` (tombstones: still stored, never returned)."""
+        return self._n_removed
+
+    def _reset_removed(self) -> None:
+        self._live = None
+        self._n_removed = 0
+        self._mask_scratch = None
 
     def _ensure_capacity(self, rows: int) -> None:
         lib = _native.load()
@@ -168,6 +220,12 @@ class FAISSIndexBuilder:
             )
         self._n += n_new
         self._bf16_rows = -1  # the bf16 screening copy is stale
+        if self._live is not None:
+            words = int(lib.sskd_row_mask_words(self._n))
+            if words > self._live.numel():   # new words all set: the appended rows are live
+                grown = torch.full((max(words, self._live.numel() * 3 // 2),), -1, dtype=torch.int32, device=self.device)
+                grown[: self._live.numel()].copy_(self._live)
+                self._live = grown
         self.index = IndexHandle(self)
 
     def build_from_embeddings(
@@ -175,6 +233,7 @@ class FAISSIndexBuilder:
     ) -> IndexHandle:
         self._n = 0
         self._tiled = None
+        self._reset_removed()
         self.add(embeddings)
         self.doc_ids = list(doc_ids) if doc_ids is not None else [f"doc_{i}" for i in range(self._n)]
         if len(self.doc_ids) != self._n:
@@ -204,6 +263,7 @@ class FAISSIndexBuilder:
         ids, texts = read_corpus_parquet(parquet_path, max_docs, text_column, id_column)
         self._n = 0
         self._tiled = None
+        self._reset_removed()
         self.reserve(len(texts))
         # stream in slabs so a multi-million-passage corpus never needs one host matrix
         slab = max(batch_size, 65536)
@@ -219,6 +279,96 @@ class FAISSIndexBuilder:
         self.index = IndexHandle(self)
         return self.index
 
+    # ------------------------------------------------------------ removal / filters
+    def remove_ids(self, ids) -> int:
+        """Take rows out of every later search (faiss ``remove_ids``).  ``ids`` are in the id space ``search``
+        returns (``id_offset + row``): a list, a NumPy array or a device tensor.  Returns the number of rows newly
+        removed (removing a row twice is not an error); raises ``ValueError`` for ids outside the index.  Removed
+        rows keep their row numbers and stay stored (``ntotal`` counts them, ``n_removed`` counts the tombstones)."""
+        lib = _native.load()
+        if isinstance(ids, torch.Tensor):
+            rows = ids.reshape(-1).to(device=self.device, dtype=torch.int64) - self.id_offset
+            bad = bool(((rows < 0) | (rows >= self._n)).any().item()) if rows.numel() else False
+        else:
+            host = np.asarray(ids, dtype=np.int64).reshape(-1) - self.id_offset
+            bad = bool(host.size and (host.min() < 0 or host.max() >= self._n))
+            rows = None if bad else torch.from_numpy(host).to(self.device)
+        if bad:
+            raise ValueError(f"ids outside [{self.id_offset}, {self.id_offset + self._n})")
+        if rows.numel() == 0:
+            return 0
+        stream = _stream(self.device)
+        if self._live is None:
+            self._live = torch.full((int(lib.sskd_row_mask_words(self._n)),), -1, dtype=torch.int32, device=self.device)
+        rows = rows.contiguous()
+        scratch = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0] live count, [1] (low word) bad ids
+        _native.check(lib.sskd_row_mask_update(self._live.data_ptr(), self._n, rows.data_ptr(), rows.numel(), 0,
+                                               scratch[1:].data_ptr(), stream))
+        _native.check(lib.sskd_row_mask_count(self._live.data_ptr(), self._n, scratch.data_ptr(), stream))
+        live, bad_ids = scratch.cpu().tolist()
+        if bad_ids:
+            raise RuntimeError("sskd_row_mask_update reported ids outside the index after they were checked")
+        removed = self._n - int(live)
+        newly, self._n_removed = removed - self._n_removed, removed
+        return newly
+
+    def removed_rows(self) -> np.ndarray:
+        """Local rows taken out by ``remove_ids``, sorted (int64)."""
+        if self._live is None or self._n_removed == 0:
+            return np.zeros(0, dtype=np.int64)
+        words = self._live[: int(_native.load().sskd_row_mask_words(self._n))].cpu().numpy().view(np.uint8)
+        live = np.unpackbits(words, bitorder="little")[: self._n].astype(bool)
+        return np.flatnonzero(~live).astype(np.int64)
+
+    def row_filter(self, allow) -> RowFilter:
+        """Prepare a per-call filter over the CURRENT ``ntotal`` rows: a bool array (one entry per row), an integer
+        array of allowed ids (``id_offset + row``), host or device, or a ``RowFilter`` (returned as is)."""
+        if isinstance(allow, RowFilter):
+            return allow
+        lib = _native.load()
+        n = self._n
+        n_words = int(lib.sskd_row_mask_words(n))
+        words = torch.zeros(max(n_words, 1), dtype=torch.int32, device=self.device)
+        if isinstance(allow, torch.Tensor) and allow.is_cuda:
+            stream = _stream(self.device)
+            if allow.dtype == torch.bool or allow.dtype == torch.uint8:
+                if allow.numel() != n:
+                    raise ValueError(f"a boolean filter needs one entry per row: {allow.numel()} for {n} rows")
+                flags = allow.reshape(-1).to(torch.uint8).contiguous()
+                _native.check(lib.sskd_row_mask_pack(flags.data_ptr(), n, words.data_ptr(), stream))
+            else:
+                rows = (allow.reshape(-1).to(torch.int64) - self.id_offset).contiguous()
+                bad = torch.empty(1, dtype=torch.int32, device=self.device)
+                _native.check(lib.sskd_row_mask_update(words.data_ptr(), n, rows.data_ptr(), rows.numel(), 1,
+                                                       bad.data_ptr(), stream))
+                if int(bad.item()):
+                    raise ValueError(f"filter ids outside [{self.id_offset}, {self.id_offset + n})")
+        else:
+            a = allow.cpu().numpy() if isinstance(allow, torch.Tensor) else np.asarray(allow)
+            if a.dtype != np.bool_:
+                a = a.astype(np.int64) - self.id_offset
+            host = mask_words(a, n)
+            if host.size:
+                words[: host.size].copy_(torch.from_numpy(host.view(np.int32)))
+        return RowFilter(words, n)
+
+    def _effective_mask(self, allow) -> Optional[torch.Tensor]:
+        """The device words a search must honour (``allow AND NOT removed``), or None for the unfiltered path."""
+        if allow is None:
+            return self._live
+        f = self.row_filter(allow)
+        if f.n_rows != self._n:
+            raise ValueError(f"the filter was prepared for {f.n_rows} rows, the index holds {self._n}")
+        if self._live is None:
+            return f.words
+        lib = _native.load()
+        words = int(lib.sskd_row_mask_words(self._n))
+        if self._mask_scratch is None or self._mask_scratch.numel() < words:
+            self._mask_scratch = torch.empty(max(words, 1), dtype=torch.int32, device=self.device)
+        _native.check(lib.sskd_row_mask_and(f.words.data_ptr(), self._live.data_ptr(), self._n,
+                                            self._mask_scratch.data_ptr(), _stream(self.device)))
+        return self._mask_scratch
+
     # ------------------------------------------------------------------- search
     def search_device(
         self,
@@ -227,11 +377,18 @@ class FAISSIndexBuilder:
         normalize_queries: Optional[bool] = None,
         out_scores: Optional[torch.Tensor] = None,
         out_ids: Optional[torch.Tensor] = None,
+        allow=None,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Top-k over the index for device-resident queries; returns device tensors.
 
-        No host synchronisation: everything is enqueued on the current stream.
+        No host synchronisation: everything is enqueued on the current stream (``allow``, when given, should then
+        be a prepared ``RowFilter``).  ``allow`` restricts the call to some rows (see ``row_filter``); removed rows
+        are never returned.
         """
+        mask = self._effective_mask(allow)
+        return self._search_device_masked(queries, k, normalize_queries, out_scores, out_ids, mask)
+
+    def _search_device_masked(self, queries, k, normalize_queries, out_scores, out_ids, mask):
         lib = _native.load()
         if k < 1 or k > _native.SSKD_K_MAX:
             raise ValueError(f"k={k} outside [1, {_native.SSKD_K_MAX}]")
@@ -265,36 +422,54 @@ class FAISSIndexBuilder:
                 if self._workspace is None or self._workspace.numel() < need:
                     self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
                 self.last_status = torch.empty(2, dtype=torch.int32, device=self.device)
-                _native.check(
-                    lib.sskd_index_search_screened(
-                        self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
-                        out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
-                        self._workspace.data_ptr(), self._workspace.numel(), stream, None, None,
+                if mask is None:
+                    _native.check(
+                        lib.sskd_index_search_screened(
+                            self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                            out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
+                            self._workspace.data_ptr(), self._workspace.numel(), stream, None, None,
+                        )
                     )
-                )
+                else:
+                    _native.check(
+                        lib.sskd_index_search_screened_filtered(
+                            self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                            mask.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
+                            self._workspace.data_ptr(), self._workspace.numel(), stream, None, None,
+                        )
+                    )
                 return out_scores, out_ids
         self.last_status = None
         need = int(lib.sskd_index_search_workspace_bytes_ex(self._n, nq, k, tuning))
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        _native.check(
-            lib.sskd_index_search_ex(
-                0 if self._tiled is None else self._tiled.data_ptr(),
-                self._n,
-                q.data_ptr(),
-                nq,
-                k,
-                self.id_offset,
-                out_scores.data_ptr(),
-                out_ids.data_ptr(),
-                self._workspace.data_ptr(),
-                self._workspace.numel(),
-                stream,
-                tuning,
-                None,
-                None,
+        if mask is None:
+            _native.check(
+                lib.sskd_index_search_ex(
+                    0 if self._tiled is None else self._tiled.data_ptr(),
+                    self._n,
+                    q.data_ptr(),
+                    nq,
+                    k,
+                    self.id_offset,
+                    out_scores.data_ptr(),
+                    out_ids.data_ptr(),
+                    self._workspace.data_ptr(),
+                    self._workspace.numel(),
+                    stream,
+                    tuning,
+                    None,
+                    None,
+                )
             )
-        )
+        else:
+            _native.check(
+                lib.sskd_index_search_filtered(
+                    0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                    mask.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr(), self._workspace.data_ptr(),
+                    self._workspace.numel(), stream, tuning, None, None,
+                )
+            )
         return out_scores, out_ids
 
     # the online shape: a handful of queries (sskd_amd.h, one-pass variant).  With a single query
@@ -303,7 +478,7 @@ class FAISSIndexBuilder:
     ONEPASS_MAX_NQ = 64
     ONEPASS_MAX_K = 256
 
-    def _search_onepass_device(self, q: torch.Tensor, k: int, normalize_queries: bool):
+    def _search_onepass_device(self, q: torch.Tensor, k: int, normalize_queries: bool, mask=None):
         """One corpus pass + proof of exactness; returns ``(scores, ids, inexact_flag)`` device tensors."""
         lib = _native.load()
         stream = _stream(self.device)
@@ -317,22 +492,32 @@ class FAISSIndexBuilder:
         need = int(lib.sskd_index_search_onepass_workspace_bytes(self._n, nq, k))
         if self._workspace is None or self._workspace.numel() < need:
             self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        _native.check(
-            lib.sskd_index_search_onepass(
-                self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
-                out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
-                self._workspace.data_ptr(), self._workspace.numel(), stream,
+        if mask is None:
+            _native.check(
+                lib.sskd_index_search_onepass(
+                    self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                    out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
+                    self._workspace.data_ptr(), self._workspace.numel(), stream,
+                )
             )
-        )
+        else:
+            _native.check(
+                lib.sskd_index_search_onepass_filtered(
+                    self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset, mask.data_ptr(),
+                    out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
+                    self._workspace.data_ptr(), self._workspace.numel(), stream,
+                )
+            )
         return out_scores, out_ids, flag
 
-    def _search_numpy(self, query_emb, k: int, normalize_queries: Optional[bool]) -> Tuple[np.ndarray, np.ndarray]:
+    def _search_numpy(self, query_emb, k: int, normalize_queries: Optional[bool], allow=None) -> Tuple[np.ndarray, np.ndarray]:
         _native.require_gpu()
         q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
         if q.ndim == 1:
             q = q[None, :]
         qd = torch.from_numpy(q).to(self.device)
         with torch.cuda.device(self.device):
+            mask = self._effective_mask(allow)
             nq = qd.shape[0]
             if (
                 1 <= k <= self.ONEPASS_MAX_K
@@ -341,7 +526,7 @@ class FAISSIndexBuilder:
                 and qd.shape[1] == self.embedding_dim
             ):
                 norm = self.metric == "cosine" if normalize_queries is None else normalize_queries
-                scores, ids, flag = self._search_onepass_device(qd, k, norm)
+                scores, ids, flag = self._search_onepass_device(qd, k, norm, mask)
                 # this host path synchronises anyway (NumPy out): read the proof flag with the result
                 if int(flag.item()) == 0:
                     self.last_search_path = "onepass"
@@ -349,16 +534,18 @@ class FAISSIndexBuilder:
                 self.last_search_path = "onepass-unproven+chained"
             else:
                 self.last_search_path = "chained" if k > _native.SSKD_K_PASS else "single"
-            scores, ids = self.search_device(qd, k, normalize_queries=normalize_queries)
+            scores, ids = self._search_device_masked(qd, k, normalize_queries, None, None, mask)
             if self.last_status is not None:
                 self.last_search_path += "+screened"
             return scores.cpu().numpy(), ids.cpu().numpy()
 
-    def search(self, query_emb: np.ndarray, k: int = 10) -> Tuple[np.ndarray, np.ndarray]:
-        """``(distances, indices)`` exactly as the serving route consumes them (app.py:293-301)."""
+    def search(self, query_emb: np.ndarray, k: int = 10, *, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``(distances, indices)`` exactly as the serving route consumes them (app.py:293-301).  ``allow``: an
+        optional filter (a bool array over ``ntotal`` rows, an integer id array, or a ``RowFilter``); removed rows
+        are never returned.  Fewer than ``k`` matching rows pad the tail with ``(-FLT_MAX, -1)``."""
         if self._n == 0 and self._tiled is None and self.index is None:
             raise RuntimeError("index is empty: call build_from_parquet/add/load first")
-        return self._search_numpy(query_emb, k, normalize_queries=None)
+        return self._search_numpy(query_emb, k, normalize_queries=None, allow=allow)
 
     # -------------------------------------------------------------- persistence
     def reconstruct(self, rows: Sequence[int]) -> np.ndarray:
@@ -397,6 +584,11 @@ class FAISSIndexBuilder:
         if self.id_offset != 0 or self.shard_info:
             with open(out / "shard.json", "w") as f:
                 json.dump({**(self.shard_info or {}), "id_offset": self.id_offset, "rows": self._n}, f)
+        # tombstones: the flat file keeps every row (it stays faiss-readable); the removed LOCAL rows go beside it
+        if self._n_removed:
+            np.save(out / "removed.npy", self.removed_rows())
+        else:
+            (out / "removed.npy").unlink(missing_ok=True)
 
     def load(self, index_dir: Union[str, Path], append: bool = False) -> None:
         """Restore a saved index (``append=True``: add its rows behind the ones already held - consecutive row
@@ -415,6 +607,7 @@ class FAISSIndexBuilder:
             if not append:
                 self._n = 0
                 self._tiled = None
+                self._reset_removed()
                 self.doc_ids = []
                 self.doc_texts = None
                 if shard is not None:
@@ -429,6 +622,11 @@ class FAISSIndexBuilder:
                 self.add(np.array(vecs[lo : lo + step], dtype=np.float32, copy=True))
         finally:
             self.metric = metric
+        removed_path = d / "removed.npy"
+        if removed_path.exists():
+            removed = np.load(removed_path).astype(np.int64)
+            if removed.size:
+                self.remove_ids(removed + first + self.id_offset)
         ids_path = d / "doc_ids.json"
         if ids_path.exists():
             with open(ids_path) as f:
@@ -445,6 +643,7 @@ class FAISSIndexBuilder:
         self._tiled = None
         self._workspace = None
         self._n = 0
+        self._reset_removed()
 
 
 # ---------------------------------------------------------------------- helpers

@@ -50,7 +50,7 @@ import torch
 from .dist import ShardedSearcher, shard_bounds
 
 MANIFEST = "shards.json"
-_OP_STOP, _OP_SEARCH, _OP_LOAD = 0, 1, 2
+_OP_STOP, _OP_SEARCH, _OP_LOAD, _OP_REMOVE = 0, 1, 2, 3
 
 
 class ShardFailure(RuntimeError):
@@ -320,6 +320,53 @@ class ShardedIndex:
         ``ShardFailure`` on every rank when any rank fails, so that the launcher exits instead of hanging."""
         self._load_local(Path(index_dir))
 
+    # ------------------------------------------------------------------ removal
+    def _remove_collective(self, ids: Optional[torch.Tensor], n_ids: int) -> int:
+        """every rank: the ids from rank 0 (ctrl group) -> its own ``[id_offset, id_offset + rows)`` share -> one
+        status word per rank -> the sum of the rows newly removed"""
+        import torch.distributed as dist
+
+        world, rank = _world(self.group)
+        if world > 1:
+            buf = ids if rank == 0 else torch.empty(n_ids, dtype=torch.int64)
+            dist.broadcast(buf, src=self._src(), group=self._ctrl())
+            ids = buf
+        error, newly = None, 0
+        try:
+            if self.local is None:
+                raise RuntimeError("no index loaded on this rank")
+            lo = int(self.local.id_offset)
+            mine = ids[(ids >= lo) & (ids < lo + int(self.local.ntotal))]
+            newly = int(self.local.remove_ids(mine.numpy())) if mine.numel() else 0
+        except Exception as exc:  # noqa: BLE001 - reported to every rank below
+            error = exc
+        failures = self._exchange_status("remove_ids", error)
+        self.last_failure = failures or None
+        if failures:
+            raise ShardFailure("remove_ids", failures) from error
+        if world > 1:
+            total = torch.tensor([newly], dtype=torch.int64)
+            dist.all_reduce(total, group=self._ctrl())
+            newly = int(total[0])
+        return newly
+
+    def remove_ids(self, global_ids) -> int:
+        """Take GLOBAL row ids out of every later search on every rank (rank 0's call; the other ranks follow from
+        ``serve_forever``).  Returns the number of rows newly removed; ``ValueError`` for ids outside
+        ``[0, ntotal)`` (nothing is announced then); ``ShardFailure`` when a rank could not apply its share."""
+        if self.local is None:
+            raise RuntimeError("index is empty: call load first")
+        world, rank = _world(self.group)
+        if world > 1 and rank != 0:
+            raise RuntimeError("ShardedIndex.remove_ids is rank 0's call; the other ranks run serve_forever()")
+        self._check_usable()
+        ids = torch.as_tensor(np.asarray(global_ids.cpu() if isinstance(global_ids, torch.Tensor) else global_ids,
+                                         dtype=np.int64).reshape(-1))
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal):
+            raise ValueError(f"ids outside [0, {self.ntotal})")
+        self._header(_OP_REMOVE, ids.numel())
+        return self._remove_collective(ids, ids.numel())
+
     # ------------------------------------------------------------------ state
     @property
     def is_loaded(self) -> bool:
@@ -402,6 +449,8 @@ class ShardedIndex:
                     box = [None]
                     dist.broadcast_object_list(box, src=self._src(), group=self._ctrl())
                     self._load_local(Path(box[0]))
+                elif op == _OP_REMOVE:
+                    self._remove_collective(None, a)
             except ShardFailure:
                 if self.broken is not None:
                     raise
