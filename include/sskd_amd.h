@@ -216,6 +216,28 @@ int sskd_index_search_onepass_filtered(const float* d_tiled, int64_t n_rows, con
                                        int64_t* d_out_ids, int* d_inexact, void* d_workspace,
                                        size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Range search (faiss IndexFlatIP::range_search): every allowed row scoring above a per-query threshold
+ * Result set of query q: R_q = { allowed local row r : score(q, r) > d_thresholds[q] }, scores in the exact scan's
+ * fp32 fma order (bit for bit what sskd_index_search returns).  The comparison is strict (faiss' inner-product
+ * rule); -inf (padding, masked rows) and NaN never match, also when the threshold is -inf; a NaN threshold
+ * matches nothing.  d_row_mask: NULL = all rows, else the format of "Filtered search" above.
+ * Output (CSR, faiss' layout): d_lims [nq + 1] int64, always written and always exact; the results of query q are
+ * d_out_scores / d_out_ids [lims[q], lims[q + 1]), ids = row + id_offset, sorted by score descending, then id
+ * ascending (faiss leaves this order unspecified; here it is deterministic).
+ * Overflow: when lims[nq] > max_results only d_lims is written (the later kernels read the total on the device
+ * and exit); nothing is ever written at or past max_results.  The caller compares lims[nq] with max_results.
+ * max_results = 0 is a count-only call: d_out_scores / d_out_ids may then be NULL.  n_rows = 0 or nq = 0 writes
+ * zero lims.  Stream-ordered, no host sync, allocates nothing.  Arguments are checked before any HIP call:
+ * negative nq / max_results / n_rows, NULL lims or inputs, a shard of 2^31 - 64 rows or more
+ * (SSKD_ERR_INVALID) and a workspace smaller than sskd_index_range_search_workspace_bytes (SSKD_ERR_WORKSPACE).
+ * ------------------------------------------------------------------------- */
+size_t sskd_index_range_search_workspace_bytes(int64_t n_rows, int nq, int64_t max_results);
+int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
+                            const float* d_thresholds, int64_t id_offset, const uint32_t* d_row_mask, int64_t* d_lims,
+                            float* d_out_scores, int64_t* d_out_ids, int64_t max_results, void* d_workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -88,6 +88,10 @@ class IndexHandle:
         """faiss ``index.search`` shape: raw inner product, no query normalisation."""
         return self._owner._search_numpy(x, k, normalize_queries=False)
 
+    def range_search(self, x: np.ndarray, thresh) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss ``index.range_search`` shape ``(lims, D, I)``: raw inner product, no query normalisation."""
+        return self._owner._range_numpy(x, thresh, normalize_queries=False)
+
 
 class FAISSIndexBuilder:
     """Exact cosine / inner-product index resident in MI355X HBM."""
@@ -139,6 +143,10 @@ class FAISSIndexBuilder:
         self._live: Optional[torch.Tensor] = None
         self._n_removed = 0
         self._mask_scratch: Optional[torch.Tensor] = None   # allow AND live of a filtered call
+        # range search: result buffers reused across calls (grown to the exact total when a call overflows them)
+        self.range_capacity = 1 << 16
+        self._range_scores: Optional[torch.Tensor] = None
+        self._range_ids: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ storage
     @property
@@ -547,6 +555,136 @@ class FAISSIndexBuilder:
             raise RuntimeError("index is empty: call build_from_parquet/add/load first")
         return self._search_numpy(query_emb, k, normalize_queries=None, allow=allow)
 
+    # ------------------------------------------------------------- range search
+    def _range_call(self, q: torch.Tensor, thr: torch.Tensor, mask, lims: torch.Tensor, scores, ids, max_results: int):
+        lib = _native.load()
+        nq = q.shape[0]
+        need = int(lib.sskd_index_range_search_workspace_bytes(self._n, nq, max_results))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _native.check(
+            lib.sskd_index_range_search(
+                0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, thr.data_ptr(),
+                self.id_offset, None if mask is None else mask.data_ptr(), lims.data_ptr(),
+                None if scores is None else scores.data_ptr(), None if ids is None else ids.data_ptr(), max_results,
+                self._workspace.data_ptr(), self._workspace.numel(), _stream(self.device),
+            )
+        )
+
+    def range_search_device(
+        self,
+        queries: torch.Tensor,
+        threshold,
+        *,
+        allow=None,
+        normalize_queries: Optional[bool] = None,
+        max_results: Optional[int] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Every allowed row scoring ``> threshold`` (faiss ``range_search``) for device-resident queries; returns
+        device tensors ``(lims [nq + 1] int64, scores float32, ids int64)``: the results of query ``q`` are
+        ``[lims[q], lims[q + 1])``, sorted by score descending, then id ascending.  ``threshold``: a float, or one
+        per query (array or device tensor).  Removed rows are never returned; ``allow`` works as in ``search``.
+
+        With ``max_results`` the call makes no host synchronisation (``threshold`` should then be a float or a
+        device tensor, and ``allow`` a prepared ``RowFilter``): ``scores`` / ``ids`` have ``max_results`` entries and
+        hold the results only if ``lims[-1] <= max_results``, which the caller checks (``lims`` is always exact).
+        Without it the call synchronises once to read ``lims[-1]``, calls again if the reused result buffer was too
+        small (grown to exactly the total), and returns tensors of exactly ``lims[-1]`` entries."""
+        if queries.dim() != 2 or queries.shape[1] != self.embedding_dim:
+            raise ValueError(f"expected [nq, {self.embedding_dim}] queries, got {tuple(queries.shape)}")
+        if queries.dtype != torch.float32 or not queries.is_cuda:
+            raise TypeError("range_search_device expects a float32 device tensor")
+        lib = _native.load()
+        q = queries.contiguous()
+        nq = q.shape[0]
+        if normalize_queries is None:
+            normalize_queries = self.metric == "cosine"
+        stream = _stream(self.device)
+        if normalize_queries and nq:
+            q = q.clone()
+            _native.check(lib.sskd_l2_normalize_rows(q.data_ptr(), nq, self.embedding_dim, stream))
+        if isinstance(threshold, torch.Tensor) and threshold.is_cuda:
+            thr = threshold.reshape(-1).to(torch.float32)
+            if thr.numel() == 1 and nq != 1:
+                thr = thr.expand(nq)
+            if thr.numel() != nq:
+                raise ValueError(f"{thr.numel()} thresholds for {nq} queries")
+            thr = thr.contiguous()
+        elif np.ndim(threshold) == 0 and not isinstance(threshold, torch.Tensor):
+            thr = torch.full((max(nq, 1),), float(threshold), dtype=torch.float32, device=self.device)
+        else:
+            host = threshold.cpu().numpy() if isinstance(threshold, torch.Tensor) else threshold
+            thr = torch.from_numpy(range_thresholds(host, nq)).to(self.device)
+        mask = self._effective_mask(allow)
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=self.device)
+        if max_results is not None:
+            max_results = int(max_results)
+            if max_results < 0:
+                raise ValueError(f"max_results={max_results} < 0")
+            scores = torch.empty(max_results, dtype=torch.float32, device=self.device)
+            ids = torch.empty(max_results, dtype=torch.int64, device=self.device)
+            self._range_call(q, thr, mask, lims, scores, ids, max_results)
+            return lims, scores, ids
+        cap = max(int(self.range_capacity), 1)
+        if self._range_scores is None or self._range_scores.numel() < cap:
+            self._range_scores = torch.empty(cap, dtype=torch.float32, device=self.device)
+            self._range_ids = torch.empty(cap, dtype=torch.int64, device=self.device)
+        cap = self._range_scores.numel()
+        self._range_call(q, thr, mask, lims, self._range_scores, self._range_ids, cap)
+        total = int(lims[-1].item())
+        if total > cap:   # the count is exact: one retry with exactly the room it needs
+            self._range_scores = torch.empty(total, dtype=torch.float32, device=self.device)
+            self._range_ids = torch.empty(total, dtype=torch.int64, device=self.device)
+            self.range_capacity = total
+            self._range_call(q, thr, mask, lims, self._range_scores, self._range_ids, total)
+        return lims, self._range_scores[:total].clone(), self._range_ids[:total].clone()
+
+    def _range_numpy(self, query_emb, threshold, normalize_queries: Optional[bool], allow=None):
+        _native.require_gpu()
+        q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None, :]
+        thr = range_thresholds(threshold, q.shape[0])
+        qd = torch.from_numpy(q).to(self.device)
+        with torch.cuda.device(self.device):
+            lims, scores, ids = self.range_search_device(
+                qd, torch.from_numpy(thr).to(self.device), allow=allow, normalize_queries=normalize_queries
+            )
+            return lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
+
+    def range_search(self, query_emb: np.ndarray, threshold, *, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss ``range_search``: every row scoring ``> threshold`` (a float, or one per query), as NumPy
+        ``(lims int64 [nq + 1], D float32, I int64)``; query ``q``'s results are ``[lims[q], lims[q + 1])``, sorted by
+        score descending, then id ascending.  Queries are normalised for the cosine metric as in ``search``;
+        ``allow`` works as in ``search`` and removed rows are never returned."""
+        return self._range_numpy(query_emb, threshold, normalize_queries=None, allow=allow)
+
+    def near_duplicates(self, threshold: float, *, batch_size: int = 4096) -> Tuple[np.ndarray, np.ndarray]:
+        """Every pair of live rows ``i < j`` (as ids) scoring ``> threshold``: ``(pairs int64 [m, 2], scores float32
+        [m])`` sorted by (i, score descending, j).  The queries are the stored rows themselves (not normalised
+        again), so score(i, j) == score(j, i) bit for bit; self-matches and removed rows are excluded."""
+        if batch_size < 1:
+            raise ValueError(f"batch_size={batch_size} < 1")
+        _native.require_gpu()
+        lib = _native.load()
+        removed = self.removed_rows()
+        live = np.ones(self._n, dtype=np.bool_)
+        live[removed] = False
+        pair_parts, score_parts = [], []
+        with torch.cuda.device(self.device):
+            for lo in range(0, self._n, batch_size):
+                b = min(batch_size, self._n - lo)
+                rows = torch.empty((b, self.embedding_dim), dtype=torch.float32, device=self.device)
+                _native.check(lib.sskd_index_get_rows(self._tiled.data_ptr(), lo, b, rows.data_ptr(), _stream(self.device)))
+                lims, scores, ids = self.range_search_device(rows, float(threshold), normalize_queries=False)
+                p, s = pairs_from_ranges(lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy(),
+                                         np.arange(lo, lo + b, dtype=np.int64) + self.id_offset, live[lo:lo + b])
+                pair_parts.append(p)
+                score_parts.append(s)
+        if not pair_parts:
+            return np.zeros((0, 2), dtype=np.int64), np.zeros(0, dtype=np.float32)
+        return np.concatenate(pair_parts), np.concatenate(score_parts)
+
     # -------------------------------------------------------------- persistence
     def reconstruct(self, rows: Sequence[int]) -> np.ndarray:
         """Stored vectors of the given local rows (``faiss.Index.reconstruct`` for a list), host fp32."""
@@ -663,6 +801,34 @@ def read_corpus_parquet(parquet_path, max_docs: Optional[int] = None, text_colum
     else:
         ids = [f"doc_{i}" for i in range(len(texts))]
     return ids, texts
+
+
+def range_thresholds(threshold, nq: int) -> np.ndarray:
+    """One float32 threshold per query: a scalar is broadcast, an array must hold ``nq`` values."""
+    t = np.asarray(threshold, dtype=np.float32)
+    if t.ndim == 0:
+        return np.full(nq, t, dtype=np.float32)
+    t = t.reshape(-1)
+    if t.size == 1 and nq != 1:
+        return np.full(nq, t[0], dtype=np.float32)
+    if t.size != nq:
+        raise ValueError(f"{t.size} thresholds for {nq} queries")
+    return np.ascontiguousarray(t)
+
+
+def pairs_from_ranges(lims: np.ndarray, scores: np.ndarray, ids: np.ndarray, query_ids: np.ndarray,
+                      query_live: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The pairs ``(i, j)``, ``i < j``, of a self range search: query ``q`` is id ``query_ids[q]``; queries that are
+    not live contribute nothing.  Keeps the per-query order (score descending, then j), so queries given in
+    ascending id order yield pairs sorted by (i, score descending, j)."""
+    lims = np.asarray(lims, dtype=np.int64)
+    counts = np.diff(lims)
+    qi = np.repeat(np.asarray(query_ids, dtype=np.int64), counts)
+    live = np.repeat(np.asarray(query_live, dtype=np.bool_), counts)
+    j = np.asarray(ids, dtype=np.int64)[: lims[-1]]
+    keep = live & (j > qi)
+    pairs = np.stack([qi[keep], j[keep]], axis=1) if keep.any() else np.zeros((0, 2), dtype=np.int64)
+    return pairs.astype(np.int64, copy=False), np.asarray(scores, dtype=np.float32)[: lims[-1]][keep]
 
 
 def _resolve_device(device: Optional[str]) -> torch.device:
