@@ -496,6 +496,79 @@ int sskd_gemm_backend(int mode);
  * SSKD_ERR_UNSUPPORTED: the step then transposes and uses the NT kernel). */
 int sskd_gemm_tn_bf16(const void* d_a, const void* d_b, float* d_c, int64_t T, int M, int N, void* stream);
 
+/* Every field of the NT GEMM the generic path launches (a plain C mirror of the library's internal argument block):
+ * C[z][M, N] (+)= alpha * A[z][M, K] . B[z][N, K]^T + bias[N] over the two-level batch z = b1 * batch2 + b2, with element
+ * strides per level.  K % 32 == 0; lda, ldb and the operand strides multiples of 8; 16-byte aligned operands.
+ * c_is_f32: fp32 output (else bf16); accumulate: fp32 output only, C += result; split_k > 1: unbatched, fp32 accumulating
+ * output without bias, K cut into split_k slices that meet through fp32 atomics; act = 1: erf-GELU of
+ * (alpha * acc + bias) in the epilogue (bf16 output only). */
+typedef struct sskd_gemm_desc {
+  const void* a;
+  const void* b;
+  void* c;
+  const float* bias;   /* [N] or NULL */
+  int64_t lda, ldb, ldc;
+  int64_t sa1, sa2, sb1, sb2, sc1, sc2;
+  int32_t m, n, k;
+  int32_t batch1, batch2;
+  float alpha;
+  int32_t c_is_f32;
+  int32_t accumulate;
+  int32_t split_k;
+  int32_t act;
+} sskd_gemm_desc;
+
+/* Test hook: launches the NT GEMM exactly as the training step and the teacher do (same launcher: its argument checks,
+ * the kernel choice, and the hipBLASLt route of sskd_gemm_backend(0)). */
+int sskd_gemm_nt_ex(const sskd_gemm_desc* d, void* stream);
+
+/* Test hook: one of the generic path's kernels by itself (csrc/generic.h), for per-kernel parity tests.  Arguments are
+ * device pointers (`ptrs`, NULL where marked optional), integers and floats, in the order listed per op.  A wrong
+ * argument count, an unknown op or a NULL where a pointer is required returns SSKD_ERR_INVALID and launches nothing;
+ * a shape outside the kernel's contract returns the launcher's own error.  bf16 unless marked f32 / i32.
+ *   ATTENTION_FWD    ptrs {qkv [B*S, 3*heads*DH], key_mask i32 [B, S], ctx [B*S, heads*DH], lse f32 [B, heads, S] opt}
+ *                    ints {B, S, heads, DH}  floats {scale}
+ *   ATTENTION_BWD    ptrs {qkv, key_mask, ctx, dctx, lse, dqkv [B*S, 3*heads*DH]}  ints {B, S, heads, DH}  floats {scale}
+ *   SOFTMAX_FWD      ptrs {scores [B, heads, S, S] (in place), key_mask i32 [B, S]}  ints {B, heads, S}  floats {scale}
+ *   SOFTMAX_BWD      ptrs {dP [rows, S] (in place), P [rows, S]}  ints {rows, S}  floats {scale}
+ *   ADD_LN_FWD       ptrs {a, b opt, gamma f32, beta f32, y, z_save opt, mean f32 opt, rstd f32 opt (with mean)}
+ *                    ints {M, H}  floats {eps}
+ *   LN_BWD           ptrs {dy, z, mean f32, rstd f32, gamma f32, dz, dgamma f32, dbeta f32, dz_colsum f32 opt, dy2 opt}
+ *                    ints {M, H}
+ *   GELU_FWD         ptrs {u, h}  ints {n}
+ *   GELU_BWD         ptrs {u, dh, du}  ints {n}
+ *   GELU_BWD_COLSUM  ptrs {u [M, F], dh, du, db f32 [F]}  ints {M, F}
+ *   COLSUM           ptrs {dY, db f32 [N]}  ints {M, N, ld}
+ *   ADD              ptrs {a, b, c}  ints {n}
+ *   TRANSPOSE        ptrs {in, out, colsum f32 opt}  ints {R, C, ld_in, ld_out, batch1, batch2, s_in1, s_in2, s_out1, s_out2}
+ *   EMBED_FWD        ptrs {ids i32 [B, S], mask i32 [B, S], word [vocab, H], pos, type0 [H], z [B*S, H]}
+ *                    ints {B, S, H, vocab, pos_offset}
+ *   EMBED_BWD        ptrs {ids, mask, dz, dword f32, dpos f32, dtype0 f32}  ints {B, S, H, vocab, pos_offset}
+ *   POOL_FWD         ptrs {hidden [B, S, H], mask i32, out f32 [B, H], pooled_save f32 opt}  ints {B, S, H, normalize}
+ *   POOL_BWD         ptrs {dout f32 [B, H], pooled f32, mask i32, dhidden}  ints {B, S, H, normalize}
+ *   GEMM_TN          ptrs {A [T, M], B [T, N], C f32 (+=)}  ints {lda, ldb, ldc, T, M, N} */
+enum {
+  SSKD_OP_ATTENTION_FWD = 1,
+  SSKD_OP_ATTENTION_BWD = 2,
+  SSKD_OP_SOFTMAX_FWD = 3,
+  SSKD_OP_SOFTMAX_BWD = 4,
+  SSKD_OP_ADD_LN_FWD = 5,
+  SSKD_OP_LN_BWD = 6,
+  SSKD_OP_GELU_FWD = 7,
+  SSKD_OP_GELU_BWD = 8,
+  SSKD_OP_GELU_BWD_COLSUM = 9,
+  SSKD_OP_COLSUM = 10,
+  SSKD_OP_ADD = 11,
+  SSKD_OP_TRANSPOSE = 12,
+  SSKD_OP_EMBED_FWD = 13,
+  SSKD_OP_EMBED_BWD = 14,
+  SSKD_OP_POOL_FWD = 15,
+  SSKD_OP_POOL_BWD = 16,
+  SSKD_OP_GEMM_TN = 17
+};
+int sskd_generic_op(int op, const void* const* ptrs, int n_ptrs, const int64_t* ints, int n_ints, const float* floats,
+                    int n_floats, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Host WordPiece tokenizer (uncased BERT): replaces the `tokenizers` call inside
  * SentenceTransformer.encode for ASCII text (reference: AutoTokenizer use src/utils/chunk.py:26;

@@ -92,6 +92,22 @@ class GenericGrads(C.Structure):
     ]
 
 
+class GemmDesc(C.Structure):
+    """``sskd_gemm_desc``: every field of the generic path's NT GEMM (test hook ``sskd_gemm_nt_ex``)."""
+
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("c", C.c_void_p), ("bias", C.c_void_p)] + [
+        (n, C.c_int64) for n in ("lda", "ldb", "ldc", "sa1", "sa2", "sb1", "sb2", "sc1", "sc2")
+    ] + [(n, C.c_int32) for n in ("m", "n", "k", "batch1", "batch2")] + [("alpha", C.c_float)] + [
+        (n, C.c_int32) for n in ("c_is_f32", "accumulate", "split_k", "act")
+    ]
+
+
+# sskd_generic_op codes (include/sskd_amd.h)
+OP_ATTENTION_FWD, OP_ATTENTION_BWD, OP_SOFTMAX_FWD, OP_SOFTMAX_BWD, OP_ADD_LN_FWD, OP_LN_BWD = 1, 2, 3, 4, 5, 6
+OP_GELU_FWD, OP_GELU_BWD, OP_GELU_BWD_COLSUM, OP_COLSUM, OP_ADD, OP_TRANSPOSE = 7, 8, 9, 10, 11, 12
+OP_EMBED_FWD, OP_EMBED_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_GEMM_TN = 13, 14, 15, 16, 17
+
+
 class SearchTuning(C.Structure):
     """``sskd_search_tuning``: explicit launch tuning, passed to the workspace query AND the search."""
 
@@ -173,6 +189,8 @@ SIGNATURES = {
     "sskd_gemm_nt_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sskd_gemm_backend": (_i, [_i]),
     "sskd_gemm_tn_bf16": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "sskd_gemm_nt_ex": (_i, [C.POINTER(GemmDesc), _vp]),
+    "sskd_generic_op": (_i, [_i, C.POINTER(_vp), _i, C.POINTER(_i64), _i, C.POINTER(_f), _i, _vp]),
     "sskd_tokenizer_create": (_i, [C.c_char_p, _i64, C.POINTER(C.c_void_p)]),
     "sskd_tokenizer_destroy": (None, [_vp]),
     "sskd_tokenizer_encode": (_i, [_vp, C.c_char_p, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, C.POINTER(_i64)]),

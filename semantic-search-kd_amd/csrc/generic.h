@@ -68,9 +68,15 @@ int launch_ln_bwd(const bf16_t* dy, const bf16_t* z, const float* mean, const fl
 // Inference attention, fused (no score matrix in memory): for every (batch row, head)
 //   ctx[b, :, h*DH : (h+1)*DH] = softmax(scale * Q K^T + (key masked ? -inf : 0)) V
 // with Q / K / V the column blocks [0, H) / [H, 2H) / [2H, 3H) of the row-major qkv [B*S, 3H].
-// DH in {32, 64, 128}; S a multiple of 32, at most 512.
+// DH in {32, 64, 128}; S a multiple of 32, at most 512, and S * DH <= 36 864: the head's K and V (4 S DH bytes) and the
+// key bias (4 S) are one workgroup's LDS, 160 KiB on gfx950 (DH 128: S <= 288; other shapes are refused, not launched).
 // `lse` (optional, fp32 [B, heads, S]): log2-domain log-sum-exp of every query's scaled scores - all the
 // backward kernel needs to rebuild the probabilities.
+// A batch row WITHOUT ANY VALID KEY (mask all 0) is defined, not an error: its ctx rows are exactly 0 (finite; not the
+// uniform average an additive -1e4 mask would give) and its lse is -inf; attention_bwd fed that lse gives exactly 0 in
+// dQ, dK and dV of the row and touches no other row.
+constexpr int ATT_FWD_MAX_SDH = 36864;
+bool attention_fwd_supported(int S, int DH);
 int launch_attention_fwd(const bf16_t* qkv, const int32_t* key_mask, int B, int S, int heads, int DH, float scale,
                          bf16_t* ctx, float* lse, hipStream_t st);
 // Fused attention backward (probabilities recomputed from qkv + lse, no S x S matrix in memory):

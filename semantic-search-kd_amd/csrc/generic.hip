@@ -772,7 +772,7 @@ __global__ __launch_bounds__(512) void attention_bwd_kernel(AttnBwdArgs p) {
   float* const lse = reinterpret_cast<float*>(blk0 + (PASS == 0 ? 3 : 4) * SD8);
   float* const Dq = lse + p.S;
   float* const mb = Dq + p.S;
-  __shared__ int s_kmax;
+  __shared__ int s_kmax, s_qmax;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, h = lane >> 5;
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(512) void attention_bwd_kernel(AttnBwdArgs p) {
   const bf16_t* obase = p.ctx + row0 * p.H + (int64_t)head * DH;
   const bf16_t* dobase = p.dctx + row0 * p.H + (int64_t)head * DH;
 
-  if (tid == 0) s_kmax = 0;
+  if (tid == 0) s_kmax = s_qmax = 0;
   __syncthreads();
   for (int i = tid; i < p.S; i += 512) {
     const bool on = p.mask[row0 + i] != 0;
@@ -791,14 +791,19 @@ __global__ __launch_bounds__(512) void attention_bwd_kernel(AttnBwdArgs p) {
     if (on) atomicMax(&s_kmax, i / 32 + 1);
     lse[i] = p.lse[((int64_t)b * p.NH + head) * p.S + i];
     float dsum = 0.f;
+    bool live = false;   // dO row not all zero
 #pragma unroll
     for (int c = 0; c < DH / 8; ++c) {
       const bf16x8 o = *reinterpret_cast<const bf16x8*>(obase + (int64_t)i * p.H + 8 * c);
       const bf16x8 g = *reinterpret_cast<const bf16x8*>(dobase + (int64_t)i * p.H + 8 * c);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) dsum = fmaf((float)o[e], (float)g[e], dsum);
+      for (int e = 0; e < 8; ++e) {
+        dsum = fmaf((float)o[e], (float)g[e], dsum);
+        live |= (float)g[e] != 0.f;
+      }
     }
     Dq[i] = dsum;
+    if (PASS == 1 && live) atomicMax(&s_qmax, i / 32 + 1);
   }
   const bf16_t* const kR = reinterpret_cast<const bf16_t*>(kT);
   const bf16_t* const qR = reinterpret_cast<const bf16_t*>(qT);
@@ -892,7 +897,10 @@ __global__ __launch_bounds__(512) void attention_bwd_kernel(AttnBwdArgs p) {
     for (int t = 0; t < DT; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) dk[t][i] = dv[t][i] = 0.f;
-    const int qmax = wave < kmax ? kmax : 0;  // a fully masked key tile gets zero gradients
+    // a fully masked key tile gets zero gradients.  Every query attends to the valid keys (padding queries included), so
+    // the loop runs over query tiles up to the last one with a nonzero dO row: a tile whose dO is all zero adds exactly
+    // 0 to dV (P dO) and to dK (dS = P (dO V^T - rowsum(dO o O)) scale) - e.g. the padding rows of the training step
+    const int qmax = wave < kmax ? s_qmax : 0;
     for (int qt = 0; qt < qmax; ++qt) {
       f32x16 sq, dp;
 #pragma unroll
@@ -1580,12 +1588,18 @@ int launch_gemm_nt(const GemmArgs& a, hipStream_t st) {
   return sskd::check_launch("gemm_nt_kernel");
 }
 
+bool attention_fwd_supported(int S, int DH) {
+  return (DH == 32 || DH == 64 || DH == 128) && S >= 32 && S % 32 == 0 && S <= 512 && S * DH <= ATT_FWD_MAX_SDH;
+}
+
 int launch_attention_fwd(const bf16_t* qkv, const int32_t* key_mask, int B, int S, int heads, int DH, float scale,
                          bf16_t* ctx, float* lse, hipStream_t st) {
   if (B == 0) return SSKD_OK;
   SSKD_REQUIRE(qkv && key_mask && ctx, "attention_fwd: null pointer");
   SSKD_REQUIRE(S >= 32 && S % 32 == 0 && S <= 512, "attention_fwd: S=%d must be a multiple of 32 in [32, 512]", S);
   SSKD_REQUIRE(DH == 32 || DH == 64 || DH == 128, "attention_fwd: head width %d not in {32, 64, 128}", DH);
+  SSKD_REQUIRE(attention_fwd_supported(S, DH), "attention_fwd: S=%d x head width %d does not fit in LDS (S * DH <= %d)", S,
+               DH, ATT_FWD_MAX_SDH);
   AttnArgs a{};
   a.qkv = qkv;
   a.mask = key_mask;

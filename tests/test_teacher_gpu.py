@@ -372,3 +372,40 @@ def test_teacher_two_branch_batch_equals_its_halves(gpu):
     assert np.isfinite(whole).all()
     halves = np.concatenate([teacher.score_token_ids(ids[lo:lo + 64], mask[lo:lo + 64]).cpu().numpy() for lo in (0, 64)])
     assert np.array_equal(whole, halves)
+
+
+@pytest.mark.gpu
+def test_teacher_batch_invariance_at_the_xlmr_large_shape(gpu):
+    """The same promise at the shape that reaches the library route (hidden 1 024, FFN 4 096, 16 heads: the QKV,
+    attention-output and FFN2 products are plain K, N >= 1 024 products that hipBLASLt serves in the automatic mode,
+    csrc/blaslt.hip), 2 layers: 128 pairs x 256 tokens (two branches) equal its two 64-pair halves, a 96-pair batch equals
+    its first 96 scores, and a repeat is bit-identical."""
+    from semantic_search_kd_amd import TeacherModel, _native
+    from semantic_search_kd_amd.teacher import TeacherConfig, synthetic_teacher_state_dict
+
+    lib = _native.load()
+    prev = lib.sskd_gemm_backend(-1)
+    try:
+        assert lib.sskd_gemm_backend(0) == 0
+        cfg = TeacherConfig(vocab_size=800, hidden_size=1024, num_hidden_layers=2, num_attention_heads=16,
+                            intermediate_size=4096, max_position_embeddings=260)
+        teacher = TeacherModel("synthetic", "cuda:0", config=cfg, state_dict=synthetic_teacher_state_dict(cfg))
+        rng = np.random.default_rng(5)
+        P, S = 128, 256
+        ids = rng.integers(4, cfg.vocab_size, size=(P, S)).astype(np.int32)
+        ids[:, 0] = 0
+        mask = np.ones((P, S), np.int32)
+        for b in (2, 50, 64, 100, 127):
+            n = int(rng.integers(3, S))
+            mask[b, n:] = 0
+            ids[b, n:] = cfg.pad_token_id
+        whole = teacher.score_token_ids(ids, mask).cpu().numpy()
+        assert np.isfinite(whole).all()
+        halves = np.concatenate([teacher.score_token_ids(ids[lo:lo + 64], mask[lo:lo + 64]).cpu().numpy() for lo in (0, 64)])
+        assert np.array_equal(whole, halves), np.abs(whole - halves).max()
+        part = teacher.score_token_ids(ids[:96], mask[:96]).cpu().numpy()
+        assert np.array_equal(whole[:96], part), np.abs(whole[:96] - part).max()
+        again = teacher.score_token_ids(ids, mask).cpu().numpy()
+        assert np.array_equal(whole, again)
+    finally:
+        lib.sskd_gemm_backend(prev)

@@ -11,6 +11,7 @@ import torch
 
 from conftest import GOLDEN
 from oracle import encoder as enc_oracle
+from oracle import generic_ops as go
 from oracle import kd_losses as kd_oracle
 from semantic_search_kd_amd import BertConfig, synthetic_state_dict
 
@@ -71,6 +72,14 @@ def test_nt_gemm_matches_torch(gpu, native_lib):
         want = a.float() @ b.float().T + bias + (c0 if acc else 0)
         tol = 2e-2 * want.abs().max().item() if not f32 else 1e-3 * max(want.abs().max().item(), 1.0)
         assert (c.float() - want).abs().max().item() <= tol, (M, N, K)
+        # per element (tests/test_generic_kernels_gpu.py): one bf16 ulp of the fp64 value (2 u for fp32 out) plus
+        # (K + split + 8) u sum_k |a_ik b_jk| for the fp32 accumulation (split <= K / 256 slices meet through atomics)
+        ref, mag = go.gemm_nt(a, b, bias)
+        if acc:
+            ref, mag = ref + c0.double().cpu(), mag + c0.double().cpu().abs()
+        err = (c.double().cpu() - ref).abs()
+        bound = (2 * 2.0 ** -24 * ref.abs() if f32 else go.bf16_ulp(ref)) + (K + K // 256 + 8) * 2.0 ** -24 * mag
+        assert bool((err <= bound).all()), (M, N, K, float((err - bound).max()))
 
 
 @pytest.mark.gpu
@@ -124,6 +133,12 @@ def test_tn_gemm_matches_torch(gpu, native_lib):
         _native.check(native_lib.sskd_gemm_tn_bf16(a.data_ptr(), b.data_ptr(), c.data_ptr(), T, M, N, st))
         want = a.float().T @ b.float() + c0
         assert (c - want).abs().max().item() <= 1e-3 * max(want.abs().max().item(), 1.0), (T, M, N)
+        # per element: 2 u |ref| + (T + 264) u sum_t |a_tm b_tn| (fp32 MFMA accumulation, then <= 256 slices of atomics)
+        ref, mag = go.gemm_tn(a, b)
+        ref, mag = ref + c0.double().cpu(), mag + c0.double().cpu().abs()
+        err = (c.double().cpu() - ref).abs()
+        bound = 2 * 2.0 ** -24 * ref.abs() + (T + 264) * 2.0 ** -24 * mag
+        assert bool((err <= bound).all()), (T, M, N, float((err - bound).max()))
     # unsupported shapes are refused, not mis-computed
     a = torch.zeros((64, 256), device="cuda", dtype=torch.bfloat16)
     c = torch.zeros((256, 128), device="cuda")
