@@ -25,6 +25,32 @@ inline int check_launch(const char* what) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Lays a caller's workspace out as consecutive buffers: take<T>(n) returns the next slot, its start aligned to
+// `align` bytes (a power of two, 256 unless asked), and moves past n elements.  With a null base every slot is null
+// and only the offsets move, so a path's size query runs the very carve its launch code uses; bytes() is the total,
+// rounded up to 256.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+  template <class T>
+  T* take(size_t count, size_t align = 256) {
+    off = (off + align - 1) & ~(align - 1);
+    T* slot = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += count * sizeof(T);
+    return slot;
+  }
+  size_t bytes() const { return align256(off); }
+};
+
+// The workspace check of every entry point that takes one: `what` is the message prefix ("index_search", ...).
+inline int require_workspace(const char* what, const void* ws, size_t bytes, size_t need) {
+  if (ws && bytes >= need) return SSKD_OK;
+  return fail(SSKD_ERR_WORKSPACE, "%s: workspace %zu B < required %zu B", what, bytes, need);
+}
+
 // compute units of the current device (256 on MI355X)
 int cu_count();
 

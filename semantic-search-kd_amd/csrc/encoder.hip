@@ -1300,24 +1300,17 @@ struct Workspace {
   size_t bytes;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline int s_pad_of(int S) { return (S + 31) / 32 * 32; }
 inline int64_t t_pad_of(int B, int S) { return ((int64_t)B * s_pad_of(S) + 255) / 256 * 256; }
 
 // Token buffers hold T_pad = roundup(B * S_pad, 256) rows (no kernel bounds-checks).
 Workspace carve(void* base, int B, int S) {
   const size_t T = (size_t)t_pad_of(B, S);
-  char* pch = static_cast<char*>(base);
+  sskd::Carver c(base);
   Workspace w{};
-  auto take = [&](size_t elems) {
-    __bf16* ptr = reinterpret_cast<__bf16*>(pch);
-    pch += align256(elems * sizeof(__bf16));
-    return ptr;
-  };
-  w.xa = take(T * H);
-  w.ctx = take(T * H);
-  w.bytes = (size_t)(pch - static_cast<char*>(base));
+  w.xa = c.take<__bf16>(T * H);
+  w.ctx = c.take<__bf16>(T * H);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -1435,12 +1428,9 @@ int prepare(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, int B
             void* d_workspace, size_t workspace_bytes, Workspace* ws) {
   int rc = check_cfg(cfg, w, B, S);
   if (rc != SSKD_OK) return rc;
-  const size_t need = sskd_encoder_workspace_bytes(cfg, B, S);
-  if (B > 0 && (!d_workspace || workspace_bytes < need))
-    return sskd::fail(SSKD_ERR_WORKSPACE, "encoder: workspace %zu B < required %zu B",
-                      workspace_bytes, need);
-  if (B > 0) *ws = carve(d_workspace, B, S);
-  return SSKD_OK;
+  if (B == 0) return SSKD_OK;
+  *ws = carve(d_workspace, B, S);
+  return sskd::require_workspace("encoder", d_workspace, workspace_bytes, ws->bytes);
 }
 
 }  // namespace

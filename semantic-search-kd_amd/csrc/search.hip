@@ -1630,7 +1630,6 @@ struct Plan {
   int passes;     // scan passes of K results each (k > K is served by chaining)
   bool pools;     // shared pruning pools on (batch shapes) or off (few tiles per wave)
   size_t part_elems;
-  int reduce_lpg;       // lists per group of a reduce step
   size_t reduce_elems;  // elements of one reduce buffer (0: no reduce step needed); two are kept
 };
 
@@ -1674,14 +1673,70 @@ Plan make_plan(int64_t n_rows, int nq, int k, const sskd_search_tuning* tn = nul
   // without them.  Measured crossover (tools/pools_sweep.py, 1 M and 125 k rows, 64..4096
   // queries): 24-32 tiles per wave; the batch configurations of bench.py have 61.
   pl.pools = (tn && tn->pruning_pools != 0) ? tn->pruning_pools > 0 : pl.tiles_per_slice >= 24 * pl.waves;
-  pl.reduce_lpg = REDUCE_MAX_CAND / pl.K;
   pl.reduce_elems = pl.lists_per_query > MERGE_DIRECT_MAX_LISTS
-                        ? (size_t)nq * sskd::ceil_div(pl.lists_per_query, pl.reduce_lpg) * pl.K
+                        ? (size_t)nq * sskd::ceil_div(pl.lists_per_query, REDUCE_MAX_CAND / pl.K) * pl.K
                         : 0;
   return pl;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// Rows of one shard: the kernels keep row ids in int32, the last tile's padding rows included.
+constexpr int64_t MAX_SHARD_ROWS = ((int64_t)1 << 31) - 64;
+
+int require_shard_rows(const char* what, int64_t n_rows) {
+  if (n_rows < MAX_SHARD_ROWS) return SSKD_OK;
+  return sskd::fail(SSKD_ERR_INVALID, "%s: shard too large for int32 row ids", what);
+}
+
+// workspace of the exact search (chained passes): sized by exact_carve(nullptr, ...).bytes
+struct ExactWs {
+  float* part_scores;
+  int* part_ids;
+  float* ub_scores;
+  int* ub_ids;
+  int* tau;             // [nq] + gpool [nq * K]
+  float* red_scores[2];  // the reduce steps' ping-pong buffers
+  int* red_ids[2];
+  size_t bytes;
+};
+
+ExactWs exact_carve(void* base, const Plan& pl, int nq) {
+  sskd::Carver c(base);
+  ExactWs w{};
+  w.part_scores = c.take<float>(pl.part_elems);
+  w.part_ids = c.take<int>(pl.part_elems);
+  w.ub_scores = c.take<float>(nq);
+  w.ub_ids = c.take<int>(nq);
+  w.tau = c.take<int>((size_t)nq * (1 + pl.K));
+  for (int i = 0; i < 2; ++i) {
+    w.red_scores[i] = c.take<float>(pl.reduce_elems);
+    w.red_ids[i] = c.take<int>(pl.reduce_elems);
+  }
+  w.bytes = c.bytes();
+  return w;
+}
+
+// One reduce_lists_kernel step: per query, the candidates' `lists` lists of k_in entries become ceil(lists / lpg)
+// lists of k_out in (out_scores, out_ids).  On return (scores, ids, lists) describe the step's output.
+int launch_reduce(const float*& scores, const int*& ids, int& lists, int k_in, int k_out, int nq, const int* nq_dev,
+                  float* out_scores, int* out_ids, hipStream_t st) {
+  ReduceParams rp{};
+  rp.scores = scores;
+  rp.ids = ids;
+  rp.k = k_in;
+  rp.k_out = k_out;
+  rp.lists_in = lists;
+  rp.lpg = REDUCE_MAX_CAND / k_in;
+  rp.groups = (int)sskd::ceil_div(lists, rp.lpg);
+  rp.nq = nq;
+  rp.nq_dev = nq_dev;
+  rp.out_scores = out_scores;
+  rp.out_ids = out_ids;
+  hipLaunchKernelGGL(reduce_lists_kernel, dim3((unsigned)sskd::ceil_div((int64_t)nq * rp.groups, 4)), dim3(256), 0, st, rp);
+  scores = out_scores;
+  ids = out_ids;
+  lists = rp.groups;
+  return sskd::check_launch("reduce_lists_kernel");
+}
 
 template <int K, int QB, bool HAS_UB, bool POOLS = true, bool MASKED = false>
 void launch_scan(const Plan& pl, const ScanParams& sp, hipStream_t st) {
@@ -1779,11 +1834,7 @@ size_t sskd_index_search_workspace_bytes(int64_t n_rows, int nq, int k) {
 size_t sskd_index_search_workspace_bytes_ex(int64_t n_rows, int nq, int k,
                                             const sskd_search_tuning* tuning) {
   if (n_rows < 0 || nq <= 0 || k <= 0) return 0;
-  const Plan pl = make_plan(n_rows, nq, k, tuning);
-  return align256(pl.part_elems * sizeof(float)) + align256(pl.part_elems * sizeof(int)) +
-         align256((size_t)nq * sizeof(float)) + align256((size_t)nq * sizeof(int)) +
-         align256((size_t)nq * (1 + pl.K) * sizeof(int)) +
-         2 * (align256(pl.reduce_elems * sizeof(float)) + align256(pl.reduce_elems * sizeof(int)));
+  return exact_carve(nullptr, make_plan(n_rows, nq, k, tuning), nq).bytes;
 }
 
 int sskd_index_search_plan(int64_t n_rows, int nq, int k, int* queries_per_block,
@@ -1893,7 +1944,8 @@ static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* 
   SSKD_REQUIRE(n_rows >= 0, "index_search: n_rows < 0");
   SSKD_REQUIRE(nq >= 0, "index_search: nq < 0");
   SSKD_REQUIRE(k >= 1 && k <= SSKD_K_MAX, "index_search: k=%d outside [1, %d]", k, SSKD_K_MAX);
-  SSKD_REQUIRE(n_rows < ((int64_t)1 << 31) - 64, "index_search: shard too large for int32 row ids");
+  int rc = require_shard_rows("index_search", n_rows);
+  if (rc != SSKD_OK) return rc;
   if (nq == 0) return SSKD_OK;
   SSKD_REQUIRE(d_queries && d_out_scores && d_out_ids, "index_search: null pointer");
   hipStream_t st = sskd::as_stream(stream);
@@ -1904,40 +1956,19 @@ static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* 
     return sskd::check_launch("fill_empty_kernel");
   }
   SSKD_REQUIRE(d_tiled, "index_search: null index");
-  const size_t need = sskd_index_search_workspace_bytes_ex(n_rows, nq, k, tuning);
-  if (!d_workspace || workspace_bytes < need)
-    return sskd::fail(SSKD_ERR_WORKSPACE, "index_search: workspace %zu B < required %zu B",
-                      workspace_bytes, need);
   const Plan pl = make_plan(n_rows, nq, k, tuning);
-  char* ws = static_cast<char*>(d_workspace);
-  float* part_scores = reinterpret_cast<float*>(ws);
-  ws += align256(pl.part_elems * sizeof(float));
-  int* part_ids = reinterpret_cast<int*>(ws);
-  ws += align256(pl.part_elems * sizeof(int));
-  float* ub_scores = reinterpret_cast<float*>(ws);
-  ws += align256((size_t)nq * sizeof(float));
-  int* ub_ids = reinterpret_cast<int*>(ws);
-  ws += align256((size_t)nq * sizeof(int));
-  int* tau = reinterpret_cast<int*>(ws);
-  ws += align256((size_t)nq * (1 + pl.K) * sizeof(int));
-  float* red_scores[2];
-  int* red_ids[2];
-  for (int i = 0; i < 2; ++i) {
-    red_scores[i] = reinterpret_cast<float*>(ws);
-    ws += align256(pl.reduce_elems * sizeof(float));
-    red_ids[i] = reinterpret_cast<int*>(ws);
-    ws += align256(pl.reduce_elems * sizeof(int));
-  }
+  const ExactWs w = exact_carve(d_workspace, pl, nq);
+  if ((rc = sskd::require_workspace("index_search", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK) return rc;
 
   ScanParams sp{};
   sp.tiled = d_tiled;
   sp.queries = d_queries;
-  sp.part_scores = part_scores;
-  sp.part_ids = part_ids;
-  sp.ub_scores = ub_scores;
-  sp.ub_ids = ub_ids;
-  sp.tau = tau;
-  sp.gpool = tau + nq;  // filled together with tau
+  sp.part_scores = w.part_scores;
+  sp.part_ids = w.part_ids;
+  sp.ub_scores = w.ub_scores;
+  sp.ub_ids = w.ub_ids;
+  sp.tau = w.tau;
+  sp.gpool = w.tau + nq;  // filled together with tau
   sp.n_rows = n_rows;
   sp.n_tiles = pl.n_tiles;
   sp.nq = nq;
@@ -1949,35 +1980,18 @@ static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* 
 
   for (int pass = 0; pass < pl.passes; ++pass) {
     hipLaunchKernelGGL(fill_int_kernel, dim3((unsigned)sskd::ceil_div(nq * (1 + pl.K), 256)), dim3(256),
-                       0, st, tau, nq * (1 + pl.K), (int)0x80000000);
+                       0, st, w.tau, nq * (1 + pl.K), (int)0x80000000);
     if (pass == 0 && ev_scan_begin) (void)hipEventRecord(static_cast<hipEvent_t>(ev_scan_begin), st);
-    int rc = pass == 0 ? dispatch_scan<false>(pl, sp, st) : dispatch_scan<true>(pl, sp, st);
+    rc = pass == 0 ? dispatch_scan<false>(pl, sp, st) : dispatch_scan<true>(pl, sp, st);
     if (pass == 0 && ev_scan_end) (void)hipEventRecord(static_cast<hipEvent_t>(ev_scan_end), st);
     if (rc != SSKD_OK) return rc;
-    const float* cand_scores = part_scores;
-    const int* cand_ids = part_ids;
+    const float* cand_scores = w.part_scores;
+    const int* cand_ids = w.part_ids;
     int lists = pl.lists_per_query;
-    for (int step = 0; lists > MERGE_DIRECT_MAX_LISTS; ++step) {
-      ReduceParams rp{};
-      rp.scores = cand_scores;
-      rp.ids = cand_ids;
-      rp.k = pl.K;
-      rp.k_out = pl.K;
-      rp.lists_in = lists;
-      rp.lpg = pl.reduce_lpg;
-      rp.groups = (int)sskd::ceil_div(lists, pl.reduce_lpg);
-      rp.nq = nq;
-      rp.nq_dev = nq_dev;
-      rp.out_scores = red_scores[step & 1];
-      rp.out_ids = red_ids[step & 1];
-      hipLaunchKernelGGL(reduce_lists_kernel, dim3((unsigned)sskd::ceil_div((int64_t)nq * rp.groups, 4)),
-                         dim3(256), 0, st, rp);
-      rc = sskd::check_launch("reduce_lists_kernel");
-      if (rc != SSKD_OK) return rc;
-      cand_scores = rp.out_scores;
-      cand_ids = rp.out_ids;
-      lists = rp.groups;
-    }
+    for (int step = 0; lists > MERGE_DIRECT_MAX_LISTS; ++step)
+      if ((rc = launch_reduce(cand_scores, cand_ids, lists, pl.K, pl.K, nq, nq_dev, w.red_scores[step & 1],
+                              w.red_ids[step & 1], st)) != SSKD_OK)
+        return rc;
     MergeParams<int> mp{};
     mp.nq_dev = nq_dev;
     mp.scores = cand_scores;
@@ -1994,8 +2008,8 @@ static int exact_search_impl(const float* d_tiled, int64_t n_rows, const float* 
     mp.out_off = pass * pl.K;
     mp.count = (k - pass * pl.K) < pl.K ? (k - pass * pl.K) : pl.K;
     mp.id_offset = id_offset;
-    mp.ub_scores = (pass + 1 < pl.passes) ? ub_scores : nullptr;
-    mp.ub_ids = ub_ids;
+    mp.ub_scores = (pass + 1 < pl.passes) ? w.ub_scores : nullptr;
+    mp.ub_ids = w.ub_ids;
     hipLaunchKernelGGL(merge_topk_kernel<int>, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0,
                        st, mp);
     rc = sskd::check_launch("merge_topk_kernel");
@@ -2009,23 +2023,65 @@ extern "C" {
 namespace {
 constexpr int ONEPASS_MAX_NQ = 64, ONEPASS_MAX_K = 256;
 
-// plan of the one-pass search: the K = 10 geometry of a k = 10 search
-Plan onepass_plan(int64_t n_rows, int nq) { return make_plan(n_rows, nq, 10); }
+// plan of the one-pass search: the K = 10 geometry of a k = 10 search, without pools
+Plan onepass_plan(int64_t n_rows, int nq) {
+  Plan pl = make_plan(n_rows, nq, 10);
+  pl.pools = false;
+  return pl;
+}
 
-// reduce levels: per-lane lists (10 each) -> [groups][k] -> ... -> [1][k]
-size_t onepass_reduce_elems(const Plan& pl, int nq, int k) {
-  const int g1 = (int)sskd::ceil_div(pl.lists_per_query, REDUCE_MAX_CAND / pl.K);
-  return (size_t)nq * g1 * k;
+struct OnepassWs {
+  float* part_scores;
+  int* part_ids;
+  float* red_scores[2];  // reduce levels: per-lane lists (10 each) -> [groups][k] -> ... -> [1][k]
+  int* red_ids[2];
+  float* bound_s;
+  int* bound_i;
+  size_t bytes;
+};
+
+OnepassWs onepass_carve(void* base, const Plan& pl, int nq, int k) {
+  const size_t re = (size_t)nq * sskd::ceil_div(pl.lists_per_query, REDUCE_MAX_CAND / pl.K) * k;
+  sskd::Carver c(base);
+  OnepassWs w{};
+  w.part_scores = c.take<float>(pl.part_elems);
+  w.part_ids = c.take<int>(pl.part_elems);
+  for (int i = 0; i < 2; ++i) {
+    w.red_scores[i] = c.take<float>(re);
+    w.red_ids[i] = c.take<int>(re);
+  }
+  w.bound_s = c.take<float>(nq);
+  w.bound_i = c.take<int>(nq);
+  w.bytes = c.bytes();
+  return w;
+}
+
+// merge of n_lists int64-id lists of k_in per query into the top k_out (sskd_topk_merge, sskd_topk_merge_packed);
+// list l of query q starts at scores[l * list_stride + q * k_in] and ids[l * id_list_stride + q * k_in]
+int launch_merge_i64(const float* scores, const int64_t* ids, int64_t list_stride, int64_t id_list_stride, int n_lists,
+                     int nq, int k_in, int k_out, float* d_out_scores, int64_t* d_out_ids, void* stream, const char* what) {
+  MergeParams<int64_t> mp{};
+  mp.scores = scores;
+  mp.ids = ids;
+  mp.list_stride = list_stride;
+  mp.id_list_stride = id_list_stride;
+  mp.q_stride = k_in;
+  mp.k_in = k_in;
+  mp.n_cand = n_lists * k_in;
+  mp.nq = nq;
+  mp.out_scores = d_out_scores;
+  mp.out_ids = d_out_ids;
+  mp.out_stride = k_out;
+  mp.count = k_out;
+  hipLaunchKernelGGL(merge_topk_kernel<int64_t>, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0,
+                     sskd::as_stream(stream), mp);
+  return sskd::check_launch(what);
 }
 }  // namespace
 
 size_t sskd_index_search_onepass_workspace_bytes(int64_t n_rows, int nq, int k) {
   if (n_rows < 0 || nq <= 0 || nq > ONEPASS_MAX_NQ || k <= 0 || k > ONEPASS_MAX_K) return 0;
-  const Plan pl = onepass_plan(n_rows, nq);
-  const size_t re = onepass_reduce_elems(pl, nq, k);
-  return align256(pl.part_elems * sizeof(float)) + align256(pl.part_elems * sizeof(int)) +
-         2 * (align256(re * sizeof(float)) + align256(re * sizeof(int))) +
-         align256((size_t)nq * sizeof(float)) + align256((size_t)nq * sizeof(int));
+  return onepass_carve(nullptr, onepass_plan(n_rows, nq), nq, k).bytes;
 }
 
 int sskd_index_search_onepass(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
@@ -2045,43 +2101,25 @@ int sskd_index_search_onepass_filtered(const float* d_tiled, int64_t n_rows, con
                ONEPASS_MAX_NQ);
   SSKD_REQUIRE(k >= 1 && k <= ONEPASS_MAX_K, "index_search_onepass: k=%d outside [1, %d]", k,
                ONEPASS_MAX_K);
-  SSKD_REQUIRE(n_rows < ((int64_t)1 << 31) - 64, "index_search_onepass: shard too large for int32 row ids");
+  int rc = require_shard_rows("index_search_onepass", n_rows);
+  if (rc != SSKD_OK) return rc;
   SSKD_REQUIRE(d_tiled && d_queries && d_out_scores && d_out_ids && d_inexact,
                "index_search_onepass: null pointer");
-  const size_t need = sskd_index_search_onepass_workspace_bytes(n_rows, nq, k);
-  if (!d_workspace || workspace_bytes < need)
-    return sskd::fail(SSKD_ERR_WORKSPACE, "index_search_onepass: workspace %zu B < required %zu B",
-                      workspace_bytes, need);
-  hipStream_t st = sskd::as_stream(stream);
   const Plan pl = onepass_plan(n_rows, nq);
-  const size_t re = onepass_reduce_elems(pl, nq, k);
-  char* ws = static_cast<char*>(d_workspace);
-  float* part_scores = reinterpret_cast<float*>(ws);
-  ws += align256(pl.part_elems * sizeof(float));
-  int* part_ids = reinterpret_cast<int*>(ws);
-  ws += align256(pl.part_elems * sizeof(int));
-  float* red_scores[2];
-  int* red_ids[2];
-  for (int i = 0; i < 2; ++i) {
-    red_scores[i] = reinterpret_cast<float*>(ws);
-    ws += align256(re * sizeof(float));
-    red_ids[i] = reinterpret_cast<int*>(ws);
-    ws += align256(re * sizeof(int));
-  }
-  float* bound_s = reinterpret_cast<float*>(ws);
-  ws += align256((size_t)nq * sizeof(float));
-  int* bound_i = reinterpret_cast<int*>(ws);
+  const OnepassWs w = onepass_carve(d_workspace, pl, nq, k);
+  if ((rc = sskd::require_workspace("index_search_onepass", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK) return rc;
+  hipStream_t st = sskd::as_stream(stream);
 
   hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(256), 0, st, d_inexact, 1, 0);
   ScanParams sp{};
   sp.tiled = d_tiled;
   sp.queries = d_queries;
-  sp.part_scores = part_scores;
-  sp.part_ids = part_ids;
+  sp.part_scores = w.part_scores;
+  sp.part_ids = w.part_ids;
   sp.ub_scores = nullptr;
   sp.ub_ids = nullptr;
-  sp.tau = bound_i;    // unused without pools (never dereferenced), kept non-null
-  sp.gpool = bound_i;
+  sp.tau = w.bound_i;    // unused without pools (never dereferenced), kept non-null
+  sp.gpool = w.bound_i;
   sp.n_rows = n_rows;
   sp.n_tiles = pl.n_tiles;
   sp.nq = nq;
@@ -2089,57 +2127,32 @@ int sskd_index_search_onepass_filtered(const float* d_tiled, int64_t n_rows, con
   sp.tiles_per_slice = pl.tiles_per_slice;
   sp.lists_per_query = pl.lists_per_query;
   sp.row_mask = d_row_mask;
-  if (d_row_mask) {
-    if (pl.QB == 1) launch_scan<10, 1, false, false, true>(pl, sp, st);
-    else launch_scan<10, 2, false, false, true>(pl, sp, st);
-  } else {
-    if (pl.QB == 1) launch_scan<10, 1, false, false>(pl, sp, st);
-    else launch_scan<10, 2, false, false>(pl, sp, st);
-  }
-  int rc = sskd::check_launch("scan_topk_kernel (no pools)");
-  if (rc != SSKD_OK) return rc;
+  if ((rc = dispatch_scan<false>(pl, sp, st)) != SSKD_OK) return rc;
 
   BoundParams bp{};
-  bp.scores = part_scores;
-  bp.ids = part_ids;
+  bp.scores = w.part_scores;
+  bp.ids = w.part_ids;
   bp.k = pl.K;
   bp.lists = pl.lists_per_query;
   bp.nq = nq;
-  bp.bound_s = bound_s;
-  bp.bound_i = bound_i;
+  bp.bound_s = w.bound_s;
+  bp.bound_i = w.bound_i;
   hipLaunchKernelGGL(last_entry_bound_kernel, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0, st, bp);
   rc = sskd::check_launch("last_entry_bound_kernel");
   if (rc != SSKD_OK) return rc;
 
-  const float* cand_scores = part_scores;
-  const int* cand_ids = part_ids;
-  int lists = pl.lists_per_query, k_in = pl.K;
-  for (int step = 0; step == 0 || lists > 1; ++step) {
-    ReduceParams rp{};
-    rp.scores = cand_scores;
-    rp.ids = cand_ids;
-    rp.k = k_in;
-    rp.k_out = k;
-    rp.lists_in = lists;
-    rp.lpg = REDUCE_MAX_CAND / k_in;
-    rp.groups = (int)sskd::ceil_div(lists, rp.lpg);
-    rp.nq = nq;
-    rp.out_scores = red_scores[step & 1];
-    rp.out_ids = red_ids[step & 1];
-    hipLaunchKernelGGL(reduce_lists_kernel, dim3((unsigned)sskd::ceil_div((int64_t)nq * rp.groups, 4)),
-                       dim3(256), 0, st, rp);
-    rc = sskd::check_launch("reduce_lists_kernel");
-    if (rc != SSKD_OK) return rc;
-    cand_scores = rp.out_scores;
-    cand_ids = rp.out_ids;
-    lists = rp.groups;
-    k_in = k;
-  }
+  const float* cand_scores = w.part_scores;
+  const int* cand_ids = w.part_ids;
+  int lists = pl.lists_per_query;
+  for (int step = 0; step == 0 || lists > 1; ++step)
+    if ((rc = launch_reduce(cand_scores, cand_ids, lists, step == 0 ? pl.K : k, k, nq, nullptr, w.red_scores[step & 1],
+                            w.red_ids[step & 1], st)) != SSKD_OK)
+      return rc;
   FinalizeParams fp{};
   fp.scores = cand_scores;
   fp.ids = cand_ids;
-  fp.bound_s = bound_s;
-  fp.bound_i = bound_i;
+  fp.bound_s = w.bound_s;
+  fp.bound_i = w.bound_i;
   fp.k = k;
   fp.nq = nq;
   fp.id_offset = id_offset;
@@ -2155,26 +2168,8 @@ int sskd_topk_merge(const float* d_scores, const int64_t* d_ids, int n_lists, in
   SSKD_REQUIRE(n_lists >= 1 && nq >= 0 && k_in >= 1 && k_out >= 1, "topk_merge: bad shape");
   if (nq == 0) return SSKD_OK;
   SSKD_REQUIRE(d_scores && d_ids && d_out_scores && d_out_ids, "topk_merge: null pointer");
-  MergeParams<int64_t> mp{};
-  mp.scores = d_scores;
-  mp.ids = d_ids;
-  mp.list_stride = (int64_t)nq * k_in;
-  mp.id_list_stride = (int64_t)nq * k_in;
-  mp.q_stride = k_in;
-  mp.k_in = k_in;
-  mp.n_cand = n_lists * k_in;
-  mp.nq = nq;
-  mp.out_scores = d_out_scores;
-  mp.out_ids = d_out_ids;
-  mp.out_stride = k_out;
-  mp.out_off = 0;
-  mp.count = k_out;
-  mp.id_offset = 0;
-  mp.ub_scores = nullptr;
-  mp.ub_ids = nullptr;
-  hipLaunchKernelGGL(merge_topk_kernel<int64_t>, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256),
-                     0, sskd::as_stream(stream), mp);
-  return sskd::check_launch("merge_topk_kernel<int64>");
+  return launch_merge_i64(d_scores, d_ids, (int64_t)nq * k_in, (int64_t)nq * k_in, n_lists, nq, k_in, k_out, d_out_scores,
+                          d_out_ids, stream, "merge_topk_kernel<int64>");
 }
 
 size_t sskd_topk_record_bytes(int nq, int k) {
@@ -2190,26 +2185,10 @@ int sskd_topk_merge_packed(const void* d_records, int n_lists, int nq, int k_in,
   SSKD_REQUIRE((reinterpret_cast<uintptr_t>(d_records) & 7) == 0, "topk_merge_packed: records must be 8-byte aligned");
   const size_t rec = sskd_topk_record_bytes(nq, k_in);
   const char* base = static_cast<const char*>(d_records);
-  MergeParams<int64_t> mp{};
-  mp.ids = reinterpret_cast<const int64_t*>(base);
-  mp.scores = reinterpret_cast<const float*>(base + (size_t)nq * k_in * sizeof(int64_t));
-  mp.list_stride = (int64_t)(rec / sizeof(float));
-  mp.id_list_stride = (int64_t)(rec / sizeof(int64_t));
-  mp.q_stride = k_in;
-  mp.k_in = k_in;
-  mp.n_cand = n_lists * k_in;
-  mp.nq = nq;
-  mp.out_scores = d_out_scores;
-  mp.out_ids = d_out_ids;
-  mp.out_stride = k_out;
-  mp.out_off = 0;
-  mp.count = k_out;
-  mp.id_offset = 0;
-  mp.ub_scores = nullptr;
-  mp.ub_ids = nullptr;
-  hipLaunchKernelGGL(merge_topk_kernel<int64_t>, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256),
-                     0, sskd::as_stream(stream), mp);
-  return sskd::check_launch("merge_topk_kernel<int64> (packed)");
+  return launch_merge_i64(reinterpret_cast<const float*>(base + (size_t)nq * k_in * sizeof(int64_t)),
+                          reinterpret_cast<const int64_t*>(base), (int64_t)(rec / sizeof(float)),
+                          (int64_t)(rec / sizeof(int64_t)), n_lists, nq, k_in, k_out, d_out_scores, d_out_ids, stream,
+                          "merge_topk_kernel<int64> (packed)");
 }
 
 int sskd_similarity(const float* d_q, int nq, const float* d_d, int nd, int dim, float* d_out,
@@ -2310,31 +2289,26 @@ struct ScreenWs {
 };
 
 ScreenWs screen_carve(void* base, const ScreenPlan& pl, int64_t n_rows, int nq, int k) {
-  char* p = static_cast<char*>(base);
-  auto take = [&](size_t bytes) {
-    char* r = p;
-    p += align256(bytes);
-    return static_cast<void*>(r);
-  };
+  sskd::Carver c(base);
   ScreenWs w{};
-  w.part_scores = static_cast<float*>(take(pl.part_elems * sizeof(float)));   // append form: the runs, 8 bytes per entry,
-  w.part_ids = static_cast<int*>(take(pl.part_elems * sizeof(int)));         //   span both arrays (contiguous: see below)
-  w.cand_cnt = static_cast<int*>(take((size_t)nq * pl.lists_per_query * sizeof(int)));
-  w.tau = static_cast<int*>(take((size_t)nq * 11 * sizeof(int)));
-  w.eps2 = static_cast<float*>(take((size_t)nq * sizeof(float)));
-  w.fb_count = static_cast<int*>(take(256));
+  w.part_scores = c.take<float>(pl.part_elems);   // append form: the runs, 8 bytes per entry,
+  w.part_ids = c.take<int>(pl.part_elems);        //   span both arrays (contiguous: see below)
+  w.cand_cnt = c.take<int>((size_t)nq * pl.lists_per_query);
+  w.tau = c.take<int>((size_t)nq * 11);
+  w.eps2 = c.take<float>(nq);
+  w.fb_count = c.take<int>(64);
   // the in-call exact fallback is sized for EVERY query: however many candidate bands cannot be proven
   // complete, the call answers them itself (its launches read the actual count from device memory)
-  w.fb_qid = static_cast<int*>(take((size_t)nq * sizeof(int)));
-  w.fb_queries = static_cast<float*>(take((size_t)nq * DIM * sizeof(float)));
-  w.fb_scores = static_cast<float*>(take((size_t)nq * k * sizeof(float)));
-  w.fb_ids = static_cast<int64_t*>(take((size_t)nq * k * sizeof(int64_t)));
+  w.fb_qid = c.take<int>(nq);
+  w.fb_queries = c.take<float>((size_t)nq * DIM);
+  w.fb_scores = c.take<float>((size_t)nq * k);
+  w.fb_ids = c.take<int64_t>((size_t)nq * k);
   const int tier1 = nq < SCREEN_FALLBACK_TIER1 ? nq : SCREEN_FALLBACK_TIER1;
   w.exact_bytes = sskd_index_search_workspace_bytes(n_rows, tier1, k);
-  w.exact_ws = take(w.exact_bytes);
+  w.exact_ws = c.take<char>(w.exact_bytes);
   w.exact_bytes2 = nq > tier1 ? sskd_index_search_workspace_bytes(n_rows, nq - tier1, k) : 0;
-  w.exact_ws2 = w.exact_bytes2 ? take(w.exact_bytes2) : nullptr;
-  w.bytes = (size_t)(p - static_cast<char*>(base));
+  w.exact_ws2 = w.exact_bytes2 ? c.take<char>(w.exact_bytes2) : nullptr;
+  w.bytes = c.bytes();
   return w;
 }
 }  // namespace
@@ -2399,14 +2373,13 @@ int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16
     return sskd::fail(SSKD_ERR_UNSUPPORTED,
                       "index_search_screened: needs k <= 10, nq >= 64 and >= 2048 rows (got k=%d nq=%d rows=%lld): "
                       "use sskd_index_search", k, nq, (long long)n_rows);
-  SSKD_REQUIRE(n_rows < ((int64_t)1 << 31) - 64, "index_search_screened: shard too large for int32 row ids");
+  int rc = require_shard_rows("index_search_screened", n_rows);
+  if (rc != SSKD_OK) return rc;
   SSKD_REQUIRE(d_tiled && d_bf16 && d_queries && d_out_scores && d_out_ids && d_status,
                "index_search_screened: null pointer");
-  const size_t need = sskd_index_search_screened_workspace_bytes(n_rows, nq, k);
-  if (!d_workspace || workspace_bytes < need)
-    return sskd::fail(SSKD_ERR_WORKSPACE, "index_search_screened: workspace %zu B < required %zu B", workspace_bytes, need);
-  hipStream_t st = sskd::as_stream(stream);
   const ScreenWs w = screen_carve(d_workspace, pl, n_rows, nq, k);
+  if ((rc = sskd::require_workspace("index_search_screened", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK) return rc;
+  hipStream_t st = sskd::as_stream(stream);
   const int64_t tiles = sskd::ceil_div(n_rows, TILE_ROWS);
   const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
 
@@ -2457,7 +2430,7 @@ int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16
       return sskd::fail(SSKD_ERR_HIP, "index_search_screened: screening launch failed");
   }
   if (ev_scan_end) (void)hipEventRecord(static_cast<hipEvent_t>(ev_scan_end), st);
-  int rc = sskd::check_launch("screen_append_kernel");
+  rc = sskd::check_launch("screen_append_kernel");
   if (rc != SSKD_OK) return rc;
 
   ScreenFinalAppendParams fp{};
@@ -2916,31 +2889,22 @@ struct RangeWs {
   int64_t* block_sums;
   int* rec_q;
   uint64_t* rec_key;
-  size_t head_bytes;   // counts + cursor + pool_next: zeroed by each call
-  size_t total;
+  size_t head_bytes;   // counts + cursor + pool_next, packed: zeroed by each call with one memset
+  size_t bytes;
 };
 
-RangeWs range_ws_layout(int64_t n_rows, int nq, int64_t max_results, char* base) {
+RangeWs range_carve(void* base, int64_t n_rows, int nq, int64_t max_results) {
+  sskd::Carver c(base);
   RangeWs w{};
+  w.counts = c.take<int>(nq, alignof(int));
+  w.cursor = c.take<int>(nq, alignof(int));
+  w.pool_next = c.take<unsigned long long>(1, alignof(unsigned long long));
+  w.head_bytes = c.off;
+  w.block_sums = c.take<int64_t>(sskd::ceil_div(nq, RANGE_SCAN_BLOCK));
   const int64_t cap = range_pool_cap(n_rows, nq, max_results);
-  const int64_t n_blocks = sskd::ceil_div(nq, RANGE_SCAN_BLOCK);
-  size_t o = 0;
-  w.counts = reinterpret_cast<int*>(base + o);
-  o += (size_t)nq * sizeof(int);
-  w.cursor = reinterpret_cast<int*>(base + o);
-  o += (size_t)nq * sizeof(int);
-  o = (o + 7) & ~(size_t)7;
-  w.pool_next = reinterpret_cast<unsigned long long*>(base + o);
-  o += sizeof(unsigned long long);
-  w.head_bytes = o;
-  o = align256(o);
-  w.block_sums = reinterpret_cast<int64_t*>(base + o);
-  o += align256((size_t)n_blocks * sizeof(int64_t));
-  w.rec_key = reinterpret_cast<uint64_t*>(base + o);
-  o += align256((size_t)cap * sizeof(uint64_t));
-  w.rec_q = reinterpret_cast<int*>(base + o);
-  o += align256((size_t)cap * sizeof(int));
-  w.total = o;
+  w.rec_key = c.take<uint64_t>(cap);
+  w.rec_q = c.take<int>(cap);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -2959,7 +2923,7 @@ extern "C" {
 
 size_t sskd_index_range_search_workspace_bytes(int64_t n_rows, int nq, int64_t max_results) {
   if (n_rows <= 0 || nq <= 0 || max_results < 0) return 0;
-  return range_ws_layout(n_rows, nq, max_results, nullptr).total;
+  return range_carve(nullptr, n_rows, nq, max_results).bytes;
 }
 
 int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
@@ -2971,14 +2935,14 @@ int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d
   SSKD_REQUIRE(nq >= 0, "index_range_search: nq < 0");
   SSKD_REQUIRE(max_results >= 0, "index_range_search: max_results < 0");
   SSKD_REQUIRE(d_lims, "index_range_search: null lims");
-  SSKD_REQUIRE(n_rows < ((int64_t)1 << 31) - 64, "index_range_search: shard too large for int32 row ids");
+  int rc = require_shard_rows("index_range_search", n_rows);
+  if (rc != SSKD_OK) return rc;
   const bool empty = nq == 0 || n_rows == 0;
+  const RangeWs w = range_carve(d_workspace, n_rows, nq, max_results);
   if (!empty) {
     SSKD_REQUIRE(d_tiled && d_queries && d_thresholds, "index_range_search: null pointer");
     SSKD_REQUIRE(max_results == 0 || (d_out_scores && d_out_ids), "index_range_search: null output with max_results > 0");
-    const size_t need = sskd_index_range_search_workspace_bytes(n_rows, nq, max_results);
-    if (!d_workspace || workspace_bytes < need)
-      return sskd::fail(SSKD_ERR_WORKSPACE, "index_range_search: workspace %zu B < required %zu B", workspace_bytes, need);
+    if ((rc = sskd::require_workspace("index_range_search", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK) return rc;
   }
   hipStream_t st = sskd::as_stream(stream);
   if (empty) {
@@ -2986,7 +2950,6 @@ int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d
       return sskd::fail(SSKD_ERR_HIP, "index_range_search: memset failed");
     return SSKD_OK;
   }
-  const RangeWs w = range_ws_layout(n_rows, nq, max_results, static_cast<char*>(d_workspace));
   const int64_t cap = range_pool_cap(n_rows, nq, max_results);
   if (hipMemsetAsync(d_workspace, 0, w.head_bytes, st) != hipSuccess)
     return sskd::fail(SSKD_ERR_HIP, "index_range_search: memset failed");
@@ -3014,7 +2977,7 @@ int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d
     if (d_row_mask) launch_range_scan<2, true>(pl, rp, st);
     else launch_range_scan<2, false>(pl, rp, st);
   }
-  int rc = sskd::check_launch("range_scan_kernel");
+  rc = sskd::check_launch("range_scan_kernel");
   if (rc != SSKD_OK) return rc;
 
   const int n_blocks = (int)sskd::ceil_div(nq, RANGE_SCAN_BLOCK);

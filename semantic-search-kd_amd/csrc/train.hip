@@ -20,8 +20,6 @@ using namespace sskd_generic;
 
 namespace {
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Dims {
   int B, S, H, NH, DH, F, L;
   int64_t M;
@@ -45,17 +43,9 @@ struct Saved {
 
 // carve the workspace; `layers_out` must hold cfg->layers entries (host memory)
 Saved carve(void* base, const Dims& d, LayerSaved* layers_out, bool training) {
-  char* p = static_cast<char*>(base);
-  auto take_b = [&](size_t elems) {
-    bf16_t* r = reinterpret_cast<bf16_t*>(p);
-    p += align256(elems * sizeof(bf16_t));
-    return r;
-  };
-  auto take_f = [&](size_t elems) {
-    float* r = reinterpret_cast<float*>(p);
-    p += align256(elems * sizeof(float));
-    return r;
-  };
+  sskd::Carver c(base);
+  auto take_b = [&](size_t elems) { return c.take<bf16_t>(elems); };
+  auto take_f = [&](size_t elems) { return c.take<float>(elems); };
   const size_t M = (size_t)d.M, MH = M * d.H, MF = M * d.F, PP = (size_t)d.B * d.NH * d.S * d.S;
   Saved s{};
   s.layer = layers_out;
@@ -105,7 +95,7 @@ Saved carve(void* base, const Dims& d, LayerSaved* layers_out, bool training) {
     s.tB = take_b((size_t)(d.H > d.F ? d.H : d.F) * M);
     s.t3H = take_b(3 * MH);
   }
-  s.bytes = (size_t)(p - static_cast<char*>(base));
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -563,7 +553,7 @@ static int generic_parts(const sskd_generic_config* cfg, int B, int S, int train
   return 2;
 }
 static size_t part_stride(const sskd_generic_config* cfg, int B, int S, int training) {   // bytes between the halves
-  return (workspace_one_part(cfg, B / 2, S, training) + 255) & ~(size_t)255;
+  return sskd::align256(workspace_one_part(cfg, B / 2, S, training));
 }
 
 size_t sskd_generic_workspace_bytes(const sskd_generic_config* cfg, int B, int S, int training) {
@@ -581,12 +571,9 @@ static int prepare(const sskd_generic_config* cfg, const sskd_generic_weights* w
   SSKD_REQUIRE(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b && (cfg->layers == 0 || w->layers),
                "generic encoder: null weight pointer");
   if (B == 0) return SSKD_OK;
-  const size_t need = workspace_one_part(cfg, B, S, training);
-  if (!d_workspace || workspace_bytes < need)
-    return sskd::fail(SSKD_ERR_WORKSPACE, "generic encoder: workspace %zu B < required %zu B", workspace_bytes, need);
   layers->resize((size_t)(d->L > 0 ? d->L : 1));
   *sv = carve(d_workspace, *d, layers->data(), training != 0);
-  return SSKD_OK;
+  return sskd::require_workspace("generic encoder", d_workspace, workspace_bytes, sv->bytes);
 }
 
 static int generic_forward_rows(const sskd_generic_config* cfg, const sskd_generic_weights* w, const int32_t* d_ids,
@@ -614,8 +601,7 @@ int sskd_generic_forward(const sskd_generic_config* cfg, const sskd_generic_weig
     int rc = check(cfg, w, B, S, &d);
     if (rc != SSKD_OK || B == 0) return rc;
     const size_t need = sskd_generic_workspace_bytes(cfg, B, S, training);
-    if (!d_workspace || workspace_bytes < need)
-      return sskd::fail(SSKD_ERR_WORKSPACE, "generic encoder: workspace %zu B < required %zu B", workspace_bytes, need);
+    if ((rc = sskd::require_workspace("generic encoder", d_workspace, workspace_bytes, need)) != SSKD_OK) return rc;
   }
   SSKD_REQUIRE(d_ids && d_mask && d_out, "generic_forward: null pointer");
   hipStream_t st = sskd::as_stream(stream);
@@ -671,8 +657,7 @@ int sskd_generic_backward(const sskd_generic_config* cfg, const sskd_generic_wei
     int rc = check(cfg, w, B, S, &d);
     if (rc != SSKD_OK || B == 0) return rc;
     const size_t need = sskd_generic_workspace_bytes(cfg, B, S, 1);
-    if (!d_workspace || workspace_bytes < need)
-      return sskd::fail(SSKD_ERR_WORKSPACE, "generic encoder: workspace %zu B < required %zu B", workspace_bytes, need);
+    if ((rc = sskd::require_workspace("generic encoder", d_workspace, workspace_bytes, need)) != SSKD_OK) return rc;
   }
   hipStream_t st = sskd::as_stream(stream);
   const int parts = generic_parts(cfg, B, S, 1);
@@ -720,8 +705,7 @@ int sskd_teacher_score(const sskd_generic_config* cfg, const sskd_generic_weight
     int rc = check(cfg, w, B, S, &d);
     if (rc != SSKD_OK || B == 0) return rc;
     const size_t need = sskd_teacher_workspace_bytes(cfg, B, S);
-    if (!d_workspace || workspace_bytes < need)
-      return sskd::fail(SSKD_ERR_WORKSPACE, "teacher_score: workspace %zu B < required %zu B", workspace_bytes, need);
+    if ((rc = sskd::require_workspace("teacher_score", d_workspace, workspace_bytes, need)) != SSKD_OK) return rc;
   }
   SSKD_REQUIRE(d_head_dense_w && d_head_dense_b && d_head_out_w && d_head_out_b && d_ids && d_mask && d_logits,
                "teacher_score: null pointer");

@@ -396,22 +396,36 @@ class FAISSIndexBuilder:
         mask = self._effective_mask(allow)
         return self._search_device_masked(queries, k, normalize_queries, out_scores, out_ids, mask)
 
+    def _prepare_queries(self, queries: torch.Tensor, normalize_queries: Optional[bool], who: str) -> torch.Tensor:
+        """Checks ``[nq, dim]`` float32 device queries and returns them contiguous; normalised (in a copy) when
+        ``normalize_queries`` is true, or is None and the metric is cosine."""
+        if queries.dim() != 2 or queries.shape[1] != self.embedding_dim:
+            raise ValueError(f"expected [nq, {self.embedding_dim}] queries, got {tuple(queries.shape)}")
+        if queries.dtype != torch.float32 or not queries.is_cuda:
+            raise TypeError(f"{who} expects a float32 device tensor")
+        q = queries.contiguous()
+        if normalize_queries is None:
+            normalize_queries = self.metric == "cosine"
+        if normalize_queries and q.shape[0]:
+            q = q.clone()
+            _native.check(_native.load().sskd_l2_normalize_rows(q.data_ptr(), q.shape[0], self.embedding_dim,
+                                                                _stream(self.device)))
+        return q
+
+    def _workspace_for(self, need: int) -> torch.Tensor:
+        """The shared search workspace, grown to at least ``need`` bytes."""
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        return self._workspace
+
     def _search_device_masked(self, queries, k, normalize_queries, out_scores, out_ids, mask):
         lib = _native.load()
         if k < 1 or k > _native.SSKD_K_MAX:
             raise ValueError(f"k={k} outside [1, {_native.SSKD_K_MAX}]")
-        if queries.dim() != 2 or queries.shape[1] != self.embedding_dim:
-            raise ValueError(f"expected [nq, {self.embedding_dim}] queries, got {tuple(queries.shape)}")
-        if queries.dtype != torch.float32 or not queries.is_cuda:
-            raise TypeError("search_device expects a float32 device tensor")
-        q = queries.contiguous()
+        q = self._prepare_queries(queries, normalize_queries, "search_device")
         nq = q.shape[0]
-        if normalize_queries is None:
-            normalize_queries = self.metric == "cosine"
         stream = _stream(self.device)
-        if normalize_queries and nq:
-            q = q.clone()
-            _native.check(lib.sskd_l2_normalize_rows(q.data_ptr(), nq, self.embedding_dim, stream))
+        mask_ptr = None if mask is None else mask.data_ptr()
         if out_scores is None:
             out_scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         if out_ids is None:
@@ -427,57 +441,24 @@ class FAISSIndexBuilder:
                     self._bf16 = torch.empty(int(lib.sskd_index_bf16_bytes(self._n)), dtype=torch.uint8, device=self.device)
                     _native.check(lib.sskd_index_make_bf16(self._tiled.data_ptr(), self._n, self._bf16.data_ptr(), stream))
                     self._bf16_rows = self._n
-                if self._workspace is None or self._workspace.numel() < need:
-                    self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+                ws = self._workspace_for(need)
                 self.last_status = torch.empty(2, dtype=torch.int32, device=self.device)
-                if mask is None:
-                    _native.check(
-                        lib.sskd_index_search_screened(
-                            self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
-                            out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
-                            self._workspace.data_ptr(), self._workspace.numel(), stream, None, None,
-                        )
+                _native.check(
+                    lib.sskd_index_search_screened_filtered(
+                        self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                        mask_ptr, out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
+                        ws.data_ptr(), ws.numel(), stream, None, None,
                     )
-                else:
-                    _native.check(
-                        lib.sskd_index_search_screened_filtered(
-                            self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
-                            mask.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
-                            self._workspace.data_ptr(), self._workspace.numel(), stream, None, None,
-                        )
-                    )
+                )
                 return out_scores, out_ids
         self.last_status = None
-        need = int(lib.sskd_index_search_workspace_bytes_ex(self._n, nq, k, tuning))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        if mask is None:
-            _native.check(
-                lib.sskd_index_search_ex(
-                    0 if self._tiled is None else self._tiled.data_ptr(),
-                    self._n,
-                    q.data_ptr(),
-                    nq,
-                    k,
-                    self.id_offset,
-                    out_scores.data_ptr(),
-                    out_ids.data_ptr(),
-                    self._workspace.data_ptr(),
-                    self._workspace.numel(),
-                    stream,
-                    tuning,
-                    None,
-                    None,
-                )
+        ws = self._workspace_for(int(lib.sskd_index_search_workspace_bytes_ex(self._n, nq, k, tuning)))
+        _native.check(
+            lib.sskd_index_search_filtered(
+                0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                mask_ptr, out_scores.data_ptr(), out_ids.data_ptr(), ws.data_ptr(), ws.numel(), stream, tuning, None, None,
             )
-        else:
-            _native.check(
-                lib.sskd_index_search_filtered(
-                    0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
-                    mask.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr(), self._workspace.data_ptr(),
-                    self._workspace.numel(), stream, tuning, None, None,
-                )
-            )
+        )
         return out_scores, out_ids
 
     # the online shape: a handful of queries (sskd_amd.h, one-pass variant).  With a single query
@@ -489,41 +470,23 @@ class FAISSIndexBuilder:
     def _search_onepass_device(self, q: torch.Tensor, k: int, normalize_queries: bool, mask=None):
         """One corpus pass + proof of exactness; returns ``(scores, ids, inexact_flag)`` device tensors."""
         lib = _native.load()
-        stream = _stream(self.device)
+        q = self._prepare_queries(q, normalize_queries, "search_device")
         nq = q.shape[0]
-        if normalize_queries:
-            q = q.clone()
-            _native.check(lib.sskd_l2_normalize_rows(q.data_ptr(), nq, self.embedding_dim, stream))
         out_scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         out_ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         flag = torch.empty(1, dtype=torch.int32, device=self.device)
-        need = int(lib.sskd_index_search_onepass_workspace_bytes(self._n, nq, k))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        if mask is None:
-            _native.check(
-                lib.sskd_index_search_onepass(
-                    self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
-                    out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
-                    self._workspace.data_ptr(), self._workspace.numel(), stream,
-                )
+        ws = self._workspace_for(int(lib.sskd_index_search_onepass_workspace_bytes(self._n, nq, k)))
+        _native.check(
+            lib.sskd_index_search_onepass_filtered(
+                self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                None if mask is None else mask.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream(self.device),
             )
-        else:
-            _native.check(
-                lib.sskd_index_search_onepass_filtered(
-                    self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset, mask.data_ptr(),
-                    out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
-                    self._workspace.data_ptr(), self._workspace.numel(), stream,
-                )
-            )
+        )
         return out_scores, out_ids, flag
 
     def _search_numpy(self, query_emb, k: int, normalize_queries: Optional[bool], allow=None) -> Tuple[np.ndarray, np.ndarray]:
-        _native.require_gpu()
-        q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
-        if q.ndim == 1:
-            q = q[None, :]
-        qd = torch.from_numpy(q).to(self.device)
+        qd = _host_queries_to_device(query_emb, self.device)
         with torch.cuda.device(self.device):
             mask = self._effective_mask(allow)
             nq = qd.shape[0]
@@ -559,15 +522,13 @@ class FAISSIndexBuilder:
     def _range_call(self, q: torch.Tensor, thr: torch.Tensor, mask, lims: torch.Tensor, scores, ids, max_results: int):
         lib = _native.load()
         nq = q.shape[0]
-        need = int(lib.sskd_index_range_search_workspace_bytes(self._n, nq, max_results))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        ws = self._workspace_for(int(lib.sskd_index_range_search_workspace_bytes(self._n, nq, max_results)))
         _native.check(
             lib.sskd_index_range_search(
                 0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, thr.data_ptr(),
                 self.id_offset, None if mask is None else mask.data_ptr(), lims.data_ptr(),
                 None if scores is None else scores.data_ptr(), None if ids is None else ids.data_ptr(), max_results,
-                self._workspace.data_ptr(), self._workspace.numel(), _stream(self.device),
+                ws.data_ptr(), ws.numel(), _stream(self.device),
             )
         )
 
@@ -590,19 +551,8 @@ class FAISSIndexBuilder:
         hold the results only if ``lims[-1] <= max_results``, which the caller checks (``lims`` is always exact).
         Without it the call synchronises once to read ``lims[-1]``, calls again if the reused result buffer was too
         small (grown to exactly the total), and returns tensors of exactly ``lims[-1]`` entries."""
-        if queries.dim() != 2 or queries.shape[1] != self.embedding_dim:
-            raise ValueError(f"expected [nq, {self.embedding_dim}] queries, got {tuple(queries.shape)}")
-        if queries.dtype != torch.float32 or not queries.is_cuda:
-            raise TypeError("range_search_device expects a float32 device tensor")
-        lib = _native.load()
-        q = queries.contiguous()
+        q = self._prepare_queries(queries, normalize_queries, "range_search_device")
         nq = q.shape[0]
-        if normalize_queries is None:
-            normalize_queries = self.metric == "cosine"
-        stream = _stream(self.device)
-        if normalize_queries and nq:
-            q = q.clone()
-            _native.check(lib.sskd_l2_normalize_rows(q.data_ptr(), nq, self.embedding_dim, stream))
         if isinstance(threshold, torch.Tensor) and threshold.is_cuda:
             thr = threshold.reshape(-1).to(torch.float32)
             if thr.numel() == 1 and nq != 1:
@@ -640,12 +590,8 @@ class FAISSIndexBuilder:
         return lims, self._range_scores[:total].clone(), self._range_ids[:total].clone()
 
     def _range_numpy(self, query_emb, threshold, normalize_queries: Optional[bool], allow=None):
-        _native.require_gpu()
-        q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
-        if q.ndim == 1:
-            q = q[None, :]
-        thr = range_thresholds(threshold, q.shape[0])
-        qd = torch.from_numpy(q).to(self.device)
+        qd = _host_queries_to_device(query_emb, self.device)
+        thr = range_thresholds(threshold, qd.shape[0])
         with torch.cuda.device(self.device):
             lims, scores, ids = self.range_search_device(
                 qd, torch.from_numpy(thr).to(self.device), allow=allow, normalize_queries=normalize_queries
@@ -845,6 +791,15 @@ def _resolve_device(device: Optional[str]) -> torch.device:
 
 def _stream(device: torch.device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _host_queries_to_device(query_emb, device: torch.device) -> torch.Tensor:
+    """Host queries (``[dim]`` or ``[nq, dim]``) as a contiguous float32 ``[nq, dim]`` device tensor."""
+    _native.require_gpu()
+    q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
+    if q.ndim == 1:
+        q = q[None, :]
+    return torch.from_numpy(q).to(device)
 
 
 def _as_device_f32(x: Union[np.ndarray, torch.Tensor], device: torch.device) -> torch.Tensor:
