@@ -43,18 +43,16 @@ constexpr int GROUPS = STEPS / GROUP;         // 6 (even: groups alternate A/B)
 constexpr int STEP_FLOATS = 8;                // a k-step = the next 8 columns of the lane's row
 // float4 index, inside a 32-row tile, of chunk c (columns 4c .. 4c + 3) of row r
 __host__ __device__ inline int tile_idx4(int r, int c) { return r * (DIM / 4) + c; }
+// D layout of both 32x32 MFMAs: accumulator register r of lane l holds column l & 31 and row acc_row(r) + 4 (l >> 5)
+__host__ __device__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
 
 // ------------------------------------------------------------------------- //
 // index add / get / normalise
 // ------------------------------------------------------------------------- //
 
-// sum of squares of one row held as 96 float4 over the lanes of one wave
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ inline int wave_sum_int(int v) {
+// sum over the lanes of one wave
+template <typename T>
+__device__ inline T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
@@ -147,8 +145,28 @@ __device__ inline int eff_nq(int nq_host, const int* nq_dev) {
 }
 
 // strict "a ranks before b": higher score first, then lower id
-__device__ inline bool ranks_before(float sa, int ia, float sb, int ib) {
+template <typename I>
+__device__ inline bool ranks_before(float sa, I ia, float sb, I ib) {
   return sa > sb || (sa == sb && ia < ib);
+}
+
+// wave-wide arg-best in rank order (higher score, then lower id); i < 0 = nothing
+template <typename I>
+__device__ inline void wave_argbest(float& s, I& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float os = __shfl_xor(s, o);
+    const I oi = __shfl_xor(i, o);
+    if (oi >= 0 && (i < 0 || ranks_before(os, oi, s, i))) { s = os; i = oi; }
+  }
+}
+
+// one candidate (v, id) of a selection round: it becomes the lane's best (s, i) when it ranks strictly after the last
+// selected entry (bs, bi) - if there is one - and before the best so far
+template <typename I>
+__device__ inline void pick_after(float& s, I& i, float v, I id, bool have, float bs, I bi) {
+  if (have && !ranks_before(bs, bi, v, id)) return;
+  if (i < 0 || ranks_before(v, id, s, i)) { s = v; i = id; }
 }
 
 // Shared threshold.  Every per-lane list that is full holds K distinct rows scoring >= its K-th
@@ -208,6 +226,25 @@ __device__ inline bool pool_offer(int* __restrict__ slots, int* __restrict__ thr
   return false;  // lost the race four times: the pool just stays a little looser
 }
 
+// bucket xid % K of query q: fire-and-forget atomicMax of a row the workgroup pool accepted
+template <int K>
+__device__ __forceinline__ void bucket_forward(int* __restrict__ gpool, int q, int xid, int xi) {
+  (void)__hip_atomic_fetch_max(gpool + (int64_t)q * K + xid % K, xi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Bound exchange of query q: the minimum of its K global buckets (agent scope) and the workgroup's own bound w are
+// published to tau; returns the fresh ordered bound (the larger of tau's old value and the buckets' minimum).
+template <int K>
+__device__ __forceinline__ int exchange_bound(const int* __restrict__ gpool, int* tau_q, int q, int w) {
+  const int* gb = gpool + (int64_t)q * K;
+  int bmin = __hip_atomic_load(&gb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+  for (int i = 1; i < K; ++i)
+    bmin = min(bmin, __hip_atomic_load(&gb[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const int old = atomicMax(tau_q, max(w, bmin));
+  return max(old, bmin);
+}
+
 #ifdef SSKD_PROBE
 // diagnostic build only (tools/scan_probe.hip): [0] tiles, [1] slow-path entries, [2] per-register
 // insertion blocks executed, [3] lane insertions, [4] threshold publications
@@ -260,7 +297,7 @@ __device__ inline void apply_tile_mask(f32x16 (&acc)[QB], uint32_t word, int h) 
   const uint32_t lw = word >> (4 * h);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const bool off = ((lw >> ((r & 3) + 8 * (r >> 2))) & 1u) == 0u;
+    const bool off = ((lw >> acc_row(r)) & 1u) == 0u;
 #pragma unroll
     for (int qq = 0; qq < QB; ++qq)
       if (off) acc[qq][r] = -INFINITY;
@@ -294,6 +331,49 @@ __device__ inline void compute_group(const float4 (&a)[GROUP], const float4* __r
   }
 }
 
+// The fp32 tile pipeline of one wave: a tile's six groups of k-steps alternate between two register buffers, and the
+// first group of the wave's next tile loads while the last group is multiplied.
+struct F32TilePipe {
+  float4 a[GROUP], b[GROUP];
+  // the first group of the wave's first tile
+  __device__ __forceinline__ void start(const float* __restrict__ tile) { load_group(a, tile); }
+  // acc = the tile's scores (a holds its first group); more: prefetch the first group of the tile WAVES further
+  template <int QB, int WAVES>
+  __device__ __forceinline__ void score(f32x16 (&acc)[QB], const float* __restrict__ tile,
+                                        const float4* __restrict__ qlane, bool more) {
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
+
+    load_group(b, tile + 1 * GROUP * STEP_FLOATS);
+    compute_group<QB, 0>(a, qlane, acc);
+    load_group(a, tile + 2 * GROUP * STEP_FLOATS);
+    compute_group<QB, 1>(b, qlane, acc);
+    load_group(b, tile + 3 * GROUP * STEP_FLOATS);
+    compute_group<QB, 2>(a, qlane, acc);
+    load_group(a, tile + 4 * GROUP * STEP_FLOATS);
+    compute_group<QB, 3>(b, qlane, acc);
+    load_group(b, tile + 5 * GROUP * STEP_FLOATS);
+    compute_group<QB, 4>(a, qlane, acc);
+    if (more) load_group(a, tile + (int64_t)WAVES * TILE_FLOATS);
+    compute_group<QB, 5>(b, qlane, acc);
+  }
+};
+
+// stage the block of 32 QB queries from q0 in LDS in B-operand order (zero rows past nq): qs[QB][96 chunks][32 queries]
+template <int QB, int WAVES>
+__device__ __forceinline__ void stage_queries_f32(float4* __restrict__ qs, const float* __restrict__ queries, int q0, int nq) {
+  for (int idx = threadIdx.x; idx < QB * 32 * CHUNKS; idx += WAVES * 64) {
+    const int c = idx % CHUNKS, jj = idx / CHUNKS;
+    const int q = q0 + jj;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q < nq) v = reinterpret_cast<const float4*>(queries)[(int64_t)q * CHUNKS + c];
+    qs[((jj >> 5) * CHUNKS + c) * 32 + (jj & 31)] = v;
+  }
+  __syncthreads();
+}
+
 // POOLS = false: plain per-lane lists, no shared bound - then the ONLY reason a row is missing from
 // a query's candidates is that its own list was full of better rows, which is what the one-pass
 // search for k > K relies on (sskd_index_search_onepass).
@@ -313,15 +393,7 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
   const int nq = eff_nq(p.nq, p.nq_dev);
   if (q0 >= nq) return;  // (workgroup-uniform)
 
-  // stage the query block in B-operand order (zero rows past nq)
-  for (int idx = tid; idx < QB * 32 * CHUNKS; idx += WAVES * 64) {
-    const int c = idx % CHUNKS, jj = idx / CHUNKS;
-    const int q = q0 + jj;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q < nq) v = reinterpret_cast<const float4*>(p.queries)[(int64_t)q * CHUNKS + c];
-    qs[((jj >> 5) * CHUNKS + c) * 32 + (jj & 31)] = v;
-  }
-  __syncthreads();
+  stage_queries_f32<QB, WAVES>(qs, p.queries, q0, nq);
   const float4* qlane = qs + h * 32 + j;
 
   // workgroup pool: [QB * 32 queries][K slots] + one cached minimum per query, behind the query block
@@ -356,9 +428,9 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
   const float* lane_base = p.tiled + (lane & 31) * DIM + 4 * (lane >> 5);   // row (lane & 31) of a tile, column half lane >> 5
   const bool ragged = (p.n_rows & 31) != 0;
 
-  float4 bufA[GROUP], bufB[GROUP];
+  F32TilePipe pipe;
   int t = t_begin + wave;
-  if (t < t_end) load_group(bufA, lane_base + (int64_t)t * TILE_FLOATS);
+  if (t < t_end) pipe.start(lane_base + (int64_t)t * TILE_FLOATS);
 
   int tiles_done = 0;
   for (; t < t_end; t += WAVES, ++tiles_done) {
@@ -373,43 +445,19 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
     for (int qq = 0; POOLS && qq < QB; ++qq) {
       const int w = wthr[qq * 32 + j];
       gthr[qq] = fmaxf(gthr[qq], ordered_to_float(w));
-      if (exchange && real[qq]) {
-        const int* gb = p.gpool + (int64_t)(q0 + qq * 32 + j) * K;
-        int bmin = __hip_atomic_load(&gb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int i = 1; i < K; ++i)
-          bmin = min(bmin, __hip_atomic_load(&gb[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        const int old = atomicMax(tau_q[qq], max(w, bmin));
-        gthr[qq] = fmaxf(gthr[qq], ordered_to_float(max(old, bmin)));
-      }
+      if (exchange && real[qq])
+        gthr[qq] = fmaxf(gthr[qq], ordered_to_float(exchange_bound<K>(p.gpool, tau_q[qq], q0 + qq * 32 + j, w)));
     }
     f32x16 acc[QB];
-#pragma unroll
-    for (int qq = 0; qq < QB; ++qq)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
-
-    load_group(bufB, tile + 1 * GROUP * STEP_FLOATS);
-    compute_group<QB, 0>(bufA, qlane, acc);
-    load_group(bufA, tile + 2 * GROUP * STEP_FLOATS);
-    compute_group<QB, 1>(bufB, qlane, acc);
-    load_group(bufB, tile + 3 * GROUP * STEP_FLOATS);
-    compute_group<QB, 2>(bufA, qlane, acc);
-    load_group(bufA, tile + 4 * GROUP * STEP_FLOATS);
-    compute_group<QB, 3>(bufB, qlane, acc);
-    load_group(bufB, tile + 5 * GROUP * STEP_FLOATS);
-    compute_group<QB, 4>(bufA, qlane, acc);
-    if (t + WAVES < t_end) load_group(bufA, tile + (int64_t)WAVES * TILE_FLOATS);
-    compute_group<QB, 5>(bufB, qlane, acc);
-
-    // D layout of the 32x32 MFMA: column = lane & 31 (query), row = (r&3) + 8(r>>2) + 4h
+    pipe.score<QB, WAVES>(acc, tile, qlane, t + WAVES < t_end);
+    // D layout of the 32x32 MFMA: column = lane & 31 (query), row = acc_row(r) + 4h
     const int rowbase = t * TILE_ROWS + 4 * h;
     if (ragged && t == p.n_tiles - 1) {
 #pragma unroll
       for (int qq = 0; qq < QB; ++qq)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (rowbase + (r & 3) + 8 * (r >> 2) >= p.n_rows) acc[qq][r] = -INFINITY;
+          if (rowbase + acc_row(r) >= p.n_rows) acc[qq][r] = -INFINITY;
     }
     if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
 #pragma unroll
@@ -424,7 +472,7 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float x = acc[qq][r];
-          const int xid = rowbase + (r & 3) + 8 * (r >> 2);
+          const int xid = rowbase + acc_row(r);
           bool take = x > list[qq].s[K - 1] && x >= gthr[qq];
           if (HAS_UB) take = take && ranks_before(ub_s[qq], ub_i[qq], x, xid);
           if (__any(take)) {
@@ -437,8 +485,7 @@ __global__ __launch_bounds__(WAVES * 64) void scan_topk_kernel(ScanParams p) {
               if (POOLS && tiles_done > 0) {
                 const int xi = float_to_ordered(x);
                 if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && real[qq])
-                  (void)__hip_atomic_fetch_max(p.gpool + (int64_t)(q0 + qq * 32 + j) * K + xid % K, xi,
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
               }
               grew = true;
             }
@@ -517,20 +564,9 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(MergeParams<IdT> p) {
       const int l = c / p.k_in, e = c - l * p.k_in;
       const long long ci = (long long)id[(int64_t)l * p.id_list_stride + e];
       if (ci < 0) continue;
-      const float cs = sc[(int64_t)l * p.list_stride + e];
-      // strictly after the bound in rank order
-      if (have_bound && !(cs < bs || (cs == bs && ci > bi))) continue;
-      if (best_i < 0 || cs > best_s || (cs == best_s && ci < best_i)) { best_s = cs; best_i = ci; }
+      pick_after(best_s, best_i, sc[(int64_t)l * p.list_stride + e], ci, have_bound, bs, bi);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float os = __shfl_xor(best_s, o);
-      const long long oi = __shfl_xor(best_i, o);
-      if (oi >= 0 && (best_i < 0 || os > best_s || (os == best_s && oi < best_i))) {
-        best_s = os;
-        best_i = oi;
-      }
-    }
+    wave_argbest(best_s, best_i);
     if (lane == 0) {
       const int64_t o = (int64_t)q * p.out_stride + p.out_off + r;
       p.out_scores[o] = best_i >= 0 ? best_s : -FLT_MAX;
@@ -610,19 +646,11 @@ __global__ __launch_bounds__(256) void reduce_lists_kernel(ReduceParams p) {
     int best_i = -1;
 #pragma unroll
     for (int j = 0; j < REDUCE_CPL; ++j)
-      if (ci[j] >= 0 && (best_i < 0 || cs[j] > best_s || (cs[j] == best_s && ci[j] < best_i))) {
+      if (ci[j] >= 0 && (best_i < 0 || ranks_before(cs[j], ci[j], best_s, best_i))) {
         best_s = cs[j];
         best_i = ci[j];
       }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float os = __shfl_xor(best_s, o);
-      const int oi = __shfl_xor(best_i, o);
-      if (oi >= 0 && (best_i < 0 || os > best_s || (os == best_s && oi < best_i))) {
-        best_s = os;
-        best_i = oi;
-      }
-    }
+    wave_argbest(best_s, best_i);
     if (lane == 0) {
       p.out_scores[ob + r] = best_i >= 0 ? best_s : -FLT_MAX;
       p.out_ids[ob + r] = best_i;
@@ -666,12 +694,7 @@ __global__ __launch_bounds__(256) void last_entry_bound_kernel(BoundParams p) {
     const float cs = p.scores[base + (int64_t)l * p.k];
     if (bi < 0 || ranks_before(cs, ci, bs, bi)) { bs = cs; bi = ci; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float os = __shfl_xor(bs, o);
-    const int oi = __shfl_xor(bi, o);
-    if (oi >= 0 && (bi < 0 || ranks_before(os, oi, bs, bi))) { bs = os; bi = oi; }
-  }
+  wave_argbest(bs, bi);
   if (lane == 0) {
     p.bound_s[q] = bs;
     p.bound_i[q] = bi;
@@ -705,7 +728,7 @@ __global__ __launch_bounds__(256) void finalize_onepass_kernel(FinalizeParams p)
       const int64_t o = (int64_t)q * p.k + (p.k - 1);
       const int ci = p.ids[o];
       const float cs = p.scores[o], bs = p.bound_s[q];
-      const bool proven = ci >= 0 && (cs > bs || (cs == bs && ci <= bi));
+      const bool proven = ci >= 0 && !ranks_before(bs, bi, cs, ci);   // at or before E
       if (!proven) atomicExch(p.inexact, 1);
     }
   }
@@ -768,8 +791,7 @@ __global__ __launch_bounds__(1024) void row_mask_count_kernel(const uint32_t* __
     if (i == n_words - 1 && (n_rows & 31)) v &= (1u << (n_rows & 31)) - 1u;
     c += __popc(v);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -807,7 +829,7 @@ __global__ __launch_bounds__(64) void similarity_kernel(const float* __restrict_
   if (qi < nq) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int di = d0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int di = d0 + acc_row(r) + 4 * h;
       if (di < nd) out[(int64_t)qi * nd + di] = acc[r];
     }
   }
@@ -1035,16 +1057,6 @@ __device__ inline void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const sbf16x8*
   }
 }
 
-// wave-wide arg-best in rank order (higher score, then lower id); i < 0 = nothing
-__device__ inline void wave_argbest(float& s, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float os = __shfl_xor(s, o);
-    const int oi = __shfl_xor(i, o);
-    if (oi >= 0 && (i < 0 || ranks_before(os, oi, s, i))) { s = os; i = oi; }
-  }
-}
-
 // ------------------------------------------------------------------------- //
 // The screening kernel.  Structure of scan_topk_kernel (query block of 128 in LDS as B fragments, every wave streams
 // its own corpus tiles through a register ring, shared pruning pools) on bf16 operands, with one difference: no
@@ -1143,15 +1155,9 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     for (int qq = 0; qq < QB; ++qq) {
       const int w = wthr[qq * 32 + j];
       gthr[qq] = fmaxf(gthr[qq], ordered_to_float(w) - band[qq]);
-      if (exchange && real[qq]) {
-        const int* gb = p.gpool + (int64_t)(q0 + qq * 32 + j) * K;
-        int bmin = __hip_atomic_load(&gb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int i = 1; i < K; ++i)
-          bmin = min(bmin, __hip_atomic_load(&gb[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        const int old = atomicMax(p.tau + q0 + qq * 32 + j, max(w, bmin));
-        gthr[qq] = fmaxf(gthr[qq], ordered_to_float(max(old, bmin)) - band[qq]);
-      }
+      if (exchange && real[qq])
+        gthr[qq] = fmaxf(gthr[qq],
+                         ordered_to_float(exchange_bound<K>(p.gpool, p.tau + q0 + qq * 32 + j, q0 + qq * 32 + j, w)) - band[qq]);
     }
     f32x16 acc[QB];
 #pragma unroll
@@ -1167,7 +1173,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
       for (int qq = 0; qq < QB; ++qq)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (rowbase + (r & 3) + 8 * (r >> 2) >= p.n_rows) acc[qq][r] = -INFINITY;
+          if (rowbase + acc_row(r) >= p.n_rows) acc[qq][r] = -INFINITY;
     }
     if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
 #ifdef SSKD_SCREEN_ABL_NOLIST  // timing ablation: no candidate / pool maintenance (accumulators kept alive)
@@ -1188,11 +1194,10 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
         if (real[qq] && m >= gthr[qq]) {
           int xid = rowbase;
 #pragma unroll
-          for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + (r & 3) + 8 * (r >> 2) : xid;
+          for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
           const int xi = float_to_ordered(m);
           if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi))
-            (void)__hip_atomic_fetch_max(p.gpool + (int64_t)(q0 + qq * 32 + j) * K + xid % K, xi, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
+            bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
           gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
         }
       } else
@@ -1214,7 +1219,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float x = acc[qq][r];
-          const int xid = rowbase + (r & 3) + 8 * (r >> 2);
+          const int xid = rowbase + acc_row(r);
           const bool take = real[qq] && x >= gthr[qq];   // (padding queries own no run)
           {   // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
             if (take) {
@@ -1227,8 +1232,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
               if (!LIGHT && tiles_done > 0) {
                 const int xi = float_to_ordered(x);
                 if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && real[qq])
-                  (void)__hip_atomic_fetch_max(p.gpool + (int64_t)(q0 + qq * 32 + j) * K + xid % K, xi,
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
               }
               grew = true;
             }
@@ -1241,11 +1245,10 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
             // much cheaper: worth it while a slice is short (125 k-row shard -6 %, 60 k -12 %; 1 M rows +1 %, 8.8 M +3 %)
             int xid = rowbase;
 #pragma unroll
-            for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + (r & 3) + 8 * (r >> 2) : xid;
+            for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
             const int xi = float_to_ordered(m);
             if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && tiles_done > 0)
-              (void)__hip_atomic_fetch_max(p.gpool + (int64_t)(q0 + qq * 32 + j) * K + xid % K, xi, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
+              bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
           } else {
             // first tile: every workgroup starts at the same instant - offer only the lane's best row
             if (tiles_done == 0) pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, float_to_ordered(m));
@@ -1391,7 +1394,7 @@ __global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalA
     const int l = l0 + lane;
     const int c = l < p.lists ? p.cand_cnt[(int64_t)q * p.lists + l] : 0;
     if (c > SCREEN_CAP) bad = true;
-    total += wave_sum_int(min(c, SCREEN_CAP));
+    total += wave_sum(min(c, SCREEN_CAP));
   }
   int M = 0;
   float tau;
@@ -1429,10 +1432,7 @@ __global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalA
       float s = -INFINITY;
       int i = -1;
       for (int e = lane; e < L; e += 64) {
-        const int id = ei[e];
-        const float v = es[e];
-        if (have && !ranks_before(bs, bi, v, id)) continue;
-        if (i < 0 || ranks_before(v, id, s, i)) { s = v; i = id; }
+        pick_after(s, i, es[e], ei[e], have, bs, bi);
       }
       wave_argbest(s, i);
       if (i < 0) break;
@@ -1493,10 +1493,7 @@ __global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalA
       int i = -1;
       for (int e = lane; e < 640; e += 64) {
         const int id = ei[e];
-        if (id < 0) continue;
-        const float v = es[e];
-        if (have && !ranks_before(bs, bi, v, id)) continue;
-        if (i < 0 || ranks_before(v, id, s, i)) { s = v; i = id; }
+        if (id >= 0) pick_after(s, i, es[e], id, have, bs, bi);
       }
       wave_argbest(s, i);
       if (i < 0) break;
@@ -1570,9 +1567,7 @@ __global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalA
     int i = -1;
 #pragma unroll
     for (int c = 0; c < SCREEN_MAX_CAND / 64; ++c) {
-      if (cid[c] < 0) continue;
-      if (have && !ranks_before(bs, bi, cs[c], cid[c])) continue;
-      if (i < 0 || ranks_before(cs[c], cid[c], s, i)) { s = cs[c]; i = cid[c]; }
+      if (cid[c] >= 0) pick_after(s, i, cs[c], cid[c], have, bs, bi);
     }
     wave_argbest(s, i);
     if (lane == 0) {
@@ -2540,14 +2535,7 @@ __global__ __launch_bounds__(WAVES * 64) void range_scan_kernel(RangeParams p) {
   const int nq = p.nq;
   if (q0 >= nq) return;  // (workgroup-uniform)
 
-  for (int idx = tid; idx < QB * 32 * CHUNKS; idx += WAVES * 64) {
-    const int c = idx % CHUNKS, jj = idx / CHUNKS;
-    const int q = q0 + jj;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q < nq) v = reinterpret_cast<const float4*>(p.queries)[(int64_t)q * CHUNKS + c];
-    qs[((jj >> 5) * CHUNKS + c) * 32 + (jj & 31)] = v;
-  }
-  __syncthreads();
+  stage_queries_f32<QB, WAVES>(qs, p.queries, q0, nq);
   const float4* qlane = qs + h * 32 + j;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -2568,40 +2556,23 @@ __global__ __launch_bounds__(WAVES * 64) void range_scan_kernel(RangeParams p) {
   const float* lane_base = p.tiled + (lane & 31) * DIM + 4 * (lane >> 5);
   const bool ragged = (p.n_rows & 31) != 0;
 
-  float4 bufA[GROUP], bufB[GROUP];
+  F32TilePipe pipe;
   int t = t_begin + wave;
-  if (t < t_end) load_group(bufA, lane_base + (int64_t)t * TILE_FLOATS);
+  if (t < t_end) pipe.start(lane_base + (int64_t)t * TILE_FLOATS);
 
   for (; t < t_end; t += WAVES) {
     const float* tile = lane_base + (int64_t)t * TILE_FLOATS;
     uint32_t mword = 0xFFFFFFFFu;
     if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);
     f32x16 acc[QB];
-#pragma unroll
-    for (int qq = 0; qq < QB; ++qq)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
-
-    load_group(bufB, tile + 1 * GROUP * STEP_FLOATS);
-    compute_group<QB, 0>(bufA, qlane, acc);
-    load_group(bufA, tile + 2 * GROUP * STEP_FLOATS);
-    compute_group<QB, 1>(bufB, qlane, acc);
-    load_group(bufB, tile + 3 * GROUP * STEP_FLOATS);
-    compute_group<QB, 2>(bufA, qlane, acc);
-    load_group(bufA, tile + 4 * GROUP * STEP_FLOATS);
-    compute_group<QB, 3>(bufB, qlane, acc);
-    load_group(bufB, tile + 5 * GROUP * STEP_FLOATS);
-    compute_group<QB, 4>(bufA, qlane, acc);
-    if (t + WAVES < t_end) load_group(bufA, tile + (int64_t)WAVES * TILE_FLOATS);
-    compute_group<QB, 5>(bufB, qlane, acc);
-
+    pipe.score<QB, WAVES>(acc, tile, qlane, t + WAVES < t_end);
     const int rowbase = t * TILE_ROWS + 4 * h;
     if (ragged && t == p.n_tiles - 1) {
 #pragma unroll
       for (int qq = 0; qq < QB; ++qq)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (rowbase + (r & 3) + 8 * (r >> 2) >= p.n_rows) acc[qq][r] = -INFINITY;
+          if (rowbase + acc_row(r) >= p.n_rows) acc[qq][r] = -INFINITY;
     }
     if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
 #pragma unroll
@@ -2634,7 +2605,7 @@ __global__ __launch_bounds__(WAVES * 64) void range_scan_kernel(RangeParams p) {
           const int64_t slot = o < old_take ? cur + o : fresh + (o - old_take);
           if (slot < p.pool_cap) {
             p.rec_q[slot] = q;
-            p.rec_key[slot] = range_key(acc[qq][r], rowbase + (r & 3) + 8 * (r >> 2));
+            p.rec_key[slot] = range_key(acc[qq][r], rowbase + acc_row(r));
           }
         }
         off += __popcll(b);
