@@ -3,6 +3,11 @@
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line on rank 0.
 ``--dump-outputs DIR`` also writes the search outputs of the last timed step to ``DIR/*.npy`` (see dump_outputs).
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps (the roofline comes from HIP
+events recorded inside those steps), the dump and the line.  ``--full`` adds everything else the line can carry: the
+CPU baselines (a fresh child process before any GPU work), the parity spot check against the host oracle, the
+hostile-data, locality and cfg-3 search legs, and the encode, teacher and KD-step legs; the ``--no-*`` switches
+trim a ``--full`` run.
 For N > 1 the driver launches it under ``python -m torch.distributed.run`` (one rank per GPU over
 RCCL); started from a bare shell without ``RANK`` in the environment it starts that launcher itself
 as a CHILD process - before anything touches the GPU - and exits with the child's return code.
@@ -13,8 +18,8 @@ Workload = BASELINE.json configs[1]:
            queries answered: local exact scan -> (N > 1) all-gather of partial top-10 -> merge.
            Fixed total work as N grows => "strong" scaling.
   encode : e5-small-v2-shaped bf16 encoder, batch 512 x seq 256 synthetic token ids per rank
-           (timed separately in the same run once the encoder kernels are built).
-``value`` is queries/s of the search step (whole job); docs/s rides along in ``encode``.
+           (``--full``: timed separately in the same run once the encoder kernels are built).
+``value`` is queries/s of the search step (whole job); under ``--full`` docs/s rides along in ``encode``.
 """
 from __future__ import annotations
 
@@ -484,6 +489,9 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--corpus", type=int, default=N_CORPUS)
     ap.add_argument("--queries", type=int, default=N_QUERIES)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines, the parity spot check, the hostile-data / locality / cfg-3 search "
+                         "legs and the encode, teacher and KD-step legs (the --no-* switches below trim such a run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-encode", action="store_true")
     ap.add_argument("--no-ragged", action="store_true", help="skip the ragged-length encode leg")
@@ -527,9 +535,10 @@ def main() -> None:
         if rank == 0:
             print(json.dumps({"launch_check": True, "ranks": world}), flush=True)
         return
-    # CPU baselines FIRST, in a child that never touches the GPU (rank 0 at N = 1 only); nothing above this line has
-    # initialised the GPU in this process either
-    cpu_lines = run_cpu_baselines_first(args) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    # --full: CPU baselines FIRST, in a child that never touches the GPU (rank 0 at N = 1 only); nothing above this line
+    # has initialised the GPU in this process either
+    with_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_lines = run_cpu_baselines_first(args) if with_cpu else None
     assert torch.cuda.is_available(), "bench.py needs an MI355X (no CPU path)"
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -642,7 +651,7 @@ def main() -> None:
         print(f"bench.py: last timed step's search outputs written to {dumped}", file=sys.stderr, flush=True)
 
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if with_cpu:
         # parity spot check of what was just measured: first 100 queries against the reference idiom
         # (numpy sgemm + argsort) on the host, same vectors
         from oracle import search as oracle
@@ -749,17 +758,17 @@ def main() -> None:
             "hbm_peak_gbs": HBM_PEAK_GBS,
         })
 
-    # ---- hostile-data leg and the cfg-3 sizes (rank 0, N = 1) -----------------------------------------------------
-    if rank == 0 and world == 1 and not args.no_hostile and n >= 100_000:
+    # ---- --full: hostile-data leg and the cfg-3 sizes (rank 0, N = 1) ----------------------------------------------
+    if args.full and rank == 0 and world == 1 and not args.no_hostile and n >= 100_000:
         line["search_anisotropic"] = bench_search_anisotropic(pkg, lib, dev, n, nq, ev)
         line["search_locality"] = bench_search_locality(pkg, lib, dev, n, nq, ev)
-    if rank == 0 and world == 1 and not args.no_cfg3:
+    if args.full and rank == 0 and world == 1 and not args.no_cfg3:
         del index, shard
         torch.cuda.empty_cache()
         line["search_cfg3"] = bench_search_cfg3(pkg, lib, dev, nq, ev)
 
-    # ---- encoder leg (docs embedded / s), once the kernels exist ---------------------------
-    if not args.no_encode:
+    # ---- --full: encoder leg (docs embedded / s), once the kernels exist -------------------
+    if args.full and not args.no_encode:
         try:
             from semantic_search_kd_amd import bench_encode  # noqa: F401
         except ImportError:
@@ -768,17 +777,17 @@ def main() -> None:
             line["encode"] = bench_encode(dev, world, args.steps, args.warmup, barrier,
                                           ragged=not args.no_ragged and rank == 0,
                                           text=not args.no_text and rank == 0)
-    # ---- teacher cross-encoder (cfg 5 model, data parallel) and KD training step (cfg 4) -------
-    if not args.no_teacher:
+    # ---- --full: teacher cross-encoder (cfg 5 model, data parallel) and KD training step (cfg 4) -------
+    if args.full and not args.no_teacher:
         from semantic_search_kd_amd.bench_support import bench_teacher
 
         line["teacher"] = bench_teacher(dev, world, max(2, args.steps // 2), 1, barrier)
-    if rank == 0 and world == 1 and not args.no_train:
+    if args.full and rank == 0 and world == 1 and not args.no_train:
         from semantic_search_kd_amd.bench_support import bench_kd_step
 
         line["kd_step"] = bench_kd_step(dev)
 
-    # ---- CPU baselines (measured first, in the child: see run_cpu_baselines_first) + parity spot check ----------
+    # ---- --full: CPU baselines (measured first, in the child: see run_cpu_baselines_first) + parity spot check ---
     if cpu_lines is not None:
         if "search" in cpu_lines:
             line["cpu_baseline"] = cpu_lines["search"]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of the split encoder forward: SSKD_FORWARD_STREAMS = 1 (one stream), 2 (default), 4; encode leg of bench.py.
 set -e
-B="python bench.py --corpus 200000 --queries 2000 --steps 10 --warmup 3 --no-cpu-baseline --no-ragged --no-text --no-train --no-teacher --no-hostile --no-cfg3"
+B="python bench.py --full --corpus 200000 --queries 2000 --steps 10 --warmup 3 --no-cpu-baseline --no-ragged --no-text --no-train --no-teacher --no-hostile --no-cfg3"
 for i in 1 2; do
   for mode in ${AB_MODES:-2 1 4}; do
     export SSKD_FORWARD_STREAMS=$mode
