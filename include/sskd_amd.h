@@ -238,6 +238,29 @@ int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d
                             float* d_out_scores, int64_t* d_out_ids, int64_t max_results, void* d_workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Merge of per-shard range results (the step after the all-gather of a row-sharded range search)
+ * Record r (r = 0 .. n_runs-1) starts at d_records + r * sskd_range_record_bytes(nq, cap) and holds
+ *   { int64 lims[nq + 1]; int64 ids[cap]; float scores[cap]; padding to 16 B },
+ * exactly one shard's sskd_index_range_search output (id_offset = the shard's first global row), padded to the common
+ * capacity cap >= every run's lims[nq].  Runs may be empty.  The ids of different runs must be distinct (shards are
+ * disjoint): the merge assumes it.
+ * Output: bit for bit what one sskd_index_range_search over the union of the shards returns.  d_lims [nq + 1] is the
+ * sum of the runs' counts, always written and always exact; query q's segment is the merge of its n_runs sorted
+ * segments in the range kernel's order: the monotone integer image of the score descending (so +0.0 ranks before
+ * -0.0), then id ascending.  Overflow as sskd_index_range_search: when lims[nq] > max_results only d_lims is written
+ * and nothing is written at or past max_results; max_results = 0 is a count-only call and d_out_scores / d_out_ids may
+ * then be NULL.  Stream-ordered, no host sync, allocates nothing.  Arguments are checked before any HIP call: n_runs
+ * outside [1, 65535], negative nq / cap / max_results, NULL or misaligned (8 B) records, NULL lims, NULL outputs with
+ * max_results > 0 (SSKD_ERR_INVALID) and a workspace smaller than sskd_range_merge_workspace_bytes
+ * (SSKD_ERR_WORKSPACE).  sskd_range_record_bytes returns 0 for negative sizes.
+ * ------------------------------------------------------------------------- */
+size_t sskd_range_record_bytes(int nq, int64_t cap);
+size_t sskd_range_merge_workspace_bytes(int n_runs, int nq, int64_t max_results);
+int sskd_range_merge_packed(const void* d_records, int n_runs, int nq, int64_t cap, int64_t* d_lims,
+                            float* d_out_scores, int64_t* d_out_ids, int64_t max_results, void* d_workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -2888,6 +2888,139 @@ void launch_range_scan(const Plan& pl, const RangeParams& rp, hipStream_t st) {
   hipLaunchKernelGGL(kern, dim3(pl.n_qblocks * pl.n_slices), dim3(WAVES * 64), lds, st, rp);
 }
 
+// ------------------------------------------------------------------------- //
+// merge of per-shard range results (sskd_range_merge_packed): n_runs packed records, each one rank's
+// sskd_index_range_search output with global ids, -> the CSR result of one range search over the union of the shards.
+//
+// lims: the count of query q is the sum of its segment lengths over the runs; the exclusive scan is the range CSR
+// build's (block sums, one-workgroup scan of the block sums, per-block scan).  Placement: one thread per input record.
+// Its output slot is lims[q] + its index in its own segment + for every other run, the number of that run's keys in
+// q's segment that rank before it (binary search).  The rank order is the range kernel's key order: the monotone
+// image float_to_ordered(score) descending, then id ascending (so +0.0 ranks before -0.0).  Ids are distinct across
+// runs, so no two keys of a query are equal and its slots are a permutation of [lims[q], lims[q + 1]).  No atomics,
+// no sort, one pass.  Every segment bound read from a record is clamped to [0, cap], so a slot never leaves its
+// query's output segment, whatever the records hold.
+// ------------------------------------------------------------------------- //
+struct RangeMergeParams {
+  const char* records;
+  int64_t rec_bytes;   // stride of the records: sskd_range_record_bytes(nq, cap)
+  int64_t cap;
+  int nq;
+  int64_t* lims;       // [nq + 1] merged
+  float* out_scores;
+  int64_t* out_ids;
+  int64_t max_results;
+};
+
+__device__ inline const int64_t* merge_run_lims(const RangeMergeParams& p, int r) {
+  return reinterpret_cast<const int64_t*>(p.records + (int64_t)r * p.rec_bytes);
+}
+
+// [a, b) of query q's segment in run r, clamped to the record's capacity
+__device__ inline void merge_run_segment(const RangeMergeParams& p, const int64_t* lr, int q, int64_t& a, int64_t& b) {
+  a = min(max(lr[q], (int64_t)0), p.cap);
+  b = min(max(lr[q + 1], a), p.cap);
+}
+
+__device__ inline int64_t merge_query_count(const RangeMergeParams& p, int n_runs, int q) {
+  int64_t c = 0;
+  for (int r = 0; r < n_runs; ++r) {
+    int64_t a, b;
+    merge_run_segment(p, merge_run_lims(p, r), q, a, b);
+    c += b - a;
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(256) void range_merge_count_blocks_kernel(RangeMergeParams p, int n_runs,
+                                                                       int64_t* __restrict__ block_sums) {
+  __shared__ int64_t s_wave[4];
+  const int64_t base = (int64_t)blockIdx.x * RANGE_SCAN_BLOCK + threadIdx.x * 16;
+  int64_t v = 0;
+  for (int i = 0; i < 16; ++i)
+    if (base + i < p.nq) v += merge_query_count(p, n_runs, (int)(base + i));
+  int64_t total;
+  (void)block_exclusive_scan_256(v, s_wave, &total);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void range_merge_lims_kernel(RangeMergeParams p, int n_runs,
+                                                               const int64_t* __restrict__ block_offsets) {
+  __shared__ int64_t s_wave[4];
+  const int64_t base = (int64_t)blockIdx.x * RANGE_SCAN_BLOCK + threadIdx.x * 16;
+  int64_t c[16];
+  int64_t v = 0;
+  for (int i = 0; i < 16; ++i) {
+    c[i] = base + i < p.nq ? merge_query_count(p, n_runs, (int)(base + i)) : 0;
+    v += c[i];
+  }
+  int64_t total;
+  int64_t run = block_offsets[blockIdx.x] + block_exclusive_scan_256(v, s_wave, &total);
+  for (int i = 0; i < 16; ++i) {
+    if (base + i < p.nq) p.lims[base + i] = run;
+    run += c[i];
+  }
+}
+
+// grid (x: records of a run, grid-stride; y: the run)
+__global__ __launch_bounds__(256) void range_merge_place_kernel(RangeMergeParams p) {
+  if (p.lims[p.nq] > p.max_results) return;   // overflow: lims only
+  const int r = blockIdx.y, n_runs = gridDim.y, nq = p.nq;
+  const int64_t* lr = merge_run_lims(p, r);
+  const int64_t* ids = lr + nq + 1;
+  const float* scores = reinterpret_cast<const float*>(ids + p.cap);
+  const int64_t n = min(max(lr[nq], (int64_t)0), p.cap);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    // the query of record i: the first q whose segment ends past i
+    int lo = 0, hi = nq;
+    while (lo < hi) {
+      const int m = (lo + hi) >> 1;
+      if (lr[m + 1] <= i) lo = m + 1; else hi = m;
+    }
+    if (lo >= nq) continue;
+    const int q = lo;
+    int64_t a, b;
+    merge_run_segment(p, lr, q, a, b);
+    if (i < a || i >= b) continue;   // (only for records whose lims are not monotone)
+    const float x = scores[i];
+    const int64_t id = ids[i];
+    const int xo = float_to_ordered(x);
+    int64_t pos = p.lims[q] + (i - a);
+    for (int s = 0; s < n_runs; ++s) {
+      if (s == r) continue;
+      const int64_t* ls = merge_run_lims(p, s);
+      const int64_t* ids_s = ls + nq + 1;
+      const float* scores_s = reinterpret_cast<const float*>(ids_s + p.cap);
+      int64_t sa, sb;
+      merge_run_segment(p, ls, q, sa, sb);
+      int64_t l = sa, h = sb;
+      while (l < h) {   // keys of run s ranking before (x, id) form a prefix of its segment
+        const int64_t m = (l + h) >> 1;
+        const int mo = float_to_ordered(scores_s[m]);
+        if (mo > xo || (mo == xo && ids_s[m] < id)) l = m + 1; else h = m;
+      }
+      pos += l - sa;
+    }
+    if (pos < p.lims[q + 1]) {
+      p.out_scores[pos] = x;
+      p.out_ids[pos] = id;
+    }
+  }
+}
+
+struct RangeMergeWs {
+  int64_t* block_sums;
+  size_t bytes;
+};
+
+RangeMergeWs range_merge_carve(void* base, int nq) {
+  sskd::Carver c(base);
+  RangeMergeWs w{};
+  w.block_sums = c.take<int64_t>(sskd::ceil_div(nq, RANGE_SCAN_BLOCK));
+  w.bytes = c.bytes();
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2979,6 +3112,58 @@ int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)big_lds);
   hipLaunchKernelGGL(range_sort_big_kernel, dim3(nq), dim3(1024), big_lds, st, sp);
   return sskd::check_launch("range_sort_big_kernel");
+}
+
+size_t sskd_range_record_bytes(int nq, int64_t cap) {
+  if (nq < 0 || cap < 0) return 0;
+  return (((size_t)nq + 1) * sizeof(int64_t) + (size_t)cap * (sizeof(int64_t) + sizeof(float)) + 15) & ~(size_t)15;
+}
+
+size_t sskd_range_merge_workspace_bytes(int n_runs, int nq, int64_t max_results) {
+  if (n_runs < 1 || nq <= 0 || max_results < 0) return 0;
+  return range_merge_carve(nullptr, nq).bytes;
+}
+
+int sskd_range_merge_packed(const void* d_records, int n_runs, int nq, int64_t cap, int64_t* d_lims,
+                            float* d_out_scores, int64_t* d_out_ids, int64_t max_results, void* d_workspace,
+                            size_t workspace_bytes, void* stream) {
+  // every check comes before the first HIP call
+  SSKD_REQUIRE(n_runs >= 1 && n_runs <= 65535, "range_merge_packed: n_runs=%d outside [1, 65535]", n_runs);
+  SSKD_REQUIRE(nq >= 0, "range_merge_packed: nq < 0");
+  SSKD_REQUIRE(cap >= 0, "range_merge_packed: cap < 0");
+  SSKD_REQUIRE(max_results >= 0, "range_merge_packed: max_results < 0");
+  SSKD_REQUIRE(d_records && d_lims, "range_merge_packed: null records or lims");
+  SSKD_REQUIRE((reinterpret_cast<uintptr_t>(d_records) & 7) == 0, "range_merge_packed: records must be 8-byte aligned");
+  SSKD_REQUIRE(max_results == 0 || (d_out_scores && d_out_ids), "range_merge_packed: null output with max_results > 0");
+  const RangeMergeWs w = range_merge_carve(d_workspace, nq);
+  int rc;
+  if (nq > 0 &&
+      (rc = sskd::require_workspace("range_merge_packed", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK)
+    return rc;
+  hipStream_t st = sskd::as_stream(stream);
+  if (nq == 0) {
+    if (hipMemsetAsync(d_lims, 0, sizeof(int64_t), st) != hipSuccess)
+      return sskd::fail(SSKD_ERR_HIP, "range_merge_packed: memset failed");
+    return SSKD_OK;
+  }
+  RangeMergeParams p{};
+  p.records = static_cast<const char*>(d_records);
+  p.rec_bytes = (int64_t)sskd_range_record_bytes(nq, cap);
+  p.cap = cap;
+  p.nq = nq;
+  p.lims = d_lims;
+  p.out_scores = d_out_scores;
+  p.out_ids = d_out_ids;
+  p.max_results = max_results;
+  const int n_blocks = (int)sskd::ceil_div(nq, RANGE_SCAN_BLOCK);
+  hipLaunchKernelGGL(range_merge_count_blocks_kernel, dim3(n_blocks), dim3(256), 0, st, p, n_runs, w.block_sums);
+  hipLaunchKernelGGL(range_scan_blocks_kernel, dim3(1), dim3(256), 0, st, w.block_sums, n_blocks, d_lims, nq);
+  hipLaunchKernelGGL(range_merge_lims_kernel, dim3(n_blocks), dim3(256), 0, st, p, n_runs, w.block_sums);
+  if ((rc = sskd::check_launch("range_merge_lims_kernel")) != SSKD_OK) return rc;
+  if (max_results == 0 || cap == 0) return SSKD_OK;   // count-only, or nothing to place
+  const int64_t blocks = std::min<int64_t>(sskd::ceil_div(cap, 256), 2048);
+  hipLaunchKernelGGL(range_merge_place_kernel, dim3((unsigned)blocks, (unsigned)n_runs), dim3(256), 0, st, p);
+  return sskd::check_launch("range_merge_place_kernel");
 }
 
 }  // extern "C"

@@ -9,6 +9,10 @@ exchange step:
     all ranks : ONE all-gather  ->  [G] records             (1.2 MB / rank at nq=10k, k=10)
     every rank: merge G*k -> k per query (``sskd_topk_merge_packed``; ties: lower global id)
 
+A range search has results of any length per rank, so it takes two collectives: an all-gather of the per-rank
+totals fixes ``cap`` = the largest, every rank pads its record ``{ lims[nq + 1]; ids[cap]; scores[cap] }`` to it, one
+all-gather moves the records, and rank 0 merges them (``sskd_range_merge_packed``).
+
 The collective goes through ``torch.distributed`` (backend ``nccl`` = RCCL on ROCm) on
 the same stream as the kernels.  ``local_search`` / ``merge`` / ``all_gather`` are injectable
 so that the sharding logic can be exercised with ``gloo`` on CPU in the tests.
@@ -40,6 +44,40 @@ def record_views(record: torch.Tensor, nq: int, k: int) -> Tuple[torch.Tensor, t
     ids = record[: nq * k * 8].view(torch.int64).view(nq, k)
     scores = record[nq * k * 8 : nq * k * 12].view(torch.float32).view(nq, k)
     return scores, ids
+
+
+def range_record_bytes(nq: int, cap: int) -> int:
+    """Bytes of one rank's packed range record (``sskd_range_record_bytes``): lims, ids, scores, pad to 16."""
+    return ((nq + 1) * 8 + cap * 12 + 15) // 16 * 16 if nq >= 0 and cap >= 0 else 0
+
+
+def range_record_views(record: torch.Tensor, nq: int, cap: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(lims int64 [nq + 1], scores fp32 [cap], ids int64 [cap])`` views into a packed uint8 range record."""
+    a = (nq + 1) * 8
+    lims = record[:a].view(torch.int64)
+    ids = record[a : a + cap * 8].view(torch.int64)
+    scores = record[a + cap * 8 : a + cap * 12].view(torch.float32)
+    return lims, scores, ids
+
+
+def hip_range_merge_packed(records: torch.Tensor, g: int, nq: int, cap: int,
+                           total: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``[G * range_record_bytes]`` gathered records -> ``(lims [nq + 1], scores [total], ids [total])`` via the HIP
+    range merge; ``total`` is the sum of the runs' totals (known to the caller from the first all-gather)."""
+    lib = _native.load()
+    dev = records.device
+    lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    scores = torch.empty(total, dtype=torch.float32, device=dev)
+    ids = torch.empty(total, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(lib.sskd_range_merge_workspace_bytes(g, nq, total)), 1), dtype=torch.uint8, device=dev)
+    _native.check(
+        lib.sskd_range_merge_packed(
+            records.data_ptr(), g, nq, cap, lims.data_ptr(), scores.data_ptr() if total else None,
+            ids.data_ptr() if total else None, total, ws.data_ptr(), ws.numel(),
+            int(torch.cuda.current_stream(dev).cuda_stream),
+        )
+    )
+    return lims, scores, ids
 
 
 def hip_merge(scores: torch.Tensor, ids: torch.Tensor, k_out: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -113,44 +151,64 @@ class ShardedSearcher:
         group=None,
         merge: Optional[Callable[[torch.Tensor, torch.Tensor, int], Tuple[torch.Tensor, torch.Tensor]]] = None,
         all_gather: Optional[Callable[[torch.Tensor, torch.Tensor], None]] = None,
+        range_merge: Optional[Callable[..., Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]] = None,
     ) -> None:
         """``local_search(queries, k[, out_scores=, out_ids=])`` must return this rank's
         ``(scores, GLOBAL ids)`` (e.g. ``FAISSIndexBuilder(id_offset=lo).search_device``); when it
         accepts ``out_scores`` / ``out_ids`` it writes straight into the packed record.
         ``merge(scores [G, nq, k], ids [G, nq, k], k)`` replaces the HIP merge (CPU tests);
         ``all_gather(out, inp)`` replaces ``dist.all_gather_into_tensor`` (e.g. host-staged gloo
-        when several test ranks share one GPU)."""
+        when several test ranks share one GPU; it carries the range path's two all-gathers as well).
+        ``range_merge(lims [G, nq + 1], scores [G, cap], ids [G, cap])`` replaces the HIP range merge (CPU tests)."""
         self.local_search = local_search
         self.group = group
         self.merge = merge
         self.all_gather = all_gather
+        self.range_merge = range_merge
         self.last_world = 1
 
-    def _local_into(self, queries, k, out_s, out_i):
+    def _local_into(self, queries, k, out_s, out_i, allow=None):
         fn = self.local_search
         try:
             params = inspect.signature(fn).parameters
         except (TypeError, ValueError):
             params = {}
+        extra = {} if allow is None else {"allow": allow}   # an unfiltered call passes no allow at all
         if "out_scores" in params and "out_ids" in params:
-            s, i = fn(queries, k, out_scores=out_s, out_ids=out_i)
+            s, i = fn(queries, k, out_scores=out_s, out_ids=out_i, **extra)
         else:
-            s, i = fn(queries, k)
+            s, i = fn(queries, k, **extra)
         if s.data_ptr() != out_s.data_ptr():
             out_s.copy_(s)
         if i.data_ptr() != out_i.data_ptr():
             out_i.copy_(i)
 
-    def search_local(self, queries: torch.Tensor, k: int) -> torch.Tensor:
+    def search_local(self, queries: torch.Tensor, k: int, allow=None) -> torch.Tensor:
         """This rank's half of a sharded search, no communication: the local scan writes its ``(scores, GLOBAL
         ids)`` straight into a fresh packed record, which is returned (``gather_merge`` takes it from there).
         Split from ``search`` so that a caller can agree with the other ranks that every local scan succeeded
-        BEFORE any rank enters the device collective (sharded_index.ShardedIndex)."""
+        BEFORE any rank enters the device collective (sharded_index.ShardedIndex).  ``allow``: this rank's local
+        filter, handed to ``local_search`` as ``allow=`` (not passed at all when None)."""
         nq = queries.shape[0]
         send = torch.empty(record_bytes(nq, k), dtype=torch.uint8, device=queries.device)
         out_s, out_i = record_views(send, nq, k)
-        self._local_into(queries, k, out_s, out_i)
+        self._local_into(queries, k, out_s, out_i, allow)
         return send
+
+    def _all_gather(self, recv: torch.Tensor, send: torch.Tensor) -> None:
+        import torch.distributed as dist
+
+        if self.all_gather is not None:
+            self.all_gather(recv, send)
+        elif dist.get_backend(self.group) == "gloo" and send.is_cuda:
+            # gloo moves host memory (several ranks sharing one GPU in tests, CPU-only rehearsals): stage the
+            # records through the host.  On a node with one GPU per rank the backend is nccl (= RCCL over xGMI) and
+            # the records never leave HBM.
+            host = torch.empty(recv.shape, dtype=recv.dtype)
+            dist.all_gather_into_tensor(host, send.cpu(), group=self.group)
+            recv.copy_(host)
+        else:
+            dist.all_gather_into_tensor(recv, send, group=self.group)
 
     def gather_merge(self, send: torch.Tensor, nq: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """ONE all-gather of the packed records (RCCL over xGMI on a GPU node) and the merge of the G lists."""
@@ -161,23 +219,44 @@ class ShardedSearcher:
         rec = record_bytes(nq, k)
         dev = send.device
         recv = torch.empty(world * rec, dtype=torch.uint8, device=dev)
-        if self.all_gather is not None:
-            self.all_gather(recv, send)
-        elif dist.get_backend(self.group) == "gloo" and send.is_cuda:
-            # gloo moves host memory (several ranks sharing one GPU in tests, CPU-only rehearsals): stage the
-            # 12-byte-per-result records through the host.  On a node with one GPU per rank the backend is nccl
-            # (= RCCL over xGMI) and the records never leave HBM.
-            host = torch.empty(recv.shape, dtype=recv.dtype)
-            dist.all_gather_into_tensor(host, send.cpu(), group=self.group)
-            recv.copy_(host)
-        else:
-            dist.all_gather_into_tensor(recv, send, group=self.group)
+        self._all_gather(recv, send)
         if self.merge is not None:
             table = recv.view(world, rec)
             all_i = table[:, : nq * k * 8].contiguous().view(torch.int64).view(world, nq, k)
             all_s = table[:, nq * k * 8 : nq * k * 12].contiguous().view(torch.float32).view(world, nq, k)
             return self.merge(all_s, all_i, k)
         return hip_merge_packed(recv, world, nq, k, k)
+
+    def range_gather_merge(self, lims: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor,
+                           nq: int) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """The range path's exchange, every rank: this rank's exact-size local range result ``(lims [nq + 1], scores,
+        GLOBAL ids)`` -> an all-gather of the per-rank totals (``cap`` = the largest) -> this rank's record padded to
+        ``cap`` -> ONE all-gather of the records -> on rank 0 the merge, returned as ``(lims, scores, ids)`` in the
+        order of one range search over the whole corpus; the other ranks return None."""
+        import torch.distributed as dist
+
+        world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
+        self.last_world = world
+        dev = lims.device
+        totals = torch.empty(world, dtype=torch.int64, device=dev)
+        self._all_gather(totals, lims[nq:].contiguous())
+        host_totals = totals.cpu()
+        cap, total = int(host_totals.max()), int(host_totals.sum())
+        rec = range_record_bytes(nq, cap)
+        send = torch.zeros(rec, dtype=torch.uint8, device=dev)
+        rec_lims, rec_scores, rec_ids = range_record_views(send, nq, cap)
+        n = scores.numel()
+        rec_lims.copy_(lims)
+        rec_scores[:n].copy_(scores)
+        rec_ids[:n].copy_(ids)
+        recv = torch.empty(world * rec, dtype=torch.uint8, device=dev)
+        self._all_gather(recv, send)
+        if rank != 0:
+            return None
+        if self.range_merge is not None:
+            views = [range_record_views(r, nq, cap) for r in recv.view(world, rec)]
+            return self.range_merge(*(torch.stack([v[j] for v in views]) for j in range(3)))
+        return hip_range_merge_packed(recv, world, nq, cap, total)
 
     def search(self, queries: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         import torch.distributed as dist

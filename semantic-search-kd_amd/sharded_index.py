@@ -19,7 +19,7 @@ served by any world size that divides the work into contiguous runs of shards (8
 loads shards ``[r S / G, (r + 1) S / G)`` back to back into one HBM buffer.
 
 Serving (``ShardedIndex``): rank 0 owns the HTTP surface and calls ``search`` like on a ``FAISSIndexBuilder``; the
-other ranks sit in ``serve_forever()``.  One search = a 3-word header on the CONTROL group, the query block from
+other ranks sit in ``serve_forever()``.  One search = a 5-word header on the CONTROL group, the query block from
 rank 0, every rank's local scan, one status word per rank on the control group, then - only when every rank
 succeeded - ``dist.ShardedSearcher``'s all-gather of the packed records and the merge.  ``torch.distributed`` backend
 ``nccl`` is RCCL over xGMI; ``gloo`` works for rehearsals (records are then staged through the host).
@@ -37,6 +37,12 @@ HIP / RCCL call must surface as a Python exception and ``/health.index_loaded`` 
   on EVERY rank (two-phase: prepare, exchange, commit);
 * status exchanges wait ``op_timeout_s``: a rank that died or hangs turns into ``ShardFailure`` on rank 0 within that
   time, the index is marked broken (``is_loaded`` False -> ``/health.index_loaded`` False) and later calls fail fast.
+
+Filters and range search: ``search(..., allow=)`` and ``range_search`` send the query block, the thresholds and the
+GLOBAL filter (a bool mask over ``ntotal`` rows or an id list) over the control group as host tensors; every rank
+applies its slice ``[lo, hi)`` as a local filter, so nothing reaches the data group before the status exchange has
+confirmed every rank's local part.  A range search then takes ``ShardedSearcher.range_gather_merge``'s two
+all-gathers (per-rank totals, then the records padded to the largest) and rank 0's ``sskd_range_merge_packed``.
 """
 from __future__ import annotations
 
@@ -48,9 +54,12 @@ import numpy as np
 import torch
 
 from .dist import ShardedSearcher, shard_bounds
+from .index import range_thresholds
 
 MANIFEST = "shards.json"
-_OP_STOP, _OP_SEARCH, _OP_LOAD, _OP_REMOVE = 0, 1, 2, 3
+_OP_STOP, _OP_SEARCH, _OP_LOAD, _OP_REMOVE, _OP_RANGE = 0, 1, 2, 3, 4
+# how a call's global filter travels on the control group (the header's 4th word; the 5th is its length)
+_FILTER_NONE, _FILTER_MASK, _FILTER_IDS = 0, 1, 2
 
 
 class ShardFailure(RuntimeError):
@@ -183,17 +192,18 @@ class ShardedIndex:
                 self._ctrl_group = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=self.idle_timeout_s))
         return self._ctrl_group
 
-    def _header(self, op: int = 0, a: int = 0, b: int = 0) -> Tuple[int, int, int]:
+    def _header(self, op: int = 0, a: int = 0, b: int = 0, fkind: int = _FILTER_NONE,
+                flen: int = 0) -> Tuple[int, int, int, int, int]:
         """rank 0 announces the next collective step; the others learn it (a HOST broadcast: waiting costs no GPU
-        and no watchdog can abort it)"""
+        and no watchdog can abort it).  ``fkind`` / ``flen``: the kind and length of the filter that follows."""
         import torch.distributed as dist
 
         world, rank = _world(self.group)
         if world == 1:
-            return op, a, b
-        h = torch.tensor([op, a, b], dtype=torch.int64)
+            return op, a, b, fkind, flen
+        h = torch.tensor([op, a, b, fkind, flen], dtype=torch.int64)
         dist.broadcast(h, src=self._src(), group=self._ctrl())
-        return int(h[0]), int(h[1]), int(h[2])
+        return tuple(int(x) for x in h)
 
     def _exchange_status(self, what: str, error: Optional[BaseException]) -> Dict[int, str]:
         """Every rank reports one word (0 = its part succeeded); returns ``{rank: message}`` of the failed ranks, the
@@ -384,23 +394,79 @@ class ShardedIndex:
             raise ShardFailure("sharded index", {-1: f"deployment is broken ({self.broken}); restart it"})
 
     # ------------------------------------------------------------------ search
-    def _local_search(self, queries: torch.Tensor, k: int, out_scores=None, out_ids=None):
-        return self.local.search_device(queries, k, normalize_queries=None, out_scores=out_scores, out_ids=out_ids)
+    def _local_search(self, queries: torch.Tensor, k: int, out_scores=None, out_ids=None, allow=None):
+        extra = {} if allow is None else {"allow": allow}   # an unfiltered search calls the local index as it always did
+        return self.local.search_device(queries, k, normalize_queries=None, out_scores=out_scores, out_ids=out_ids,
+                                        **extra)
 
-    def _collective_search(self, queries: Optional[torch.Tensor], nq: int, k: int):
+    def _check_filter(self, allow) -> Tuple[int, Optional[torch.Tensor]]:
+        """rank 0, before anything is announced: a GLOBAL filter -> ``(kind, host tensor)`` as it goes on the wire (a
+        bool mask over ``ntotal`` rows as uint8, or int64 global ids); ValueError for a wrong length, dtype or id"""
+        if allow is None:
+            return _FILTER_NONE, None
+        a = allow.cpu().numpy() if isinstance(allow, torch.Tensor) else np.asarray(allow)
+        if a.dtype == np.bool_:
+            if a.shape != (self.ntotal,):
+                raise ValueError(f"a boolean filter needs one entry per row: shape {a.shape}, index has {self.ntotal} rows")
+            return _FILTER_MASK, torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+        if a.dtype.kind in "iu" or a.size == 0:
+            ids = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+            if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal):
+                raise ValueError(f"filter ids outside [0, {self.ntotal})")
+            return _FILTER_IDS, torch.from_numpy(ids)
+        raise ValueError(f"a filter is a bool array over the rows or an integer id array, got dtype {a.dtype}")
+
+    def _local_filter(self, fkind: int, filt: Optional[torch.Tensor]):
+        """this rank's slice ``[lo, lo + rows)`` of a global filter, in the form its local index takes"""
+        if fkind == _FILTER_NONE:
+            return None
+        lo, rows = int(self.local.id_offset), int(self.local.ntotal)
+        if fkind == _FILTER_MASK:
+            return filt[lo : lo + rows].numpy().astype(np.bool_)
+        ids = filt.numpy()
+        return ids[(ids >= lo) & (ids < lo + rows)]
+
+    def _call_inputs(self, q, thr, filt, nq: int, fkind: int, flen: int, with_thresholds: bool):
+        """rank 0's queries [, thresholds] [, filter] of a filtered search or a range search -> every rank, as host
+        tensors over the CONTROL group (never the data group: nothing is entered there before the status exchange)"""
+        import torch.distributed as dist
+
+        rank = _world(self.group)[1]
+
+        def bcast(t, shape, dtype):
+            buf = t.contiguous() if rank == 0 else torch.empty(shape, dtype=dtype)
+            dist.broadcast(buf, src=self._src(), group=self._ctrl())
+            return buf
+
+        q = bcast(q, (nq, self.embedding_dim), torch.float32)
+        if with_thresholds:
+            thr = bcast(thr, (nq,), torch.float32)
+        if fkind != _FILTER_NONE:
+            filt = bcast(filt, (flen,), torch.uint8 if fkind == _FILTER_MASK else torch.int64)
+        return q, thr, filt
+
+    def _collective_search(self, queries: Optional[torch.Tensor], nq: int, k: int, fkind: int = _FILTER_NONE,
+                           filt: Optional[torch.Tensor] = None, flen: int = 0):
         import torch.distributed as dist
 
         world, rank = _world(self.group)
         if world == 1:
+            if fkind != _FILTER_NONE:
+                return self._local_search(queries.to(torch.device(self.local.device)), k,
+                                          allow=self._local_filter(fkind, filt))
             return self._searcher.search(queries.to(torch.device(self.local.device)), k)
         error, partial = None, None
-        comm = self._comm_device()
-        buf = queries.to(comm) if rank == 0 else torch.empty((nq, self.embedding_dim), dtype=torch.float32, device=comm)
-        dist.broadcast(buf, src=self._src(), group=self.group)
+        if fkind != _FILTER_NONE:   # a filtered search: queries and filter over the control group
+            buf, _, filt = self._call_inputs(queries, None, filt, nq, fkind, flen, with_thresholds=False)
+        else:
+            comm = self._comm_device()
+            buf = queries.to(comm) if rank == 0 else torch.empty((nq, self.embedding_dim), dtype=torch.float32, device=comm)
+            dist.broadcast(buf, src=self._src(), group=self.group)
         try:
             if self.local is None:
                 raise RuntimeError("no index loaded on this rank")
-            partial = self._searcher.search_local(buf.to(torch.device(self.local.device)), k)
+            partial = self._searcher.search_local(buf.to(torch.device(self.local.device)), k,
+                                                  allow=self._local_filter(fkind, filt))
         except Exception as exc:  # noqa: BLE001 - reported below; this rank still answers the status exchange
             error = exc
         failures = self._exchange_status("search", error)
@@ -411,27 +477,76 @@ class ShardedIndex:
             return None
         return self._searcher.gather_merge(partial, nq, k)
 
-    def search(self, query_emb: np.ndarray, k: int = 10) -> Tuple[np.ndarray, np.ndarray]:
-        """``(distances [nq, k] fp32 desc, GLOBAL row ids [nq, k] int64, -1 padded)`` - rank 0's call."""
+    def _check_queries(self, query_emb, what: str) -> np.ndarray:
         if self.local is None:
             raise RuntimeError("index is empty: call load first")
         world, rank = _world(self.group)
         if world > 1 and rank != 0:
-            raise RuntimeError("ShardedIndex.search is rank 0's call; the other ranks run serve_forever()")
+            raise RuntimeError(f"ShardedIndex.{what} is rank 0's call; the other ranks run serve_forever()")
         self._check_usable()
-        # everything that can be wrong with the CALL is found before the other ranks hear of it
         q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
         if q.ndim == 1:
             q = q[None, :]
         if q.ndim != 2 or q.shape[1] != self.embedding_dim:
             raise ValueError(f"queries have shape {q.shape}, expected [nq, {self.embedding_dim}]")
+        return q
+
+    def search(self, query_emb: np.ndarray, k: int = 10, *, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``(distances [nq, k] fp32 desc, GLOBAL row ids [nq, k] int64, -1 padded)`` - rank 0's call.  ``allow``: an
+        optional GLOBAL filter, a bool array over ``ntotal`` rows or an integer array of global ids; removed rows are
+        never returned."""
+        # everything that can be wrong with the CALL is found before the other ranks hear of it
+        q = self._check_queries(query_emb, "search")
         if int(k) < 1:
             raise ValueError(f"k must be >= 1, got {k}")
+        fkind, filt = self._check_filter(allow)
         if q.shape[0] == 0:
             return np.zeros((0, int(k)), np.float32), np.zeros((0, int(k)), np.int64)
-        self._header(_OP_SEARCH, q.shape[0], int(k))
-        s, i = self._collective_search(torch.from_numpy(q), q.shape[0], int(k))
+        flen = 0 if filt is None else filt.numel()
+        self._header(_OP_SEARCH, q.shape[0], int(k), fkind, flen)
+        s, i = self._collective_search(torch.from_numpy(q), q.shape[0], int(k), fkind, filt, flen)
         return s.cpu().numpy(), i.cpu().numpy()
+
+    def _local_range(self, q: torch.Tensor, thr: torch.Tensor, allow):
+        dev = torch.device(self.local.device)
+        return self.local.range_search_device(q.to(dev), thr.to(dev), allow=allow, normalize_queries=None)
+
+    def _collective_range(self, queries: Optional[torch.Tensor], thr: Optional[torch.Tensor], nq: int, fkind: int,
+                          filt: Optional[torch.Tensor], flen: int):
+        world, rank = _world(self.group)
+        if world == 1:
+            return self._local_range(queries, thr, self._local_filter(fkind, filt))
+        q, thr, filt = self._call_inputs(queries, thr, filt, nq, fkind, flen, with_thresholds=True)
+        error, part = None, None
+        try:
+            if self.local is None:
+                raise RuntimeError("no index loaded on this rank")
+            part = self._local_range(q, thr, self._local_filter(fkind, filt))
+        except Exception as exc:  # noqa: BLE001 - reported below; this rank still answers the status exchange
+            error = exc
+        failures = self._exchange_status("range_search", error)   # nothing on the data group before this agreement
+        self.last_failure = failures or None
+        if failures:
+            if rank == 0:
+                raise ShardFailure("range_search", failures) from error
+            return None
+        return self._searcher.range_gather_merge(*part, nq)
+
+    def range_search(self, query_emb: np.ndarray, threshold, *, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss ``range_search`` over every shard - rank 0's call: every allowed, not removed row scoring
+        ``> threshold`` (a float, or one per query) as NumPy ``(lims int64 [nq + 1], D float32, I int64)`` with GLOBAL
+        ids; query ``q``'s results are ``[lims[q], lims[q + 1])``, sorted by score descending, then id ascending - bit
+        for bit what one ``FAISSIndexBuilder.range_search`` over the whole corpus returns.  ``allow`` as in ``search``."""
+        q = self._check_queries(query_emb, "range_search")
+        thr = range_thresholds(threshold, q.shape[0])
+        fkind, filt = self._check_filter(allow)
+        nq = q.shape[0]
+        if nq == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.float32), np.zeros(0, np.int64)
+        flen = 0 if filt is None else filt.numel()
+        self._header(_OP_RANGE, nq, 0, fkind, flen)
+        lims, scores, ids = self._collective_range(torch.from_numpy(q), torch.from_numpy(thr), nq, fkind, filt, flen)
+        return lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
 
     def serve_forever(self) -> None:
         """Ranks other than 0: answer rank 0's announcements until it says stop.  An operation that fails HERE is
@@ -439,12 +554,14 @@ class ShardedIndex:
         import torch.distributed as dist
 
         while True:
-            op, a, b = self._header()
+            op, a, b, fkind, flen = self._header()
             if op == _OP_STOP:
                 return
             try:
                 if op == _OP_SEARCH:
-                    self._collective_search(None, a, b)
+                    self._collective_search(None, a, b, fkind, None, flen)
+                elif op == _OP_RANGE:
+                    self._collective_range(None, None, a, fkind, None, flen)
                 elif op == _OP_LOAD:
                     box = [None]
                     dist.broadcast_object_list(box, src=self._src(), group=self._ctrl())
