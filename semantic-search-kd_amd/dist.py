@@ -20,11 +20,20 @@ so that the sharding logic can be exercised with ``gloo`` on CPU in the tests.
 from __future__ import annotations
 
 import inspect
-from typing import Callable, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
 from . import _native
+
+
+def _world(group=None) -> Tuple[int, int]:
+    """``(world size, rank)`` of ``group``; ``(1, 0)`` without an initialised process group"""
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_world_size(group), dist.get_rank(group)
+    return 1, 0
 
 
 def shard_bounds(n_rows: int, world_size: int, rank: int) -> Tuple[int, int]:
@@ -80,28 +89,6 @@ def hip_range_merge_packed(records: torch.Tensor, g: int, nq: int, cap: int,
     return lims, scores, ids
 
 
-def hip_merge(scores: torch.Tensor, ids: torch.Tensor, k_out: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``[G, nq, k_in]`` device lists -> ``[nq, k_out]`` via the HIP merge kernel."""
-    lib = _native.load()
-    g, nq, k_in = scores.shape
-    out_s = torch.empty((nq, k_out), dtype=torch.float32, device=scores.device)
-    out_i = torch.empty((nq, k_out), dtype=torch.int64, device=scores.device)
-    _native.check(
-        lib.sskd_topk_merge(
-            scores.contiguous().data_ptr(),
-            ids.contiguous().data_ptr(),
-            g,
-            nq,
-            k_in,
-            k_out,
-            out_s.data_ptr(),
-            out_i.data_ptr(),
-            int(torch.cuda.current_stream(scores.device).cuda_stream),
-        )
-    )
-    return out_s, out_i
-
-
 def hip_merge_packed(records: torch.Tensor, g: int, nq: int, k_in: int, k_out: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """``[G * record_bytes]`` gathered uint8 records -> ``[nq, k_out]`` (no unpacking copies)."""
     lib = _native.load()
@@ -140,6 +127,11 @@ def sharded_scores(score_fn: Callable[[int, int], torch.Tensor], n_items: int, g
     recv = torch.empty(world * per, dtype=torch.float32, device=comm_dev)
     dist.all_gather_into_tensor(recv, send, group=group)
     return recv[:n_items].to(local.device)   # ceil-sized shards: only the tail of the LAST ranks is padding
+
+
+def _stacked(views) -> List[torch.Tensor]:
+    """the G ranks' record views -> one ``[G, ...]`` tensor per field (what the injected CPU merges take)"""
+    return [torch.stack(field) for field in zip(*views)]
 
 
 class ShardedSearcher:
@@ -195,9 +187,11 @@ class ShardedSearcher:
         self._local_into(queries, k, out_s, out_i, allow)
         return send
 
-    def _all_gather(self, recv: torch.Tensor, send: torch.Tensor) -> None:
+    def _all_gather(self, send: torch.Tensor, world: int) -> torch.Tensor:
+        """every rank's ``send`` (one size on every rank) -> ``[G, send.numel()]`` on ``send``'s device"""
         import torch.distributed as dist
 
+        recv = torch.empty(world * send.numel(), dtype=send.dtype, device=send.device)
         if self.all_gather is not None:
             self.all_gather(recv, send)
         elif dist.get_backend(self.group) == "gloo" and send.is_cuda:
@@ -209,59 +203,47 @@ class ShardedSearcher:
             recv.copy_(host)
         else:
             dist.all_gather_into_tensor(recv, send, group=self.group)
+        return recv.view(world, -1)
 
     def gather_merge(self, send: torch.Tensor, nq: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """ONE all-gather of the packed records (RCCL over xGMI on a GPU node) and the merge of the G lists."""
-        import torch.distributed as dist
-
-        world = dist.get_world_size(self.group)
-        self.last_world = world
-        rec = record_bytes(nq, k)
-        dev = send.device
-        recv = torch.empty(world * rec, dtype=torch.uint8, device=dev)
-        self._all_gather(recv, send)
+        """ONE all-gather of the packed records (RCCL over xGMI on a GPU node) and the merge of the G lists; at world
+        size 1 the record's own ``(scores, ids)``."""
+        world = self.last_world = _world(self.group)[0]
+        if world == 1:
+            return record_views(send, nq, k)
+        records = self._all_gather(send, world)
         if self.merge is not None:
-            table = recv.view(world, rec)
-            all_i = table[:, : nq * k * 8].contiguous().view(torch.int64).view(world, nq, k)
-            all_s = table[:, nq * k * 8 : nq * k * 12].contiguous().view(torch.float32).view(world, nq, k)
-            return self.merge(all_s, all_i, k)
-        return hip_merge_packed(recv, world, nq, k, k)
+            return self.merge(*_stacked(record_views(r, nq, k) for r in records), k)
+        return hip_merge_packed(records, world, nq, k, k)
 
     def range_gather_merge(self, lims: torch.Tensor, scores: torch.Tensor, ids: torch.Tensor,
                            nq: int) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """The range path's exchange, every rank: this rank's exact-size local range result ``(lims [nq + 1], scores,
         GLOBAL ids)`` -> an all-gather of the per-rank totals (``cap`` = the largest) -> this rank's record padded to
         ``cap`` -> ONE all-gather of the records -> on rank 0 the merge, returned as ``(lims, scores, ids)`` in the
-        order of one range search over the whole corpus; the other ranks return None."""
-        import torch.distributed as dist
-
-        world, rank = dist.get_world_size(self.group), dist.get_rank(self.group)
+        order of one range search over the whole corpus; the other ranks return None.  World size 1: the local
+        result itself."""
+        world, rank = _world(self.group)
         self.last_world = world
-        dev = lims.device
-        totals = torch.empty(world, dtype=torch.int64, device=dev)
-        self._all_gather(totals, lims[nq:].contiguous())
-        host_totals = totals.cpu()
+        if world == 1:
+            return lims, scores, ids
+        host_totals = self._all_gather(lims[nq:].contiguous(), world).cpu()
         cap, total = int(host_totals.max()), int(host_totals.sum())
-        rec = range_record_bytes(nq, cap)
-        send = torch.zeros(rec, dtype=torch.uint8, device=dev)
+        send = torch.zeros(range_record_bytes(nq, cap), dtype=torch.uint8, device=lims.device)
         rec_lims, rec_scores, rec_ids = range_record_views(send, nq, cap)
         n = scores.numel()
         rec_lims.copy_(lims)
         rec_scores[:n].copy_(scores)
         rec_ids[:n].copy_(ids)
-        recv = torch.empty(world * rec, dtype=torch.uint8, device=dev)
-        self._all_gather(recv, send)
+        records = self._all_gather(send, world)
         if rank != 0:
             return None
         if self.range_merge is not None:
-            views = [range_record_views(r, nq, cap) for r in recv.view(world, rec)]
-            return self.range_merge(*(torch.stack([v[j] for v in views]) for j in range(3)))
-        return hip_range_merge_packed(recv, world, nq, cap, total)
+            return self.range_merge(*_stacked(range_record_views(r, nq, cap) for r in records))
+        return hip_range_merge_packed(records, world, nq, cap, total)
 
     def search(self, queries: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        import torch.distributed as dist
-
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.group) == 1:
+        if _world(self.group)[0] == 1:
             self.last_world = 1
             return self.local_search(queries, k)
         nq = queries.shape[0]

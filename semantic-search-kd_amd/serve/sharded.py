@@ -5,7 +5,7 @@
 
 Rank 0 runs the FastAPI application of ``serve/app.py`` (the reference's surface: src/serve/app.py:221-457) with a
 ``ShardedIndex`` as its index object; ranks 1 .. G-1 hold their shards in HBM and answer rank 0's searches
-(``ShardedIndex.serve_forever``: broadcast of the query block, local scan, ONE all-gather, merge).  The student
+(``ShardedIndex.serve_forever``: host broadcast of the query block, local scan, ONE all-gather, merge).  The student
 model lives on rank 0 only - a query is encoded once.  Without ``torch.distributed.run`` this is a one-process server
 of the same directory (all shards on one GPU).
 """
@@ -31,9 +31,10 @@ def init_group_from_env() -> tuple:
     device = f"cuda:{local_rank}" if one_gpu_each else "cuda:0"
     torch.cuda.set_device(torch.device(device))
     if not dist.is_initialized():
-        # The DATA group's timeout bounds one search (query broadcast + all-gather, entered only after every rank
-        # has reported a successful local scan).  Idle ranks do not wait in it: they park in a host broadcast on
-        # ShardedIndex's gloo control group, which no watchdog aborts (sharded_index.py, "Failure path").
+        # The DATA group's timeout bounds one search's record all-gathers, entered only after every rank has
+        # reported a successful local scan.  Idle ranks do not wait in it: they park in a host broadcast on
+        # ShardedIndex's gloo control group, which also carries the query block and no watchdog aborts
+        # (sharded_index.py, "Failure path").
         timeout = datetime.timedelta(seconds=float(os.environ.get("SEMANTIC_KD_SHARD_OP_TIMEOUT_S", "120")))
         if one_gpu_each:
             dist.init_process_group("nccl", device_id=torch.device(device), timeout=timeout)   # RCCL over xGMI

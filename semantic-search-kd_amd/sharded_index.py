@@ -19,10 +19,24 @@ served by any world size that divides the work into contiguous runs of shards (8
 loads shards ``[r S / G, (r + 1) S / G)`` back to back into one HBM buffer.
 
 Serving (``ShardedIndex``): rank 0 owns the HTTP surface and calls ``search`` like on a ``FAISSIndexBuilder``; the
-other ranks sit in ``serve_forever()``.  One search = a 5-word header on the CONTROL group, the query block from
-rank 0, every rank's local scan, one status word per rank on the control group, then - only when every rank
-succeeded - ``dist.ShardedSearcher``'s all-gather of the packed records and the merge.  ``torch.distributed`` backend
-``nccl`` is RCCL over xGMI; ``gloo`` works for rehearsals (records are then staged through the host).
+other ranks sit in ``serve_forever()``.  Every operation (``load``, ``remove_ids``, ``search``, ``range_search``) is
+one protocol, ``ShardedIndex._step`` with a row of ``_OPS``:
+
+1. rank 0 checks the call (its rank, a usable deployment, a loaded index, the arguments, the manifest);
+2. rank 0 sends a 5-word header (op, nq or length, k, filter kind, filter length) and the call's inputs as host
+   tensors on the CONTROL group - the query block, the thresholds, the GLOBAL filter (a bool mask over ``ntotal`` rows
+   or an id list), the ids to remove or the directory to load;
+3. every rank runs the op's local part inside ``try`` (a search applies its slice ``[lo, hi)`` of the filter) and
+   reports one status word on the control group;
+4. only when every word is zero does every rank run the op's finish: a load commits, a removal sums its counts on the
+   control group, a search takes ``dist.ShardedSearcher``'s all-gather of the packed records and the merge, a range
+   search its two all-gathers (per-rank totals, then the records padded to the largest) and rank 0's
+   ``sskd_range_merge_packed``.
+
+So the data group is entered only by the record all-gathers, after every rank has agreed.  World size 1 runs the
+same local part and finish with no header and no communication; ``load_all_ranks`` (every rank at start-up) runs the
+step without a header.  ``torch.distributed`` backend ``nccl`` is RCCL over xGMI; ``gloo`` works for rehearsals
+(records are then staged through the host).
 
 Failure path (reference: src/serve/app.py:354-361 turns any exception into a 500; SURVEY.md section 5: a failed
 HIP / RCCL call must surface as a Python exception and ``/health.index_loaded`` must reflect shard state):
@@ -30,33 +44,29 @@ HIP / RCCL call must surface as a Python exception and ``/health.index_loaded`` 
 * the control group is a CPU (``gloo``) group of the same ranks with an effectively unbounded timeout: the waiting
   ranks park in a HOST broadcast, never inside a device collective (an RCCL collective that rank 0 has not joined
   is aborted by the watchdog after the group's timeout - an idle server would die - and spins a GPU meanwhile);
-* rank 0 validates arguments and the manifest BEFORE it announces an operation; every rank runs its part of the
-  operation inside ``try`` and reports one status word; the device collective of the data path starts only when all
-  words are zero.  Otherwise every rank skips it, rank 0 raises ``ShardFailure`` (-> the route's 500) naming the
-  ranks and their messages, and the deployment keeps serving: a failed ``load`` leaves the previous index in place
-  on EVERY rank (two-phase: prepare, exchange, commit);
+* a call that is wrong in itself raises ``ValueError`` on rank 0 before anything is announced;
+* when some rank's local part fails, every rank skips the finish (a load drops what it staged), rank 0 raises
+  ``ShardFailure`` (-> the route's 500) naming the ranks and their messages, and the deployment keeps serving: a
+  failed ``load`` leaves the previous index in place on EVERY rank (two-phase: prepare, exchange, commit).  At world
+  size 1 a search or range search raises the local exception itself;
 * status exchanges wait ``op_timeout_s``: a rank that died or hangs turns into ``ShardFailure`` on rank 0 within that
   time, the index is marked broken (``is_loaded`` False -> ``/health.index_loaded`` False) and later calls fail fast.
-
-Filters and range search: ``search(..., allow=)`` and ``range_search`` send the query block, the thresholds and the
-GLOBAL filter (a bool mask over ``ntotal`` rows or an id list) over the control group as host tensors; every rank
-applies its slice ``[lo, hi)`` as a local filter, so nothing reaches the data group before the status exchange has
-confirmed every rank's local part.  A range search then takes ``ShardedSearcher.range_gather_merge``'s two
-all-gathers (per-rank totals, then the records padded to the largest) and rank 0's ``sskd_range_merge_packed``.
 """
 from __future__ import annotations
 
 import json
 from pathlib import Path
-from typing import Callable, Dict, List, Optional, Tuple, Union
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
-from .dist import ShardedSearcher, shard_bounds
+from .dist import ShardedSearcher, _world, shard_bounds
 from .index import range_thresholds
 
 MANIFEST = "shards.json"
+# the header's first word; the second is the number of queries (search, range) or the length of the ids to remove or
+# of the directory to load, the third k
 _OP_STOP, _OP_SEARCH, _OP_LOAD, _OP_REMOVE, _OP_RANGE = 0, 1, 2, 3, 4
 # how a call's global filter travels on the control group (the header's 4th word; the 5th is its length)
 _FILTER_NONE, _FILTER_MASK, _FILTER_IDS = 0, 1, 2
@@ -69,14 +79,6 @@ class ShardFailure(RuntimeError):
         self.failures = dict(failures)
         detail = "; ".join(f"rank {r}: {m}" for r, m in sorted(self.failures.items()))
         super().__init__(f"{what} failed on {len(self.failures)} rank(s): {detail}")
-
-
-def _world(group=None) -> Tuple[int, int]:
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size(group), dist.get_rank(group)
-    return 1, 0
 
 
 def _default_factory(embedding_dim: int, metric: str, device, id_offset: int):
@@ -145,9 +147,9 @@ class ShardedIndex:
     def __init__(self, embedding_dim: int = 384, index_type: str = "HNSW", metric: str = "cosine",
                  device: Optional[str] = None, group=None, index_factory: Optional[Callable] = None,
                  ctrl_group=None, op_timeout_s: float = 60.0, idle_timeout_s: float = 365 * 86400.0) -> None:
-        """``group``: the data-path group (queries, packed records); ``ctrl_group``: a gloo group of the same ranks for
-        headers and status words (made on first use when ``group`` is the default group); ``op_timeout_s``: how long a
-        status exchange may take before the missing ranks are declared failed; ``idle_timeout_s``: how long the
+        """``group``: the data-path group (packed records); ``ctrl_group``: a gloo group of the same ranks for headers,
+        call inputs and status words (made on first use when ``group`` is the default group); ``op_timeout_s``: how
+        long a status exchange may take before the missing ranks are declared failed; ``idle_timeout_s``: how long the
         waiting ranks may sit without an announcement from rank 0."""
         self.embedding_dim, self.index_type, self.metric, self.device, self.group = embedding_dim, index_type, metric, device, group
         self._factory = index_factory or _default_factory
@@ -156,21 +158,13 @@ class ShardedIndex:
         self.doc_texts: Optional[Dict[str, str]] = None
         self.ntotal = 0
         self.manifest: Optional[Dict] = None
-        self._searcher: Optional[ShardedSearcher] = None
+        self._searcher = ShardedSearcher(self._local_search, group=group)   # reads self.local at call time
         self._ctrl_group = ctrl_group
         self.op_timeout_s, self.idle_timeout_s = float(op_timeout_s), float(idle_timeout_s)
         self.broken: Optional[str] = None      # set when a rank stopped answering: the process group is unusable
         self.last_failure: Optional[Dict[int, str]] = None
 
-    # ------------------------------------------------------------------ collective plumbing
-    def _comm_device(self) -> torch.device:
-        import torch.distributed as dist
-
-        world, _ = _world(self.group)
-        if world > 1 and dist.get_backend(self.group) != "gloo":
-            return torch.device(self.local.device if self.local is not None else (self.device or "cuda"))
-        return torch.device("cpu")
-
+    # ------------------------------------------------------------------ the collective step
     def _src(self) -> int:
         import torch.distributed as dist
 
@@ -192,18 +186,37 @@ class ShardedIndex:
                 self._ctrl_group = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=self.idle_timeout_s))
         return self._ctrl_group
 
-    def _header(self, op: int = 0, a: int = 0, b: int = 0, fkind: int = _FILTER_NONE,
-                flen: int = 0) -> Tuple[int, int, int, int, int]:
-        """rank 0 announces the next collective step; the others learn it (a HOST broadcast: waiting costs no GPU
-        and no watchdog can abort it).  ``fkind`` / ``flen``: the kind and length of the filter that follows."""
+    def _wire(self, header: Tuple[int, ...]) -> List[Tuple[Tuple[int, ...], torch.dtype]]:
+        """``(shape, dtype)`` of the host tensors that follow a header: a call's inputs are fixed by its header words"""
+        op, n, _, fkind, flen = header
+        if op == _OP_STOP:
+            return []
+        if op == _OP_LOAD:
+            return [((n,), torch.uint8)]                              # the directory, utf-8
+        if op == _OP_REMOVE:
+            return [((n,), torch.int64)]                              # global row ids
+        wire = [((n, self.embedding_dim), torch.float32)]             # the query block
+        if op == _OP_RANGE:
+            wire.append(((n,), torch.float32))                        # one threshold per query
+        if fkind != _FILTER_NONE:                                     # the GLOBAL filter
+            wire.append(((flen,), torch.uint8 if fkind == _FILTER_MASK else torch.int64))
+        return wire
+
+    def _announce(self, header: Tuple[int, ...] = (_OP_STOP, 0, 0, _FILTER_NONE, 0),
+                  inputs: Sequence[torch.Tensor] = ()) -> Tuple[Tuple[int, ...], List[torch.Tensor]]:
+        """rank 0 sends a call's header and inputs, the other ranks receive them: HOST broadcasts on the CONTROL group
+        (waiting costs no GPU and no watchdog can abort it), never on the data group, which nothing enters before the
+        status exchange"""
         import torch.distributed as dist
 
-        world, rank = _world(self.group)
-        if world == 1:
-            return op, a, b, fkind, flen
-        h = torch.tensor([op, a, b, fkind, flen], dtype=torch.int64)
+        h = torch.tensor(header, dtype=torch.int64)
         dist.broadcast(h, src=self._src(), group=self._ctrl())
-        return tuple(int(x) for x in h)
+        header = tuple(int(x) for x in h)
+        if _world(self.group)[1] != 0:
+            inputs = [torch.empty(shape, dtype=dtype) for shape, dtype in self._wire(header)]
+        for t in inputs:
+            dist.broadcast(t, src=self._src(), group=self._ctrl())
+        return header, list(inputs)
 
     def _exchange_status(self, what: str, error: Optional[BaseException]) -> Dict[int, str]:
         """Every rank reports one word (0 = its part succeeded); returns ``{rank: message}`` of the failed ranks, the
@@ -231,6 +244,46 @@ class ShardedIndex:
         texts: List[Optional[str]] = [None] * world
         dist.all_gather_object(texts, None if error is None else f"{type(error).__name__}: {error}", group=ctrl)
         return {r: texts[r] or "failed" for r in failed}
+
+    def _step(self, header: Tuple[int, ...], inputs: Sequence[torch.Tensor]):
+        """One operation, run alike by every rank once it has the header and the inputs: the op's local part inside
+        ``try``, ONE status exchange, then the op's finish only when every rank succeeded - the data group is entered
+        nowhere else.  Otherwise every rank runs the op's abort and raises ``ShardFailure``; at world 1 a search or
+        range search raises the local exception itself."""
+        op = _OPS[header[0]]
+        what = f"load {_text(inputs[0])}" if header[0] == _OP_LOAD else op.name
+        part, error = None, None
+        try:
+            if op.needs_index and self.local is None:
+                raise RuntimeError("no index loaded on this rank")
+            part = op.part(self, header, inputs)
+        except Exception as exc:  # noqa: BLE001 - reported to every rank below
+            if op.bare_at_world_1 and _world(self.group)[0] == 1:
+                raise
+            error = exc
+        failures = self._exchange_status(what, error)
+        self.last_failure = failures or None
+        if failures:
+            if part is not None and op.abort is not None:
+                op.abort(self, part)
+            raise ShardFailure(what, failures) from error
+        return op.finish(self, header, part)
+
+    def _call(self, header: Tuple[int, ...], inputs: Sequence[torch.Tensor]):
+        """rank 0 (or the one process): announce a checked call to the ranks in ``serve_forever`` and take part in it"""
+        if _world(self.group)[0] > 1:
+            self._announce(header, inputs)
+        return self._step(header, inputs)
+
+    def _prelude(self, op: int) -> None:
+        """rank 0, before a call's arguments are checked: it is rank 0's call, the deployment answers, and an index is
+        loaded when the op needs one"""
+        if _OPS[op].needs_index and self.local is None:
+            raise RuntimeError("index is empty: call load first")
+        world, rank = _world(self.group)
+        if world > 1 and rank != 0:
+            raise RuntimeError(f"ShardedIndex.{_OPS[op].name} is rank 0's call; the other ranks run serve_forever()")
+        self._check_usable()
 
     # ------------------------------------------------------------------ load
     @staticmethod
@@ -282,100 +335,66 @@ class ShardedIndex:
             staged["doc_ids"], staged["doc_texts"] = ids, (texts or None)
         return staged
 
-    def _commit(self, staged: Dict) -> None:
+    def _load_part(self, header, inputs) -> Dict:
+        return self._prepare_local(Path(_text(inputs[0])))
+
+    def _commit(self, header, staged: Dict) -> None:
+        """phase 2 of a load, on EVERY rank or on none"""
         old = self.local
         self.local, self.manifest = staged["local"], staged["manifest"]
         self.ntotal = int(self.manifest["n_total"])
         self.metric = self.manifest.get("metric", self.metric)
         self.doc_ids, self.doc_texts = staged["doc_ids"], staged["doc_texts"]
-        self._searcher = ShardedSearcher(self._local_search, group=self.group)
         if old is not None and old is not self.local and hasattr(old, "cleanup"):
             old.cleanup()
 
-    def _load_local(self, index_dir: Path) -> None:
-        """prepare -> one status word per rank -> commit on EVERY rank or on none"""
-        staged, error = None, None
-        try:
-            staged = self._prepare_local(Path(index_dir))
-        except Exception as exc:  # noqa: BLE001 - reported to every rank below
-            error = exc
-        failures = self._exchange_status(f"load {index_dir}", error)
-        self.last_failure = failures or None
-        if failures:
-            if staged is not None and hasattr(staged["local"], "cleanup"):
-                staged["local"].cleanup()
-            raise ShardFailure(f"load {index_dir}", failures) from error
-        self._commit(staged)
+    def _discard(self, staged: Dict) -> None:
+        if hasattr(staged["local"], "cleanup"):
+            staged["local"].cleanup()
 
     def load(self, index_dir: Union[str, Path]) -> None:
         """Collective: on rank 0 (the caller in a served deployment) this tells the ranks waiting in
         ``serve_forever`` to load the same directory.  When every rank calls it directly (start-up), pass through
         ``load_all_ranks`` instead.  Raises ``ShardFailure`` when any rank cannot load its shards; the index that
         was being served stays in place on every rank."""
-        import torch.distributed as dist
-
         index_dir = Path(index_dir)
-        world, rank = _world(self.group)
-        if world > 1:
-            if rank != 0:
-                raise RuntimeError("ShardedIndex.load is rank 0's call; the other ranks run serve_forever()")
-            self._check_usable()
+        self._prelude(_OP_LOAD)
+        if _world(self.group)[0] > 1:
             self.read_manifest(index_dir, self.embedding_dim)   # nothing is announced for a directory rank 0 cannot read
-            self._header(_OP_LOAD)
-            dist.broadcast_object_list([str(index_dir)], src=self._src(), group=self._ctrl())
-        self._load_local(index_dir)
+        self._call(*_load_call(index_dir))
 
     def load_all_ranks(self, index_dir: Union[str, Path]) -> None:
         """Start-up form: EVERY rank calls this with the same directory (no announcement needed).  Raises
         ``ShardFailure`` on every rank when any rank fails, so that the launcher exits instead of hanging."""
-        self._load_local(Path(index_dir))
+        self._step(*_load_call(Path(index_dir)))
 
     # ------------------------------------------------------------------ removal
-    def _remove_collective(self, ids: Optional[torch.Tensor], n_ids: int) -> int:
-        """every rank: the ids from rank 0 (ctrl group) -> its own ``[id_offset, id_offset + rows)`` share -> one
-        status word per rank -> the sum of the rows newly removed"""
+    def _remove_part(self, header, inputs) -> int:
+        """this rank's ``[id_offset, id_offset + rows)`` share of the ids -> the rows it newly removed"""
+        ids, lo = inputs[0], int(self.local.id_offset)
+        mine = ids[(ids >= lo) & (ids < lo + int(self.local.ntotal))]
+        return int(self.local.remove_ids(mine.numpy())) if mine.numel() else 0
+
+    def _remove_finish(self, header, newly: int) -> int:
+        """the sum over the ranks of the rows newly removed (control group)"""
         import torch.distributed as dist
 
-        world, rank = _world(self.group)
-        if world > 1:
-            buf = ids if rank == 0 else torch.empty(n_ids, dtype=torch.int64)
-            dist.broadcast(buf, src=self._src(), group=self._ctrl())
-            ids = buf
-        error, newly = None, 0
-        try:
-            if self.local is None:
-                raise RuntimeError("no index loaded on this rank")
-            lo = int(self.local.id_offset)
-            mine = ids[(ids >= lo) & (ids < lo + int(self.local.ntotal))]
-            newly = int(self.local.remove_ids(mine.numpy())) if mine.numel() else 0
-        except Exception as exc:  # noqa: BLE001 - reported to every rank below
-            error = exc
-        failures = self._exchange_status("remove_ids", error)
-        self.last_failure = failures or None
-        if failures:
-            raise ShardFailure("remove_ids", failures) from error
-        if world > 1:
-            total = torch.tensor([newly], dtype=torch.int64)
-            dist.all_reduce(total, group=self._ctrl())
-            newly = int(total[0])
-        return newly
+        if _world(self.group)[0] == 1:
+            return newly
+        total = torch.tensor([newly], dtype=torch.int64)
+        dist.all_reduce(total, group=self._ctrl())
+        return int(total[0])
 
     def remove_ids(self, global_ids) -> int:
         """Take GLOBAL row ids out of every later search on every rank (rank 0's call; the other ranks follow from
         ``serve_forever``).  Returns the number of rows newly removed; ``ValueError`` for ids outside
         ``[0, ntotal)`` (nothing is announced then); ``ShardFailure`` when a rank could not apply its share."""
-        if self.local is None:
-            raise RuntimeError("index is empty: call load first")
-        world, rank = _world(self.group)
-        if world > 1 and rank != 0:
-            raise RuntimeError("ShardedIndex.remove_ids is rank 0's call; the other ranks run serve_forever()")
-        self._check_usable()
-        ids = torch.as_tensor(np.asarray(global_ids.cpu() if isinstance(global_ids, torch.Tensor) else global_ids,
-                                         dtype=np.int64).reshape(-1))
+        self._prelude(_OP_REMOVE)
+        ids = torch.from_numpy(np.ascontiguousarray(global_ids.cpu() if isinstance(global_ids, torch.Tensor) else global_ids,
+                                                    dtype=np.int64).reshape(-1))
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal):
             raise ValueError(f"ids outside [0, {self.ntotal})")
-        self._header(_OP_REMOVE, ids.numel())
-        return self._remove_collective(ids, ids.numel())
+        return self._call((_OP_REMOVE, ids.numel(), 0, _FILTER_NONE, 0), [ids])
 
     # ------------------------------------------------------------------ state
     @property
@@ -399,91 +418,36 @@ class ShardedIndex:
         return self.local.search_device(queries, k, normalize_queries=None, out_scores=out_scores, out_ids=out_ids,
                                         **extra)
 
-    def _check_filter(self, allow) -> Tuple[int, Optional[torch.Tensor]]:
-        """rank 0, before anything is announced: a GLOBAL filter -> ``(kind, host tensor)`` as it goes on the wire (a
-        bool mask over ``ntotal`` rows as uint8, or int64 global ids); ValueError for a wrong length, dtype or id"""
+    def _check_filter(self, allow) -> Tuple[Tuple[int, int], List[torch.Tensor]]:
+        """rank 0, before anything is announced: a GLOBAL filter -> its header words ``(kind, length)`` and the host
+        tensor that goes on the wire (a bool mask over ``ntotal`` rows as uint8, or int64 global ids; none for no
+        filter); ValueError for a wrong length, dtype or id"""
         if allow is None:
-            return _FILTER_NONE, None
+            return (_FILTER_NONE, 0), []
         a = allow.cpu().numpy() if isinstance(allow, torch.Tensor) else np.asarray(allow)
         if a.dtype == np.bool_:
             if a.shape != (self.ntotal,):
                 raise ValueError(f"a boolean filter needs one entry per row: shape {a.shape}, index has {self.ntotal} rows")
-            return _FILTER_MASK, torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
+            return (_FILTER_MASK, a.size), [torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))]
         if a.dtype.kind in "iu" or a.size == 0:
             ids = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
             if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal):
                 raise ValueError(f"filter ids outside [0, {self.ntotal})")
-            return _FILTER_IDS, torch.from_numpy(ids)
+            return (_FILTER_IDS, ids.size), [torch.from_numpy(ids)]
         raise ValueError(f"a filter is a bool array over the rows or an integer id array, got dtype {a.dtype}")
 
-    def _local_filter(self, fkind: int, filt: Optional[torch.Tensor]):
-        """this rank's slice ``[lo, lo + rows)`` of a global filter, in the form its local index takes"""
-        if fkind == _FILTER_NONE:
+    def _local_filter(self, filt: Sequence[torch.Tensor]):
+        """this rank's slice ``[lo, lo + rows)`` of the call's global filter (none, a uint8 mask or int64 ids), in the
+        form its local index takes"""
+        if not filt:
             return None
         lo, rows = int(self.local.id_offset), int(self.local.ntotal)
-        if fkind == _FILTER_MASK:
-            return filt[lo : lo + rows].numpy().astype(np.bool_)
-        ids = filt.numpy()
+        if filt[0].dtype == torch.uint8:
+            return filt[0][lo : lo + rows].numpy().astype(np.bool_)
+        ids = filt[0].numpy()
         return ids[(ids >= lo) & (ids < lo + rows)]
 
-    def _call_inputs(self, q, thr, filt, nq: int, fkind: int, flen: int, with_thresholds: bool):
-        """rank 0's queries [, thresholds] [, filter] of a filtered search or a range search -> every rank, as host
-        tensors over the CONTROL group (never the data group: nothing is entered there before the status exchange)"""
-        import torch.distributed as dist
-
-        rank = _world(self.group)[1]
-
-        def bcast(t, shape, dtype):
-            buf = t.contiguous() if rank == 0 else torch.empty(shape, dtype=dtype)
-            dist.broadcast(buf, src=self._src(), group=self._ctrl())
-            return buf
-
-        q = bcast(q, (nq, self.embedding_dim), torch.float32)
-        if with_thresholds:
-            thr = bcast(thr, (nq,), torch.float32)
-        if fkind != _FILTER_NONE:
-            filt = bcast(filt, (flen,), torch.uint8 if fkind == _FILTER_MASK else torch.int64)
-        return q, thr, filt
-
-    def _collective_search(self, queries: Optional[torch.Tensor], nq: int, k: int, fkind: int = _FILTER_NONE,
-                           filt: Optional[torch.Tensor] = None, flen: int = 0):
-        import torch.distributed as dist
-
-        world, rank = _world(self.group)
-        if world == 1:
-            if fkind != _FILTER_NONE:
-                return self._local_search(queries.to(torch.device(self.local.device)), k,
-                                          allow=self._local_filter(fkind, filt))
-            return self._searcher.search(queries.to(torch.device(self.local.device)), k)
-        error, partial = None, None
-        if fkind != _FILTER_NONE:   # a filtered search: queries and filter over the control group
-            buf, _, filt = self._call_inputs(queries, None, filt, nq, fkind, flen, with_thresholds=False)
-        else:
-            comm = self._comm_device()
-            buf = queries.to(comm) if rank == 0 else torch.empty((nq, self.embedding_dim), dtype=torch.float32, device=comm)
-            dist.broadcast(buf, src=self._src(), group=self.group)
-        try:
-            if self.local is None:
-                raise RuntimeError("no index loaded on this rank")
-            partial = self._searcher.search_local(buf.to(torch.device(self.local.device)), k,
-                                                  allow=self._local_filter(fkind, filt))
-        except Exception as exc:  # noqa: BLE001 - reported below; this rank still answers the status exchange
-            error = exc
-        failures = self._exchange_status("search", error)
-        self.last_failure = failures or None
-        if failures:
-            if rank == 0:
-                raise ShardFailure("search", failures) from error
-            return None
-        return self._searcher.gather_merge(partial, nq, k)
-
-    def _check_queries(self, query_emb, what: str) -> np.ndarray:
-        if self.local is None:
-            raise RuntimeError("index is empty: call load first")
-        world, rank = _world(self.group)
-        if world > 1 and rank != 0:
-            raise RuntimeError(f"ShardedIndex.{what} is rank 0's call; the other ranks run serve_forever()")
-        self._check_usable()
+    def _check_queries(self, query_emb) -> np.ndarray:
         q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
         if q.ndim == 1:
             q = q[None, :]
@@ -491,83 +455,59 @@ class ShardedIndex:
             raise ValueError(f"queries have shape {q.shape}, expected [nq, {self.embedding_dim}]")
         return q
 
+    def _search_part(self, header, inputs) -> torch.Tensor:
+        q, *filt = inputs
+        return self._searcher.search_local(q.to(torch.device(self.local.device)), header[2], allow=self._local_filter(filt))
+
+    def _search_finish(self, header, record: torch.Tensor):
+        return self._searcher.gather_merge(record, header[1], header[2])
+
     def search(self, query_emb: np.ndarray, k: int = 10, *, allow=None) -> Tuple[np.ndarray, np.ndarray]:
         """``(distances [nq, k] fp32 desc, GLOBAL row ids [nq, k] int64, -1 padded)`` - rank 0's call.  ``allow``: an
         optional GLOBAL filter, a bool array over ``ntotal`` rows or an integer array of global ids; removed rows are
         never returned."""
         # everything that can be wrong with the CALL is found before the other ranks hear of it
-        q = self._check_queries(query_emb, "search")
+        self._prelude(_OP_SEARCH)
+        q = self._check_queries(query_emb)
         if int(k) < 1:
             raise ValueError(f"k must be >= 1, got {k}")
-        fkind, filt = self._check_filter(allow)
+        fwords, filt = self._check_filter(allow)
         if q.shape[0] == 0:
             return np.zeros((0, int(k)), np.float32), np.zeros((0, int(k)), np.int64)
-        flen = 0 if filt is None else filt.numel()
-        self._header(_OP_SEARCH, q.shape[0], int(k), fkind, flen)
-        s, i = self._collective_search(torch.from_numpy(q), q.shape[0], int(k), fkind, filt, flen)
+        s, i = self._call((_OP_SEARCH, q.shape[0], int(k), *fwords), [torch.from_numpy(q), *filt])
         return s.cpu().numpy(), i.cpu().numpy()
 
-    def _local_range(self, q: torch.Tensor, thr: torch.Tensor, allow):
+    def _range_part(self, header, inputs):
+        q, thr, *filt = inputs
         dev = torch.device(self.local.device)
-        return self.local.range_search_device(q.to(dev), thr.to(dev), allow=allow, normalize_queries=None)
+        return self.local.range_search_device(q.to(dev), thr.to(dev), allow=self._local_filter(filt), normalize_queries=None)
 
-    def _collective_range(self, queries: Optional[torch.Tensor], thr: Optional[torch.Tensor], nq: int, fkind: int,
-                          filt: Optional[torch.Tensor], flen: int):
-        world, rank = _world(self.group)
-        if world == 1:
-            return self._local_range(queries, thr, self._local_filter(fkind, filt))
-        q, thr, filt = self._call_inputs(queries, thr, filt, nq, fkind, flen, with_thresholds=True)
-        error, part = None, None
-        try:
-            if self.local is None:
-                raise RuntimeError("no index loaded on this rank")
-            part = self._local_range(q, thr, self._local_filter(fkind, filt))
-        except Exception as exc:  # noqa: BLE001 - reported below; this rank still answers the status exchange
-            error = exc
-        failures = self._exchange_status("range_search", error)   # nothing on the data group before this agreement
-        self.last_failure = failures or None
-        if failures:
-            if rank == 0:
-                raise ShardFailure("range_search", failures) from error
-            return None
-        return self._searcher.range_gather_merge(*part, nq)
+    def _range_finish(self, header, part):
+        return self._searcher.range_gather_merge(*part, header[1])
 
     def range_search(self, query_emb: np.ndarray, threshold, *, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """faiss ``range_search`` over every shard - rank 0's call: every allowed, not removed row scoring
         ``> threshold`` (a float, or one per query) as NumPy ``(lims int64 [nq + 1], D float32, I int64)`` with GLOBAL
         ids; query ``q``'s results are ``[lims[q], lims[q + 1])``, sorted by score descending, then id ascending - bit
         for bit what one ``FAISSIndexBuilder.range_search`` over the whole corpus returns.  ``allow`` as in ``search``."""
-        q = self._check_queries(query_emb, "range_search")
+        self._prelude(_OP_RANGE)
+        q = self._check_queries(query_emb)
         thr = range_thresholds(threshold, q.shape[0])
-        fkind, filt = self._check_filter(allow)
-        nq = q.shape[0]
-        if nq == 0:
+        fwords, filt = self._check_filter(allow)
+        if q.shape[0] == 0:
             return np.zeros(1, np.int64), np.zeros(0, np.float32), np.zeros(0, np.int64)
-        flen = 0 if filt is None else filt.numel()
-        self._header(_OP_RANGE, nq, 0, fkind, flen)
-        lims, scores, ids = self._collective_range(torch.from_numpy(q), torch.from_numpy(thr), nq, fkind, filt, flen)
+        lims, scores, ids = self._call((_OP_RANGE, q.shape[0], 0, *fwords), [torch.from_numpy(q), torch.from_numpy(thr), *filt])
         return lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
 
     def serve_forever(self) -> None:
         """Ranks other than 0: answer rank 0's announcements until it says stop.  An operation that fails HERE is
         reported to rank 0 through the status word and the loop goes on; only a broken process group ends it."""
-        import torch.distributed as dist
-
         while True:
-            op, a, b, fkind, flen = self._header()
-            if op == _OP_STOP:
+            header, inputs = self._announce()
+            if header[0] == _OP_STOP:
                 return
             try:
-                if op == _OP_SEARCH:
-                    self._collective_search(None, a, b, fkind, None, flen)
-                elif op == _OP_RANGE:
-                    self._collective_range(None, None, a, fkind, None, flen)
-                elif op == _OP_LOAD:
-                    box = [None]
-                    dist.broadcast_object_list(box, src=self._src(), group=self._ctrl())
-                    self._load_local(Path(box[0]))
-                elif op == _OP_REMOVE:
-                    self._remove_collective(None, a)
+                self._step(header, inputs)
             except ShardFailure:
                 if self.broken is not None:
                     raise
@@ -577,11 +517,40 @@ class ShardedIndex:
         """rank 0: release the ranks waiting in ``serve_forever``"""
         world, rank = _world(self.group)
         if world > 1 and rank == 0 and self.broken is None:
-            self._header(_OP_STOP)
+            self._announce()
 
     def cleanup(self) -> None:
         if self.local is not None:
             self.local.cleanup()
+
+
+class _Op(NamedTuple):
+    """What every rank runs for one operation in ``ShardedIndex._step``."""
+
+    name: str                          # the public call (rank 0's checks, ShardFailure)
+    part: Callable                     # (index, header, inputs) -> this rank's part; runs inside try
+    finish: Callable                   # (index, header, part) -> the call's result, once every rank has succeeded
+    abort: Optional[Callable] = None   # (index, part): drop this rank's part when another rank failed
+    needs_index: bool = True           # every rank must hold an index
+    bare_at_world_1: bool = False      # world 1 raises the local exception itself rather than ShardFailure
+
+
+_OPS = {
+    _OP_SEARCH: _Op("search", ShardedIndex._search_part, ShardedIndex._search_finish, bare_at_world_1=True),
+    _OP_RANGE: _Op("range_search", ShardedIndex._range_part, ShardedIndex._range_finish, bare_at_world_1=True),
+    _OP_LOAD: _Op("load", ShardedIndex._load_part, ShardedIndex._commit, ShardedIndex._discard, needs_index=False),
+    _OP_REMOVE: _Op("remove_ids", ShardedIndex._remove_part, ShardedIndex._remove_finish),
+}
+
+
+def _load_call(index_dir: Path) -> Tuple[Tuple[int, ...], List[torch.Tensor]]:
+    """the header and the input of a load: the directory as utf-8 bytes"""
+    path = torch.from_numpy(np.frombuffer(str(index_dir).encode(), dtype=np.uint8).copy())
+    return (_OP_LOAD, path.numel(), 0, _FILTER_NONE, 0), [path]
+
+
+def _text(t: torch.Tensor) -> str:
+    return t.numpy().tobytes().decode()
 
 
 def open_index(index_dir: Union[str, Path], embedding_dim: int = 384, current=None, device: Optional[str] = None):

@@ -123,14 +123,7 @@ def _serve_worker(rank, world, port, tmp, index_dir, second_dir):
     try:
         index = ShardedIndex(index_factory=_factory)
         index.load_all_ranks(index_dir)
-        index._searcher.merge = _oracle_merge
-        orig_commit = index._commit
-
-        def commit(staged):   # a reload builds a new searcher: give it the CPU merge again
-            orig_commit(staged)
-            index._searcher.merge = _oracle_merge
-
-        index._commit = commit
+        index._searcher.merge = _oracle_merge   # the one searcher of the index: a reload keeps it
         if rank != 0:
             index.serve_forever()
             return
@@ -143,7 +136,6 @@ def _serve_worker(rank, world, port, tmp, index_dir, second_dir):
         assert index.ntotal == N_DOCS
         # hot reload (the /index/load route): the waiting ranks follow rank 0
         index.load(second_dir)
-        index._searcher.merge = _oracle_merge
         s, i = index.search(_queries(), 10)
         assert np.array_equal(i, ref_i) and np.array_equal(s, ref_s)
         index.close()
@@ -219,13 +211,6 @@ def _failing_worker(rank, world, port, tmp, good_dir, bad_dir):
     try:
         index = ShardedIndex(index_factory=_flaky_factory, op_timeout_s=30.0)
         index.load_all_ranks(good_dir)
-        orig_commit = index._commit
-
-        def commit(staged):   # every (re)load builds a new searcher: give it the CPU merge again
-            orig_commit(staged)
-            index._searcher.merge = _oracle_merge
-
-        index._commit = commit
         index._searcher.merge = _oracle_merge
         if rank != 0:
             index.serve_forever()

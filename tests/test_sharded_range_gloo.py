@@ -113,14 +113,6 @@ def _factory(embedding_dim, metric, device, id_offset):
 def _cpu_merges(index):
     index._searcher.merge = _oracle_merge
     index._searcher.range_merge = numpy_range_merge
-    orig_commit = index._commit
-
-    def commit(staged):   # every (re)load builds a new searcher: give it the CPU merges again
-        orig_commit(staged)
-        index._searcher.merge = _oracle_merge
-        index._searcher.range_merge = numpy_range_merge
-
-    index._commit = commit
 
 
 def _thresholds(s):
@@ -239,6 +231,75 @@ def test_sharded_range_and_filtered_search_over_gloo(tmp_path, world):
     mp.spawn(_build_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     mp.spawn(_serve_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     assert (tmp_path / f"range_ok_w{world}").exists()
+
+
+def _record_groups(data):
+    """wrap the collectives the sharded index calls; returns the names of those called on the ``data`` group"""
+    on_data = []
+    for name in ("broadcast", "all_gather_into_tensor", "all_reduce", "broadcast_object_list"):
+        def wrapped(*args, _orig=getattr(dist, name), _name=name, **kwargs):
+            if kwargs.get("group") is data:
+                on_data.append(_name)
+            return _orig(*args, **kwargs)
+
+        setattr(dist, name, wrapped)
+    return on_data
+
+
+def _groups_worker(rank, world, port, tmp):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    FilterOracleIndex.tmp = tmp
+    try:
+        data, ctrl = dist.new_group(backend="gloo"), dist.new_group(backend="gloo")
+        index = ShardedIndex(group=data, ctrl_group=ctrl, index_factory=_factory, op_timeout_s=30.0)
+        index.load_all_ranks(Path(tmp) / "index")
+        _cpu_merges(index)
+        on_data = _record_groups(data)
+        if rank != 0:
+            index.serve_forever()   # the same collectives as rank 0: only the record all-gathers of the good calls
+            assert on_data == ["all_gather_into_tensor"] * int((Path(tmp) / "data_calls").read_text()), on_data
+            (Path(tmp) / f"groups_ok_rank{rank}").write_text("ok")
+            return
+        q = _queries()
+        s = _expected_scores(set())
+        thr = _thresholds(s)
+        mask = np.arange(N_DOCS) % 3 != 0
+        # a rank's local part raises: nothing reaches the data group, on any rank
+        for r, what, call in ((1, "search", lambda: index.search(q, 10)),
+                              (0, "search", lambda: index.search(q, 10)),
+                              (1, "search", lambda: index.search(q, 10, allow=mask)),
+                              (1, "range", lambda: index.range_search(q, thr)),
+                              (0, "range", lambda: index.range_search(q, thr, allow=mask))):
+            (Path(tmp) / f"fail_{what}_rank{r}").write_text("x")
+            with pytest.raises(ShardFailure):
+                call()
+            assert on_data == [], (r, what, on_data)
+        # load and remove stay on the control group; a good search or range call enters the data group only with
+        # the record all-gathers (one for a search, the totals and the records for a range search)
+        index.load(Path(tmp) / "index")
+        assert index.remove_ids([5]) == 1 and on_data == []
+        s = _expected_scores({5})
+        for n, call, check in ((1, lambda: index.search(q, 10), lambda got: _same_topk(got, oracle.topk_of_scores(s, 10), "")),
+                               (1, lambda: index.search(q, 10, allow=mask),
+                                lambda got: _same_topk(got, oracle.topk_of_scores(_expected_scores({5}, mask), 10), "")),
+                               (2, lambda: index.range_search(q, thr), lambda got: _same_range(got, range_of_scores(s, thr), ""))):
+            before = len(on_data)
+            check(call())
+            assert on_data[before:] == ["all_gather_into_tensor"] * n, on_data
+        (Path(tmp) / "data_calls").write_text(str(len(on_data)))
+        index.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_sharded_calls_enter_the_data_group_only_after_agreement(tmp_path):
+    """data and control on two separate gloo groups: a call in which some rank's local part fails makes no call on the
+    data group at all, and a good search or range call uses it only for the record all-gathers"""
+    _corpus(tmp_path)
+    mp.spawn(_build_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_groups_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    assert (tmp_path / "groups_ok_rank1").exists()
 
 
 def test_sharded_range_and_filtered_search_world_one(tmp_path):
