@@ -376,6 +376,17 @@ int sskd_encoder_hidden(const sskd_encoder_config* cfg, const sskd_encoder_weigh
                         void* d_hidden_bf16, void* d_workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Per-kernel test hook: runs cfg->layers layers (0 is legal: the embedding LayerNorm alone) and
+ * returns BOTH activation buffers as row-major bf16 [B, S, 384]: the hidden states and the
+ * attention context of the last layer run (unspecified for 0 layers).  d_seg != NULL: packed rows
+ * (segment words of sskd_pack_tokens, S = capacity, a multiple of 32 up to 256), d_mask is then
+ * unused.  Two calls with cfg->layers = l and l + 1 give every kernel of layer l its own inputs and
+ * outputs (the kernels are bit-deterministic).  No kernel beyond those of sskd_encoder_hidden. */
+int sskd_encoder_probe(const sskd_encoder_config* cfg, const sskd_encoder_weights* w,
+                       const int32_t* d_ids, const int32_t* d_mask, const int32_t* d_seg, int B, int S,
+                       void* d_hidden_bf16, void* d_context_bf16, void* d_workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Sequence packing (varlen / "cu_seqlens"): SentenceTransformer.encode pads every text of a
  * batch to the longest one (reference: tests/test_model_validation.py:80-110); here whole

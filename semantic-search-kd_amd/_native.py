@@ -201,6 +201,10 @@ SIGNATURES = {
         _i,
         [C.POINTER(EncoderConfig), C.POINTER(EncoderWeights), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp],
     ),
+    "sskd_encoder_probe": (
+        _i,
+        [C.POINTER(EncoderConfig), C.POINTER(EncoderWeights), _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    ),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1457,6 +1457,33 @@ int sskd_encoder_hidden(const sskd_encoder_config* cfg, const sskd_encoder_weigh
   return sskd::check_launch("untile_hidden_kernel");
 }
 
+// Host-only test hook: `cfg->layers` layers (0 = the embedding LayerNorm alone), then BOTH workspace buffers un-tiled:
+// the final hidden states and the attention context of the last layer run (undefined when no layer ran).  With d_seg
+// the rows are packed (d_mask is unused).  Launches the kernels of sskd_encoder_hidden, nothing else.
+int sskd_encoder_probe(const sskd_encoder_config* cfg, const sskd_encoder_weights* w,
+                       const int32_t* d_ids, const int32_t* d_mask, const int32_t* d_seg, int B, int S,
+                       void* d_hidden_bf16, void* d_context_bf16, void* d_workspace, size_t workspace_bytes,
+                       void* stream) {
+  Workspace ws{};
+  int rc = prepare(cfg, w, B, S, d_workspace, workspace_bytes, &ws);
+  if (rc != SSKD_OK || B == 0) return rc;
+  SSKD_REQUIRE(d_ids && (d_mask || d_seg) && d_hidden_bf16 && d_context_bf16, "encoder_probe: null pointer");
+  SSKD_REQUIRE(!d_seg || (S >= 32 && S % 32 == 0 && S <= 256),"encoder_probe: packed rows hold a multiple of 32 tokens, at most 256");
+  hipStream_t st = sskd::as_stream(stream);
+  __bf16* fin = nullptr;
+  rc = run_layers(cfg, w, d_ids, d_seg ? nullptr : d_mask, B, S, ws, st, &fin, d_seg);
+  if (rc != SSKD_OK) return rc;
+  const int64_t total = (int64_t)B * S * H;
+  int64_t blocks = sskd::ceil_div(total, 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(untile_hidden_kernel, dim3((unsigned)blocks), dim3(256), 0, st, fin, B, S,
+                     s_pad_of(S) / 32, static_cast<__bf16*>(d_hidden_bf16));
+  if ((rc = sskd::check_launch("untile_hidden_kernel")) != SSKD_OK) return rc;
+  hipLaunchKernelGGL(untile_hidden_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ws.ctx, B, S,
+                     s_pad_of(S) / 32, static_cast<__bf16*>(d_context_bf16));
+  return sskd::check_launch("untile_hidden_kernel");
+}
+
 namespace {
 int forward_rows(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, const int32_t* d_ids,
                  const int32_t* d_mask, int B, int S, int normalize, float* d_out, const Workspace& ws, hipStream_t st) {

@@ -268,12 +268,18 @@ class Mi355xSentenceEncoder:
             mask[i, : len(r)] = 1
         return {"input_ids": ids, "attention_mask": mask}
 
+    def _splits(self, B: int, S: int) -> bool:
+        """Whether ``encode_token_ids`` runs a ``[B, S]`` batch as two halves on two HIP streams."""
+        return self.split_streams and B >= 512 and B % 2 == 0 and S <= 256
+
     def encode_token_ids(
-        self, input_ids, attention_mask=None, normalize: bool = True, out: Optional[torch.Tensor] = None
+        self, input_ids, attention_mask=None, normalize: bool = True, out: Optional[torch.Tensor] = None,
+        _workspaces: Optional[Sequence[torch.Tensor]] = None,
     ) -> torch.Tensor:
         """One forward pass over pre-tokenised ``[B, S]`` int32 ids; returns fp32 ``[B, 384]`` on device.
 
-        Everything is enqueued on the current stream; no host synchronisation.
+        Everything is enqueued on the current stream; no host synchronisation.  ``_workspaces`` (a captured forward's
+        own buffers, one per half when the batch splits) replaces the encoder's shared, growing workspace.
         """
         lib = _native.load()
         self.sync_inference_weights()
@@ -288,7 +294,8 @@ class Mi355xSentenceEncoder:
             out = torch.empty((B, self.config.hidden_size), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        if self.split_streams and B >= 512 and B % 2 == 0 and S <= 256:
+        own = list(_workspaces) if _workspaces is not None else [None, None]
+        if self._splits(B, S):
             # Two halves on two HIP streams: the load/store-bound output projection of one half runs
             # beside the matrix-bound fused MLP of the other (same work, 5-6 % less time at 512 x 256).
             # Fork / join with events: the caller's stream semantics are unchanged.
@@ -298,12 +305,12 @@ class Mi355xSentenceEncoder:
                 self._side_stream = torch.cuda.Stream(self.device)
             side = self._side_stream
             side.wait_stream(main)
-            self._forward_rows(lib, ids[:h], mask[:h], normalize, out[:h], main, "_workspace")
+            self._forward_rows(lib, ids[:h], mask[:h], normalize, out[:h], main, "_workspace", own[0])
             with torch.cuda.stream(side):
-                self._forward_rows(lib, ids[h:], mask[h:], normalize, out[h:], side, "_workspace2")
+                self._forward_rows(lib, ids[h:], mask[h:], normalize, out[h:], side, "_workspace2", own[1])
             main.wait_stream(side)
             return out
-        self._forward_rows(lib, ids, mask, normalize, out, torch.cuda.current_stream(self.device), "_workspace")
+        self._forward_rows(lib, ids, mask, normalize, out, torch.cuda.current_stream(self.device), "_workspace", own[0])
         return out
 
     def capture_forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
@@ -320,11 +327,15 @@ class Mi355xSentenceEncoder:
             out = torch.empty((ids.shape[0], self.config.hidden_size), dtype=torch.float32, device=self.device)
         return GraphedForward(self, ids, mask, bool(normalize), out)
 
-    def _forward_rows(self, lib, ids, mask, normalize, out, stream, ws_name: str) -> None:
+    def _forward_rows(self, lib, ids, mask, normalize, out, stream, ws_name: str,
+                      own_ws: Optional[torch.Tensor] = None) -> None:
         B, S = ids.shape
         need = int(lib.sskd_encoder_workspace_bytes(self.weights.cstruct_cfg, B, S))
-        ws = getattr(self, ws_name)
-        if ws is None or ws.numel() < need:
+        ws = own_ws if own_ws is not None else getattr(self, ws_name)
+        if own_ws is not None:
+            if ws.numel() < need:
+                raise ValueError(f"workspace of {ws.numel()} bytes given, [{B}, {S}] needs {need}")
+        elif ws is None or ws.numel() < need:
             setattr(self, ws_name, None)
             ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             setattr(self, ws_name, ws)
@@ -674,15 +685,23 @@ class GraphedForward:
         self.enc, self.ids, self.mask, self.normalize, self.out = enc, ids, mask, normalize, out
         enc.sync_inference_weights()
         self._weights = enc.weights
+        # The graph bakes in the workspace ADDRESS, and the encoder drops and reallocates its shared workspace whenever a
+        # later eager call needs more bytes: the captured launches get buffers this object owns (one per half when the
+        # forward splits), alive as long as the graph is.
+        B, S = ids.shape
+        lib = _native.load()
+        parts = 2 if enc._splits(B, S) else 1
+        need = max(int(lib.sskd_encoder_workspace_bytes(enc.weights.cstruct_cfg, B // parts, S)), 1)
+        self.workspaces = [torch.empty(need, dtype=torch.uint8, device=enc.device) for _ in range(parts)]
         side = torch.cuda.Stream(enc.device)
         side.wait_stream(torch.cuda.current_stream(enc.device))
-        with torch.cuda.stream(side):          # warm-up off the capture stream: workspace allocation, code load
-            enc.encode_token_ids(ids, mask, normalize=normalize, out=out)
+        with torch.cuda.stream(side):          # warm-up off the capture stream: code load, side-stream creation
+            enc.encode_token_ids(ids, mask, normalize=normalize, out=out, _workspaces=self.workspaces)
         torch.cuda.current_stream(enc.device).wait_stream(side)
         torch.cuda.synchronize(enc.device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            enc.encode_token_ids(ids, mask, normalize=normalize, out=out)
+            enc.encode_token_ids(ids, mask, normalize=normalize, out=out, _workspaces=self.workspaces)
 
     def replay(self) -> torch.Tensor:
         if self.enc.weights is not self._weights or self.enc.sync_inference_weights():

@@ -4,6 +4,10 @@ Tolerances (floating point, stated here as the north star requires): the HIP pat
 bf16 (8-bit mantissa) with fp32 accumulation, the reference in fp32.  For L2-normalised 384-d
 embeddings we require cosine(e_hip, e_ref) >= 0.999 (SURVEY.md §7) and max |e_hip - e_ref| <= 4e-3;
 fp32 kernels (pool + normalise) must agree to 2e-6.
+
+These are END-TO-END gates (after 2-12 layers, the masked mean and the normalisation).  The per-kernel gate - every
+kernel of csrc/encoder.hip against an fp64 reference on its own inputs, per-element derived bounds - is
+tests/test_encoder_kernels_gpu.py.
 """
 import numpy as np
 import pytest
@@ -112,6 +116,28 @@ def test_encoder_cfg2_shape_sampled_rows_vs_oracle(gpu, stress):
     assert emb.shape == (B, 384) and np.isfinite(emb).all()
     np.testing.assert_allclose(np.linalg.norm(emb, axis=1), 1.0, atol=1e-5)
     rows = np.array([0, 5, 100, 255, 256, 257, 300, 511])
+    want = enc_oracle.encode_token_ids(sd, ids[rows], mask[rows], cfg.num_hidden_layers)
+    cos = _cos(emb[rows], want)
+    assert cos.min() >= COS_MIN, cos
+    assert np.abs(emb[rows] - want).max() <= EMB_ATOL
+
+
+@pytest.mark.parametrize("B,S", [(131, 128), (100, 200)])
+def test_encoder_four_heads_per_workgroup_sampled_rows_vs_oracle(enc_l2, B, S):
+    """The attention launch with 4 heads per workgroup (64 <= workgroup rows < 256, csrc/encoder.hip run_layers): 131 x 128
+    is 66 workgroup rows of two sequences, 100 x 200 is 100 rows of one.  Sampled rows (first / last of the batch and of a
+    workgroup, ragged ones) against the fp32 oracle run on those rows alone, same gate as every other shape."""
+    enc, cfg, sd = enc_l2
+    nkt = (S + 31) // 32
+    spw = 8 // nkt if nkt <= 4 else 1
+    assert 64 <= (B + spw - 1) // spw < 256
+    rng = np.random.default_rng(B)
+    lengths = [int(x) for x in rng.integers(2, S + 1, size=B)]
+    lengths[0] = lengths[B - 1] = S
+    ids, mask = enc_oracle.synthetic_token_ids(B, S, seed=700 + S, lengths=lengths)
+    emb = enc.encode_token_ids(ids, mask).cpu().numpy()
+    assert emb.shape == (B, 384) and np.isfinite(emb).all()
+    rows = np.array([0, 1, 2, 63, 64, 65, B - 2, B - 1])
     want = enc_oracle.encode_token_ids(sd, ids[rows], mask[rows], cfg.num_hidden_layers)
     cos = _cos(emb[rows], want)
     assert cos.min() >= COS_MIN, cos
@@ -325,6 +351,42 @@ def test_captured_forward_replays_the_eager_forward(gpu):
     enc.weights = DeviceWeights(cfg, enc._host_state, enc.device)      # e.g. after a training step re-tiled them
     with pytest.raises(RuntimeError, match="weights changed"):
         fwd.replay()
+
+
+@pytest.mark.gpu
+def test_captured_forward_survives_a_larger_eager_encode(gpu):
+    """A captured forward bakes its workspace address into the graph.  The encoder drops and reallocates its shared
+    workspace when a later eager call needs more bytes; a graph that had captured THAT buffer would then write its
+    activations into memory the caching allocator hands to other tensors.  Capture at 64 x 96, encode 512 x 256 eagerly,
+    fill tensors of the old workspace's size with a byte pattern (one of them must land on the shared workspace's old
+    address, or the test proves nothing), replay: the pattern is intact and the replay equals a fresh eager encode bit
+    for bit.  (The cache is never emptied here: the block stays mapped, so a stale address shows as a wrong byte.)"""
+    from semantic_search_kd_amd import _native
+    from semantic_search_kd_amd.bench_support import synthetic_ids
+
+    cfg = BertConfig(num_hidden_layers=2)
+    enc = Mi355xSentenceEncoder.from_synthetic(cfg, device="cuda:0")
+    dev = torch.device("cuda:0")
+    ids, mask = synthetic_ids(64, 96, cfg.vocab_size, dev, seed=3)
+    enc.encode_token_ids(ids, mask)
+    fwd = enc.capture_forward(ids, mask)
+    old_addr, old_bytes = enc._workspace.data_ptr(), enc._workspace.numel()
+    own = getattr(fwd, "workspaces", None)
+    captured_addr = own[0].data_ptr() if own else old_addr     # without a private workspace the graph holds the shared one
+    assert old_bytes == int(_native.load().sskd_encoder_workspace_bytes(enc.weights.cstruct_cfg, 64, 96))
+    big_ids, big_mask = synthetic_ids(512, 256, cfg.vocab_size, dev, seed=5)
+    enc.encode_token_ids(big_ids, big_mask)
+    torch.cuda.synchronize()
+    assert enc._workspace.data_ptr() != old_addr and enc._workspace.numel() > old_bytes
+    sentinels = [torch.full((old_bytes,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(8)]
+    torch.cuda.synchronize()
+    assert any(t.data_ptr() <= old_addr < t.data_ptr() + t.numel() for t in sentinels), \
+        "no sentinel landed on the freed workspace: the scenario is not exercised"
+    got = fwd.replay().clone()
+    torch.cuda.synchronize()
+    hit = [i for i, t in enumerate(sentinels) if not bool((t == 0xA5).all())]
+    assert not hit, f"the replay wrote into tensors {hit} that now own the old workspace (captured address {captured_addr:#x})"
+    assert torch.equal(got, enc.encode_token_ids(ids, mask))
 
 
 @pytest.mark.gpu
