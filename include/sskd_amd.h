@@ -132,7 +132,8 @@ int sskd_index_search_profiled(const float* d_tiled, int64_t n_rows,
  * The band is measured, not assumed: |screen - exact| <= |q~ - q| max|row~| + |q| max|row~ - row| +
  * 1e-4 |q| max(max|row|, max|row~|) (Cauchy-Schwarz on the two bf16 roundings + fp32 accumulation slack), with the
  * query norms taken per query and the row maxima when the sidecar is made; in the worst case (every
- * element on a bf16 tie) that is 2^-7 (1 + 2^-9) |q| max|row|, on random data about 0.42 of it.
+ * element on a bf16 tie) that is 2^-7 (1 + 2^-9) |q| max|row|, on random data about 0.42 of it (DESIGN.md 3.1b records
+ * the measured figures; tests/test_screen_band_gpu.py holds the band and the sidecar to an fp64 reference).
  * The bf16 copy holds the rows MINUS their mean row (q.mean is the same for every row of a query, so
  * ranking is untouched): on anisotropic embeddings (e5: mean pairwise cosine 0.7-0.8) the centred norms,
  * and with them the band, are 2-2.2x smaller.
@@ -151,7 +152,18 @@ int sskd_index_search_profiled(const float* d_tiled, int64_t n_rows,
  * (re-make it after sskd_index_add_rows): the bf16 tiles of the centred rows (768 B per row) and a 4-KiB
  * block with max |row|^2, max |row~|^2, max |row~ - (row - mean)|^2 and the column sums.  Exact re-scoring
  * reads the fp32 index itself (row-major since round 4: index + sidecar = 1.5x the corpus; rounds 2-3 kept a
- * second fp32 copy in the sidecar, 2.5x). */
+ * second fp32 copy in the sidecar, 2.5x).
+ * Sidecar layout, a tested contract (tests/test_screen_band_gpu.py, oracle/search.py sidecar_decode):
+ *   bytes [0, T x 24576), T = ceil(n_rows / 32): tile t, k-step s (0..23), lane l (0..63), element e (0..7) - the
+ *     bf16 at byte ((t x 24 + s) x 64 + l) x 16 + 2 e - holds row 32 t + (l & 31), column 16 s + 8 (l >> 5) + e of
+ *     bf16(fl32(row - mean)), mean = fl32(colsum x fl32(1 / n_rows)); rows past n_rows are all-zero bits;
+ *   norm block at byte T x 24576, 4096 bytes: int32 words 0..2 = the bit patterns of the three maxima above, in that
+ *     order (a row norm that is not finite is stored as +inf), word 3 = the bit pattern of max |element| of the fp32
+ *     rows, floats 64..447 = the column sums of the fp32 rows, everything else zero.  The mean row is not stored.
+ * Range of the band: a query gets no band, and is answered by the exact scan inside the call, when it or a row norm
+ * is not finite, when its largest element is below 2^-96 or the largest corpus element below 2^-40 (an all-zero query
+ * or corpus excepted), or when the band itself falls outside [2^-100, 2^100]: there fp32 sums of squares and
+ * near-denormal products no longer carry the bound. */
 size_t sskd_index_bf16_bytes(int64_t n_rows);
 int sskd_index_make_bf16(const float* d_tiled, int64_t n_rows, void* d_bf16, void* stream);
 size_t sskd_index_search_screened_workspace_bytes(int64_t n_rows, int nq, int k);
@@ -162,6 +174,16 @@ int sskd_index_search_screened(const float* d_tiled, const void* d_bf16, int64_t
                                int nq, int k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
                                int* d_status, void* d_workspace, size_t workspace_bytes, void* stream,
                                void* ev_scan_begin, void* ev_scan_end);
+
+/* Test hook, like sskd_encoder_probe and sskd_generic_op: the error band of every query, d_eps2_out[q] = 2 e(q)
+ * (fp32 [nq]), computed by the same set-up launch sskd_index_search_screened opens with and from the same
+ * sidecar.  +inf means "no band": the query is answered by the exact scan inside the call.  The launch's other
+ * outputs (pruning-bound words, fallback counters, status) go to d_scratch,
+ * sskd_index_screen_band_scratch_bytes(nq) bytes.  tests/test_screen_band_gpu.py holds the band, and the sidecar
+ * it is made from, to an fp64 reference. */
+size_t sskd_index_screen_band_scratch_bytes(int nq);
+int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_eps2_out,
+                           void* d_scratch, size_t scratch_bytes, void* stream);
 
 /* One-pass variant for the online shape (reference: src/serve/app.py:285-301, schemas.py:12-16 -
  * one query, k <= 100, rerank_top_k <= 200).  sskd_index_search serves k > SSKD_K_PASS by chained

@@ -10,7 +10,7 @@ Two restatements of the reference's exact search, which must agree with each oth
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import numpy as np
 
@@ -110,3 +110,96 @@ def seeded_unit_rows(n: int, dim: int, seed: int) -> np.ndarray:
     x = g.standard_normal((n, dim), dtype=np.float32)
     x /= np.linalg.norm(x, axis=1, keepdims=True)
     return x.astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------------------
+# Screened search: the sidecar and the error band, restated on the CPU (fp64 where it matters).
+#
+# Sidecar layout (include/sskd_amd.h): ceil(n / 32) bf16 tiles of 24 576 bytes, then a 4 096-byte norm block.
+# Tile t, k-step s (0..23), lane l (0..63), element e (0..7) holds row 32 t + (l & 31), column 16 s + 8 (l >> 5) + e
+# of bf16(fl32(c - mu)), mu = fl32(colsum * fl32(1 / n)).  Norm block: int32 words 0..2 = the bit patterns of
+# max |c|^2, max |c~|^2, max |c~ - fl32(c - mu)|^2, word 3 = the bit pattern of max |c_ij|, floats 64..447 = colsum.
+# --------------------------------------------------------------------------------------------------
+SIDECAR_TILE_BYTES = 24576
+SIDECAR_NORM_BYTES = 4096
+SIDECAR_COLSUM_OFF = 64                           # in floats
+SCREEN_ACC_SLACK = float(np.float32(1.0e-4))      # the kernel's constant, as the fp32 it is compiled to
+SCREEN_ACC_NEEDED = 3 * 384 * 2.0 ** -24 * (1 + 2.0 ** -8) ** 2   # what the source derives it from (6.9e-5)
+
+
+class Sidecar(NamedTuple):
+    tiles: np.ndarray     # fp32 [padded, 384]: the bf16 values, widened exactly
+    words: np.ndarray     # fp32 [3]: max |c|^2, max |c~|^2, max |c~ - fl32(c - mu)|^2
+    colsum: np.ndarray    # fp32 [384]
+    absmax: np.float32    # max |c_ij|
+
+
+def bf16_round(x: np.ndarray) -> np.ndarray:
+    """fp32 -> bf16 (round to nearest even) -> fp32, torch's conversion."""
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
+
+
+def sidecar_decode(raw_bytes: np.ndarray, n_rows: int) -> Sidecar:
+    raw = np.ascontiguousarray(raw_bytes, np.uint8)
+    tiles = -(-n_rows // 32)
+    assert raw.size == tiles * SIDECAR_TILE_BYTES + SIDECAR_NORM_BYTES, (raw.size, n_rows)
+    h = raw[: tiles * SIDECAR_TILE_BYTES].view(np.uint16).reshape(tiles, 24, 2, 32, 8)   # [t][s][l >> 5][l & 31][e]
+    h = h.transpose(0, 3, 1, 2, 4).reshape(tiles * 32, 384)                               # [row][16 s + 8 (l >> 5) + e]
+    vals = (h.astype(np.uint32) << 16).view(np.float32)
+    block = raw[tiles * SIDECAR_TILE_BYTES:]
+    f = block.view(np.float32)
+    return Sidecar(vals, f[:3].copy(), f[SIDECAR_COLSUM_OFF: SIDECAR_COLSUM_OFF + 384].copy(), f[3])
+
+
+def sidecar_encode(tiles_f32: np.ndarray, words, colsum: np.ndarray, absmax, n_rows: int) -> np.ndarray:
+    """Inverse of ``sidecar_decode`` (values must be bf16-representable): the bytes sskd_index_make_bf16 writes."""
+    tiles = -(-n_rows // 32)
+    vals = np.zeros((tiles * 32, 384), np.float32)
+    vals[: tiles_f32.shape[0]] = tiles_f32
+    bits = vals.view(np.uint32)
+    assert not (bits & 0xFFFF).any(), "not bf16 values"
+    h = (bits >> 16).astype(np.uint16).reshape(tiles, 32, 24, 2, 8).transpose(0, 2, 3, 1, 4)
+    block = np.zeros(SIDECAR_NORM_BYTES // 4, np.float32)
+    block[:3] = np.asarray(words, np.float32)
+    block[3] = np.float32(absmax)
+    block[SIDECAR_COLSUM_OFF: SIDECAR_COLSUM_OFF + 384] = colsum
+    return np.concatenate([np.ascontiguousarray(h).reshape(-1).view(np.uint8), block.view(np.uint8)])
+
+
+class SidecarExpected(NamedTuple):
+    mu: np.ndarray        # fp32 [384]
+    xc: np.ndarray        # fp32 [n, 384] = fl32(c - mu)
+    ct: np.ndarray        # fp32 [n, 384] = bf16_rne(xc)
+    words: np.ndarray     # fp64 [3]
+
+
+def row_norm2_max(c: np.ndarray, xc: np.ndarray, ct: np.ndarray, rows=slice(None)) -> np.ndarray:
+    """The three maxima over ``rows``, in fp64."""
+    c64, xc64, ct64 = (np.asarray(a[rows], np.float64) for a in (c, xc, ct))
+    return np.array([(c64 * c64).sum(1).max(), (ct64 * ct64).sum(1).max(), ((ct64 - xc64) ** 2).sum(1).max()])
+
+
+def sidecar_expected(corpus: np.ndarray, colsum_f32: np.ndarray) -> SidecarExpected:
+    c = np.ascontiguousarray(corpus, np.float32)
+    inv_n = np.float32(1.0) / np.float32(c.shape[0])
+    mu = (np.asarray(colsum_f32, np.float32) * inv_n).astype(np.float32)
+    xc = (c - mu[None]).astype(np.float32)
+    ct = bf16_round(xc)
+    return SidecarExpected(mu, xc, ct, row_norm2_max(c, xc, ct))
+
+
+def band_terms(queries: np.ndarray, words) -> np.ndarray:
+    """fp64 [nq, 3]: |q~ - q| max|c~|, |q| max|c~ - fl(c - mu)|, SLACK |q| max(max|c|, max|c~|)."""
+    q = np.ascontiguousarray(queries, np.float32)
+    q64 = q.astype(np.float64)
+    qn = np.sqrt((q64 * q64).sum(1))
+    qd = np.sqrt(((bf16_round(q).astype(np.float64) - q64) ** 2).sum(1))
+    cn, cb, cd = np.sqrt(np.asarray(words, np.float64))
+    return np.stack([qd * cb, qn * cd, SCREEN_ACC_SLACK * qn * max(cn, cb)], axis=1)
+
+
+def band_expected(queries: np.ndarray, words) -> np.ndarray:
+    """E64[q] = 2 e(q): the full band width screen_setup_kernel rounds up into eps2[q]."""
+    return 2.0 * band_terms(queries, words).sum(1)

@@ -931,16 +931,21 @@ __global__ __launch_bounds__(256) void tile_colsum_kernel(const float4* __restri
 }
 
 // norm block of the sidecar: ints [0..2] = max |c|^2, max |c~|^2, max |c~ - fl(c - mu)|^2 (bit patterns of
-// non-negative floats), floats [64 .. 64 + 384) = column sums, then the mean row
+// non-negative floats; a row norm that is not finite is published as +inf), int [3] = max |c_ij| (bit pattern: the
+// range check of screen_setup_kernel), floats [64 .. 64 + 384) = column sums, the rest zero.  The mean row is not
+// stored: make_bf16_tiles_kernel derives it from the column sums, mu = fl(colsum * fl(1 / n)).
 constexpr int SIDECAR_NORM_BYTES = 4096;
+constexpr int SIDECAR_ABSMAX_WORD = 3;
 constexpr int SIDECAR_COLSUM_OFF = 64;   // in floats
 
 __global__ __launch_bounds__(256) void make_bf16_tiles_kernel(const float4* __restrict__ tiled, int64_t n_tiles, int64_t n_rows,
                                                               sbf16x8* __restrict__ out, int* __restrict__ norm_block) {
   __shared__ float rowss[3][32];   // per row: |c|^2, |c~|^2, |c~ - fl(c - mu)|^2
   __shared__ float mu[DIM];
+  __shared__ int amax;             // max |c_ij| of the tile, as bits (|NaN| and inf order above every finite value)
   const int64_t t = blockIdx.x;
   if (threadIdx.x < 96) rowss[threadIdx.x >> 5][threadIdx.x & 31] = 0.f;
+  if (threadIdx.x == 0) amax = 0;
   const float inv_n = 1.0f / (float)n_rows;
   for (int c = threadIdx.x; c < DIM; c += 256) mu[c] = reinterpret_cast<const float*>(norm_block)[SIDECAR_COLSUM_OFF + c] * inv_n;
   __syncthreads();
@@ -953,12 +958,14 @@ __global__ __launch_bounds__(256) void make_bf16_tiles_kernel(const float4* __re
     const bool live = t * TILE_ROWS + r < n_rows;   // padding rows stay all-zero (the kernel masks them anyway)
     sbf16x8 o;
     float nn = 0.f, bb = 0.f, dd = 0.f;
+    int am = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float xc = live ? x[e] - mu[8 * u + e] : 0.f;   // fl(c - mu)
       o[e] = (__bf16)xc;
       const float xr = (float)o[e];
       const float d = xr - xc;       // exact in fp32: xr is xc rounded to fewer bits
+      am = max(am, __float_as_int(x[e]) & 0x7fffffff);
       nn = fmaf(x[e], x[e], nn);
       bb = fmaf(xr, xr, bb);
       dd = fmaf(d, d, dd);
@@ -967,16 +974,40 @@ __global__ __launch_bounds__(256) void make_bf16_tiles_kernel(const float4* __re
     atomicAdd(&rowss[0][r], nn);
     atomicAdd(&rowss[1][r], bb);
     atomicAdd(&rowss[2][r], dd);
+    atomicMax(&amax, am);
   }
   __syncthreads();
-  // non-negative floats order as ints; words 0..2 of the sidecar's norm block
-  if (threadIdx.x < 96) atomicMax(norm_block + (threadIdx.x >> 5), __float_as_int(rowss[threadIdx.x >> 5][threadIdx.x & 31]));
+  // non-negative floats order as ints; words 0..2 of the sidecar's norm block.  A sum that is not finite goes out as
+  // +inf, never as a NaN (a NaN word made eps2 NaN for every query, and its bit pattern orders by its sign bit)
+  if (threadIdx.x < 96) {
+    const float v = rowss[threadIdx.x >> 5][threadIdx.x & 31];
+    atomicMax(norm_block + (threadIdx.x >> 5), __float_as_int(v < INFINITY ? v : INFINITY));
+  }
+  if (threadIdx.x == 96) atomicMax(norm_block + SIDECAR_ABSMAX_WORD, amax);
 }
 
 // One set-up launch per call.  Per query: 2e = 2 (|q~ - q| max|c~| + |q| max|c~ - c| + SCREEN_ACC_SLACK |q| max(max|c|, max|c~|)),
 // rounded UP; and the call's scratch state: tau + the global buckets (11 words per query) to "empty", the fallback
 // counters and the status words to zero (these were four launches / memsets: on a 125 k-row shard the short launches
 // of a call add up to a tenth of it).
+// RANGE.  The norms are square roots of fp32 sums of squares, and the bound above is a statement about real numbers: it
+// holds in fp32 only while no square, product or partial sum leaves the normal range.  So
+//  - the query is scaled by an exact power of two (largest element into [1, 2)) before it is squared, and the band is
+//    scaled back at the end: the same bits as the unscaled sum wherever that was exact, and no square of a small query
+//    is lost (unscaled, a query of norm 2^-80 measured |q| = 0: band 1e-30 against a screening error of 4e-28);
+//  - eps2[q] = +inf - "no band": screen_finalize_append_kernel hands such a query to the in-call exact scan - when the
+//    query or a row norm is not finite, when the largest corpus element is below SCREEN_MIN_CORPUS (the row sums of
+//    squares are not scaled and lose terms below 2^-63), when the largest query element is below SCREEN_MIN_QUERY (its
+//    bf16 elements and their products approach the denormals), or when the band itself leaves [SCREEN_MIN_BAND,
+//    SCREEN_MAX_BAND] (scores near the ends of the fp32 range round absolutely, not relatively).  An all-zero query or
+//    corpus scores exactly 0 on both paths and keeps the floor.
+// The thresholds are derived, not observed: the fp64 checks of tests/test_screen_band_gpu.py compute q~.c~ on the CPU and
+// never see how the MFMA treats near-denormal products, so on the device they are guarded only by that file's
+// bit-equality cases against the oracle (queries down to 2^-140, corpora at 2^-70, 2^-35 and 2^60).
+// Room: what lost denormal terms can hide on a norm is <= sqrt(384 x 2^-126) = 2^-58.7, times the other side's norm;
+// the slack term holds 3.1e-5 |q| max|c| = 2^-15 |q| max|c| beyond the 6.9e-5 it is derived from, and max|c| >= 2^-40.
+constexpr float SCREEN_MIN_CORPUS = 0x1p-40f, SCREEN_MIN_QUERY = 0x1p-96f;
+constexpr float SCREEN_MIN_BAND = 0x1p-100f, SCREEN_MAX_BAND = 0x1p+100f;
 __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restrict__ queries, int nq,
                                                            const int* __restrict__ max_norm2, float* __restrict__ eps2,
                                                            int* __restrict__ tau, int* __restrict__ fb_count,
@@ -992,11 +1023,25 @@ __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restri
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= nq) return;
+  float xs[DIM / 64];
+  int am = 0;   // max |x| as bits: |NaN| and inf order above every finite value
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) {
+    xs[i] = queries[(int64_t)q * DIM + lane + 64 * i];
+    am = max(am, __float_as_int(xs[i]) & 0x7fffffff);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) am = max(am, __shfl_xor(am, o));
+  // 2^-E for the largest element's exponent E (denormals: E = -126); exact, and 1 for elements in [1, 2)
+  const int ex = min(max(am >> 23, 1), 253);
+  const float down = __int_as_float(ex << 23), up = __int_as_float((254 - ex) << 23);
   float ss = 0.f, dd = 0.f;
-  for (int i = lane; i < DIM; i += 64) {
-    const float x = queries[(int64_t)q * DIM + i];
-    const float d = (float)(__bf16)x - x;   // the same conversion the screening kernel applies; exact difference
-    ss = fmaf(x, x, ss);
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) {
+    const float x = xs[i];
+    const float d = ((float)(__bf16)x - x) * up;   // the same conversion the screening kernel applies; exact difference
+    const float xu = x * up;
+    ss = fmaf(xu, xu, ss);
     dd = fmaf(d, d, dd);
   }
   ss = wave_sum(ss);
@@ -1004,12 +1049,17 @@ __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restri
   if (lane == 0) {
     const float cn = sqrtf(__int_as_float(max_norm2[0])), cb = sqrtf(__int_as_float(max_norm2[1])),
                 cd = sqrtf(__int_as_float(max_norm2[2]));
+    const float ca = __int_as_float(max_norm2[SIDECAR_ABSMAX_WORD]), qa = __int_as_float(am);
     const float qn = sqrtf(ss), qd = sqrtf(dd);
     // the sums of squares carry <= 385 x 2^-24 relative error, the square roots and products a few ulps more:
     // 1.0002 rounds the whole bound up
     // (the accumulation slack scales with the operands that are actually multiplied: the exact chain's rows |c| AND the
     // screening pass's centred, rounded rows |c~|, which can reach 2 max|c| on a shard whose mean row is large)
-    eps2[q] = 2.0f * (qd * cb + qn * cd + SCREEN_ACC_SLACK * qn * fmaxf(cn, cb)) * 1.0002f + 1e-30f;
+    const float band = 2.0f * (qd * cb + qn * cd + SCREEN_ACC_SLACK * qn * fmaxf(cn, cb)) * 1.0002f * down;
+    const bool zero = (qa == 0.f || ca == 0.f) && band == 0.f;   // (0 x inf = NaN is not "zero": no band)
+    const bool sound = zero || (qa >= SCREEN_MIN_QUERY && ca >= SCREEN_MIN_CORPUS && ca < INFINITY &&
+                                band >= SCREEN_MIN_BAND && band <= SCREEN_MAX_BAND);
+    eps2[q] = sound ? band + 1e-30f : INFINITY;
   }
 }
 
@@ -1376,8 +1426,8 @@ struct ScreenFinalAppendParams {
 };
 
 // One WAVE per query: gather the appended runs -> k-th best screen score -> candidate band -> exact re-scoring (the
-// fp32 MFMA's k-ordered fma chain) -> exact top k.  A query goes to the exact fallback when a run overflowed, when its
-// entries do not fit the LDS stage, or when the band holds more than SCREEN_MAX_CAND rows.
+// fp32 MFMA's k-ordered fma chain) -> exact top k.  A query goes to the exact fallback when it has no band (eps2 = +inf),
+// when a run overflowed, when its entries do not fit the LDS stage, or when the band holds more than SCREEN_MAX_CAND rows.
 // Dynamic LDS: [E] scores, [E] ids (E = SCREEN_FIN_ENTRIES), [384] query, [SCREEN_MAX_CAND] candidate rows.
 __global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalAppendParams p) {
   extern __shared__ __attribute__((aligned(16))) float fin_lds[];
@@ -1388,7 +1438,8 @@ __global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalA
   const int q = blockIdx.x, lane = threadIdx.x;
   for (int c = lane; c < DIM; c += 64) qv[c] = p.queries[(int64_t)q * DIM + c];
 
-  bool bad = false;
+  // eps2 = +inf: no band was established for this query (screen_setup_kernel) - its screen scores prove nothing
+  bool bad = !(p.eps2[q] < INFINITY);
   int total = 0;
   for (int l0 = 0; l0 < p.lists; l0 += 64) {
     const int l = l0 + lane;
@@ -2312,6 +2363,13 @@ ScreenWs screen_carve(void* base, const ScreenPlan& pl, int64_t n_rows, int nq, 
 static inline size_t sidecar_norm_offset(int64_t n_rows) { return (size_t)sskd::ceil_div(n_rows, TILE_ROWS) * BTILE_VEC * 16; }
 static inline size_t sidecar_rows_offset(int64_t n_rows) { return sidecar_norm_offset(n_rows) + SIDECAR_NORM_BYTES; }
 
+// the one launch of screen_setup_kernel: the search's first launch, and all that sskd_index_screen_band does
+static inline void launch_screen_setup(const int* max_norm2, const float* d_queries, int nq, float* eps2, int* tau,
+                                       int* fb_count, int* d_status, hipStream_t st) {
+  hipLaunchKernelGGL(screen_setup_kernel, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0, st, d_queries, nq, max_norm2,
+                     eps2, tau, fb_count, d_status);
+}
+
 size_t sskd_index_bf16_bytes(int64_t n_rows) {
   if (n_rows <= 0) return 0;
   return sidecar_rows_offset(n_rows);
@@ -2332,6 +2390,33 @@ int sskd_index_make_bf16(const float* d_tiled, int64_t n_rows, void* d_bf16, voi
   hipLaunchKernelGGL(make_bf16_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, st,
                      reinterpret_cast<const float4*>(d_tiled), tiles, n_rows, static_cast<sbf16x8*>(d_bf16), max_norm2);
   return sskd::check_launch("make_bf16_tiles_kernel");
+}
+
+// test hook: the band of every query (eps2 = 2e), from the launch the search itself opens with; the set-up kernel's
+// scratch state (tau + buckets, fallback counters, status words) lands in the caller's scratch
+size_t sskd_index_screen_band_scratch_bytes(int nq) {
+  if (nq <= 0) return 0;
+  sskd::Carver c(nullptr);
+  c.take<int>((size_t)nq * 11);
+  c.take<int>(64);
+  c.take<int>(2);
+  return c.bytes();
+}
+
+int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_eps2_out,
+                           void* d_scratch, size_t scratch_bytes, void* stream) {
+  SSKD_REQUIRE(n_rows > 0 && nq > 0, "index_screen_band: needs rows and queries (got rows=%lld nq=%d)", (long long)n_rows, nq);
+  int rc = require_shard_rows("index_screen_band", n_rows);
+  if (rc != SSKD_OK) return rc;
+  SSKD_REQUIRE(d_bf16 && d_queries && d_eps2_out, "index_screen_band: null pointer");
+  sskd::Carver c(d_scratch);
+  int* const tau = c.take<int>((size_t)nq * 11);
+  int* const fb_count = c.take<int>(64);
+  int* const status = c.take<int>(2);
+  if ((rc = sskd::require_workspace("index_screen_band", d_scratch, scratch_bytes, c.bytes())) != SSKD_OK) return rc;
+  const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
+  launch_screen_setup(max_norm2, d_queries, nq, d_eps2_out, tau, fb_count, status, sskd::as_stream(stream));
+  return sskd::check_launch("screen_setup_kernel");
 }
 
 int sskd_index_search_screened_plan(int64_t n_rows, int nq, int k, int* queries_per_block, int* corpus_passes,
@@ -2378,8 +2463,7 @@ int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16
   const int64_t tiles = sskd::ceil_div(n_rows, TILE_ROWS);
   const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
 
-  hipLaunchKernelGGL(screen_setup_kernel, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0, st, d_queries, nq, max_norm2,
-                     w.eps2, w.tau, w.fb_count, d_status);
+  launch_screen_setup(max_norm2, d_queries, nq, w.eps2, w.tau, w.fb_count, d_status, st);
 
   static_assert((SCREEN_CAP * sizeof(float)) % 256 == 0, "the runs span part_scores and part_ids back to back");
   ScreenAppendParams sp{};
