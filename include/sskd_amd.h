@@ -283,6 +283,42 @@ int sskd_range_merge_packed(const void* d_records, int n_runs, int nq, int64_t c
                             float* d_out_scores, int64_t* d_out_ids, int64_t max_results, void* d_workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Grouped search: the top-k DISTINCT groups by their best row (MaxSim: a document scores as its best chunk)
+ *   reference: src/utils/chunk.py (a text becomes overlapping chunks, chunk_id = "<doc_id>_<n>") and its
+ *   maxsim_aggregation (doc score = max over the document's chunks)
+ * d_row_group: DEVICE int32 [n_rows], the group number g(r) >= 0 of every local row.  For a query q and the allowed
+ * rows (d_row_mask: NULL = all rows, else the format of "Filtered search"):
+ *   - the score of group G is max { score(q, r) : r allowed, g(r) = G }, score being the exact scan's fp32 fma chain,
+ *     bit for bit the value sskd_index_search returns;
+ *   - the representative of G is the row attaining that maximum that ranks first in sskd_index_search's order (score
+ *     descending, then lower id);
+ *   - a group with no allowed row does not exist for the call.
+ * The result is the first k groups in the order of their representatives - equivalently: walk sskd_index_search's full
+ * ranking and keep the first row of every group not yet seen.  All-singleton groups reproduce sskd_index_search;
+ * masking the best row of a group lowers the group to its next row, it does not drop it.
+ * Outputs per query: d_out_scores fp32 [k], d_out_ids int64 [k] (representative row + id_offset), d_out_groups
+ * int32 [k] (group numbers are local: id_offset does not shift them); fewer than k groups pad the tail with
+ * (-FLT_MAX, -1, -1).  d_out_count int32 [nq] = entries written before the padding.
+ * How: the exact row search ranks the best k_rows rows per query into the workspace (k_rows > SSKD_K_PASS through the
+ * chained passes), then one wave per query walks that ranking.  The walk is a proof when it found k groups or met
+ * the end of the allowed rows.  Otherwise - k_rows ranks held fewer than k groups and rows remain - d_unproved[q] = 1
+ * and *d_n_unproved (device int32, zeroed by the call) counts such queries; the d_out_count[q] entries already written
+ * are then STILL the exact top-count groups, in order: only what follows them is unknown, and the caller asks again
+ * with a larger k_rows (or with those groups' rows masked).  k_rows = (k - 1) * (largest group size) + 1 can never be
+ * unproved.  (A query whose allowed rows number exactly k_rows < n_rows is reported unproved although nothing follows:
+ * the walk cannot see that; asking again settles it.)
+ * Limits: 1 <= k <= k_rows <= SSKD_K_MAX.  Stream-ordered, no host sync, allocates nothing; arguments are checked
+ * before any HIP call (SSKD_ERR_INVALID; a workspace smaller than the call needs: SSKD_ERR_WORKSPACE).  The size
+ * query is monotone in nq and k_rows and never below sskd_index_search_workspace_bytes(n_rows, nq, k_rows).
+ * ------------------------------------------------------------------------- */
+size_t sskd_index_search_grouped_workspace_bytes(int64_t n_rows, int nq, int k, int k_rows);
+int sskd_index_search_grouped(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq, int k, int k_rows,
+                              int64_t id_offset, const uint32_t* d_row_mask, const int32_t* d_row_group,
+                              float* d_out_scores, int64_t* d_out_ids, int32_t* d_out_groups, int32_t* d_out_count,
+                              int32_t* d_unproved, int32_t* d_n_unproved, void* d_workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

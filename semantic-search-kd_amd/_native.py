@@ -164,6 +164,10 @@ SIGNATURES = {
     "sskd_range_record_bytes": (_sz, [_i, _i64]),
     "sskd_range_merge_workspace_bytes": (_sz, [_i, _i, _i64]),
     "sskd_range_merge_packed": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "sskd_index_search_grouped_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "sskd_index_search_grouped": (
+        _i, [_vp, _i64, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

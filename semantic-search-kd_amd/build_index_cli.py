@@ -50,6 +50,9 @@ def main(argv=None) -> int:
     ap.add_argument("--shards", type=int, default=0,
                     help="0 = one shard per rank when launched under torch.distributed.run, plain single index otherwise; "
                          "1 = write the sharded layout (shards.json + shard_0/) from this single process")
+    ap.add_argument("--group-column", type=str, default=None,
+                    help="parquet column holding the group key of every row (for example doc_id): the saved index "
+                         "then answers search_grouped with distinct documents; single-index builds only")
     args = ap.parse_args(argv)
     for flag, p in (("--model-path", args.model_path), ("--data-path", args.data_path)):
         if not Path(p).exists():
@@ -57,6 +60,8 @@ def main(argv=None) -> int:
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 or args.shards == 1:
+        if args.group_column:
+            ap.error("--group-column: the row-sharded index has no grouped search yet")
         return _build_sharded(args, world)
 
     model = StudentModel(args.model_path, device=args.device)
@@ -68,6 +73,7 @@ def main(argv=None) -> int:
         max_docs=args.max_docs,
         hnsw_m=args.hnsw_m,
         hnsw_ef_construction=args.hnsw_ef_construction,
+        group_column=args.group_column,
     )
     builder.save(Path(args.output_dir))
     print(f"Index saved to: {args.output_dir}")

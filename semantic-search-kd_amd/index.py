@@ -92,6 +92,10 @@ class IndexHandle:
         """faiss ``index.range_search`` shape ``(lims, D, I)``: raw inner product, no query normalisation."""
         return self._owner._range_numpy(x, thresh, normalize_queries=False)
 
+    def search_grouped(self, x: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``(D, I, G)``: the top-k distinct groups by their best row; raw inner product, no query normalisation."""
+        return self._owner._search_grouped_numpy(x, k, normalize_queries=False)
+
 
 class FAISSIndexBuilder:
     """Exact cosine / inner-product index resident in MI355X HBM."""
@@ -147,6 +151,18 @@ class FAISSIndexBuilder:
         self.range_capacity = 1 << 16
         self._range_scores: Optional[torch.Tensor] = None
         self._range_ids: Optional[torch.Tensor] = None
+        # row groups (grouped search: a document = the group of its chunks).  ``group_keys`` is None until groups are
+        # set: every row is then its own group, numbered by its row.
+        self.group_keys: Optional[List] = None              # group number -> key (None for a row added without one)
+        self._row_group_host: Optional[np.ndarray] = None    # int32 per row
+        self._group_of_key: dict = {}
+        self._row_group_dev: Optional[torch.Tensor] = None   # device int32 per row, made lazily
+        self._group_csr: Optional[Tuple[np.ndarray, np.ndarray]] = None   # host CSR group -> rows, made lazily
+        self._max_group: Optional[int] = None
+        # device int32 tensors of the last search_grouped_device call: entries written per query, and the number of
+        # unproved queries
+        self.last_group_counts: Optional[torch.Tensor] = None
+        self.last_group_n_unproved: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ storage
     @property
@@ -182,11 +198,22 @@ class FAISSIndexBuilder:
         """Pre-size the HBM buffer (avoids regrowth while streaming a large corpus in)."""
         self._ensure_capacity(rows)
 
-    def add(self, embeddings: Union[np.ndarray, torch.Tensor]) -> None:
+    def add(self, embeddings: Union[np.ndarray, torch.Tensor], groups: Optional[Sequence] = None) -> None:
         """Append rows (``faiss.normalize_L2`` + ``index.add``); host or device fp32 ``[n, 384]``.
 
-        Rows are L2-normalised on the GPU when ``metric == "cosine"`` (configs/index.yaml:30).
+        Rows are L2-normalised on the GPU when ``metric == "cosine"`` (configs/index.yaml:30).  ``groups``: one
+        hashable key per new row (see ``set_groups``); a key the index already knows joins that group.  Rows added
+        without a key (no ``groups``, or a ``None`` entry) become singleton groups.
         """
+        if groups is not None:
+            groups = list(groups)
+            if len(groups) != len(embeddings):
+                raise ValueError(f"{len(groups)} group keys for {len(embeddings)} vectors")
+        first = self._n
+        self._add_rows(embeddings)
+        self._extend_groups(first, self._n - first, groups)
+
+    def _add_rows(self, embeddings: Union[np.ndarray, torch.Tensor]) -> None:
         lib = _native.load()
         x = _as_device_f32(embeddings, self.device)
         if x.dim() != 2 or x.shape[1] != self.embedding_dim:
@@ -237,12 +264,15 @@ class FAISSIndexBuilder:
         self.index = IndexHandle(self)
 
     def build_from_embeddings(
-        self, embeddings: Union[np.ndarray, torch.Tensor], doc_ids: Optional[Sequence[str]] = None
+        self, embeddings: Union[np.ndarray, torch.Tensor], doc_ids: Optional[Sequence[str]] = None,
+        groups: Optional[Sequence] = None,
     ) -> IndexHandle:
+        """``groups``: one key per row (for example the document of every chunk), see ``set_groups``."""
         self._n = 0
         self._tiled = None
         self._reset_removed()
-        self.add(embeddings)
+        self._reset_groups()
+        self.add(embeddings, groups=groups)
         self.doc_ids = list(doc_ids) if doc_ids is not None else [f"doc_{i}" for i in range(self._n)]
         if len(self.doc_ids) != self._n:
             raise ValueError(f"{len(self.doc_ids)} doc_ids for {self._n} vectors")
@@ -260,8 +290,12 @@ class FAISSIndexBuilder:
         text_column: str = "text",
         id_column: str = "chunk_id",
         show_progress: bool = True,
+        group_column: Optional[str] = None,
     ) -> IndexHandle:
         """Encode a parquet corpus with ``model.encode_documents`` and index it.
+
+        ``group_column``: a column whose value is the group key of every row, such as ``"doc_id"`` (the reference's
+        corpus schema carries it beside ``chunk_id``): ``search_grouped`` then returns distinct documents.
 
         Columns follow the reference's corpus schema (src/data/prepare.py:72-84,
         tests/conftest.py:210-216): ``text`` and ``chunk_id``.  ``hnsw_*`` are accepted for
@@ -269,9 +303,11 @@ class FAISSIndexBuilder:
         """
         del hnsw_m, hnsw_ef_construction
         ids, texts = read_corpus_parquet(parquet_path, max_docs, text_column, id_column)
+        keys = None if group_column is None else read_parquet_column(parquet_path, group_column, max_docs)
         self._n = 0
         self._tiled = None
         self._reset_removed()
+        self._reset_groups()
         self.reserve(len(texts))
         # stream in slabs so a multi-million-passage corpus never needs one host matrix
         slab = max(batch_size, 65536)
@@ -281,11 +317,108 @@ class FAISSIndexBuilder:
                 embs = on_device(texts[lo : lo + slab], batch_size=batch_size)
             else:
                 embs = model.encode_documents(texts[lo : lo + slab], batch_size=batch_size, show_progress=show_progress)
-            self.add(embs)
+            self.add(embs, groups=None if keys is None else keys[lo : lo + slab])
         self.doc_ids = ids
         self.doc_texts = dict(zip(ids, texts))
         self.index = IndexHandle(self)
         return self.index
+
+    # ------------------------------------------------------------------- groups
+    def _reset_groups(self) -> None:
+        self.group_keys = None
+        self._row_group_host = None
+        self._group_of_key = {}
+        self._groups_changed()
+
+    def _groups_changed(self) -> None:
+        self._row_group_dev = None
+        self._group_csr = None
+        self._max_group = None
+
+    def _extend_groups(self, n_old: int, n_new: int, keys: Optional[Sequence]) -> None:
+        """Group numbers of ``n_new`` rows appended behind ``n_old``: a known key joins its group, a new key opens
+        one, no key (``keys`` None or a None entry) opens a singleton group."""
+        self._groups_changed()
+        if keys is None and self.group_keys is None:
+            return   # still ungrouped: every row is its own group
+        if self.group_keys is None:   # the rows stored so far become singleton groups
+            self.group_keys = [None] * n_old
+            self._row_group_host = np.arange(n_old, dtype=np.int32)
+        new = np.empty(n_new, dtype=np.int32)
+        if keys is None:
+            new[:] = np.arange(len(self.group_keys), len(self.group_keys) + n_new, dtype=np.int32)
+            self.group_keys.extend([None] * n_new)
+        else:
+            for i, key in enumerate(keys):
+                g = None if key is None else self._group_of_key.get(key)
+                if g is None:
+                    g = len(self.group_keys)
+                    self.group_keys.append(key)
+                    if key is not None:
+                        self._group_of_key[key] = g
+                new[i] = g
+        self._row_group_host = np.concatenate([self._row_group_host, new])
+
+    def set_groups(self, keys: Sequence) -> None:
+        """Group the stored rows: ``keys`` holds one hashable per row (for example the ``doc_id`` of every chunk);
+        rows with equal keys form one group, a ``None`` entry makes its row a singleton group.  Group numbers follow
+        first appearance; ``group_keys[g]`` is the key of group ``g``.  Replaces any earlier grouping."""
+        keys = list(keys)
+        if len(keys) != self._n:
+            raise ValueError(f"{len(keys)} group keys for {self._n} rows")
+        self._reset_groups()
+        self.group_keys, self._row_group_host = [], np.zeros(0, dtype=np.int32)
+        self._extend_groups(0, self._n, keys)
+
+    @property
+    def n_groups(self) -> int:
+        return self._n if self.group_keys is None else len(self.group_keys)
+
+    @property
+    def max_group_size(self) -> int:
+        """Rows of the largest group (1 without groups)."""
+        if self._max_group is None:
+            g = self._row_group_host
+            self._max_group = 1 if g is None or g.size == 0 else int(np.bincount(g).max())
+        return self._max_group
+
+    def group_key(self, g):
+        """The key of group ``g``, or the list of keys of an array of group numbers (``G`` of ``search_grouped``, any
+        shape, flattened row by row into nested lists).  Padding (-1), a singleton group without a key and every
+        group of an index without groups give None."""
+        if np.ndim(g) == 0:
+            g = int(g)
+            return None if g < 0 or self.group_keys is None else self.group_keys[g]
+        return [self.group_key(x) for x in np.asarray(g)]
+
+    def row_groups(self) -> np.ndarray:
+        """int32 group number of every stored row."""
+        if self._row_group_host is None:
+            return np.arange(self._n, dtype=np.int32)
+        return self._row_group_host
+
+    def _row_group_device(self) -> torch.Tensor:
+        if self._row_group_dev is None or self._row_group_dev.numel() != max(self._n, 1):
+            if self._row_group_host is None:
+                self._row_group_dev = torch.arange(max(self._n, 1), dtype=torch.int32, device=self.device)
+            else:
+                host = self._row_group_host if self._n else np.zeros(1, dtype=np.int32)
+                self._row_group_dev = torch.from_numpy(np.ascontiguousarray(host)).to(self.device)
+        return self._row_group_dev
+
+    def _rows_of_groups(self, groups) -> np.ndarray:
+        """Local rows (int64) of the given group numbers, from the host CSR."""
+        groups = np.asarray(groups, dtype=np.int64).reshape(-1)
+        if self._row_group_host is None:
+            return groups.copy()
+        if self._group_csr is None:
+            g = self._row_group_host
+            indptr = np.zeros(len(self.group_keys) + 1, dtype=np.int64)
+            np.cumsum(np.bincount(g, minlength=len(self.group_keys)), out=indptr[1:])
+            self._group_csr = (indptr, np.argsort(g, kind="stable").astype(np.int64))
+        indptr, rows = self._group_csr
+        parts = [rows[indptr[x]:indptr[x + 1]] for x in groups]
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
 
     # ------------------------------------------------------------ removal / filters
     def remove_ids(self, ids) -> int:
@@ -518,6 +651,138 @@ class FAISSIndexBuilder:
             raise RuntimeError("index is empty: call build_from_parquet/add/load first")
         return self._search_numpy(query_emb, k, normalize_queries=None, allow=allow)
 
+    # ----------------------------------------------------------- grouped search
+    def _default_k_rows(self, k: int) -> int:
+        """Rows to rank for ``k`` groups: ``(k - 1) m + 1`` (m = largest group) always holds k groups or every row -
+        taken when one scan pass serves it; otherwise one pass's worth (the caller doubles on ``unproved``)."""
+        need = (k - 1) * self.max_group_size + 1
+        return need if need <= _native.SSKD_K_PASS else max(k, _native.SSKD_K_PASS)
+
+    def search_grouped_device(
+        self,
+        queries: torch.Tensor,
+        k: int,
+        k_rows: Optional[int] = None,
+        allow=None,
+        normalize_queries: Optional[bool] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Top-k distinct groups by their best row (``include/sskd_amd.h``, grouped search) for device-resident
+        queries: device tensors ``(scores [nq, k], ids [nq, k] int64, groups [nq, k] int32, unproved [nq] int32)``.
+        ``ids`` are the groups' best rows; fewer than k groups pad with ``(-FLT_MAX, -1, -1)``.  No host
+        synchronisation (``allow`` should then be a prepared ``RowFilter``).  The result is exact for every query
+        with ``unproved == 0``; where it is 1 the best ``k_rows`` rows (default: ``(k - 1) * max_group_size + 1`` if
+        one scan pass serves that, else 32) held fewer than k groups, the entries written (``last_group_counts``)
+        are still the exact first groups, and the caller asks again with a larger ``k_rows`` - ``search_grouped``
+        does all of that."""
+        mask = self._effective_mask(allow)
+        q = self._prepare_queries(queries, normalize_queries, "search_grouped_device")
+        return self._search_grouped_masked(q, k, k_rows, mask)
+
+    def _search_grouped_masked(self, q: torch.Tensor, k: int, k_rows: Optional[int], mask):
+        lib = _native.load()
+        if k < 1 or k > _native.SSKD_K_MAX:
+            raise ValueError(f"k={k} outside [1, {_native.SSKD_K_MAX}]")
+        if k_rows is None:
+            k_rows = self._default_k_rows(k)
+        if k_rows < k or k_rows > _native.SSKD_K_MAX:
+            raise ValueError(f"k_rows={k_rows} outside [k={k}, {_native.SSKD_K_MAX}]")
+        nq = q.shape[0]
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        groups = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+        counts = torch.empty(nq, dtype=torch.int32, device=self.device)
+        unproved = torch.empty(nq, dtype=torch.int32, device=self.device)
+        n_unproved = torch.empty(1, dtype=torch.int32, device=self.device)
+        ws = self._workspace_for(int(lib.sskd_index_search_grouped_workspace_bytes(self._n, nq, k, k_rows)))
+        _native.check(
+            lib.sskd_index_search_grouped(
+                0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, k_rows, self.id_offset,
+                None if mask is None else mask.data_ptr(), self._row_group_device().data_ptr(), scores.data_ptr(),
+                ids.data_ptr(), groups.data_ptr(), counts.data_ptr(), unproved.data_ptr(), n_unproved.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream(self.device),
+            )
+        )
+        self.last_group_counts, self.last_group_n_unproved = counts, n_unproved
+        return scores, ids, groups, unproved
+
+    def _grouped_rounds(self, q: torch.Tensor, k: int, mask):
+        """Host loop of the exact grouped search short of the mask route: the default ``k_rows``, then only the
+        unproved queries again with ``k_rows`` doubled, up to SSKD_K_MAX.  Returns NumPy ``(D, I, G, counts,
+        unproved)`` and the largest ``k_rows`` used."""
+        nq = q.shape[0]
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        G = np.empty((nq, k), dtype=np.int32)
+        counts = np.zeros(nq, dtype=np.int32)
+        unproved = np.zeros(nq, dtype=np.bool_)
+        pending = np.arange(nq)
+        k_rows = self._default_k_rows(k)
+        while pending.size:
+            sub = q if pending.size == nq else q[torch.from_numpy(pending).to(self.device)].contiguous()
+            s, i, g, u = self._search_grouped_masked(sub, k, k_rows, mask)
+            D[pending], I[pending], G[pending] = s.cpu().numpy(), i.cpu().numpy(), g.cpu().numpy()
+            counts[pending] = self.last_group_counts.cpu().numpy()
+            open_ = u.cpu().numpy().astype(np.bool_)
+            unproved[pending] = open_
+            if k_rows >= _native.SSKD_K_MAX:
+                break
+            pending = pending[open_]
+            if pending.size:
+                k_rows = min(2 * k_rows, _native.SSKD_K_MAX)
+        return D, I, G, counts, unproved, k_rows
+
+    def _search_grouped_numpy(self, query_emb, k: int, normalize_queries: Optional[bool], allow=None):
+        lib = _native.load()
+        qd = _host_queries_to_device(query_emb, self.device)
+        with torch.cuda.device(self.device):
+            mask = self._effective_mask(allow)
+            q = self._prepare_queries(qd, normalize_queries, "search_grouped")
+            first = self._default_k_rows(k)
+            D, I, G, counts, unproved, k_rows = self._grouped_rounds(q, k, mask)
+            if (k - 1) * self.max_group_size + 1 <= _native.SSKD_K_PASS:
+                path = "grouped:counted"
+            else:
+                path = f"grouped:rows{first}" if k_rows == first else f"grouped:doubled{k_rows}"
+            # a query still unproved at SSKD_K_MAX rows (one group fills them): take its groups found so far out
+            # through the allow-mask and search for the rest; every round finds a new group, so at most k rounds
+            words = int(lib.sskd_row_mask_words(self._n))
+            for qi in np.flatnonzero(unproved):
+                found = int(counts[qi])
+                m_q = (torch.full((max(words, 1),), -1, dtype=torch.int32, device=self.device) if mask is None
+                       else mask[: max(words, 1)].clone())
+                bad = torch.empty(1, dtype=torch.int32, device=self.device)
+                new = G[qi, :found]
+                while True:
+                    rows = torch.from_numpy(self._rows_of_groups(new)).to(self.device)
+                    _native.check(lib.sskd_row_mask_update(m_q.data_ptr(), self._n, rows.data_ptr(), rows.numel(), 0,
+                                                           bad.data_ptr(), _stream(self.device)))
+                    d, i, g, c, u, _ = self._grouped_rounds(q[qi:qi + 1], k - found, m_q)
+                    c0 = int(c[0])
+                    D[qi, found:found + c0], I[qi, found:found + c0], G[qi, found:found + c0] = d[0, :c0], i[0, :c0], g[0, :c0]
+                    new = g[0, :c0]
+                    found += c0
+                    if not u[0] or found >= k:
+                        break
+                counts[qi] = found
+            if unproved.any():
+                path += "+mask"
+            self.last_search_path = path
+            return D, I, G
+
+    def search_grouped(self, query_emb: np.ndarray, k: int = 10, *, allow=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The top-k distinct groups (documents) by their best row (chunk), always exact: NumPy ``(D [nq, k], I [nq, k],
+        G [nq, k])`` - group score, its best row's id, group number (``group_key`` maps it back).  It is what
+        walking ``search``'s full ranking and keeping the first row of every new group gives; without groups it
+        equals ``search``.  ``allow`` and removed rows act as in ``search``: a group is scored by its allowed rows
+        alone.  Fewer than k groups pad the tail with ``(-FLT_MAX, -1, -1)``.  ``last_search_path`` records the
+        route: ``grouped:counted`` (``(k - 1) * max_group_size + 1`` rows fit one scan pass: proven by counting),
+        ``grouped:rows32`` / ``grouped:doubledN`` (the best 32 rows, then only the unproved queries again with the
+        row count doubled up to N), and a ``+mask`` suffix when a query still unproved at 1024 rows was finished by
+        masking the groups found so far and searching again."""
+        if self._n == 0 and self._tiled is None and self.index is None:
+            raise RuntimeError("index is empty: call build_from_parquet/add/load first")
+        return self._search_grouped_numpy(query_emb, k, normalize_queries=None, allow=allow)
+
     # ------------------------------------------------------------- range search
     def _range_call(self, q: torch.Tensor, thr: torch.Tensor, mask, lims: torch.Tensor, scores, ids, max_results: int):
         lib = _native.load()
@@ -673,10 +938,22 @@ class FAISSIndexBuilder:
             np.save(out / "removed.npy", self.removed_rows())
         else:
             (out / "removed.npy").unlink(missing_ok=True)
+        # groups: written only when set (an index without groups writes the files it always wrote)
+        if self.group_keys is not None:
+            np.save(out / "groups.npy", np.ascontiguousarray(self._row_group_host, dtype=np.int32))
+            with open(out / "group_keys.json", "w") as f:
+                json.dump(list(self.group_keys), f)
+        else:
+            (out / "groups.npy").unlink(missing_ok=True)
+            (out / "group_keys.json").unlink(missing_ok=True)
 
     def load(self, index_dir: Union[str, Path], append: bool = False) -> None:
         """Restore a saved index (``append=True``: add its rows behind the ones already held - consecutive row
-        shards served by one process).  ``shard.json``, when present, restores ``id_offset``."""
+        shards served by one process).  ``shard.json``, when present, restores ``id_offset``; ``groups.npy`` +
+        ``group_keys.json``, when present, restore the row groups.  With ``append=True`` the loaded part's group
+        numbers are offset behind the ones already held and keys are NEVER merged across the two parts: a document
+        whose chunks were saved in both parts stays two groups.  A part without groups joins a grouped index as
+        singleton groups."""
         d = Path(index_dir)
         path = d / "index.faiss"
         if not path.exists():
@@ -692,6 +969,7 @@ class FAISSIndexBuilder:
                 self._n = 0
                 self._tiled = None
                 self._reset_removed()
+                self._reset_groups()
                 self.doc_ids = []
                 self.doc_texts = None
                 if shard is not None:
@@ -703,9 +981,10 @@ class FAISSIndexBuilder:
             self.reserve(self._n + vecs.shape[0])
             step = 1 << 18  # stream the (memory-mapped) matrix in 400 MB slabs
             for lo in range(0, vecs.shape[0], step):
-                self.add(np.array(vecs[lo : lo + step], dtype=np.float32, copy=True))
+                self._add_rows(np.array(vecs[lo : lo + step], dtype=np.float32, copy=True))
         finally:
             self.metric = metric
+        self._load_groups(d, first, self._n - first)
         removed_path = d / "removed.npy"
         if removed_path.exists():
             removed = np.load(removed_path).astype(np.int64)
@@ -723,11 +1002,33 @@ class FAISSIndexBuilder:
                 self.doc_texts = {**(self.doc_texts or {}), **json.load(f)}
         self.index = IndexHandle(self)
 
+    def _load_groups(self, d: Path, first: int, n_new: int) -> None:
+        """Group numbers of the ``n_new`` rows just loaded behind ``first``: the part's own numbers offset behind the
+        groups already held (no key is looked up: parts never merge)."""
+        path = d / "groups.npy"
+        if not path.exists():
+            self._extend_groups(first, n_new, None)
+            return
+        numbers = np.load(path).astype(np.int32).reshape(-1)
+        with open(d / "group_keys.json") as f:
+            keys = list(json.load(f))
+        if numbers.size != n_new or (numbers.size and (numbers.min() < 0 or numbers.max() >= len(keys))):
+            raise ValueError(f"{d}: groups.npy does not match the index ({numbers.size} entries for {n_new} rows, {len(keys)} keys)")
+        self._extend_groups(first, 0, [])   # rows already held become singleton groups if they had none
+        base = len(self.group_keys)
+        self.group_keys.extend(keys)
+        self._row_group_host = np.concatenate([self._row_group_host, numbers + np.int32(base)])
+        for g, key in enumerate(keys, start=base):
+            if key is not None:
+                self._group_of_key.setdefault(key, g)
+        self._groups_changed()
+
     def cleanup(self) -> None:
         self._tiled = None
         self._workspace = None
         self._n = 0
         self._reset_removed()
+        self._reset_groups()
 
 
 # ---------------------------------------------------------------------- helpers
@@ -747,6 +1048,28 @@ def read_corpus_parquet(parquet_path, max_docs: Optional[int] = None, text_colum
     else:
         ids = [f"doc_{i}" for i in range(len(texts))]
     return ids, texts
+
+
+def read_parquet_column(parquet_path, column: str, max_docs: Optional[int] = None) -> List[str]:
+    """One column of a corpus parquet file as strings (the group keys of ``build_from_parquet(group_column=...)``)."""
+    import pandas as pd
+
+    df = pd.read_parquet(parquet_path)
+    if max_docs is not None:
+        df = df.head(max_docs)
+    if column not in df.columns:
+        raise KeyError(f"parquet file {parquet_path} has no {column!r} column")
+    return df[column].astype(str).tolist()
+
+
+def groups_from_chunk_ids(chunk_ids: Sequence[str]) -> List[str]:
+    """The document of every chunk by the reference's rule (its ``maxsim_aggregation``): the chunk id up to its last
+    ``_`` - ``"_".join(chunk_id.split("_")[:-1])`` - and the whole id when it holds no ``_``."""
+    out = []
+    for cid in chunk_ids:
+        parts = str(cid).split("_")
+        out.append("_".join(parts[:-1]) if len(parts) > 1 else str(cid))
+    return out
 
 
 def range_thresholds(threshold, nq: int) -> np.ndarray:
