@@ -1063,47 +1063,91 @@ __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restri
   }
 }
 
+// k-steps [0, BG) at the wave-uniform address `base`: lane l reads the 16 bytes at lane_off = 16 l of every step.  Uniform
+// base + 32-bit lane offset is the scalar-base form of global_load: tile addresses cost scalar adds, no 64-bit vector
+// pointers held (and spilled) across the tile loop.
 template <int BG>
-__device__ inline void load_bgroup(sbf16x8 (&buf)[BG], const sbf16x8* __restrict__ base) {
+__device__ __forceinline__ void load_bgroup(sbf16x8 (&buf)[BG], const sbf16x8* __restrict__ base, unsigned lane_off) {
+  asm volatile("" : "+v"(lane_off));   // widened next to its loads, not once per kernel into a 64-bit pair that spills
 #pragma unroll
-  for (int s = 0; s < BG; ++s) buf[s] = base[s * 64];
+  for (int s = 0; s < BG; ++s)
+    buf[s] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 64) + lane_off);
 }
 
-// One group of k-steps.  (A two-deep register pipeline of the LDS query-fragment reads, pinned with
-// sched_group_barrier, was built and measured: 9.6 ms against 8.5 ms for the compiler's own
-// "two reads, wait, MFMA" placement below - the pinned order delays the tile prefetch loads.)
-template <int QB, int G, int BG>
-__device__ inline void compute_bgroup(const sbf16x8 (&a)[BG], const sbf16x8* __restrict__ qlane, f32x16 (&acc)[QB]) {
-  asm volatile("" ::: "memory");  // keep the (tile-invariant) LDS query reads inside the group (see compute_group)
-#pragma unroll
-  for (int s = 0; s < BG; ++s) {
-#pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-#ifdef SSKD_SCREEN_ABL_NOLDS   // timing ablation (tools/ab_search.py, AB_NOCHECK): no LDS query-fragment reads
-      const sbf16x8 b = a[(s + qq) % BG];
-#else
-      const sbf16x8 b = qlane[(qq * BSTEPS + G * BG + s) * 64];
+// The query fragments of a workgroup sit in LDS as [QB][24 k-steps][64 lanes] x 16 bytes: 1 KiB per (sub-block, k-step),
+// up to 120 KiB in all, and a ds_read takes a 16-bit byte offset.  One base address per 64 fragments, set up once per
+// phase and hidden from the optimiser, makes every fragment address "base + immediate"; left alone, the compiler forms
+// the far addresses with a v_add_u32 and a register of their own per read.
+typedef __attribute__((address_space(3))) const sbf16x8 screen_lds_frag;
+constexpr int SCREEN_FRAGS_PER_BASE = 64;
+template <int QB>
+constexpr int screen_frag_bases() { return (QB * BSTEPS + SCREEN_FRAGS_PER_BASE - 1) / SCREEN_FRAGS_PER_BASE; }
+// Fragment ring of a wave: the LDS read of MFMA i + SCREEN_FRAG_DEPTH - 1 is issued in front of MFMA i.  The register
+// budget of three waves per SIMD (168) decides the depth: 3 compiles with 8 spilled registers in the 160-query kernel
+// and a scratch reload inside its tile loop, 2 with the 2 it had before the ring (per instantiation: DESIGN.md 3.1b)
+#ifndef SSKD_SCREEN_FRAG_DEPTH
+#define SSKD_SCREEN_FRAG_DEPTH 2
 #endif
-      acc[qq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], b, acc[qq], 0, 0, 0);
-    }
+constexpr int SCREEN_FRAG_DEPTH = SSKD_SCREEN_FRAG_DEPTH;
+static_assert(SCREEN_FRAG_DEPTH >= 2, "the fragment ring holds the MFMA's own operand and at least one read ahead");
+
+// fragment of the tile's I-th MFMA: MFMAs run k-step major, sub-block minor (I = kstep * QB + qq)
+template <int QB, int NB>
+__device__ __forceinline__ sbf16x8 read_qfrag(screen_lds_frag* const (&qbase)[NB], int I) {
+  const int f = (I % QB) * BSTEPS + I / QB;
+  return qbase[f / SCREEN_FRAGS_PER_BASE][(f % SCREEN_FRAGS_PER_BASE) * 64];
+}
+
+// One group of k-steps: BG x QB MFMAs, each accumulator's k ascending.  The query fragments go through a register ring
+// D deep that runs D - 1 LDS reads ahead of the MFMA that consumes them, across the groups of a tile (the fragments do
+// not depend on the tile): every MFMA waits with a counted lgkmcnt(D - 2) for its own fragment while the next reads are
+// in flight, so ONE ready wave keeps the matrix pipe of its SIMD fed when its partners are parked on their tile ring or
+// in their epilogue.  A scheduling barrier on both sides of each MFMA pins that order - left to itself the machine
+// scheduler sinks every read to "read, lgkmcnt(0), MFMA", a full LDS round trip in front of each 32-cycle MFMA.  The
+// tile ring's global loads are issued by the caller ahead of the group and stay there.  (Rounds 2-3 measured a two-deep
+// pipeline pinned with sched_group_barrier on the list form of the kernel - two waves per SIMD, 255 registers - at
+// 9.6 ms against 8.5 ms: that order delayed the tile prefetch loads.  Numbers for this form: DESIGN.md section 3.1b.)
+template <int QB, int G, int BG, int D, int NB>
+__device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG], screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D],
+                                               f32x16 (&acc)[QB]) {
+  constexpr int N = BG * QB, I0 = G * N, TOTAL = BSTEPS * QB;
+  asm volatile("" ::: "memory");  // keep the (tile-invariant) LDS query reads inside the tile (see compute_group)
+#ifndef SSKD_SCREEN_ABL_NOLDS
+  if constexpr (G == 0) {
+#pragma unroll
+    for (int i = 0; i < D - 1; ++i) b[i % D] = read_qfrag<QB>(qbase, i);
+  }
+#endif
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int I = I0 + i, s = i / QB, qq = i % QB;
+#ifdef SSKD_SCREEN_ABL_NOLDS   // timing ablation (tools/ab_search.py, AB_NOCHECK): no LDS query-fragment reads
+    const sbf16x8 bi = a[(s + qq) % BG];
+#else
+    if (I + D - 1 < TOTAL) b[(I + D - 1) % D] = read_qfrag<QB>(qbase, I + D - 1);
+    const sbf16x8 bi = b[I % D];
+#endif
+    __builtin_amdgcn_sched_barrier(0);
+    acc[qq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bi, acc[qq], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
 // one tile's groups, compile-time unrolled over a ring of RG register buffers: group G is multiplied
 // from buffer G % RG while group G + RG - 1 (of this tile, or of the wave's next tile) loads
-template <int QB, int G, int BG, int RG>
-__device__ inline void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const sbf16x8* __restrict__ tile,
-                                          const sbf16x8* __restrict__ qlane, f32x16 (&acc)[QB], bool more,
-                                          int64_t next_tile) {
+template <int QB, int G, int BG, int RG, int D, int NB>
+__device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const sbf16x8* __restrict__ tile,
+                                                   screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D], f32x16 (&acc)[QB],
+                                                   bool more, int64_t next_tile, unsigned lane_off) {
   constexpr int NG = BSTEPS / BG;
   if constexpr (G < NG) {
     constexpr int PG = G + RG - 1;  // group to prefetch now
 #ifndef SSKD_SCREEN_ABL_NOGLOBAL  // timing ablation: no corpus tile loads (the ring keeps its first contents)
-    if constexpr (PG < NG) load_bgroup<BG>(buf[PG % RG], tile + PG * BG * 64);
-    else if (more) load_bgroup<BG>(buf[PG % RG], tile + next_tile + (PG - NG) * BG * 64);
+    if constexpr (PG < NG) load_bgroup<BG>(buf[PG % RG], tile + PG * BG * 64, lane_off);
+    else if (more) load_bgroup<BG>(buf[PG % RG], tile + next_tile + (PG - NG) * BG * 64, lane_off);
 #endif
-    compute_bgroup<QB, G, BG>(buf[G % RG], qlane, acc);
-    screen_tile_groups<QB, G + 1, BG, RG>(buf, tile, qlane, acc, more, next_tile);
+    compute_bgroup<QB, G, BG, D, NB>(buf[G % RG], qbase, b, acc);
+    screen_tile_groups<QB, G + 1, BG, RG, D, NB>(buf, tile, qbase, b, acc, more, next_tile, lane_off);
   }
 }
 
@@ -1181,20 +1225,32 @@ __device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* 
 // The in-call exact fallback scans with the same mask.
 template <int K, int QB, int WAVES, bool BOUND_ONLY, bool LIGHT, int BG, int RG, bool MASKED = false>
 __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_begin, int t_end, int wave, int j, int h, int q0,
-                                             const sbf16x8* __restrict__ lane_base, const sbf16x8* __restrict__ qlane,
+                                             const sbf16x8* __restrict__ qlane,
                                              int* __restrict__ pool, int* __restrict__ wthr, uint2* run0, int64_t run_stride,
-                                             bool ragged, float (&gthr)[QB], const float (&band)[QB], int (&cnt)[QB],
-                                             const bool (&real)[QB]) {
+                                             bool ragged, float (&gthr)[QB], const float (&band)[QB], int (&cnt)[QB]) {
   sbf16x8 buf[RG][BG];
+  constexpr int NB = screen_frag_bases<QB>();
+  screen_lds_frag* qbase[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    qbase[nb] = (screen_lds_frag*)qlane + nb * SCREEN_FRAGS_PER_BASE * 64;
+    asm volatile("" : "+v"(qbase[nb]));   // one register each, not re-derived per read
+  }
+  sbf16x8 qfrag[SCREEN_FRAG_DEPTH];
+  const unsigned lane_off = (unsigned)(j + 32 * h) * 16u;
+  // sub-block qq of this lane holds a real query (not padding of the last block) while 32 qq < n_real: one register and
+  // a compare per use instead of QB flags held across the MFMA burst
+  int n_real = p.nq - q0 - j;
+  asm volatile("" : "+v"(n_real));
   int t = t_begin + wave;
   if (t < t_end) {
 #pragma unroll
-    for (int g = 0; g + 1 < RG; ++g) load_bgroup<BG>(buf[g], lane_base + (int64_t)t * BTILE_VEC + g * BG * 64);
+    for (int g = 0; g + 1 < RG; ++g) load_bgroup<BG>(buf[g], p.tiled + (int64_t)t * BTILE_VEC + g * BG * 64, lane_off);
   }
 
   int tiles_done = 0;
   for (; t < t_end; t += WAVES, ++tiles_done) {
-    const sbf16x8* tile = lane_base + (int64_t)t * BTILE_VEC;
+    const sbf16x8* tile = p.tiled + (int64_t)t * BTILE_VEC;   // wave-uniform
     uint32_t mword = 0xFFFFFFFFu;
     if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
     // bounds are exchanged with global memory at tile 0 (the sample phases' bounds), tile 16 and every 64th: an exchange is
@@ -1205,7 +1261,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     for (int qq = 0; qq < QB; ++qq) {
       const int w = wthr[qq * 32 + j];
       gthr[qq] = fmaxf(gthr[qq], ordered_to_float(w) - band[qq]);
-      if (exchange && real[qq])
+      if (exchange && (qq * 32 < n_real))
         gthr[qq] = fmaxf(gthr[qq],
                          ordered_to_float(exchange_bound<K>(p.gpool, p.tau + q0 + qq * 32 + j, q0 + qq * 32 + j, w)) - band[qq]);
     }
@@ -1215,7 +1271,8 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
 
-    screen_tile_groups<QB, 0, BG, RG>(buf, tile, qlane, acc, t + WAVES < t_end, (int64_t)WAVES * BTILE_VEC);
+    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tile, qbase, qfrag, acc, t + WAVES < t_end,
+                                                             (int64_t)WAVES * BTILE_VEC, lane_off);
 
     const int rowbase = t * TILE_ROWS + 4 * h;
     if (ragged && (int64_t)(t + 1) * TILE_ROWS > p.n_rows) {
@@ -1241,7 +1298,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
       if constexpr (BOUND_ONLY) {
         // the sample phase only needs a bound: ONE offer per lane and tile (its best row) instead of one per row - every
         // row of a cold sample passes, and 80 compare-and-swap loops per lane and tile cost 0.05 ms per call
-        if (real[qq] && m >= gthr[qq]) {
+        if ((qq * 32 < n_real) && m >= gthr[qq]) {
           int xid = rowbase;
 #pragma unroll
           for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
@@ -1251,7 +1308,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
           gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
         }
       } else
-      if (__any(real[qq] && m >= gthr[qq])) {
+      if (__any((qq * 32 < n_real) && m >= gthr[qq])) {
 #ifndef SSKD_SCREEN_NO_COMPACT
         {
           // A run that could fill up inside this tile (16 rows) first drops what the bound has overtaken since it was
@@ -1270,7 +1327,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
         for (int r = 0; r < 16; ++r) {
           const float x = acc[qq][r];
           const int xid = rowbase + acc_row(r);
-          const bool take = real[qq] && x >= gthr[qq];   // (padding queries own no run)
+          const bool take = (qq * 32 < n_real) && x >= gthr[qq];   // (padding queries own no run)
           {   // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
             if (take) {
               {
@@ -1281,7 +1338,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
               }
               if (!LIGHT && tiles_done > 0) {
                 const int xi = float_to_ordered(x);
-                if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && real[qq])
+                if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && (qq * 32 < n_real))
                   bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
               }
               grew = true;
@@ -1366,7 +1423,6 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   uint2* const run0 = p.cand + ((int64_t)min(q0 + j, p.nq - 1) * p.lists_per_query + my_list) * SCREEN_CAP;
   const int64_t run_stride = (int64_t)32 * p.lists_per_query * SCREEN_CAP;
 
-  const sbf16x8* lane_base = p.tiled + lane;
   const bool ragged = (p.n_rows & 31) != 0;
 
   // Two phases.  0: this workgroup's share of the SAMPLE (the shard's first pre_tiles tiles, cut over the slices),
@@ -1380,8 +1436,8 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   if (p.pre_tps > 0) {
     const int s_begin = slice * p.pre_tps;
     const int s_end = min(s_begin + p.pre_tps, p.pre_tiles);
-    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, wave, j, h, q0, lane_base, qlane,
-                                             pool, wthr, run0, run_stride, ragged, gthr, band, cnt, real);
+    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, wave, j, h, q0, qlane,
+                                             pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
     // what this workgroup learned from its share of the sample; everybody's offers are in before phase 1
 #pragma unroll
     for (int qq = 0; qq < QB; ++qq)
@@ -1400,8 +1456,8 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
       __syncthreads();
     }
   }
-  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, wave, j, h, q0, lane_base,
-                                            qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt, real);
+  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, wave, j, h, q0,
+                                            qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
 
 #pragma unroll
   for (int qq = 0; qq < QB; ++qq) {
