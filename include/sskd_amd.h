@@ -319,6 +319,30 @@ int sskd_index_search_grouped(const float* d_tiled, int64_t n_rows, const float*
                               int32_t* d_unproved, int32_t* d_n_unproved, void* d_workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Compaction: drop the rows a mask clears from HBM and renumber the rest
+ *   (faiss: IndexFlat::remove_ids shifts the surviving rows down)
+ * d_mask: the format of "Filtered search" (bit set = the row stays); bits at or past n_rows are ignored.
+ * sskd_row_mask_rank writes d_word_prefix, DEVICE int64 [sskd_row_mask_words(n_rows) + 1]: entry w = the number of set
+ * bits in words 0 .. w-1 (an exclusive prefix sum of popcounts), the last entry = the live count.  The new number of
+ * a live row r is
+ *     new(r) = d_word_prefix[r >> 5] + popcount(d_mask[r >> 5] & ((1u << (r & 31)) - 1)),
+ * which is monotone in r.  One workgroup walks the mask; the call needs no scratch.
+ * sskd_index_compact_rows copies every live row of the source matrix to row new(r) of the destination, bit for bit (no
+ * arithmetic: NaN, +-0 and denormal patterns survive), zero-fills the destination rows [n_live,
+ * sskd_index_padded_rows(n_live)) and writes nothing at or past them; n_live = 0 writes nothing.  d_mask and
+ * d_word_prefix are the ones of the rank call for the same n_rows.  The call is OUT OF PLACE: the destination needs
+ * sskd_index_tiled_bytes(n_live) bytes that do not overlap the source.  The live count is on the device, so the call
+ * refuses (SSKD_ERR_INVALID) what it can see from the host - a destination that starts inside the source's
+ * sskd_index_tiled_bytes(n_rows), a source that starts inside the destination's first tile - and a destination placed
+ * below the source must end before it: the caller guarantees that.
+ * Both: stream-ordered, no host sync, allocate nothing; arguments are checked before any launch (n_rows < 0, a shard
+ * of 2^31 - 64 rows or more, NULL pointers: SSKD_ERR_INVALID); n_rows = 0 is a successful no-op that writes nothing.
+ * ------------------------------------------------------------------------- */
+int sskd_row_mask_rank(const uint32_t* d_mask, int64_t n_rows, int64_t* d_word_prefix, void* stream);
+int sskd_index_compact_rows(const float* d_src_tiled, int64_t n_rows, const uint32_t* d_mask,
+                            const int64_t* d_word_prefix, float* d_dst_tiled, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

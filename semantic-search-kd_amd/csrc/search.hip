@@ -3507,3 +3507,167 @@ int sskd_index_search_grouped(const float* d_tiled, int64_t n_rows, const float*
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------- //
+// Compaction (sskd_amd.h): drop the rows a mask clears and renumber the rest.
+//
+// Step 1 ranks the mask: the exclusive prefix sum of the popcounts of its words, so live row r moves to
+// prefix[r >> 5] + popcount(word & ((1u << (r & 31)) - 1)).  Step 2 copies the live rows, out of place, source tile by
+// source tile.  A mask word IS a source tile (32 rows each), so a wave needs one word and one prefix entry, and the live
+// rows of its tile land on one contiguous run of destination lines.
+// ------------------------------------------------------------------------- //
+namespace {
+
+constexpr int RANK_THREADS = 1024;
+constexpr int RANK_WORDS = 4;  // consecutive words per thread and step: one workgroup ranks 4 096 words per step
+
+// One workgroup walks the whole mask (276 k words at 8.84 M rows: 68 steps), carrying the running count.
+__global__ __launch_bounds__(RANK_THREADS) void row_mask_rank_kernel(const uint32_t* __restrict__ mask, int64_t n_rows,
+                                                                     int64_t* __restrict__ prefix) {
+  __shared__ uint32_t wave_total[RANK_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t n_words = (n_rows + 31) >> 5;
+  // the bits at or past n_rows are ignored (the index keeps them set)
+  const uint32_t last_keep = (n_rows & 31) ? (1u << (n_rows & 31)) - 1u : ~0u;
+  int64_t carry = 0;  // set bits in the words before this step
+  for (int64_t base = 0; base < n_words; base += (int64_t)RANK_THREADS * RANK_WORDS) {
+    const int64_t w0 = base + (int64_t)tid * RANK_WORDS;
+    uint32_t c[RANK_WORDS], mine = 0;
+#pragma unroll
+    for (int j = 0; j < RANK_WORDS; ++j) {
+      const int64_t w = w0 + j;
+      uint32_t v = w < n_words ? mask[w] : 0u;
+      if (w == n_words - 1) v &= last_keep;
+      c[j] = __popc(v);
+      mine += c[j];
+    }
+    uint32_t incl = mine;  // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t below = __shfl_up(incl, o);
+      if (lane >= o) incl += below;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int i = 0; i < RANK_THREADS / 64; ++i) {
+      const uint32_t x = wave_total[i];
+      if (i < wave) before += x;
+      total += x;
+    }
+    int64_t p = carry + before + (incl - mine);
+#pragma unroll
+    for (int j = 0; j < RANK_WORDS; ++j) {
+      if (w0 + j < n_words) prefix[w0 + j] = p;
+      p += c[j];
+    }
+    carry += total;
+    __syncthreads();  // wave_total is rewritten by the next step
+  }
+  if (tid == 0) prefix[n_words] = carry;
+}
+
+constexpr int COMPACT_WAVES = 4;
+constexpr int COMPACT_ROWS = 4;                               // live rows moved per step
+constexpr int COMPACT_LOADS = COMPACT_ROWS * CHUNKS / 64;     // 6 wave-wide 16-byte loads in flight, then 6 stores
+static_assert(COMPACT_ROWS * CHUNKS % 64 == 0, "a step is a whole number of wave-wide accesses");
+
+__device__ inline int64_t wave_uniform(int64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// One wave per SOURCE tile t (= mask word t); wave n_tiles zero-fills the tail of the last destination tile.  Everything
+// that steers the wave (word, prefix, the rows of a step) is wave-uniform; lanes differ only in the 16-byte chunk they
+// move.  The live rows of a tile are consecutive in the destination, so chunk c of a step goes to out + c: a step of four
+// rows is 6 KiB of whole 128-byte lines on both sides.
+__global__ __launch_bounds__(COMPACT_WAVES * 64) void index_compact_rows_kernel(
+    const float4* __restrict__ src, int64_t n_rows, const uint32_t* __restrict__ mask,
+    const int64_t* __restrict__ prefix, float4* __restrict__ dst, int64_t n_tiles) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * COMPACT_WAVES + (threadIdx.x >> 6);
+  if (t > n_tiles) return;
+  if (t == n_tiles) {
+    const int64_t n_live = wave_uniform(prefix[n_tiles]);
+    const int64_t end = (n_live + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS * CHUNKS;
+    for (int64_t i = n_live * CHUNKS + lane; i < end; i += 64) dst[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  uint32_t word = __builtin_amdgcn_readfirstlane(mask[t]);
+  if (t == n_tiles - 1 && (n_rows & 31)) word &= (1u << (n_rows & 31)) - 1u;
+  if (word == 0) return;  // a tile without live rows: its rows are never touched
+  const float4* in = src + t * (int64_t)(TILE_ROWS * CHUNKS);
+  float4* out = dst + wave_uniform(prefix[t]) * CHUNKS;
+  while (word) {
+    int row[COMPACT_ROWS], n = 0;
+#pragma unroll
+    for (int j = 0; j < COMPACT_ROWS; ++j) {
+      row[j] = 0;
+      if (word) {
+        row[j] = __ffs((int)word) - 1;
+        word &= word - 1;
+        ++n;
+      }
+    }
+    const int total = n * CHUNKS;
+    float4 v[COMPACT_LOADS];
+#pragma unroll
+    for (int i = 0; i < COMPACT_LOADS; ++i) {
+      const int c = i * 64 + lane;
+      const int which = c / CHUNKS;
+      int r = row[0];
+#pragma unroll
+      for (int j = 1; j < COMPACT_ROWS; ++j) r = which == j ? row[j] : r;
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < total) x = in[r * CHUNKS + (c - which * CHUNKS)];
+      v[i] = x;
+    }
+#pragma unroll
+    for (int i = 0; i < COMPACT_LOADS; ++i) {
+      const int c = i * 64 + lane;
+      if (c < total) out[c] = v[i];
+    }
+    out += total;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sskd_row_mask_rank(const uint32_t* d_mask, int64_t n_rows, int64_t* d_word_prefix, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "row_mask_rank: n_rows < 0");
+  const int rc = require_shard_rows("row_mask_rank", n_rows);
+  if (rc != SSKD_OK) return rc;
+  if (n_rows == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_mask && d_word_prefix, "row_mask_rank: null pointer");
+  hipLaunchKernelGGL(row_mask_rank_kernel, dim3(1), dim3(RANK_THREADS), 0, sskd::as_stream(stream), d_mask, n_rows,
+                     d_word_prefix);
+  return sskd::check_launch("row_mask_rank_kernel");
+}
+
+int sskd_index_compact_rows(const float* d_src_tiled, int64_t n_rows, const uint32_t* d_mask,
+                            const int64_t* d_word_prefix, float* d_dst_tiled, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "index_compact_rows: n_rows < 0");
+  const int rc = require_shard_rows("index_compact_rows", n_rows);
+  if (rc != SSKD_OK) return rc;
+  if (n_rows == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_src_tiled && d_mask && d_word_prefix && d_dst_tiled, "index_compact_rows: null pointer");
+  // out of place.  The live count is on the device, so the host knows the source's extent but of the destination's
+  // only that it is at least one tile (unless nothing is live): a destination that starts inside the source, or a
+  // source that starts inside the destination's first tile, is refused.  A destination placed BELOW the source must
+  // end (padded_rows(n_live) rows) before the source begins: that is the caller's to guarantee.
+  const uintptr_t s = reinterpret_cast<uintptr_t>(d_src_tiled), d = reinterpret_cast<uintptr_t>(d_dst_tiled);
+  const uintptr_t src_bytes = sskd_index_tiled_bytes(n_rows), tile_bytes = (uintptr_t)TILE_FLOATS * sizeof(float);
+  SSKD_REQUIRE(!(d >= s && d < s + src_bytes) && !(s >= d && s < d + tile_bytes),
+               "index_compact_rows: source and destination overlap");
+  const int64_t n_tiles = sskd::ceil_div(n_rows, TILE_ROWS);
+  hipLaunchKernelGGL(index_compact_rows_kernel, dim3((unsigned)sskd::ceil_div(n_tiles + 1, COMPACT_WAVES)),
+                     dim3(COMPACT_WAVES * 64), 0, sskd::as_stream(stream), reinterpret_cast<const float4*>(d_src_tiled),
+                     n_rows, d_mask, d_word_prefix, reinterpret_cast<float4*>(d_dst_tiled), n_tiles);
+  return sskd::check_launch("index_compact_rows_kernel");
+}
+
+}  // extern "C"

@@ -76,6 +76,9 @@ class IndexHandle:
     def remove_ids(self, ids) -> int:
         return self._owner.remove_ids(ids)
 
+    def compact(self) -> np.ndarray:
+        return self._owner.compact()
+
     @property
     def ntotal(self) -> int:
         return self._owner.ntotal
@@ -460,6 +463,62 @@ class FAISSIndexBuilder:
         words = self._live[: int(_native.load().sskd_row_mask_words(self._n))].cpu().numpy().view(np.uint8)
         live = np.unpackbits(words, bitorder="little")[: self._n].astype(bool)
         return np.flatnonzero(~live).astype(np.int64)
+
+    def compact(self) -> np.ndarray:
+        """Drop the rows taken out by ``remove_ids`` from HBM and renumber the rest (what faiss' flat ``remove_ids``
+        does at once).  Returns ``kept``: the OLD ids (``id_offset + old row``, int64, ascending) of the surviving rows
+        in their new order - new id ``id_offset + j`` was old id ``kept[j]``, so a caller remaps its own references with
+        ``np.searchsorted(kept, old_id)``.  The surviving rows keep their order and their bits, so every search
+        returns the same scores as before, with the ids renumbered.
+
+        The rows move into a new buffer of exactly the size they need (the old capacity is given back), the tombstones
+        are reset, ``doc_ids`` and the row groups are gathered and ``doc_texts`` loses the texts no surviving row refers
+        to.  Group numbers do NOT change: a group whose rows are all gone stays as an empty group, so ``G`` values a
+        caller holds stay valid.  ``id_offset`` stays.  A ``RowFilter`` prepared before the call no longer fits.
+        Nothing removed: returns the identity and touches nothing.  A piece of a row-sharded build (``shard_info``
+        set) raises ``ValueError``: compacting one shard alone would break the manifest's contiguous id ranges."""
+        if self.shard_info:
+            raise ValueError("compact(): this index is one piece of a row-sharded build (shard_info is set); compacting "
+                             "one shard alone would break the contiguous id ranges of the shard manifest")
+        if self._n_removed == 0:
+            return self.id_offset + np.arange(self._n, dtype=np.int64)
+        lib = _native.load()
+        n_old = self._n
+        gone = self.removed_rows()
+        n_live = n_old - gone.size
+        with torch.cuda.device(self.device):
+            stream = _stream(self.device)
+            prefix = torch.empty(int(lib.sskd_row_mask_words(n_old)) + 1, dtype=torch.int64, device=self.device)
+            _native.check(lib.sskd_row_mask_rank(self._live.data_ptr(), n_old, prefix.data_ptr(), stream))
+            new = torch.empty(int(lib.sskd_index_padded_rows(n_live)) * self.embedding_dim, dtype=torch.float32,
+                              device=self.device)
+            if n_live:
+                _native.check(lib.sskd_index_compact_rows(self._tiled.data_ptr(), n_old, self._live.data_ptr(),
+                                                          prefix.data_ptr(), new.data_ptr(), stream))
+            if int(prefix[-1].item()) != n_live:
+                raise RuntimeError("sskd_row_mask_rank disagrees with the tombstone count")
+        self._tiled = new   # the old buffer (and its spare capacity) goes back to the allocator
+        self._n = n_live
+        self._reset_removed()
+        self._bf16 = None
+        self._bf16_rows = -1   # the screening sidecar is stale (its mean row changes anyway)
+        self.index = IndexHandle(self)
+        kept = _kept_rows(n_old, gone)
+        self._compact_host(kept)
+        return kept + self.id_offset
+
+    def _compact_host(self, kept: np.ndarray) -> None:
+        """The host-side bookkeeping of ``compact``: ``kept`` = the surviving old local rows, ascending."""
+        # ``add`` appends rows without doc ids, so the list may be shorter than the rows: the rows that have one keep it
+        # (``kept`` ascends, so the gathered list still lines up with the first rows)
+        n_ids = len(self.doc_ids)
+        self.doc_ids = [self.doc_ids[r] for r in kept.tolist() if r < n_ids]
+        if self.doc_texts is not None:
+            alive = set(self.doc_ids)
+            self.doc_texts = {key: text for key, text in self.doc_texts.items() if key in alive}
+        if self._row_group_host is not None:
+            self._row_group_host = np.ascontiguousarray(self._row_group_host[kept])
+        self._groups_changed()
 
     def row_filter(self, allow) -> RowFilter:
         """Prepare a per-call filter over the CURRENT ``ntotal`` rows: a bool array (one entry per row), an integer
@@ -1070,6 +1129,13 @@ def groups_from_chunk_ids(chunk_ids: Sequence[str]) -> List[str]:
         parts = str(cid).split("_")
         out.append("_".join(parts[:-1]) if len(parts) > 1 else str(cid))
     return out
+
+
+def _kept_rows(n_rows: int, removed: np.ndarray) -> np.ndarray:
+    """The rows of ``range(n_rows)`` not in ``removed`` (sorted local rows), ascending int64."""
+    live = np.ones(n_rows, dtype=np.bool_)
+    live[removed] = False
+    return np.flatnonzero(live).astype(np.int64)
 
 
 def range_thresholds(threshold, nq: int) -> np.ndarray:
