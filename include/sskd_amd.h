@@ -343,6 +343,36 @@ int sskd_row_mask_rank(const uint32_t* d_mask, int64_t n_rows, int64_t* d_word_p
 int sskd_index_compact_rows(const float* d_src_tiled, int64_t n_rows, const uint32_t* d_mask,
                             const int64_t* d_word_prefix, float* d_dst_tiled, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Hard-negative mining over a row ranking (ANCE refresh): the rows that fool the student
+ *   reference: ANCEMiner.mine, src/mining/miners.py:232-247 (max positive score, margin rule, stable descending sort,
+ *   the first top_k)
+ * Inputs per query q: the ranking d_rank_scores / d_rank_ids [nq, search_k] as any of the searches above writes it
+ * with id_offset 0 (LOCAL rows, score descending then lower row, padded with id -1), and the query's positives
+ * d_pos_rows[d_pos_lims[q] .. d_pos_lims[q + 1]) (DEVICE int64 [nq + 1] / int32, local rows in any order; the caller
+ * guarantees d_pos_lims is non-decreasing and ends inside d_pos_rows; d_pos_rows == NULL: no query has positives).
+ *   - max_pos = the maximum of score(q, r) over the positives r, score being the fp32 fma chain of the exact scan: bit
+ *     for bit the value a search returns for row r.  Positives are labels, not candidates: they are scored whether or
+ *     not a row mask or a removal hides them from the search.  No positives: max_pos = 0.0f (the reference's rule).  A
+ *     positive outside [0, n_rows) is ignored.
+ *   - the walk stops at the first id -1.  A rank is DROPPED when its row is one of the positives, or when d_row_groups
+ *     (DEVICE int32 [n_rows], NULL = off) is given and its group equals the group of a positive.
+ *   - a rank is KEPT when (double)score >= (double)max_pos - margin, decided in fp64 (the reference's expression under
+ *     the NumPy it pins: a float32 score against a Python float).
+ *   - the kept ranks are written in rank order, which is the stable descending order the reference sorts into: the
+ *     first top_k to d_out_scores fp32 / d_out_ids int64 [nq, top_k] (row + id_offset; id_offset shifts the ids
+ *     written, never the positives read), the tail padded with (-FLT_MAX, -1).  d_out_counts int32 [nq] = ALL kept
+ *     ranks of the window, before the top_k cut; d_out_max_pos fp32 [nq].
+ * One wave per query.  Limits: 1 <= top_k <= search_k <= SSKD_K_MAX; d_queries and d_tiled 16-byte aligned.
+ * Stream-ordered, no host sync, no workspace, allocates nothing; arguments are checked before the launch
+ * (SSKD_ERR_INVALID); nq = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_index_mine_select(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq,
+                           const float* d_rank_scores, const int64_t* d_rank_ids, int search_k,
+                           const int64_t* d_pos_lims, const int32_t* d_pos_rows, const int32_t* d_row_groups,
+                           double margin, int top_k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
+                           int32_t* d_out_counts, float* d_out_max_pos, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

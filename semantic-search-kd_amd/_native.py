@@ -170,6 +170,9 @@ SIGNATURES = {
     ),
     "sskd_row_mask_rank": (_i, [_vp, _i64, _vp, _vp]),
     "sskd_index_compact_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "sskd_index_mine_select": (
+        _i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, C.c_double, _i, _i64, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

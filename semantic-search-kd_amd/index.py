@@ -610,8 +610,10 @@ class FAISSIndexBuilder:
             self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
         return self._workspace
 
-    def _search_device_masked(self, queries, k, normalize_queries, out_scores, out_ids, mask):
+    def _search_device_masked(self, queries, k, normalize_queries, out_scores, out_ids, mask, id_offset=None):
+        """``id_offset``: the id of local row 0 in the ids written (None: the index's own)."""
         lib = _native.load()
+        id_offset = self.id_offset if id_offset is None else int(id_offset)
         if k < 1 or k > _native.SSKD_K_MAX:
             raise ValueError(f"k={k} outside [1, {_native.SSKD_K_MAX}]")
         q = self._prepare_queries(queries, normalize_queries, "search_device")
@@ -637,7 +639,7 @@ class FAISSIndexBuilder:
                 self.last_status = torch.empty(2, dtype=torch.int32, device=self.device)
                 _native.check(
                     lib.sskd_index_search_screened_filtered(
-                        self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                        self._tiled.data_ptr(), self._bf16.data_ptr(), self._n, q.data_ptr(), nq, k, id_offset,
                         mask_ptr, out_scores.data_ptr(), out_ids.data_ptr(), self.last_status.data_ptr(),
                         ws.data_ptr(), ws.numel(), stream, None, None,
                     )
@@ -647,7 +649,7 @@ class FAISSIndexBuilder:
         ws = self._workspace_for(int(lib.sskd_index_search_workspace_bytes_ex(self._n, nq, k, tuning)))
         _native.check(
             lib.sskd_index_search_filtered(
-                0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
+                0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, id_offset,
                 mask_ptr, out_scores.data_ptr(), out_ids.data_ptr(), ws.data_ptr(), ws.numel(), stream, tuning, None, None,
             )
         )
@@ -709,6 +711,90 @@ class FAISSIndexBuilder:
         if self._n == 0 and self._tiled is None and self.index is None:
             raise RuntimeError("index is empty: call build_from_parquet/add/load first")
         return self._search_numpy(query_emb, k, normalize_queries=None, allow=allow)
+
+    # ------------------------------------------------------- hard-negative mining
+    def mine_negatives_device(
+        self,
+        queries: torch.Tensor,
+        pos_lims: torch.Tensor,
+        pos_rows: torch.Tensor,
+        *,
+        top_k: int = 5,
+        search_k: int = 100,
+        margin: float = 0.1,
+        allow=None,
+        by_group: bool = False,
+        normalize_queries: Optional[bool] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The ANCE rule on the device (``include/sskd_amd.h``, hard-negative mining): the ``search_k`` best rows of
+        every query are its candidates, its positives ``pos_rows[pos_lims[q]:pos_lims[q + 1]]`` (device int64 / int32,
+        LOCAL rows) are left out, and the candidates scoring ``>= max(positive scores) - margin`` (0.0 without
+        positives; decided in fp64) survive.  Returns device tensors ``(D [nq, top_k] float32, I [nq, top_k] int64,
+        counts [nq] int32, max_pos [nq] float32)``: the first ``top_k`` survivors in ``search``'s order, padded with
+        ``(-FLT_MAX, -1)``; ``counts`` is every survivor among the ``search_k`` candidates, before the cut.
+
+        ``allow`` and removed rows act on the candidates as in ``search``; a positive they hide still sets
+        ``max_pos``.  ``by_group=True`` also leaves out every row that shares a group with a positive (the other
+        chunks of a positive document).  No host synchronisation (``allow`` should then be a prepared ``RowFilter``):
+        the caller guarantees that ``pos_lims`` is non-decreasing and ends inside ``pos_rows``; ``mine_negatives``
+        checks all of that on the host."""
+        lib = _native.load()
+        top_k, search_k = int(top_k), int(search_k)
+        if top_k < 1 or top_k > search_k:
+            raise ValueError(f"top_k={top_k} outside [1, search_k={search_k}]")
+        if search_k > _native.SSKD_K_MAX:
+            raise ValueError(f"search_k={search_k} outside [1, {_native.SSKD_K_MAX}]")
+        if not isinstance(queries, torch.Tensor):
+            raise TypeError("mine_negatives_device expects a float32 device tensor")
+        q = self._prepare_queries(queries, normalize_queries, "mine_negatives_device")
+        nq = q.shape[0]
+        for name, t, dtype in (("pos_lims", pos_lims, torch.int64), ("pos_rows", pos_rows, torch.int32)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != 1:
+                raise TypeError(f"mine_negatives_device expects {name} as a 1-d {dtype} device tensor")
+        if pos_lims.numel() != nq + 1:
+            raise ValueError(f"pos_lims holds {pos_lims.numel()} entries for {nq} queries (needs nq + 1)")
+        mask = self._effective_mask(allow)
+        # the ranking in LOCAL rows: the kernel compares them with the positives and looks their groups up
+        rank_scores, rank_rows = self._search_device_masked(q, search_k, False, None, None, mask, id_offset=0)
+        scores = torch.empty((nq, top_k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((nq, top_k), dtype=torch.int64, device=self.device)
+        counts = torch.empty(nq, dtype=torch.int32, device=self.device)
+        max_pos = torch.empty(nq, dtype=torch.float32, device=self.device)
+        if nq == 0:
+            return scores, ids, counts, max_pos
+        lims, rows = pos_lims.contiguous(), pos_rows.contiguous()
+        groups = self._row_group_device() if by_group and self.group_keys is not None else None   # no groups: rows
+        _native.check(
+            lib.sskd_index_mine_select(
+                0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq,
+                rank_scores.data_ptr(), rank_rows.data_ptr(), search_k, lims.data_ptr(),
+                rows.data_ptr() if rows.numel() else None, None if groups is None else groups.data_ptr(),
+                float(margin), top_k, self.id_offset, scores.data_ptr(), ids.data_ptr(), counts.data_ptr(),
+                max_pos.data_ptr(), _stream(self.device),
+            )
+        )
+        return scores, ids, counts, max_pos
+
+    def mine_negatives(self, query_emb: np.ndarray, positives, *, top_k: int = 5, search_k: int = 100,
+                       margin: float = 0.1, allow=None, by_group: bool = False):
+        """``mine_negatives_device`` for host queries: NumPy ``(D, I, counts, max_pos)``.  ``positives``: one list of
+        LOCAL rows per query, or a ``(lims, rows)`` tuple (query ``q`` owns ``rows[lims[q]:lims[q + 1]]``); rows are
+        sorted and de-duplicated per query, rows outside the index raise ``ValueError``.  ``by_group=True`` on an index
+        without groups means every row is its own group, as in ``search_grouped``."""
+        if top_k < 1 or top_k > search_k:
+            raise ValueError(f"top_k={top_k} outside [1, search_k={search_k}]")
+        if search_k > _native.SSKD_K_MAX:
+            raise ValueError(f"search_k={search_k} outside [1, {_native.SSKD_K_MAX}]")
+        q = np.ascontiguousarray(np.asarray(query_emb, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None, :]
+        lims, rows = normalize_positives(positives, q.shape[0], self._n)
+        qd = _host_queries_to_device(q, self.device)
+        with torch.cuda.device(self.device):
+            out = self.mine_negatives_device(
+                qd, torch.from_numpy(lims).to(self.device), torch.from_numpy(rows).to(self.device), top_k=top_k,
+                search_k=search_k, margin=margin, allow=allow, by_group=by_group)
+            return tuple(t.cpu().numpy() for t in out)
 
     # ----------------------------------------------------------- grouped search
     def _default_k_rows(self, k: int) -> int:
@@ -1129,6 +1215,44 @@ def groups_from_chunk_ids(chunk_ids: Sequence[str]) -> List[str]:
         parts = str(cid).split("_")
         out.append("_".join(parts[:-1]) if len(parts) > 1 else str(cid))
     return out
+
+
+def normalize_positives(positives, nq: int, n_rows: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The positives of ``nq`` queries as ``(lims int64 [nq + 1], rows int32)``, each query's rows sorted and
+    de-duplicated.  ``positives``: a sequence of ``nq`` row sequences, or a ``(lims, rows)`` TUPLE in that CSR form.
+    Raises ``ValueError`` for a wrong number of queries, limits that do not start at 0, decrease or do not end at
+    ``len(rows)``, and rows outside ``[0, n_rows)``."""
+    if isinstance(positives, tuple):
+        if len(positives) != 2:
+            raise ValueError("positives as a tuple is (lims, rows)")
+        lims_in = np.asarray(positives[0]).reshape(-1)
+        rows_in = np.asarray(positives[1]).reshape(-1)
+        if lims_in.size != nq + 1:
+            raise ValueError(f"positives: {lims_in.size} limits for {nq} queries (needs nq + 1)")
+        if lims_in.dtype.kind not in "iu" or (rows_in.size and rows_in.dtype.kind not in "iu"):
+            raise ValueError("positives: limits and rows must be integers")
+        lims_in = lims_in.astype(np.int64)
+        if lims_in[0] != 0 or (np.diff(lims_in) < 0).any() or lims_in[-1] != rows_in.size:
+            raise ValueError(f"positives: limits must start at 0, never decrease and end at len(rows)={rows_in.size}")
+        parts = [rows_in[lims_in[i]:lims_in[i + 1]] for i in range(nq)]
+    else:
+        parts = list(positives)
+        if len(parts) != nq:
+            raise ValueError(f"positives for {len(parts)} queries, {nq} queries given")
+    out = []
+    for i, part in enumerate(parts):
+        a = np.asarray(part)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError(f"positives[{i}] is not a flat list of integer rows")
+        a = np.unique(a.astype(np.int64))
+        if a.size and (a[0] < 0 or a[-1] >= n_rows):
+            raise ValueError(f"positives[{i}]: rows outside [0, {n_rows})")
+        out.append(a.astype(np.int32))
+    lims = np.zeros(nq + 1, dtype=np.int64)
+    if nq:
+        np.cumsum([a.size for a in out], out=lims[1:])
+    rows = np.concatenate(out) if out else np.zeros(0, dtype=np.int32)
+    return lims, np.ascontiguousarray(rows, dtype=np.int32)
 
 
 def _kept_rows(n_rows: int, removed: np.ndarray) -> np.ndarray:

@@ -17,7 +17,8 @@ same ``mine`` signature and the same selection rule -
 (three ``encode`` calls per query), every text is encoded ONCE here, in a few large launches of the
 packed varlen encoder, and the scores are ``q @ d.T`` on the GPU.  ``refresh`` + ``mine_from_index``
 is the "ANCE refresh" use of the fast path (docs/adr-003: re-encode the corpus with the current
-student every N steps, re-search it, mine): corpus -> ``FAISSIndexBuilder`` in HBM -> exact top-k.
+student every N steps, re-search it, mine): corpus -> ``FAISSIndexBuilder`` in HBM -> exact top-k
+-> the selection kernel (``sskd_index_mine_select``), one call for all queries.
 The student is duck-typed exactly as in the reference (``encode_queries`` / ``encode_documents`` /
 ``compute_similarity``).
 """
@@ -30,9 +31,12 @@ import numpy as np
 
 def select_adversarial(cand_ids: Sequence[str], cand_scores: np.ndarray, pos_scores: np.ndarray,
                        margin: float, top_k: int) -> List[str]:
-    """The reference's rule (src/mining/miners.py:232-247), including its stable descending sort."""
+    """The reference's rule (src/mining/miners.py:232-247), including its stable descending sort.  The threshold
+    test is decided in fp64, as the reference's expression is under the NumPy it pins (1.x: a float32 scalar against
+    a Python float is compared as float64); ``float(s)`` says so whatever NumPy is installed (2.x would round the
+    threshold to float32 first and keep a score that equals the rounded value but lies below the threshold)."""
     max_pos = float(pos_scores.max()) if len(pos_scores) > 0 else 0.0
-    adversarial = [(d, float(s)) for d, s in zip(cand_ids, cand_scores) if s >= max_pos - margin]
+    adversarial = [(d, float(s)) for d, s in zip(cand_ids, cand_scores) if float(s) >= max_pos - margin]
     adversarial.sort(key=lambda x: x[1], reverse=True)
     return [d for d, _ in adversarial[:top_k]]
 
@@ -78,6 +82,7 @@ class ANCEMiner:
         self.margin = margin
         self._index = None
         self._corpus_ids: List[str] = []
+        self._rows_of_id: Dict[str, List[int]] = {}
 
     # ------------------------------------------------------------------ reference API
     def mine(
@@ -134,12 +139,52 @@ class ANCEMiner:
         index = FAISSIndexBuilder(embedding_dim=int(embs.shape[1]), index_type="Flat", metric="ip", device=dev)
         index.add(embs)
         self._index, self._corpus_ids = index, list(corpus_ids)
+        # doc id -> every row that carries it (an id may repeat: all of its rows are positives of a query naming it)
+        self._rows_of_id = {}
+        for row, doc_id in enumerate(self._corpus_ids):
+            self._rows_of_id.setdefault(doc_id, []).append(row)
         return index
+
+    def _window(self, top_k: int, search_k: int):
+        """``(top_k, search_k)`` clipped to the rows the index holds."""
+        search_k = min(search_k, max(self._index.ntotal, 1))
+        return min(top_k, search_k), search_k
 
     def mine_from_index(self, queries: List[str], positives: List[List[str]], top_k: int = 5,
                         search_k: int = 100) -> List[List[str]]:
         """Adversarial negatives straight from the refreshed index: the ``search_k`` nearest corpus
-        rows of each query are its candidates (its positives excluded), then the same margin rule."""
+        rows of each query are its candidates (its positives excluded), then the same margin rule.
+
+        One search and one selection kernel for all queries (``FAISSIndexBuilder.mine_negatives``): the positives of a
+        query are every row carrying one of its ids, so where an id repeats with different texts all of its rows set
+        the positive score (``_mine_from_index_host`` scores the last such row only; the exclusion is the same).
+        ``positives`` needs one list per query: another length raises ``ValueError`` (the host loop zipped the two
+        lists and silently stopped at the shorter)."""
+        if self._index is None:
+            raise RuntimeError("call refresh(corpus_ids, corpus_texts) first")
+        if not queries:
+            return []
+        q_embs = np.ascontiguousarray(self.student.encode_queries(list(queries)), np.float32)
+        pos_rows = [[r for d in pos_ids for r in self._rows_of_id.get(d, ())] for pos_ids in positives]
+        top_k, search_k = self._window(top_k, search_k)
+        _, ids, _, _ = self._index.mine_negatives(q_embs, pos_rows, top_k=top_k, search_k=search_k, margin=self.margin)
+        return [[self._corpus_ids[r] for r in row if r >= 0] for row in ids.tolist()]
+
+    def mine_from_index_device(self, q_embs, pos_lims, pos_rows, top_k: int = 5, search_k: int = 100):
+        """The same selection for callers that hold everything in HBM: ``q_embs`` float32 ``[nq, dim]``, positives as
+        device ``(pos_lims int64 [nq + 1], pos_rows int32)`` rows of the refreshed index.  Returns device ``(D, I,
+        counts, max_pos)`` of ``FAISSIndexBuilder.mine_negatives_device`` (``I`` = rows of ``refresh``'s corpus, -1
+        padded); nothing leaves the device and nothing synchronises."""
+        if self._index is None:
+            raise RuntimeError("call refresh(corpus_ids, corpus_texts) first")
+        top_k, search_k = self._window(top_k, search_k)
+        return self._index.mine_negatives_device(q_embs, pos_lims, pos_rows, top_k=top_k, search_k=search_k,
+                                                 margin=self.margin)
+
+    def _mine_from_index_host(self, queries: List[str], positives: List[List[str]], top_k: int = 5,
+                              search_k: int = 100) -> List[List[str]]:
+        """``mine_from_index`` as a host loop over the queries (one ``reconstruct`` and one ``compute_similarity``
+        round trip each): what the device selection is checked and timed against."""
         if self._index is None:
             raise RuntimeError("call refresh(corpus_ids, corpus_texts) first")
         if not queries:
