@@ -373,6 +373,37 @@ int sskd_index_mine_select(const float* d_tiled, int64_t n_rows, const float* d_
                            double margin, int top_k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
                            int32_t* d_out_counts, float* d_out_max_pos, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * BM25 search over an inverted index in HBM (stage 1 of the mining curriculum)
+ *   reference: BM25Index.search, src/data/bm25.py:162-192, over rank_bm25.BM25Okapi.get_scores
+ * The index is built on the host (semantic-search-kd_amd/bm25.py) and uploaded once: postings in CSR by term id,
+ * d_term_offsets int64 [n_terms + 1], each list ascending by row, posting i = (d_post_rows[i] int32, d_post_w[i] fp64)
+ * with w = f (k1 + 1) / (f + k1 (1 - b + b dl / avgdl)) evaluated at build time, and d_idf fp64 [n_terms] (negative
+ * idfs already replaced by epsilon * average_idf).  Queries are a CSR of term ids: d_q_lims int64 [nq + 1] (non-
+ * decreasing), d_q_terms int32 in query order, repeats kept, out-of-vocabulary tokens dropped by the host (they add
+ * nothing, so dropping them is exact); a term id outside [0, n_terms) is skipped.  An empty query is legal.
+ *   score(q, row) = the fp64 sum, in query-token order, of idf[t] * w(t, row) over the tokens whose list holds the row:
+ *   the product rounded, then the sum rounded (no fma), starting from +0.0 - the bits of `score += idf * w_array`.
+ *   Result per query: the best k rows under (score descending, row ascending), rows matching no token included with
+ *   +0.0, to d_out_scores fp64 [nq][k] / d_out_ids int64 [nq][k]; slots past n_rows hold (-inf, -1).
+ * Two kernels per chunk of queries: one workgroup per (tile of rows, query) scores term at a time into LDS and selects
+ * the tile's best min(k, rows) into the workspace; one workgroup per query merges the tiles' records.  Nothing of size
+ * n_rows x nq exists: the workspace holds queries_per_chunk x tiles x k records of 16 bytes, and the search runs
+ * floor(workspace_bytes / bytes of one query) queries per chunk, so any workspace that holds one query is accepted
+ * (less: SSKD_ERR_WORKSPACE).  sskd_bm25_search_workspace_bytes is what keeps the whole batch in one chunk up to a
+ * 256 MiB budget (0 for nq = 0 or arguments the search rejects); sskd_bm25_search_plan reports the tile size in rows,
+ * the number of tiles and the queries per chunk under that size (any out pointer may be NULL).
+ * Limits: 1 <= k <= 256; n_rows < 2^31 - 64 (rows are int32 per index); workspace 16-byte aligned.  Stream-ordered, no
+ * host sync, allocates nothing; arguments are checked before the first launch (SSKD_ERR_INVALID); nq = 0 is a
+ * successful no-op.
+ * ------------------------------------------------------------------------- */
+size_t sskd_bm25_search_workspace_bytes(int64_t n_rows, int nq, int k);
+int sskd_bm25_search_plan(int64_t n_rows, int nq, int k, int* tile_rows, int* tiles, int* queries_per_chunk);
+int sskd_bm25_search(const int64_t* d_term_offsets, const int32_t* d_post_rows, const double* d_post_w,
+                     const double* d_idf, int64_t n_rows, int64_t n_terms, const int64_t* d_q_lims,
+                     const int32_t* d_q_terms, int nq, int k, double* d_out_scores, int64_t* d_out_ids,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

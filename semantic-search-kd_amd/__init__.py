@@ -13,7 +13,8 @@ from .weights import BertConfig, synthetic_state_dict  # noqa: F401
 from .encoder import Mi355xSentenceEncoder, build_wordpiece_tokenizer  # noqa: F401
 from .student import StudentModel  # noqa: F401
 from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELoss  # noqa: F401
-from .mining import ANCEMiner, TeacherMiner  # noqa: F401
+from .bm25 import BM25Index, build_bm25_index  # noqa: F401
+from .mining import ANCEMiner, BM25Miner, TeacherMiner, build_mining_curriculum  # noqa: F401
 from .teacher import TeacherConfig, TeacherModel  # noqa: F401
 from .bench_support import bench_encode  # noqa: F401
 
@@ -21,6 +22,10 @@ Mi355xIndexBuilder = FAISSIndexBuilder
 
 __all__ = [
     "ANCEMiner",
+    "BM25Index",
+    "BM25Miner",
+    "build_bm25_index",
+    "build_mining_curriculum",
     "TeacherMiner",
     "TeacherConfig",
     "TeacherModel",

@@ -18,7 +18,7 @@ INCLUDE = REPO_ROOT / "include"
 OBJ_DIR = PKG_DIR / "build"
 LIB_PATH = PKG_DIR / "libsskd_amd.so"
 
-SOURCES = ["capi_common.hip", "search.hip", "mine.hip", "pool.hip", "encoder.hip", "kd_loss.hip", "tokenizer.hip", "generic.hip", "train.hip", "blaslt.hip", "testhooks.hip"]
+SOURCES = ["capi_common.hip", "search.hip", "mine.hip", "bm25.hip", "pool.hip", "encoder.hip", "kd_loss.hip", "tokenizer.hip", "generic.hip", "train.hip", "blaslt.hip", "testhooks.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

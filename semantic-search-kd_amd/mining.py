@@ -1,4 +1,10 @@
-"""Teacher (stage 2) and ANCE (stage 3) hard-negative mining on the MI355X teacher / encoder + exact scan.
+"""BM25 (stage 1), teacher (stage 2) and ANCE (stage 3) hard-negative mining on the MI355X, and the reference's
+three-stage curriculum over them (``build_mining_curriculum``).
+
+``BM25Miner`` is the drop-in for the reference's class of that name (src/mining/miners.py:22-78): same ``mine``
+signature and the same host filter, but ONE ``BM25Index.batch_search`` device call for all queries instead of one
+host search per query.
+
 
 ``TeacherMiner`` is the drop-in for the reference's class of that name (src/mining/miners.py:80-158): same
 constructor, same ``mine`` signature, same selection rule (stable descending sort by teacher score, the first
@@ -24,7 +30,7 @@ The student is duck-typed exactly as in the reference (``encode_queries`` / ``en
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -52,6 +58,36 @@ def select_confident(cand_ids: Sequence[str], scores: Sequence[float], get_confi
             ids.append(doc_id)
             kept.append(score)
     return ids, kept
+
+
+class BM25Miner:
+    def __init__(self, index_or_path):
+        """``index_or_path``: a built / loaded ``BM25Index``, or the directory of a saved one (loaded here, as the
+        reference's constructor does)."""
+        from .bm25 import BM25Index
+
+        if hasattr(index_or_path, "batch_search"):
+            self.index = index_or_path
+        else:
+            self.index = BM25Index(str(index_or_path))
+            self.index.load()
+
+    def mine(self, queries: List[str], positives: List[List[str]], top_k: int = 100,
+             exclude_positives: bool = True) -> List[List[str]]:
+        """The ``top_k`` BM25 candidates of every query, best first, its positives filtered out afterwards on the host
+        as in the reference (src/mining/miners.py:66-73), so a list may be shorter than ``top_k``.  ``positives`` needs
+        one list per query (the reference zipped the two lists and silently stopped at the shorter)."""
+        if len(positives) != len(queries):
+            raise ValueError(f"{len(positives)} positive lists for {len(queries)} queries")
+        results = self.index.batch_search(list(queries), top_k=top_k)
+        all_negatives: List[List[str]] = []
+        for hits, pos_ids in zip(results, positives):
+            if exclude_positives:
+                pos_set = set(pos_ids)
+                all_negatives.append([doc_id for doc_id, _ in hits if doc_id not in pos_set])
+            else:
+                all_negatives.append([doc_id for doc_id, _ in hits])
+        return all_negatives
 
 
 class TeacherMiner:
@@ -204,3 +240,38 @@ class ANCEMiner:
             out.append(select_adversarial([d for d, _ in keep], np.array([s for _, s in keep], np.float32),
                                           pos_scores, self.margin, top_k))
         return out
+
+
+def build_mining_curriculum(queries: List[str], positives: List[List[str]], bm25_index_path, teacher_model,
+                            student_model, corpus_texts: Dict[str, str],
+                            stage: int = 1) -> Tuple[List[List[str]], List[List[float]]]:
+    """``(hard_negatives, teacher_scores)`` of one curriculum stage, the reference's three branches
+    (src/mining/miners.py:256-335):
+
+    1. BM25, ``top_k=100``; placeholder scores 0.0.
+    2. BM25 ``top_k=100`` -> teacher ``top_k=10`` at confidence 0.6; the teacher's scores.
+    3. BM25 ``top_k=100`` -> teacher ``top_k=20`` -> ANCE ``top_k=5`` at margin 0.1; the negatives of a query are
+       ``list(set(first five teacher negatives + ANCE negatives))`` and the scores are the first five teacher scores
+       followed by one 0.0 per ANCE negative.  As in the reference, the set has no defined order (it varies with the
+       interpreter's string hashing) and drops duplicates, so the order of a stage-3 list is unspecified and it does
+       not line up with its scores one to one.
+
+    ``bm25_index_path`` is the directory of a saved index (a ``BM25Index`` is accepted too)."""
+    if stage == 1:
+        negatives = BM25Miner(bm25_index_path).mine(queries, positives, top_k=100)
+        return negatives, [[0.0] * len(n) for n in negatives]
+    if stage == 2:
+        candidates = BM25Miner(bm25_index_path).mine(queries, positives, top_k=100)
+        return TeacherMiner(teacher_model, confidence_threshold=0.6).mine(queries, candidates, corpus_texts, top_k=10)
+    if stage == 3:
+        candidates = BM25Miner(bm25_index_path).mine(queries, positives, top_k=100)
+        teacher_negatives, teacher_scores = TeacherMiner(teacher_model, confidence_threshold=0.6).mine(
+            queries, candidates, corpus_texts, top_k=20)
+        ance_negatives = ANCEMiner(student_model, margin=0.1).mine(
+            queries, positives, teacher_negatives, corpus_texts, corpus_texts, top_k=5)
+        combined_negatives, combined_scores = [], []
+        for t_negs, t_scores, a_negs in zip(teacher_negatives, teacher_scores, ance_negatives):
+            combined_negatives.append(list(set(t_negs[:5] + a_negs)))
+            combined_scores.append(t_scores[:5] + [0.0] * len(a_negs))
+        return combined_negatives, combined_scores
+    raise ValueError(f"Invalid stage: {stage}. Must be 1, 2, or 3.")
