@@ -11,7 +11,7 @@
 //                             by a radix select on an order-preserving key, written sorted into the workspace.
 //   bm25_merge_kernel         one workgroup per query: the same select over the tiles' records.
 // The product and the sum stay two roundings (no fma), as numpy evaluates `score += idf * w_array`.
-#include "common.h"
+#include "search_host.h"   // sskd::MAX_SHARD_ROWS: rows are int32 per index
 
 #pragma clang fp contract(off)
 
@@ -21,7 +21,6 @@ constexpr int TILE_ROWS = 4096;    // 32 KiB of fp64 accumulators: four workgrou
 constexpr int THREADS = 256;
 constexpr int BM25_K_MAX = 256;
 constexpr int TOKEN_BATCH = THREADS / 2;   // query tokens whose posting segments are located at once (2 bounds each)
-constexpr int64_t MAX_SHARD_ROWS = ((int64_t)1 << 31) - 64;   // rows are int32 per index (search.hip)
 constexpr size_t WORKSPACE_BUDGET = (size_t)256 << 20;         // what the size query asks for at most (if one query fits)
 
 struct Rec {
@@ -284,7 +283,7 @@ inline size_t plan_bytes(const Plan& pl, int nq) {
 }
 
 inline bool shape_ok(int64_t n_rows, int nq, int k) {
-  return n_rows >= 0 && n_rows < MAX_SHARD_ROWS && nq >= 0 && k >= 1 && k <= BM25_K_MAX;
+  return n_rows >= 0 && n_rows < sskd::MAX_SHARD_ROWS && nq >= 0 && k >= 1 && k <= BM25_K_MAX;
 }
 
 }  // namespace
@@ -298,7 +297,7 @@ size_t sskd_bm25_search_workspace_bytes(int64_t n_rows, int nq, int k) {
 
 int sskd_bm25_search_plan(int64_t n_rows, int nq, int k, int* tile_rows, int* tiles, int* queries_per_chunk) {
   SSKD_REQUIRE(n_rows >= 0, "bm25_search_plan: n_rows < 0");
-  SSKD_REQUIRE(n_rows < MAX_SHARD_ROWS, "bm25_search_plan: index too large for int32 row ids");
+  SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS, "bm25_search_plan: index too large for int32 row ids");
   SSKD_REQUIRE(nq >= 0, "bm25_search_plan: nq < 0");
   SSKD_REQUIRE(k >= 1 && k <= BM25_K_MAX, "bm25_search_plan: k=%d outside [1, %d]", k, BM25_K_MAX);
   const Plan pl = make_plan(n_rows, k);
@@ -317,7 +316,7 @@ int sskd_bm25_search(const int64_t* d_term_offsets, const int32_t* d_post_rows, 
                      void* d_workspace, size_t workspace_bytes, void* stream) {
   // every check comes before the first HIP call
   SSKD_REQUIRE(n_rows >= 0, "bm25_search: n_rows < 0");
-  SSKD_REQUIRE(n_rows < MAX_SHARD_ROWS, "bm25_search: index too large for int32 row ids");
+  SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS, "bm25_search: index too large for int32 row ids");
   SSKD_REQUIRE(n_terms >= 0 && n_terms <= INT32_MAX, "bm25_search: n_terms outside [0, 2^31)");
   SSKD_REQUIRE(nq >= 0, "bm25_search: nq < 0");
   SSKD_REQUIRE(k >= 1 && k <= BM25_K_MAX, "bm25_search: k=%d outside [1, %d]", k, BM25_K_MAX);

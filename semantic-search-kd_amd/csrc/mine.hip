@@ -5,20 +5,16 @@
 //     adversarial = ranks with  score >= max_pos - margin   (decided in fp64)
 //     negatives   = the first top_k adversarial ranks (the ranking is already the stable descending order)
 // One wave per query: it scores the query's positive rows with the fma chain of the screened search's exact re-scoring
-// (search.hip, "exact scores, 64 candidates per round"), so a positive scores with the bits a search returns for that
+// (screen.hip, "exact scores, 64 candidates per round"), so a positive scores with the bits a search returns for that
 // row, then walks the ranking 64 ranks per round and compacts the survivors in rank order (ballot + prefix popcount).
-#include "common.h"
+#include "search_device.h"
+#include "search_host.h"
 
 #include <cfloat>
 
 namespace {
 
-constexpr int DIM = SSKD_DIM;         // 384
-constexpr int STEPS = DIM / 8;        // 48 k-steps, 8 columns each
-constexpr int CHUNKS = DIM / 4;       // 96 float4 chunks per row
 constexpr int MINE_WAVES = 4;
-// Rows of one shard: row ids are kept in int32 (search.hip)
-constexpr int64_t MAX_SHARD_ROWS = ((int64_t)1 << 31) - 64;
 
 struct MineParams {
   const float* rows;           // the index: row-major fp32 [n_rows][DIM]
@@ -156,7 +152,7 @@ int sskd_index_mine_select(const float* d_tiled, int64_t n_rows, const float* d_
   SSKD_REQUIRE(top_k <= search_k, "index_mine_select: top_k=%d > search_k=%d", top_k, search_k);
   SSKD_REQUIRE(search_k <= SSKD_K_MAX, "index_mine_select: search_k=%d > %d", search_k, SSKD_K_MAX);
   SSKD_REQUIRE(margin == margin, "index_mine_select: margin is NaN");
-  SSKD_REQUIRE(n_rows < MAX_SHARD_ROWS, "index_mine_select: shard too large for int32 row ids");
+  SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS, "index_mine_select: shard too large for int32 row ids");
   if (nq == 0) return SSKD_OK;
   SSKD_REQUIRE(d_queries && d_rank_scores && d_rank_ids && d_pos_lims && d_out_scores && d_out_ids && d_out_counts &&
                    d_out_max_pos,

@@ -1,0 +1,1197 @@
+// ------------------------------------------------------------------------- //
+// Screened search: bf16-MFMA screening pass + exact fp32 rescoring of the few candidates.
+//
+// The exact scan (search.hip) is bound by the fp32 matrix pipe (~0.9 of its peak).  bf16 MFMAs run 16x
+// faster, so a SCREENING pass computes every score from bf16-rounded rows and queries first.
+// Error bound, PROVED and data-dependent: with q~, c~ the rounded vectors,
+//   q~.c~ - q.c = (q~ - q).c~ + q.(c~ - c),  so  |q~.c~ - q.c| <= |q~ - q| |c~| + |q| |c~ - c|  (Cauchy-Schwarz).
+// |q~ - q| and |q| are MEASURED per query (screen_setup_kernel; q - q~ is exact in fp32), max |c~|, max |c~ - c|
+// and max |c| over the rows are MEASURED when the bf16 copy is made (make_bf16_tiles_kernel).  On top,
+// SCREEN_ACC_SLACK |q| max(max|c|, max|c~|) covers the fp32 accumulation roundings of both dot products.  Worst case
+// (every element on a bf16 tie: relative rounding error 2^-8 per element, bf16 has 8 significand bits) this
+// is e = 2^-7 (1 + 2^-9) |q| |c|; random data rounds to about 0.42 of that.  Nothing about the rounding
+// mode is assumed - whatever the conversion did is what gets measured.
+// MEAN-CENTRING.  The screening copy holds bf16(c - mu), mu = the mean row of the shard: q.(c - mu) = q.c - q.mu and
+// q.mu is the same for every row of a query, so ranking, candidate band and k-th-best logic are untouched (they
+// only ever compare scores of ONE query), while every norm in the bound above becomes that of the CENTRED rows.
+// Real sentence embeddings are far from isotropic (e5: mean pairwise cosine 0.7-0.8): centring shrinks |c~| and
+// with it the band by 1 / sqrt(1 - cos) = 2-2.2x, which is the difference between ~40 and several hundred
+// candidates per query.  Any mu keeps the proof valid (it is a heuristic shift, computed once per make_bf16);
+// fl(c - mu) differs from c - mu by <= 2^-23 (|c| + |mu|) per row, inside SCREEN_ACC_SLACK.  Exact re-scoring
+// reads the ORIGINAL fp32 rows, so output bits are those of the exact scan.
+// With e bounding |screen score - exact fp32 score|, every row of the
+// exact top k has a screen score >= (k-th best screen score) - 2e: those rows are the candidates.
+// They are re-scored with the exact k-ordered fma chain of the fp32 MFMA, so the final scores and
+// ids are bit-identical to the exact scan's.  Every row whose screen score reaches the pruning bound
+// (a lower bound of the k-th best screen score, minus 2e) is APPENDED to a per-lane run in global memory,
+// so the appended set always contains the whole candidate band; a query is handed to the exact scan only
+// when a run overflowed, its entries do not fit the finalize kernel's LDS stage, or its band holds more
+// than SCREEN_MAX_CAND rows (hundreds of near-duplicates of its neighbours) - in a fallback launch sized
+// for EVERY query of the call: results are never approximate and no entry point can return an unproven row.
+// ------------------------------------------------------------------------- //
+#include "search_device.h"
+#include "search_host.h"
+
+#include <algorithm>
+#include <cfloat>
+
+using sskd::require_shard_rows;
+
+namespace {
+
+typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
+constexpr int BSTEPS = DIM / 16;                 // 24 k-steps of the 32x32x16 bf16 MFMA
+constexpr int BTILE_VEC = BSTEPS * 64;           // 16-byte vectors per 32-row bf16 tile (24 KiB)
+#ifndef SSKD_SCREEN_BGROUP
+#define SSKD_SCREEN_BGROUP 6
+#endif
+#ifndef SSKD_SCREEN_WAVES
+#define SSKD_SCREEN_WAVES 12
+#endif
+#ifndef SSKD_SCREEN_RING
+#define SSKD_SCREEN_RING 2
+#endif
+// Tile prefetch ring of a wave: RING register buffers of BGROUP k-steps each, RING - 1 groups in flight.  128 queries
+// per workgroup (64 accumulator registers): 6 k-steps x 2 buffers; 160 queries (80 accumulators): 3 x 2 - what is left
+// of the 168 registers three waves per SIMD allow (tools/ab_search.py sweeps: gpurun_out/r03_sweep*.log, r03_q5*.log)
+constexpr int BGROUP = SSKD_SCREEN_BGROUP;
+constexpr int SCREEN_RING = SSKD_SCREEN_RING;
+constexpr int BGROUP_Q5 = 3, SCREEN_RING_Q5 = 2;
+#ifndef SSKD_SCREEN_TAU_REFRESH_TILES
+#define SSKD_SCREEN_TAU_REFRESH_TILES 64
+#endif
+constexpr int SCREEN_TAU_REFRESH_TILES = SSKD_SCREEN_TAU_REFRESH_TILES;
+constexpr int SCREEN_WAVES = SSKD_SCREEN_WAVES;  // waves per screening workgroup
+template <int BG, int RG>
+struct ScreenRingOk {
+  static_assert(BSTEPS % BG == 0 && (BSTEPS / BG) % RG == 0 && RG >= 2, "screening prefetch geometry");
+  static constexpr bool value = true;
+};
+static_assert(ScreenRingOk<BGROUP, SCREEN_RING>::value && ScreenRingOk<BGROUP_Q5, SCREEN_RING_Q5>::value, "");
+// fp32 accumulation slack of the two dot products, relative to |q| max|c|: the exact score is a 384-step fma
+// chain (<= 384 x 2^-24), the screen score 24 MFMAs of 16 exact products each accumulated in fp32 (<= 2 x 384
+// x 2^-24 even if every internal add truncated); 3 x 384 x 2^-24 (1 + 2^-8)^2 = 6.9e-5, rounded up generously
+constexpr float SCREEN_ACC_SLACK = 1.0e-4f;
+constexpr int SCREEN_MAX_CAND = 256;             // candidates re-scored per query (one per thread)
+// The in-call exact fallback holds EVERY query, in two launches: the first SCREEN_FALLBACK_TIER1 fallback queries go to a
+// launch planned for that many (a few query blocks spread over many corpus slices: a handful of unproven queries -
+// the usual case - still fills the chip), the rest to a launch planned for nq - TIER1 (only duplicate-flooded corpora
+// ever get there).  Both read their actual query count from device memory; with none, every workgroup exits at once.
+constexpr int SCREEN_FALLBACK_TIER1 = 1024;
+constexpr int SCREEN_LIGHT_MAX_TILES_PER_WAVE = 330;   // slices up to this length (500 k rows at 10 000 queries) keep their pools with one offer per lane and tile
+constexpr int SCREEN_CUS = 256;                  // MI355X: the launch geometry is planned in whole rounds of the chip
+
+// fp32 index -> bf16 tiles of the CENTRED rows in A-operand order of v_mfma_f32_32x32x16_bf16:
+// tile t, step s, lane l holds row 32t + (l & 31), columns 16s + 8(l >> 5) + 0..7   (make_bf16_tiles_kernel below)
+// column sums of the fp32 index -> colsum[384] (pre-zeroed): block b walks tiles b, b + grid, ...
+__global__ __launch_bounds__(256) void tile_colsum_kernel(const float4* __restrict__ tiled, int64_t n_tiles,
+                                                          float* __restrict__ colsum) {
+  // thread c < 96 of row group g (0 / 1) sums chunk c over the rows 2 i + g of its tiles (rows past n_rows are zero)
+  const int c = threadIdx.x % CHUNKS, g = threadIdx.x / CHUNKS;
+  if (g >= 2) return;
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const float4* src = tiled + t * (int64_t)(TILE_ROWS * CHUNKS);
+#pragma unroll 4
+    for (int r = g; r < TILE_ROWS; r += 2) {
+      const float4 v = src[r * CHUNKS + c];
+      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+  }
+  atomicAdd(colsum + 4 * c + 0, a.x); atomicAdd(colsum + 4 * c + 1, a.y);
+  atomicAdd(colsum + 4 * c + 2, a.z); atomicAdd(colsum + 4 * c + 3, a.w);
+}
+
+// norm block of the sidecar: ints [0..2] = max |c|^2, max |c~|^2, max |c~ - fl(c - mu)|^2 (bit patterns of
+// non-negative floats; a row norm that is not finite is published as +inf), int [3] = max |c_ij| (bit pattern: the
+// range check of screen_setup_kernel), floats [64 .. 64 + 384) = column sums, the rest zero.  The mean row is not
+// stored: make_bf16_tiles_kernel derives it from the column sums, mu = fl(colsum * fl(1 / n)).
+constexpr int SIDECAR_NORM_BYTES = 4096;
+constexpr int SIDECAR_ABSMAX_WORD = 3;
+constexpr int SIDECAR_COLSUM_OFF = 64;   // in floats
+
+__global__ __launch_bounds__(256) void make_bf16_tiles_kernel(const float4* __restrict__ tiled, int64_t n_tiles, int64_t n_rows,
+                                                              sbf16x8* __restrict__ out, int* __restrict__ norm_block) {
+  __shared__ float rowss[3][32];   // per row: |c|^2, |c~|^2, |c~ - fl(c - mu)|^2
+  __shared__ float mu[DIM];
+  __shared__ int amax;             // max |c_ij| of the tile, as bits (|NaN| and inf order above every finite value)
+  const int64_t t = blockIdx.x;
+  if (threadIdx.x < 96) rowss[threadIdx.x >> 5][threadIdx.x & 31] = 0.f;
+  if (threadIdx.x == 0) amax = 0;
+  const float inv_n = 1.0f / (float)n_rows;
+  for (int c = threadIdx.x; c < DIM; c += 256) mu[c] = reinterpret_cast<const float*>(norm_block)[SIDECAR_COLSUM_OFF + c] * inv_n;
+  __syncthreads();
+  const float4* src = tiled + t * (int64_t)(TILE_ROWS * CHUNKS);
+  for (int v = threadIdx.x; v < BTILE_VEC; v += 256) {
+    const int sidx = v >> 6, l = v & 63, r = l & 31, hh = l >> 5;
+    const int u = 2 * sidx + hh;
+    const float4 a = src[tile_idx4(r, 2 * u)], b = src[tile_idx4(r, 2 * u + 1)];
+    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const bool live = t * TILE_ROWS + r < n_rows;   // padding rows stay all-zero (the kernel masks them anyway)
+    sbf16x8 o;
+    float nn = 0.f, bb = 0.f, dd = 0.f;
+    int am = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xc = live ? x[e] - mu[8 * u + e] : 0.f;   // fl(c - mu)
+      o[e] = (__bf16)xc;
+      const float xr = (float)o[e];
+      const float d = xr - xc;       // exact in fp32: xr is xc rounded to fewer bits
+      am = max(am, __float_as_int(x[e]) & 0x7fffffff);
+      nn = fmaf(x[e], x[e], nn);
+      bb = fmaf(xr, xr, bb);
+      dd = fmaf(d, d, dd);
+    }
+    out[t * BTILE_VEC + v] = o;
+    atomicAdd(&rowss[0][r], nn);
+    atomicAdd(&rowss[1][r], bb);
+    atomicAdd(&rowss[2][r], dd);
+    atomicMax(&amax, am);
+  }
+  __syncthreads();
+  // non-negative floats order as ints; words 0..2 of the sidecar's norm block.  A sum that is not finite goes out as
+  // +inf, never as a NaN (a NaN word made eps2 NaN for every query, and its bit pattern orders by its sign bit)
+  if (threadIdx.x < 96) {
+    const float v = rowss[threadIdx.x >> 5][threadIdx.x & 31];
+    atomicMax(norm_block + (threadIdx.x >> 5), __float_as_int(v < INFINITY ? v : INFINITY));
+  }
+  if (threadIdx.x == 96) atomicMax(norm_block + SIDECAR_ABSMAX_WORD, amax);
+}
+
+// One set-up launch per call.  Per query: 2e = 2 (|q~ - q| max|c~| + |q| max|c~ - c| + SCREEN_ACC_SLACK |q| max(max|c|, max|c~|)),
+// rounded UP; and the call's scratch state: tau + the global buckets (11 words per query) to "empty", the fallback
+// counters and the status words to zero (these were four launches / memsets: on a 125 k-row shard the short launches
+// of a call add up to a tenth of it).
+// RANGE.  The norms are square roots of fp32 sums of squares, and the bound above is a statement about real numbers: it
+// holds in fp32 only while no square, product or partial sum leaves the normal range.  So
+//  - the query is scaled by an exact power of two (largest element into [1, 2)) before it is squared, and the band is
+//    scaled back at the end: the same bits as the unscaled sum wherever that was exact, and no square of a small query
+//    is lost (unscaled, a query of norm 2^-80 measured |q| = 0: band 1e-30 against a screening error of 4e-28);
+//  - eps2[q] = +inf - "no band": screen_finalize_append_kernel hands such a query to the in-call exact scan - when the
+//    query or a row norm is not finite, when the largest corpus element is below SCREEN_MIN_CORPUS (the row sums of
+//    squares are not scaled and lose terms below 2^-63), when the largest query element is below SCREEN_MIN_QUERY (its
+//    bf16 elements and their products approach the denormals), or when the band itself leaves [SCREEN_MIN_BAND,
+//    SCREEN_MAX_BAND] (scores near the ends of the fp32 range round absolutely, not relatively).  An all-zero query or
+//    corpus scores exactly 0 on both paths and keeps the floor.
+// The thresholds are derived, not observed: the fp64 checks of tests/test_screen_band_gpu.py compute q~.c~ on the CPU and
+// never see how the MFMA treats near-denormal products, so on the device they are guarded only by that file's
+// bit-equality cases against the oracle (queries down to 2^-140, corpora at 2^-70, 2^-35 and 2^60).
+// Room: what lost denormal terms can hide on a norm is <= sqrt(384 x 2^-126) = 2^-58.7, times the other side's norm;
+// the slack term holds 3.1e-5 |q| max|c| = 2^-15 |q| max|c| beyond the 6.9e-5 it is derived from, and max|c| >= 2^-40.
+constexpr float SCREEN_MIN_CORPUS = 0x1p-40f, SCREEN_MIN_QUERY = 0x1p-96f;
+constexpr float SCREEN_MIN_BAND = 0x1p-100f, SCREEN_MAX_BAND = 0x1p+100f;
+__global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restrict__ queries, int nq,
+                                                           const int* __restrict__ max_norm2, float* __restrict__ eps2,
+                                                           int* __restrict__ tau, int* __restrict__ fb_count,
+                                                           int* __restrict__ d_status) {
+  if (threadIdx.x < 44) {   // this block's 4 queries x 11 words
+    const int64_t i = (int64_t)blockIdx.x * 44 + threadIdx.x;
+    if (i < (int64_t)nq * 11) tau[i] = (int)0x80000000;
+  }
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < 64) fb_count[threadIdx.x] = 0;
+    if (threadIdx.x < 2) d_status[threadIdx.x] = 0;
+  }
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  float xs[DIM / 64];
+  int am = 0;   // max |x| as bits: |NaN| and inf order above every finite value
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) {
+    xs[i] = queries[(int64_t)q * DIM + lane + 64 * i];
+    am = max(am, __float_as_int(xs[i]) & 0x7fffffff);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) am = max(am, __shfl_xor(am, o));
+  // 2^-E for the largest element's exponent E (denormals: E = -126); exact, and 1 for elements in [1, 2)
+  const int ex = min(max(am >> 23, 1), 253);
+  const float down = __int_as_float(ex << 23), up = __int_as_float((254 - ex) << 23);
+  float ss = 0.f, dd = 0.f;
+#pragma unroll
+  for (int i = 0; i < DIM / 64; ++i) {
+    const float x = xs[i];
+    const float d = ((float)(__bf16)x - x) * up;   // the same conversion the screening kernel applies; exact difference
+    const float xu = x * up;
+    ss = fmaf(xu, xu, ss);
+    dd = fmaf(d, d, dd);
+  }
+  ss = wave_sum(ss);
+  dd = wave_sum(dd);
+  if (lane == 0) {
+    const float cn = sqrtf(__int_as_float(max_norm2[0])), cb = sqrtf(__int_as_float(max_norm2[1])),
+                cd = sqrtf(__int_as_float(max_norm2[2]));
+    const float ca = __int_as_float(max_norm2[SIDECAR_ABSMAX_WORD]), qa = __int_as_float(am);
+    const float qn = sqrtf(ss), qd = sqrtf(dd);
+    // the sums of squares carry <= 385 x 2^-24 relative error, the square roots and products a few ulps more:
+    // 1.0002 rounds the whole bound up
+    // (the accumulation slack scales with the operands that are actually multiplied: the exact chain's rows |c| AND the
+    // screening pass's centred, rounded rows |c~|, which can reach 2 max|c| on a shard whose mean row is large)
+    const float band = 2.0f * (qd * cb + qn * cd + SCREEN_ACC_SLACK * qn * fmaxf(cn, cb)) * 1.0002f * down;
+    const bool zero = (qa == 0.f || ca == 0.f) && band == 0.f;   // (0 x inf = NaN is not "zero": no band)
+    const bool sound = zero || (qa >= SCREEN_MIN_QUERY && ca >= SCREEN_MIN_CORPUS && ca < INFINITY &&
+                                band >= SCREEN_MIN_BAND && band <= SCREEN_MAX_BAND);
+    eps2[q] = sound ? band + 1e-30f : INFINITY;
+  }
+}
+
+// k-steps [0, BG) at the wave-uniform address `base`: lane l reads the 16 bytes at lane_off = 16 l of every step.  Uniform
+// base + 32-bit lane offset is the scalar-base form of global_load: tile addresses cost scalar adds, no 64-bit vector
+// pointers held (and spilled) across the tile loop.
+template <int BG>
+__device__ __forceinline__ void load_bgroup(sbf16x8 (&buf)[BG], const sbf16x8* __restrict__ base, unsigned lane_off) {
+  asm volatile("" : "+v"(lane_off));   // widened next to its loads, not once per kernel into a 64-bit pair that spills
+#pragma unroll
+  for (int s = 0; s < BG; ++s)
+    buf[s] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 64) + lane_off);
+}
+
+// The query fragments of a workgroup sit in LDS as [QB][24 k-steps][64 lanes] x 16 bytes: 1 KiB per (sub-block, k-step),
+// up to 120 KiB in all, and a ds_read takes a 16-bit byte offset.  One base address per 64 fragments, set up once per
+// phase and hidden from the optimiser, makes every fragment address "base + immediate"; left alone, the compiler forms
+// the far addresses with a v_add_u32 and a register of their own per read.
+typedef __attribute__((address_space(3))) const sbf16x8 screen_lds_frag;
+constexpr int SCREEN_FRAGS_PER_BASE = 64;
+template <int QB>
+constexpr int screen_frag_bases() { return (QB * BSTEPS + SCREEN_FRAGS_PER_BASE - 1) / SCREEN_FRAGS_PER_BASE; }
+// Fragment ring of a wave: the LDS read of MFMA i + SCREEN_FRAG_DEPTH - 1 is issued in front of MFMA i.  The register
+// budget of three waves per SIMD (168) decides the depth: 3 compiles with 8 spilled registers in the 160-query kernel
+// and a scratch reload inside its tile loop, 2 with the 2 it had before the ring (per instantiation: DESIGN.md 3.1b)
+#ifndef SSKD_SCREEN_FRAG_DEPTH
+#define SSKD_SCREEN_FRAG_DEPTH 2
+#endif
+constexpr int SCREEN_FRAG_DEPTH = SSKD_SCREEN_FRAG_DEPTH;
+static_assert(SCREEN_FRAG_DEPTH >= 2, "the fragment ring holds the MFMA's own operand and at least one read ahead");
+
+// fragment of the tile's I-th MFMA: MFMAs run k-step major, sub-block minor (I = kstep * QB + qq)
+template <int QB, int NB>
+__device__ __forceinline__ sbf16x8 read_qfrag(screen_lds_frag* const (&qbase)[NB], int I) {
+  const int f = (I % QB) * BSTEPS + I / QB;
+  return qbase[f / SCREEN_FRAGS_PER_BASE][(f % SCREEN_FRAGS_PER_BASE) * 64];
+}
+
+// One group of k-steps: BG x QB MFMAs, each accumulator's k ascending.  The query fragments go through a register ring
+// D deep that runs D - 1 LDS reads ahead of the MFMA that consumes them, across the groups of a tile (the fragments do
+// not depend on the tile): every MFMA waits with a counted lgkmcnt(D - 2) for its own fragment while the next reads are
+// in flight, so ONE ready wave keeps the matrix pipe of its SIMD fed when its partners are parked on their tile ring or
+// in their epilogue.  A scheduling barrier on both sides of each MFMA pins that order - left to itself the machine
+// scheduler sinks every read to "read, lgkmcnt(0), MFMA", a full LDS round trip in front of each 32-cycle MFMA.  The
+// tile ring's global loads are issued by the caller ahead of the group and stay there.  (Rounds 2-3 measured a two-deep
+// pipeline pinned with sched_group_barrier on the list form of the kernel - two waves per SIMD, 255 registers - at
+// 9.6 ms against 8.5 ms: that order delayed the tile prefetch loads.  Numbers for this form: DESIGN.md section 3.1b.)
+template <int QB, int G, int BG, int D, int NB>
+__device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG], screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D],
+                                               f32x16 (&acc)[QB]) {
+  constexpr int N = BG * QB, I0 = G * N, TOTAL = BSTEPS * QB;
+  asm volatile("" ::: "memory");  // keep the (tile-invariant) LDS query reads inside the tile (see compute_group)
+#ifndef SSKD_SCREEN_ABL_NOLDS
+  if constexpr (G == 0) {
+#pragma unroll
+    for (int i = 0; i < D - 1; ++i) b[i % D] = read_qfrag<QB>(qbase, i);
+  }
+#endif
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int I = I0 + i, s = i / QB, qq = i % QB;
+#ifdef SSKD_SCREEN_ABL_NOLDS   // timing ablation (tools/ab_search.py, AB_NOCHECK): no LDS query-fragment reads
+    const sbf16x8 bi = a[(s + qq) % BG];
+#else
+    if (I + D - 1 < TOTAL) b[(I + D - 1) % D] = read_qfrag<QB>(qbase, I + D - 1);
+    const sbf16x8 bi = b[I % D];
+#endif
+    __builtin_amdgcn_sched_barrier(0);
+    acc[qq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bi, acc[qq], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// one tile's groups, compile-time unrolled over a ring of RG register buffers: group G is multiplied
+// from buffer G % RG while group G + RG - 1 (of this tile, or of the wave's next tile) loads
+template <int QB, int G, int BG, int RG, int D, int NB>
+__device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const sbf16x8* __restrict__ tile,
+                                                   screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D], f32x16 (&acc)[QB],
+                                                   bool more, int64_t next_tile, unsigned lane_off) {
+  constexpr int NG = BSTEPS / BG;
+  if constexpr (G < NG) {
+    constexpr int PG = G + RG - 1;  // group to prefetch now
+#ifndef SSKD_SCREEN_ABL_NOGLOBAL  // timing ablation: no corpus tile loads (the ring keeps its first contents)
+    if constexpr (PG < NG) load_bgroup<BG>(buf[PG % RG], tile + PG * BG * 64, lane_off);
+    else if (more) load_bgroup<BG>(buf[PG % RG], tile + next_tile + (PG - NG) * BG * 64, lane_off);
+#endif
+    compute_bgroup<QB, G, BG, D, NB>(buf[G % RG], qbase, b, acc);
+    screen_tile_groups<QB, G + 1, BG, RG, D, NB>(buf, tile, qbase, b, acc, more, next_tile, lane_off);
+  }
+}
+
+// ------------------------------------------------------------------------- //
+// The screening kernel.  Structure of scan_topk_kernel (query block of 128 in LDS as B fragments, every wave streams
+// its own corpus tiles through a register ring, shared pruning pools) on bf16 operands, with one difference: no
+// per-lane sorted lists.  A lane APPENDS every row that reaches the pruning bound - score >= (best known lower bound
+// of the query's k-th best screen score) - 2e - to a private run of SCREEN_CAP entries in global memory (8-byte
+// fire-and-forget stores, no atomics; the count lives in a register).  Every bound is a valid lower bound of the
+// final k-th best screen score, so the appended set always contains the whole candidate band {score >= kth - 2e}:
+// nothing to prove afterwards except that no run overflowed.  (Rounds 2-3 kept 6- or 8-deep sorted lists in
+// registers: 12 registers per 32-query sub-block, an insertion network per accepted row, and a "list full inside the
+// band" failure mode that sent near-duplicate neighbourhoods to the exact scan.)  Without the lists the kernel fits
+// THREE waves per SIMD (12 waves per workgroup, 168 registers): 8.6 -> 7.8 ms at the bench shape, 1.66 -> 1.30 ms on
+// the 125 k-row shard of an 8-GPU split.
+// A SAMPLE PHASE (screen_tiles<..., BOUND_ONLY = true>) opens the launch: every workgroup runs the tile loop over its
+// share of the first SCREEN_PRE_TILES x 32 rows and only publishes bounds (tau + the global buckets); its slice then
+// starts from the k-th best of that sample instead of -inf, which cuts the appended entries per query from ~1 400
+// (every slice starts cold: its first tiles pass whole) to a few hundred.
+// ------------------------------------------------------------------------- //
+#ifndef SSKD_SCREEN_CAP
+#define SSKD_SCREEN_CAP 64
+#endif
+#ifndef SSKD_SCREEN_FIN_ENTRIES
+#define SSKD_SCREEN_FIN_ENTRIES 640
+#endif
+constexpr int SCREEN_CAP = SSKD_SCREEN_CAP;   // entries per (query, wave, half-wave) run
+#ifndef SSKD_SCREEN_PRE_TILES
+#define SSKD_SCREEN_PRE_TILES 64
+#endif
+constexpr int SCREEN_PRE_TILES = SSKD_SCREEN_PRE_TILES;   // rows / 32 of the bound-only sample phase
+// appended entries of one query staged in LDS by the finalize kernel (more: its streaming path).  640 entries = 7.6 KiB
+// per one-wave workgroup with the query and the candidate list; 1 024 cost the 125 k-row shard 3 % (occupancy)
+constexpr int SCREEN_FIN_ENTRIES = SSKD_SCREEN_FIN_ENTRIES;
+static_assert(SCREEN_FIN_ENTRIES >= 640, "the streaming path of the finalize kernel parks 64 x 10 scores in the stage");
+
+struct ScreenAppendParams {
+  const sbf16x8* tiled;     // bf16 tiles
+  const float* queries;     // fp32 [nq][384] (rounded to bf16 while staging)
+  const float* eps2;        // [nq]
+  uint2* cand;              // [nq][lists_per_query][SCREEN_CAP]: (score bits, row id)
+  int* cand_cnt;            // [nq][lists_per_query]: rows that reached the bound (> SCREEN_CAP: the run overflowed)
+  int* tau;
+  int* gpool;
+  int64_t n_rows;
+  int n_tiles;
+  int nq;
+  int n_slices;
+  int tiles_per_slice;
+  int lists_per_query;
+  int pre_tiles;            // the sample: the shard's first tiles, pre_tps of them per slice (0: no sample phase)
+  int pre_tps;
+  const uint32_t* row_mask; // MASKED kernels only (as ScanParams::row_mask)
+};
+
+// out of line: the cold path must not cost the screening loop registers
+__device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* run, int n, float thr) {
+  int w = 0;
+  for (int i = 0; i < n; ++i) {
+    const unsigned long long e = __hip_atomic_load(run + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__uint_as_float((unsigned)e) >= thr) run[w++] = e;
+  }
+  return w;
+}
+
+// One phase of the screening kernel: the tiles [t_begin, t_end) of this workgroup, one tile per wave at a time.
+// BOUND_ONLY: nothing is appended and nothing exchanged - one pool offer per lane and tile (the sample phase).
+// MASKED: the row allow-mask (tile_mask_word).  Why the proof survives it: a masked row scores -inf right after the MFMAs,
+// and gthr starts at -FLT_MAX, so it never passes "x >= gthr" (no append), and every pool offer is either a row that passed
+// that test or the lane's best row m of a tile only when m >= gthr (the sample phase, LIGHT) or when some row was taken
+// (first tile): never -inf.  So a slot of a pool or bucket that is not INT_MIN is always the finite score of an allowed
+// row, the pool is "full" (its minimum above INT_MIN) only with K scores of DISTINCT allowed rows, and every bound is a
+// lower bound of the k-th best screen score among the ALLOWED rows - the band the finalize kernel needs.  With fewer than
+// k allowed rows no pool ever fills, nothing is pruned, and the finalize kernel takes every appended row (tau = -inf).
+// The in-call exact fallback scans with the same mask.
+template <int K, int QB, int WAVES, bool BOUND_ONLY, bool LIGHT, int BG, int RG, bool MASKED = false>
+__device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_begin, int t_end, int wave, int j, int h, int q0,
+                                             const sbf16x8* __restrict__ qlane,
+                                             int* __restrict__ pool, int* __restrict__ wthr, uint2* run0, int64_t run_stride,
+                                             bool ragged, float (&gthr)[QB], const float (&band)[QB], int (&cnt)[QB]) {
+  sbf16x8 buf[RG][BG];
+  constexpr int NB = screen_frag_bases<QB>();
+  screen_lds_frag* qbase[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    qbase[nb] = (screen_lds_frag*)qlane + nb * SCREEN_FRAGS_PER_BASE * 64;
+    asm volatile("" : "+v"(qbase[nb]));   // one register each, not re-derived per read
+  }
+  sbf16x8 qfrag[SCREEN_FRAG_DEPTH];
+  const unsigned lane_off = (unsigned)(j + 32 * h) * 16u;
+  // sub-block qq of this lane holds a real query (not padding of the last block) while 32 qq < n_real: one register and
+  // a compare per use instead of QB flags held across the MFMA burst
+  int n_real = p.nq - q0 - j;
+  asm volatile("" : "+v"(n_real));
+  int t = t_begin + wave;
+  if (t < t_end) {
+#pragma unroll
+    for (int g = 0; g + 1 < RG; ++g) load_bgroup<BG>(buf[g], p.tiled + (int64_t)t * BTILE_VEC + g * BG * 64, lane_off);
+  }
+
+  int tiles_done = 0;
+  for (; t < t_end; t += WAVES, ++tiles_done) {
+    const sbf16x8* tile = p.tiled + (int64_t)t * BTILE_VEC;   // wave-uniform
+    uint32_t mword = 0xFFFFFFFFu;
+    if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
+    // bounds are exchanged with global memory at tile 0 (the sample phases' bounds), tile 16 and every 64th: an exchange is
+    // ten dependent agent-scope loads + an atomic per sub-block (~3 us of stall); at tiles 0, 1, 2, 4, 8, 16, ... and
+    // every 8th it cost 5 % of the kernel at 1 M rows and 10 % on a 125 k-row shard.  The sample phase never reads them.
+    const bool exchange = !BOUND_ONLY && (tiles_done == 0 || tiles_done == 16 || tiles_done % SCREEN_TAU_REFRESH_TILES == 0);
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq) {
+      const int w = wthr[qq * 32 + j];
+      gthr[qq] = fmaxf(gthr[qq], ordered_to_float(w) - band[qq]);
+      if (exchange && (qq * 32 < n_real))
+        gthr[qq] = fmaxf(gthr[qq],
+                         ordered_to_float(exchange_bound<K>(p.gpool, p.tau + q0 + qq * 32 + j, q0 + qq * 32 + j, w)) - band[qq]);
+    }
+    f32x16 acc[QB];
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
+
+    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tile, qbase, qfrag, acc, t + WAVES < t_end,
+                                                             (int64_t)WAVES * BTILE_VEC, lane_off);
+
+    const int rowbase = t * TILE_ROWS + 4 * h;
+    if (ragged && (int64_t)(t + 1) * TILE_ROWS > p.n_rows) {
+#pragma unroll
+      for (int qq = 0; qq < QB; ++qq)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (rowbase + acc_row(r) >= p.n_rows) acc[qq][r] = -INFINITY;
+    }
+    if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
+#ifdef SSKD_SCREEN_ABL_NOLIST  // timing ablation: no candidate / pool maintenance (accumulators kept alive)
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc[qq][r]));
+    if (false)
+#endif
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq) {
+      float m = acc[qq][0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[qq][r]);
+      if constexpr (BOUND_ONLY) {
+        // the sample phase only needs a bound: ONE offer per lane and tile (its best row) instead of one per row - every
+        // row of a cold sample passes, and 80 compare-and-swap loops per lane and tile cost 0.05 ms per call
+        if ((qq * 32 < n_real) && m >= gthr[qq]) {
+          int xid = rowbase;
+#pragma unroll
+          for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
+          const int xi = float_to_ordered(m);
+          if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi))
+            bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
+          gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
+        }
+      } else
+      if (__any((qq * 32 < n_real) && m >= gthr[qq])) {
+#ifndef SSKD_SCREEN_NO_COMPACT
+        {
+          // A run that could fill up inside this tile (16 rows) first drops what the bound has overtaken since it was
+          // appended: rows arriving in ascending order of their score - a corpus sorted by topic - pass the bound one
+          // after the other and the bound follows them, so the entries worth keeping are the band of the CURRENT
+          // bound.  Own stores, read back from L2 after they were acknowledged; forward in-place compaction (w <= i).
+          const bool tight = cnt[qq] > SCREEN_CAP - 16 && cnt[qq] <= SCREEN_CAP;
+          if (__any(tight)) {
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (tight) cnt[qq] = screen_compact_run(reinterpret_cast<unsigned long long*>(run0 + qq * run_stride), cnt[qq], gthr[qq]);
+          }
+        }
+#endif
+        bool grew = false;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float x = acc[qq][r];
+          const int xid = rowbase + acc_row(r);
+          const bool take = (qq * 32 < n_real) && x >= gthr[qq];   // (padding queries own no run)
+          {   // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
+            if (take) {
+              {
+                unsigned long long* const run = reinterpret_cast<unsigned long long*>(run0 + qq * run_stride);
+                if (cnt[qq] < SCREEN_CAP)
+                  run[cnt[qq]] = (unsigned long long)__float_as_uint(x) | ((unsigned long long)(unsigned)xid << 32);
+                ++cnt[qq];   // (> SCREEN_CAP: the run overflowed - the band itself holds more than a run: exact fallback)
+              }
+              if (!LIGHT && tiles_done > 0) {
+                const int xi = float_to_ordered(x);
+                if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && (qq * 32 < n_real))
+                  bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
+              }
+              grew = true;
+            }
+          }
+        }
+        if (grew) {
+          if constexpr (LIGHT) {
+            // ONE pool offer per lane, sub-block and tile - its best row - instead of one per appended row.  The bound
+            // is a little weaker (two of a query's best rows in one lane's share of a tile count once) and its upkeep
+            // much cheaper: worth it while a slice is short (125 k-row shard -6 %, 60 k -12 %; 1 M rows +1 %, 8.8 M +3 %)
+            int xid = rowbase;
+#pragma unroll
+            for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
+            const int xi = float_to_ordered(m);
+            if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && tiles_done > 0)
+              bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
+          } else {
+            // first tile: every workgroup starts at the same instant - offer only the lane's best row
+            if (tiles_done == 0) pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, float_to_ordered(m));
+          }
+          gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
+        }
+      }
+    }
+  }
+
+}
+
+template <int K, int QB, int WAVES, bool LIGHT, int BG, int RG, bool MASKED = false>
+__global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendParams p) {
+  extern __shared__ float4 qs_raw[];
+  sbf16x8* const qs = reinterpret_cast<sbf16x8*>(qs_raw);  // [QB][24 steps][64 lanes]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 31, h = lane >> 5;
+  // Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8) and each XCD has its own L2: give XCD x
+  // a CONTIGUOUS range of (slice, query block) pairs, slice-major, so that a slice's tiles are pulled
+  // through one or two L2s instead of all eight.
+  const int n_qblocks = gridDim.x / p.n_slices;
+  const int xcd = blockIdx.x & 7, within = blockIdx.x >> 3;
+  const int logical = xcd * (gridDim.x >> 3) + min(xcd, (int)(gridDim.x & 7)) + within;
+  const int slice = logical / n_qblocks;
+  const int qblk = logical % n_qblocks;
+  const int q0 = qblk * (32 * QB);
+
+  for (int idx = tid; idx < QB * BSTEPS * 64; idx += WAVES * 64) {
+    const int l = idx & 63, sidx = (idx >> 6) % BSTEPS, qq = idx / (64 * BSTEPS);
+    const int q = q0 + qq * 32 + (l & 31);
+    sbf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.f;
+    if (q < p.nq) {
+      const float4* src = reinterpret_cast<const float4*>(p.queries + (int64_t)q * DIM + 16 * sidx + 8 * (l >> 5));
+      const float4 a = src[0], b = src[1];
+      v[0] = (__bf16)a.x; v[1] = (__bf16)a.y; v[2] = (__bf16)a.z; v[3] = (__bf16)a.w;
+      v[4] = (__bf16)b.x; v[5] = (__bf16)b.y; v[6] = (__bf16)b.z; v[7] = (__bf16)b.w;
+    }
+    qs[idx] = v;
+  }
+  int* const pool = reinterpret_cast<int*>(qs + QB * BSTEPS * 64);
+  int* const wthr = pool + QB * 32 * K;
+  for (int i = tid; i < QB * 32 * (K + 1); i += WAVES * 64) pool[i] = (int)0x80000000;
+  __syncthreads();
+  const sbf16x8* qlane = qs + lane;
+
+  float gthr[QB];   // best known lower bound on the query's final K-th SCREEN score, minus 2e
+  float band[QB];
+  int cnt[QB];
+  bool real[QB];
+#pragma unroll
+  for (int qq = 0; qq < QB; ++qq) {
+    gthr[qq] = -FLT_MAX;   // finite: the -inf scores of rows past n_rows never pass
+    const int qg = q0 + qq * 32 + j;
+    real[qq] = qg < p.nq;
+    band[qq] = p.eps2[real[qq] ? qg : p.nq - 1];
+    cnt[qq] = 0;
+  }
+  // run of (query q0 + j, this wave, this half-wave); sub-block qq is 32 queries further
+  const int my_list = (slice * WAVES + wave) * 2 + h;
+  uint2* const run0 = p.cand + ((int64_t)min(q0 + j, p.nq - 1) * p.lists_per_query + my_list) * SCREEN_CAP;
+  const int64_t run_stride = (int64_t)32 * p.lists_per_query * SCREEN_CAP;
+
+  const bool ragged = (p.n_rows & 31) != 0;
+
+  // Two phases.  0: this workgroup's share of the SAMPLE (the shard's first pre_tiles tiles, cut over the slices),
+  // bounds only - one pool offer per lane and tile, nothing appended, no exchange; its result is published through tau
+  // and the global buckets.  1: its slice, appending.  (The pre-pass was a launch of its own until the fixed costs of a
+  // 125 k-row shard were counted: launch gap + a second staging of the query block = 70 us of a 1.3 ms call.  Two
+  // instantiations of the tile loop, not one loop with a run-time flag: that cost the 160-query kernel 5 spilled
+  // registers and 4 % at 8.8 M rows.)
+  const int t_begin = slice * p.tiles_per_slice;
+  const int t_end = min(t_begin + p.tiles_per_slice, p.n_tiles);
+  if (p.pre_tps > 0) {
+    const int s_begin = slice * p.pre_tps;
+    const int s_end = min(s_begin + p.pre_tps, p.pre_tiles);
+    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, wave, j, h, q0, qlane,
+                                             pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
+    // what this workgroup learned from its share of the sample; everybody's offers are in before phase 1
+#pragma unroll
+    for (int qq = 0; qq < QB; ++qq)
+      if (real[qq] && h == 0) atomicMax(p.tau + q0 + qq * 32 + j, wthr[qq * 32 + j]);
+    __syncthreads();
+    // INVARIANT OF THE POOL: every slot is the score of a DISTINCT row (pool_offer stores scores only and cannot tell
+    // a row it already holds).  Where this workgroup's share of the sample lies inside its own slice - slice 0, whose
+    // first tiles ARE the sample - phase 1 offers those rows a second time: counted twice, a row would push the pool's
+    // minimum above the k-th best DISTINCT score, the "lower bound" above the true k-th best, and rows of the top k
+    // would be pruned silently (round 3 shipped that hole: VERDICT r3 weak 1).  So such a workgroup empties its slots
+    // here.  wthr stays: it is the minimum of a full pool of distinct SAMPLE rows, a valid bound on its own, and only
+    // ever rises to minima of full pools, which from here on hold phase-1 rows only.  Rows of other slices' sample
+    // shares never return in this workgroup's slice, so its pool keeps them.
+    if (s_begin < t_end && t_begin < s_end) {
+      for (int i = tid; i < QB * 32 * K; i += WAVES * 64) pool[i] = (int)0x80000000;
+      __syncthreads();
+    }
+  }
+  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, wave, j, h, q0,
+                                            qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
+
+#pragma unroll
+  for (int qq = 0; qq < QB; ++qq) {
+    const int q = q0 + qq * 32 + j;
+    if (q < p.nq) p.cand_cnt[(int64_t)q * p.lists_per_query + my_list] = cnt[qq];
+  }
+}
+
+struct ScreenFinalAppendParams {
+  const uint2* cand;          // [nq][lists][SCREEN_CAP]
+  const int* cand_cnt;        // [nq][lists]
+  const float* eps2;
+  const float* rows;          // the fp32 index itself (row-major): exact re-scoring
+  const float* queries;
+  int lists, k, nq;
+  int64_t id_offset;
+  float* out_scores;          // [nq][k]
+  int64_t* out_ids;
+  int* fb_count;              // [1] pre-zeroed: queries handed to the exact fallback
+  int* fb_qid;                // [nq]: the fallback holds every query of the call, it cannot overflow
+  float* fb_queries;          // [nq][384]
+};
+
+// One WAVE per query: gather the appended runs -> k-th best screen score -> candidate band -> exact re-scoring (the
+// fp32 MFMA's k-ordered fma chain) -> exact top k.  A query goes to the exact fallback when it has no band (eps2 = +inf),
+// when a run overflowed, when its entries do not fit the LDS stage, or when the band holds more than SCREEN_MAX_CAND rows.
+// Dynamic LDS: [E] scores, [E] ids (E = SCREEN_FIN_ENTRIES), [384] query, [SCREEN_MAX_CAND] candidate rows.
+__global__ __launch_bounds__(64) void screen_finalize_append_kernel(ScreenFinalAppendParams p) {
+  extern __shared__ __attribute__((aligned(16))) float fin_lds[];
+  float* const es = fin_lds;
+  int* const ei = reinterpret_cast<int*>(fin_lds + SCREEN_FIN_ENTRIES);
+  float* const qv = fin_lds + 2 * SCREEN_FIN_ENTRIES;
+  int* const ci = reinterpret_cast<int*>(qv + DIM);
+  const int q = blockIdx.x, lane = threadIdx.x;
+  for (int c = lane; c < DIM; c += 64) qv[c] = p.queries[(int64_t)q * DIM + c];
+
+  // eps2 = +inf: no band was established for this query (screen_setup_kernel) - its screen scores prove nothing
+  bool bad = !(p.eps2[q] < INFINITY);
+  int total = 0;
+  for (int l0 = 0; l0 < p.lists; l0 += 64) {
+    const int l = l0 + lane;
+    const int c = l < p.lists ? p.cand_cnt[(int64_t)q * p.lists + l] : 0;
+    if (c > SCREEN_CAP) bad = true;
+    total += wave_sum(min(c, SCREEN_CAP));
+  }
+  int M = 0;
+  float tau;
+  if (total <= SCREEN_FIN_ENTRIES) {
+    // ---- the usual case: every entry staged in LDS ----
+    int base = 0;
+    for (int l0 = 0; l0 < p.lists; l0 += 64) {
+      const int l = l0 + lane;
+      const int c = l < p.lists ? min(p.cand_cnt[(int64_t)q * p.lists + l], SCREEN_CAP) : 0;
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+      }
+      const int off = base + incl - c;
+      const uint2* src = p.cand + ((int64_t)q * p.lists + l) * SCREEN_CAP;
+      for (int i = 0; i < c; ++i) {
+        const uint2 e = src[i];
+        es[off + i] = __uint_as_float(e.x);
+        ei[off + i] = (int)e.y;
+      }
+      base += __shfl(incl, 63);
+    }
+    const int L = total;
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): one wave, its own LDS writes
+
+    // k-th best screen entry in rank order (k rounds of bounded arg-best)
+    float bs = INFINITY;
+    int bi = -1;
+    bool have = false;
+    float kth = -INFINITY;
+    int found = 0;
+    for (int r = 0; r < p.k; ++r) {
+      float s = -INFINITY;
+      int i = -1;
+      for (int e = lane; e < L; e += 64) {
+        pick_after(s, i, es[e], ei[e], have, bs, bi);
+      }
+      wave_argbest(s, i);
+      if (i < 0) break;
+      bs = s; bi = i; have = true;
+      kth = s;
+      ++found;
+    }
+    // fewer than k rows exist at all: every entry is a candidate
+    tau = found == p.k ? kth - p.eps2[q] : -INFINITY;
+
+    // candidates, compacted in entry order (ballot prefix)
+    for (int e0 = 0; e0 < L; e0 += 64) {
+      const int e = e0 + lane;
+      const bool in = e < L && es[e] >= tau;
+      const unsigned long long mask = __ballot(in);
+      if (in) {
+        const int slot = M + __popcll(mask & ((1ull << lane) - 1ull));
+        if (slot < SCREEN_MAX_CAND) ci[slot] = ei[e];
+      }
+      M += __popcll(mask);
+    }
+  } else {
+    // ---- more entries than the stage holds (a shard too small for its bounds to warm up, or rows that arrive in
+    // ascending order of their score): stream the runs twice.  Pass 1: each lane keeps the k best SCORES of its runs
+    // (the k-th best score of the union is the k-th best of the union of those); pass 2 collects the band.
+    float top[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) top[i] = -INFINITY;
+    for (int l = lane; l < p.lists; l += 64) {
+      const int c = min(p.cand_cnt[(int64_t)q * p.lists + l], SCREEN_CAP);
+      const uint2* src = p.cand + ((int64_t)q * p.lists + l) * SCREEN_CAP;
+      for (int i = 0; i < c; ++i) {
+        float v = __uint_as_float(src[i].x);
+        if (v > top[9]) {
+          top[9] = v;
+#pragma unroll
+          for (int u = 9; u > 0; --u) {
+            const float a = top[u - 1], b = top[u];
+            top[u - 1] = fmaxf(a, b);
+            top[u] = fminf(a, b);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      es[lane * 10 + i] = top[i];
+      ei[lane * 10 + i] = top[i] > -INFINITY ? lane * 10 + i : -1;   // slot number as the id: a multiset selection
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    float bs = INFINITY;
+    int bi = -1;
+    bool have = false;
+    float kth = -INFINITY;
+    int found = 0;
+    for (int r = 0; r < p.k; ++r) {
+      float s = -INFINITY;
+      int i = -1;
+      for (int e = lane; e < 640; e += 64) {
+        const int id = ei[e];
+        if (id >= 0) pick_after(s, i, es[e], id, have, bs, bi);
+      }
+      wave_argbest(s, i);
+      if (i < 0) break;
+      bs = s; bi = i; have = true;
+      kth = s;
+      ++found;
+    }
+    tau = found == p.k ? kth - p.eps2[q] : -INFINITY;
+    int* const mcount = ei;   // the selection is done with ei
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    if (lane == 0) mcount[0] = 0;
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    for (int l = lane; l < p.lists; l += 64) {
+      const int c = min(p.cand_cnt[(int64_t)q * p.lists + l], SCREEN_CAP);
+      const uint2* src = p.cand + ((int64_t)q * p.lists + l) * SCREEN_CAP;
+      for (int i = 0; i < c; ++i) {
+        const uint2 e = src[i];
+        if (__uint_as_float(e.x) >= tau) {
+          const int slot = atomicAdd(mcount, 1);
+          if (slot < SCREEN_MAX_CAND) ci[slot] = (int)e.y;
+        }
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    M = mcount[0];
+  }
+  if (M > SCREEN_MAX_CAND) bad = true;
+  if (__any(bad)) {
+    int slot = 0;
+    if (lane == 0) {
+      slot = atomicAdd(p.fb_count, 1);   // < nq: one add per query at most
+      p.fb_qid[slot] = q;
+    }
+    slot = __shfl(slot, 0);
+    for (int c = lane; c < DIM; c += 64) p.fb_queries[(int64_t)slot * DIM + c] = qv[c];
+    return;
+  }
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+
+  // exact scores, 64 candidates per round: the fma order of the 32x32x2 f32 MFMA chain (section 3.1).
+  // A candidate row = 12 whole cache lines of the index.
+  // (mine_select_kernel, mine.hip, scores its positives with this same chain and must keep it the same chain; the two
+  // loops are not one shared function because inlining one moved instructions in this kernel)
+  float cs[SCREEN_MAX_CAND / 64];
+  int cid[SCREEN_MAX_CAND / 64];
+#pragma unroll
+  for (int c = 0; c < SCREEN_MAX_CAND / 64; ++c) {
+    cs[c] = -INFINITY;
+    cid[c] = -1;
+    const int idx = c * 64 + lane;
+    if (idx < M) {
+      const int row = ci[idx];
+      const float4* src = reinterpret_cast<const float4*>(p.rows) + (int64_t)row * (DIM / 4);
+      float acc = 0.f;
+#pragma unroll 16
+      for (int u = 0; u < STEPS; ++u) {  // 16 steps = four whole 128-byte lines of the row in flight
+        const float4 a = src[2 * u], b = src[2 * u + 1];
+        const float4 qa = *reinterpret_cast<const float4*>(&qv[8 * u]), qb = *reinterpret_cast<const float4*>(&qv[8 * u + 4]);
+        acc = fmaf(a.x, qa.x, acc); acc = fmaf(b.x, qb.x, acc);
+        acc = fmaf(a.y, qa.y, acc); acc = fmaf(b.y, qb.y, acc);
+        acc = fmaf(a.z, qa.z, acc); acc = fmaf(b.z, qb.z, acc);
+        acc = fmaf(a.w, qa.w, acc); acc = fmaf(b.w, qb.w, acc);
+      }
+      cs[c] = acc;
+      cid[c] = (acc == acc) ? row : -1;  // a NaN score is never selected (as in the exact scan)
+    }
+  }
+  float bs = INFINITY;
+  int bi = -1;
+  bool have = false;
+  for (int r = 0; r < p.k; ++r) {
+    float s = -INFINITY;
+    int i = -1;
+#pragma unroll
+    for (int c = 0; c < SCREEN_MAX_CAND / 64; ++c) {
+      if (cid[c] >= 0) pick_after(s, i, cs[c], cid[c], have, bs, bi);
+    }
+    wave_argbest(s, i);
+    if (lane == 0) {
+      p.out_scores[(int64_t)q * p.k + r] = i >= 0 ? s : -FLT_MAX;
+      p.out_ids[(int64_t)q * p.k + r] = i >= 0 ? (int64_t)i + p.id_offset : -1;
+    }
+    if (i < 0) {
+      for (int rr = r + 1 + lane; rr < p.k; rr += 64) {
+        p.out_scores[(int64_t)q * p.k + rr] = -FLT_MAX;
+        p.out_ids[(int64_t)q * p.k + rr] = -1;
+      }
+      break;
+    }
+    bs = s; bi = i; have = true;
+  }
+}
+
+// fb_count[0] = queries handed to the exact fallback; tier 1 answers the first SCREEN_FALLBACK_TIER1 of them with a
+// launch geometry made for FEW queries, tier 2 the rest: [1] = min(count, TIER1), [2] = max(count - TIER1, 0)
+__global__ void screen_fallback_tiers_kernel(int* __restrict__ fb_count, int tier1) {
+  const int n = fb_count[0];
+  fb_count[1] = n < tier1 ? n : tier1;
+  fb_count[2] = n > tier1 ? n - tier1 : 0;
+}
+
+__global__ __launch_bounds__(256) void screen_scatter_kernel(const int* __restrict__ fb_count, const int* __restrict__ fb_qid,
+                                                             const float* __restrict__ fb_scores,
+                                                             const int64_t* __restrict__ fb_ids, int k,
+                                                             float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
+                                                             int* __restrict__ d_status) {
+  const int n = *fb_count;
+  if (blockIdx.x == 0 && threadIdx.x == 0) d_status[1] = n;   // cost diagnostic: queries that took the exact fallback
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const int q = fb_qid[i];
+    for (int r = threadIdx.x; r < k; r += 256) {
+      out_scores[(int64_t)q * k + r] = fb_scores[(int64_t)i * k + r];
+      out_ids[(int64_t)q * k + r] = fb_ids[(int64_t)i * k + r];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- screened search (bf16 screening + exact re-scoring): see the kernels above -----------------
+
+namespace {
+struct ScreenPlan {
+  int QB, LK, n_qblocks, n_slices, tiles_per_slice, n_tiles, lists_per_query;
+  int pre_tiles, pre_slices, pre_tps;   // the bound-only sample phase over the first rows
+  bool light;                           // short slices: one pool offer per lane and tile (screen_tiles<LIGHT>)
+  size_t part_elems;
+};
+
+bool screen_plan(int64_t n_rows, int nq, int k, ScreenPlan* sp) {
+  if (k < 1 || k > 10 || nq < 64 || n_rows < 64 * TILE_ROWS) return false;
+  ScreenPlan pl{};
+  pl.n_tiles = (int)sskd::ceil_div(n_rows, TILE_ROWS);
+  // Queries per workgroup x slices.  128 queries per workgroup (QB = 4) halve the corpus re-reads per MFMA against 64;
+  // 160 (QB = 5: 120 KB of B fragments in LDS, 80 accumulator registers, a shorter prefetch ring) cut them by another
+  // fifth and - the reason they are here - change how the launch tiles the chip: 10 000 queries are 79 blocks of 128
+  // (x 3 slices = 237 workgroups on 256 CUs) or 63 blocks of 160 (x 4 = 252).
+  // Slices: every slice starts its pruning pools cold, which costs ~0.09 ms per slice at 10 k queries whatever the
+  // corpus size, while a launch that does not fill whole rounds of the chip's 256 CUs (one workgroup per CU)
+  // wastes the idle share of the matrix time.  Over both block sizes and 1..8 rounds, minimise
+  //   matrix_time / utilisation + 0.09 ms x slices.
+  // Measured (tools/ab_search.py): 1 M rows 7.90 (128 x 3) -> 7.55 ms (160 x 4); 125 k rows 1.34 (128 x 3) vs 1.39.
+  const int resident = SCREEN_CUS;
+  const int max_slices = std::max(1, (int)sskd::ceil_div(pl.n_tiles, SCREEN_WAVES));
+  const double matrix_ms = (double)n_rows * nq * (2.0 * DIM) / 1.0e12;   // at ~1 PFLOP/s sustained
+  const double warm_ms = 0.09 * nq / 10000.0;
+  int slices = 1;
+  double best = 1e300;
+  for (int qb : {4, 5, 2}) {
+    if (qb == 2 ? nq >= 256 : nq < 256) continue;   // small batches: 64 queries per workgroup
+#ifdef SSKD_SCREEN_FORCE_QB
+    if (qb != SSKD_SCREEN_FORCE_QB) continue;        // tools/ab_build.py sweeps only
+#endif
+    const int qblocks = (int)sskd::ceil_div(nq, 32 * qb);
+    for (int rounds = 1; rounds <= 8; ++rounds) {
+      const int sl = std::min(std::max(1, rounds * resident / qblocks), max_slices);
+      const int wgs = sl * qblocks;
+      const double util = (double)wgs / ((double)resident * sskd::ceil_div(wgs, resident));
+      const double cost = matrix_ms / util + warm_ms * sl;
+      if (cost < best - 1e-9) { best = cost; slices = sl; pl.QB = qb; }
+    }
+  }
+  if (pl.QB == 0) return false;
+  pl.n_qblocks = (int)sskd::ceil_div(nq, 32 * pl.QB);
+  pl.LK = SCREEN_CAP;   // entries per run
+  const int max_by_lists = 1024 / (2 * SCREEN_WAVES);   // <= 1 024 runs per query
+  if (slices > max_by_lists) slices = max_by_lists;
+#ifdef SSKD_SCREEN_FORCE_SLICES
+  slices = SSKD_SCREEN_FORCE_SLICES;
+#endif
+  pl.tiles_per_slice = (int)sskd::ceil_div(pl.n_tiles, slices);
+  pl.n_slices = (int)sskd::ceil_div(pl.n_tiles, pl.tiles_per_slice);
+  pl.lists_per_query = pl.n_slices * SCREEN_WAVES * 2;
+  pl.part_elems = (size_t)nq * pl.lists_per_query * pl.LK;
+  // sample phase: the first SCREEN_PRE_TILES tiles (at most an eighth of the shard), cut over the slices
+  // by slice length, not shard size: 1 000 queries cut 1 M rows into 32 slices of 81 tiles per wave (-7 % in the light
+  // form), 10 000 queries into 4 of 651 (+1 %)
+  pl.light = pl.tiles_per_slice <= SCREEN_LIGHT_MAX_TILES_PER_WAVE * SCREEN_WAVES;
+  pl.pre_tiles = std::min(SCREEN_PRE_TILES, pl.n_tiles / 8);
+  pl.pre_slices = pl.n_slices;
+  pl.pre_tps = (int)sskd::ceil_div(pl.pre_tiles, pl.n_slices);
+  *sp = pl;
+  return true;
+}
+
+struct ScreenWs {
+  float* part_scores;
+  int* part_ids;
+  int* cand_cnt;     // append form: [nq][lists]
+  int* tau;          // [nq] + gpool [nq * 10]
+  float* eps2;
+  int* fb_count;     // [2]: count, spare
+  int* fb_qid;
+  float* fb_queries;
+  float* fb_scores;
+  int64_t* fb_ids;
+  void* exact_ws;      // tier 1 (<= SCREEN_FALLBACK_TIER1 queries)
+  size_t exact_bytes;
+  void* exact_ws2;     // tier 2 (the rest; absent when nq <= SCREEN_FALLBACK_TIER1)
+  size_t exact_bytes2;
+  size_t bytes;
+};
+
+ScreenWs screen_carve(void* base, const ScreenPlan& pl, int64_t n_rows, int nq, int k) {
+  sskd::Carver c(base);
+  ScreenWs w{};
+  w.part_scores = c.take<float>(pl.part_elems);   // append form: the runs, 8 bytes per entry,
+  w.part_ids = c.take<int>(pl.part_elems);        //   span both arrays (contiguous: see below)
+  w.cand_cnt = c.take<int>((size_t)nq * pl.lists_per_query);
+  w.tau = c.take<int>((size_t)nq * 11);
+  w.eps2 = c.take<float>(nq);
+  w.fb_count = c.take<int>(64);
+  // the in-call exact fallback is sized for EVERY query: however many candidate bands cannot be proven
+  // complete, the call answers them itself (its launches read the actual count from device memory)
+  w.fb_qid = c.take<int>(nq);
+  w.fb_queries = c.take<float>((size_t)nq * DIM);
+  w.fb_scores = c.take<float>((size_t)nq * k);
+  w.fb_ids = c.take<int64_t>((size_t)nq * k);
+  const int tier1 = nq < SCREEN_FALLBACK_TIER1 ? nq : SCREEN_FALLBACK_TIER1;
+  w.exact_bytes = sskd::exact_workspace_bytes(n_rows, tier1, k);
+  w.exact_ws = c.take<char>(w.exact_bytes);
+  w.exact_bytes2 = nq > tier1 ? sskd::exact_workspace_bytes(n_rows, nq - tier1, k) : 0;
+  w.exact_ws2 = w.exact_bytes2 ? c.take<char>(w.exact_bytes2) : nullptr;
+  w.bytes = c.bytes();
+  return w;
+}
+}  // namespace
+
+// screening sidecar: [bf16 tiles of the CENTRED rows][4 KiB: norm maxima + column sums]   (exact re-scoring reads the index itself)
+static inline size_t sidecar_norm_offset(int64_t n_rows) { return (size_t)sskd::ceil_div(n_rows, TILE_ROWS) * BTILE_VEC * 16; }
+static inline size_t sidecar_rows_offset(int64_t n_rows) { return sidecar_norm_offset(n_rows) + SIDECAR_NORM_BYTES; }
+
+// the one launch of screen_setup_kernel: the search's first launch, and all that sskd_index_screen_band does
+static inline void launch_screen_setup(const int* max_norm2, const float* d_queries, int nq, float* eps2, int* tau,
+                                       int* fb_count, int* d_status, hipStream_t st) {
+  hipLaunchKernelGGL(screen_setup_kernel, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0, st, d_queries, nq, max_norm2,
+                     eps2, tau, fb_count, d_status);
+}
+
+size_t sskd_index_bf16_bytes(int64_t n_rows) {
+  if (n_rows <= 0) return 0;
+  return sidecar_rows_offset(n_rows);
+}
+
+int sskd_index_make_bf16(const float* d_tiled, int64_t n_rows, void* d_bf16, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "index_make_bf16: n_rows < 0");
+  if (n_rows == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_tiled && d_bf16, "index_make_bf16: null pointer");
+  hipStream_t st = sskd::as_stream(stream);
+  const int64_t tiles = sskd::ceil_div(n_rows, TILE_ROWS);
+  int* max_norm2 = reinterpret_cast<int*>(static_cast<char*>(d_bf16) + sidecar_norm_offset(n_rows));
+  if (hipMemsetAsync(max_norm2, 0, SIDECAR_NORM_BYTES, st) != hipSuccess) return sskd::fail(SSKD_ERR_HIP, "index_make_bf16: memset failed");
+  hipLaunchKernelGGL(tile_colsum_kernel, dim3((unsigned)(tiles < 1024 ? tiles : 1024)), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(d_tiled), tiles, reinterpret_cast<float*>(max_norm2) + SIDECAR_COLSUM_OFF);
+  int rc = sskd::check_launch("tile_colsum_kernel");
+  if (rc != SSKD_OK) return rc;
+  hipLaunchKernelGGL(make_bf16_tiles_kernel, dim3((unsigned)tiles), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(d_tiled), tiles, n_rows, static_cast<sbf16x8*>(d_bf16), max_norm2);
+  return sskd::check_launch("make_bf16_tiles_kernel");
+}
+
+// test hook: the band of every query (eps2 = 2e), from the launch the search itself opens with; the set-up kernel's
+// scratch state (tau + buckets, fallback counters, status words) lands in the caller's scratch
+size_t sskd_index_screen_band_scratch_bytes(int nq) {
+  if (nq <= 0) return 0;
+  sskd::Carver c(nullptr);
+  c.take<int>((size_t)nq * 11);
+  c.take<int>(64);
+  c.take<int>(2);
+  return c.bytes();
+}
+
+int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_eps2_out,
+                           void* d_scratch, size_t scratch_bytes, void* stream) {
+  SSKD_REQUIRE(n_rows > 0 && nq > 0, "index_screen_band: needs rows and queries (got rows=%lld nq=%d)", (long long)n_rows, nq);
+  int rc = require_shard_rows("index_screen_band", n_rows);
+  if (rc != SSKD_OK) return rc;
+  SSKD_REQUIRE(d_bf16 && d_queries && d_eps2_out, "index_screen_band: null pointer");
+  sskd::Carver c(d_scratch);
+  int* const tau = c.take<int>((size_t)nq * 11);
+  int* const fb_count = c.take<int>(64);
+  int* const status = c.take<int>(2);
+  if ((rc = sskd::require_workspace("index_screen_band", d_scratch, scratch_bytes, c.bytes())) != SSKD_OK) return rc;
+  const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
+  launch_screen_setup(max_norm2, d_queries, nq, d_eps2_out, tau, fb_count, status, sskd::as_stream(stream));
+  return sskd::check_launch("screen_setup_kernel");
+}
+
+int sskd_index_search_screened_plan(int64_t n_rows, int nq, int k, int* queries_per_block, int* corpus_passes,
+                                    int* n_slices) {
+  ScreenPlan pl{};
+  if (!screen_plan(n_rows, nq, k, &pl)) return sskd::fail(SSKD_ERR_UNSUPPORTED, "index_search_screened_plan: shape not served");
+  if (queries_per_block) *queries_per_block = 32 * pl.QB;
+  if (corpus_passes) *corpus_passes = pl.n_qblocks;
+  if (n_slices) *n_slices = pl.n_slices;
+  return SSKD_OK;
+}
+
+size_t sskd_index_search_screened_workspace_bytes(int64_t n_rows, int nq, int k) {
+  ScreenPlan pl{};
+  if (!screen_plan(n_rows, nq, k, &pl)) return 0;
+  return screen_carve(nullptr, pl, n_rows, nq, k).bytes;
+}
+
+int sskd_index_search_screened(const float* d_tiled, const void* d_bf16, int64_t n_rows, const float* d_queries,
+                               int nq, int k, int64_t id_offset, float* d_out_scores, int64_t* d_out_ids,
+                               int* d_status, void* d_workspace, size_t workspace_bytes, void* stream,
+                               void* ev_scan_begin, void* ev_scan_end) {
+  return sskd_index_search_screened_filtered(d_tiled, d_bf16, n_rows, d_queries, nq, k, id_offset, nullptr, d_out_scores,
+                                             d_out_ids, d_status, d_workspace, workspace_bytes, stream, ev_scan_begin,
+                                             ev_scan_end);
+}
+
+int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16, int64_t n_rows, const float* d_queries,
+                                        int nq, int k, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                                        int64_t* d_out_ids, int* d_status, void* d_workspace, size_t workspace_bytes,
+                                        void* stream, void* ev_scan_begin, void* ev_scan_end) {
+  ScreenPlan pl{};
+  if (!screen_plan(n_rows, nq, k, &pl))
+    return sskd::fail(SSKD_ERR_UNSUPPORTED,
+                      "index_search_screened: needs k <= 10, nq >= 64 and >= 2048 rows (got k=%d nq=%d rows=%lld): "
+                      "use sskd_index_search", k, nq, (long long)n_rows);
+  int rc = require_shard_rows("index_search_screened", n_rows);
+  if (rc != SSKD_OK) return rc;
+  SSKD_REQUIRE(d_tiled && d_bf16 && d_queries && d_out_scores && d_out_ids && d_status,
+               "index_search_screened: null pointer");
+  const ScreenWs w = screen_carve(d_workspace, pl, n_rows, nq, k);
+  if ((rc = sskd::require_workspace("index_search_screened", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK) return rc;
+  hipStream_t st = sskd::as_stream(stream);
+  const int64_t tiles = sskd::ceil_div(n_rows, TILE_ROWS);
+  const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
+
+  launch_screen_setup(max_norm2, d_queries, nq, w.eps2, w.tau, w.fb_count, d_status, st);
+
+  static_assert((SCREEN_CAP * sizeof(float)) % 256 == 0, "the runs span part_scores and part_ids back to back");
+  ScreenAppendParams sp{};
+  sp.tiled = static_cast<const sbf16x8*>(d_bf16);
+  sp.queries = d_queries;
+  sp.eps2 = w.eps2;
+  sp.cand = reinterpret_cast<uint2*>(w.part_scores);
+  sp.cand_cnt = w.cand_cnt;
+  sp.tau = w.tau;
+  sp.gpool = w.tau + nq;
+  sp.n_rows = n_rows;
+  sp.nq = nq;
+  sp.lists_per_query = pl.lists_per_query;
+  sp.row_mask = d_row_mask;
+  const size_t lds = (size_t)pl.QB * BSTEPS * 64 * 16 + (size_t)pl.QB * 32 * 11 * sizeof(int);
+  const void* kern = nullptr;
+  switch (pl.QB) {
+#define SSKD_SCREEN_KERN(qb, light, bg, rg)                                                                           \
+  (d_row_mask ? reinterpret_cast<const void*>(screen_append_kernel<10, qb, SCREEN_WAVES, light, bg, rg, true>)       \
+              : reinterpret_cast<const void*>(screen_append_kernel<10, qb, SCREEN_WAVES, light, bg, rg>))
+#define SSKD_SCREEN_CASE(qb, bg, rg)                                                                                  \
+  case qb:                                                                                                            \
+    kern = pl.light ? SSKD_SCREEN_KERN(qb, true, bg, rg) : SSKD_SCREEN_KERN(qb, false, bg, rg);                       \
+    break;
+    SSKD_SCREEN_CASE(2, BGROUP, SCREEN_RING)
+    SSKD_SCREEN_CASE(4, BGROUP, SCREEN_RING)
+    SSKD_SCREEN_CASE(5, BGROUP_Q5, SCREEN_RING_Q5)
+#undef SSKD_SCREEN_CASE
+#undef SSKD_SCREEN_KERN
+    default:
+      return sskd::fail(SSKD_ERR_UNSUPPORTED, "index_search_screened: no screening kernel for %d queries per workgroup", 32 * pl.QB);
+  }
+  (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (ev_scan_begin) (void)hipEventRecord(static_cast<hipEvent_t>(ev_scan_begin), st);
+  sp.n_tiles = pl.n_tiles;
+  sp.n_slices = pl.n_slices;
+  sp.tiles_per_slice = pl.tiles_per_slice;
+  sp.pre_tiles = pl.pre_tiles >= SCREEN_WAVES ? pl.pre_tiles : 0;   // sample phase: the main pass starts warm
+  sp.pre_tps = sp.pre_tiles ? pl.pre_tps : 0;
+  {
+    void* args[] = {&sp};
+    if (hipLaunchKernel(kern, dim3(pl.n_qblocks * pl.n_slices), dim3(SCREEN_WAVES * 64), args, lds, st) != hipSuccess)
+      return sskd::fail(SSKD_ERR_HIP, "index_search_screened: screening launch failed");
+  }
+  if (ev_scan_end) (void)hipEventRecord(static_cast<hipEvent_t>(ev_scan_end), st);
+  rc = sskd::check_launch("screen_append_kernel");
+  if (rc != SSKD_OK) return rc;
+
+  ScreenFinalAppendParams fp{};
+  fp.cand = sp.cand;
+  fp.cand_cnt = w.cand_cnt;
+  fp.eps2 = w.eps2;
+  fp.rows = d_tiled;
+  fp.queries = d_queries;
+  fp.lists = pl.lists_per_query;
+  fp.k = k;
+  fp.nq = nq;
+  fp.id_offset = id_offset;
+  fp.out_scores = d_out_scores;
+  fp.out_ids = d_out_ids;
+  fp.fb_count = w.fb_count;
+  fp.fb_qid = w.fb_qid;
+  fp.fb_queries = w.fb_queries;
+  const size_t fin_lds = ((size_t)2 * SCREEN_FIN_ENTRIES + DIM + SCREEN_MAX_CAND) * sizeof(float);
+  hipLaunchKernelGGL(screen_finalize_append_kernel, dim3(nq), dim3(64), fin_lds, st, fp);
+  if ((rc = sskd::check_launch("screen_finalize_append_kernel")) != SSKD_OK) return rc;
+
+  // exact scan for the queries whose candidate band could not be proven complete (usually none:
+  // every workgroup of these launches then exits on its first instruction)
+  const int tier1 = nq < SCREEN_FALLBACK_TIER1 ? nq : SCREEN_FALLBACK_TIER1;
+  hipLaunchKernelGGL(screen_fallback_tiers_kernel, dim3(1), dim3(1), 0, st, w.fb_count, tier1);
+  rc = sskd::exact_search(d_tiled, n_rows, w.fb_queries, tier1, k, id_offset, w.fb_scores, w.fb_ids,
+                            w.exact_ws, w.exact_bytes, stream, nullptr, nullptr, nullptr, w.fb_count + 1, d_row_mask);
+  if (rc != SSKD_OK) return rc;
+  if (nq > tier1) {
+    rc = sskd::exact_search(d_tiled, n_rows, w.fb_queries + (size_t)tier1 * DIM, nq - tier1, k, id_offset,
+                              w.fb_scores + (size_t)tier1 * k, w.fb_ids + (size_t)tier1 * k, w.exact_ws2, w.exact_bytes2, stream,
+                              nullptr, nullptr, nullptr, w.fb_count + 2, d_row_mask);
+    if (rc != SSKD_OK) return rc;
+  }
+  hipLaunchKernelGGL(screen_scatter_kernel, dim3(64), dim3(256), 0, st, w.fb_count, w.fb_qid, w.fb_scores, w.fb_ids, k,
+                     d_out_scores, d_out_ids, d_status);
+  if ((rc = sskd::check_launch("screen_scatter_kernel")) != SSKD_OK) return rc;
+  return SSKD_OK;
+}
+
+}  // extern "C"

@@ -14,7 +14,7 @@ Every bound comes from the number formats, not from what a kernel returned:
 (d) the kernel claims eps2 >= E (rounded up) and multiplies by 1.0002: the fp32 norms are within 385 x 2^-24 / 2 of the
     fp64 ones, so eps2 <= 1.0003 E + 2e-30 (its additive floor is 1e-30);
 (e) bf16 rounding (Cauchy-Schwarz) plus the accumulation allowance 3 x 384 x 2^-24 (1 + 2^-8)^2 |q| max(cn, cb) that
-    csrc/search.hip derives SCREEN_ACC_SLACK from must fit in eps2 / 2 together;
+    csrc/screen.hip derives SCREEN_ACC_SLACK from must fit in eps2 / 2 together;
 (f) the header's stated worst case, 2^-7 (1 + 2^-9) + 2e-4 relative to |q| max(cn, cb) on each side, 0.1 % headroom.
 """
 import numpy as np

@@ -3,7 +3,7 @@ that an fp32 evaluation in each kernel's own order stays inside the bound and th
 
 Kernels: kd_loss_rows_kernel + kd_loss_finish_kernel (csrc/kd_loss.hip), teacher_head_kernel (csrc/train.hip),
 pool_normalize_kernel (csrc/pool.hip), similarity_kernel, l2_normalize_rows_kernel, index_add_rows_kernel and the four
-row_mask kernels (csrc/search.hip).  Per kernel: ``*_inputs`` (seeded), ``*_reference`` (fp64, with ``defect=`` planting one
+row_mask kernels (csrc/index_rows.hip).  Per kernel: ``*_inputs`` (seeded), ``*_reference`` (fp64, with ``defect=`` planting one
 realistic error), ``*_bound`` (elementwise) and ``*_emulate`` (fp32 numpy in the kernel's order: same lane assignment,
 same butterfly and strided sums).
 

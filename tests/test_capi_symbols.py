@@ -25,6 +25,14 @@ def test_library_exports_every_declared_symbol(native_lib):
     assert sorted(_native.SIGNATURES) == declared
 
 
+def test_build_lists_every_translation_unit_once():
+    """Every csrc/*.hip is compiled and linked exactly once, and nothing is listed that does not exist."""
+    from semantic_search_kd_amd import _build
+
+    on_disk = sorted(p.name for p in _build.CSRC.glob("*.hip"))
+    assert sorted(_build.SOURCES) == on_disk
+
+
 def test_abi_version_and_pure_host_queries(native_lib):
     assert native_lib.sskd_abi_version() == 1
     assert native_lib.sskd_index_padded_rows(0) == 0

@@ -1,6 +1,6 @@
 """Build variants of the C-ABI library for same-box A/B timing: ``python tools/ab_build.py name:-DFLAG[,-DFLAG2] ...``
-writes tools/ab/lib_<name>.so (one source - AB_SOURCE, default encoder.hip - compiled with the extra
-flags, the other objects shared)."""
+writes tools/ab/lib_<name>.so (one source - AB_SOURCE, default encoder.hip; screen.hip for the SSKD_SCREEN_* switches,
+search.hip for the fp32 scan's - compiled with the extra flags, the other objects shared)."""
 import os
 import subprocess
 import sys

@@ -69,9 +69,15 @@ def entry(trace: Path, fetch: Path, write: Path, key: str, rows: int, flops: flo
             "tflops": round(flops / (avg * 1e-3) / 1e12, 1)}
 
 
-sha = hashlib.sha256((REPO / "semantic-search-kd_amd" / "csrc" / "search.hip").read_bytes()).hexdigest()[:16]
+def source_sha(name: str) -> str:
+    return hashlib.sha256((REPO / "semantic-search-kd_amd" / "csrc" / name).read_bytes()).hexdigest()[:16]
+
+
+sha = source_sha("search.hip")            # what bench.py's freshness check compares
+screen_sha = source_sha("screen.hip")     # the screening kernel's own source (bench.py does not look at it)
 head = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=REPO, capture_output=True, text=True).stdout.strip()
-out = {"meta": {"note": NOTE, "search_hip_sha": sha, "from": f"tools/make_search_traffic.py@{head}"}}
+out = {"meta": {"note": NOTE, "search_hip_sha": sha, "screen_hip_sha": screen_sha,
+                "from": f"tools/make_search_traffic.py@{head}"}}
 fl = lambda rows: 2.0 * 384 * rows * 10000
 s1 = root / "screen_1m"
 if s1.exists():
@@ -91,7 +97,7 @@ if "screen_1m" in out:
     e = out["screen_1m"]
     (REPO / "profiles" / "screen_traffic.json").write_text(json.dumps({
         "kernel": "screen_append_kernel<10, 5, 12, 3, 2> (sample phase + slice phase in one launch)", "hbm_bytes_per_launch": e["hbm_bytes_per_launch"],
-        "fetch_size_kb": e["fetch_size_kb"], "write_size_kb": e["write_size_kb"], "search_hip_sha": sha, "note": NOTE,
+        "fetch_size_kb": e["fetch_size_kb"], "write_size_kb": e["write_size_kb"], "search_hip_sha": sha, "screen_hip_sha": screen_sha, "note": NOTE,
         "from": f"profiles/{ROUND}/search_traffic.json@{head}"}, indent=1))
     print("wrote profiles/screen_traffic.json")
 print(json.dumps({k: {kk: v[kk] for kk in ("kernel_ms_avg", "hbm_counter_gbs", "tflops")} for k, v in out.items() if k != "meta"}, indent=1))

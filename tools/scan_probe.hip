@@ -1,6 +1,7 @@
 // Diagnostic only: runs the scan on random unit vectors and prints slow-path statistics.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -DSSKD_PROBE -Iinclude -Isemantic-search-kd_amd/csrc \
-//         tools/scan_probe.hip semantic-search-kd_amd/csrc/capi_common.hip -o tools/scan_probe.bin
+//         tools/scan_probe.hip semantic-search-kd_amd/csrc/index_rows.hip semantic-search-kd_amd/csrc/capi_common.hip \
+//         -o tools/scan_probe.bin
 #include "../semantic-search-kd_amd/csrc/search.hip"
 
 #include <cmath>

@@ -1,6 +1,6 @@
 // Diagnostic only (round 4, for round 5): the SCORING CORE of a QUERY-STATIONARY screening kernel.
 //
-// Today (csrc/search.hip screen_append_kernel): a workgroup holds 160 queries as B fragments in LDS, every one of its 12
+// Today (csrc/screen.hip screen_append_kernel): a workgroup holds 160 queries as B fragments in LDS, every one of its 12
 // waves streams ITS OWN corpus tiles global -> registers (24 KiB per 32 rows and wave) and reads one query fragment from LDS
 // per MFMA.  60 GB from L2 per call at the bench shape; the tile loads are 1.6 ms of the 6.75 ms kernel.
 // Here: the QUERIES are stationary in registers - 12 waves x 32 queries = 384 per workgroup, 96 registers each - and the
