@@ -185,6 +185,18 @@ size_t sskd_index_screen_band_scratch_bytes(int nq);
 int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_eps2_out,
                            void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* Test hooks of the screening kernel's tile claiming (tests/test_screen_tile_claim_gpu.py).
+ * sskd_index_search_screened_plan_claims: *claims = 1 when the plan has the waves of the slice phase CLAIM their tiles
+ * in chunks from per-slice cursors, 0 when it deals every 12th tile to a wave.
+ * sskd_index_search_screened_claim is sskd_index_search_screened_filtered (d_row_mask may be NULL) with that choice
+ * as an argument: claim < 0 follows the plan, 0 deals, 1 claims whatever the geometry.  The results do not depend on
+ * it; workspace and plan queries are those of sskd_index_search_screened. */
+int sskd_index_search_screened_plan_claims(int64_t n_rows, int nq, int k, int* claims);
+int sskd_index_search_screened_claim(const float* d_tiled, const void* d_bf16, int64_t n_rows, const float* d_queries,
+                                     int nq, int k, int64_t id_offset, const uint32_t* d_row_mask, int claim,
+                                     float* d_out_scores, int64_t* d_out_ids, int* d_status, void* d_workspace,
+                                     size_t workspace_bytes, void* stream, void* ev_scan_begin, void* ev_scan_end);
+
 /* One-pass variant for the online shape (reference: src/serve/app.py:285-301, schemas.py:12-16 -
  * one query, k <= 100, rerank_top_k <= 200).  sskd_index_search serves k > SSKD_K_PASS by chained
  * corpus passes; this entry point scans the corpus ONCE with plain per-lane lists, collects the best

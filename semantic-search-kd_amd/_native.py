@@ -143,6 +143,10 @@ SIGNATURES = {
     "sskd_index_search_screened_workspace_bytes": (_sz, [_i64, _i, _i]),
     "sskd_index_search_screened_plan": (_i, [_i64, _i, _i, _ip, _ip, _ip]),
     "sskd_index_search_screened": (_i, [_vp, _vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "sskd_index_search_screened_plan_claims": (_i, [_i64, _i, _i, _ip]),
+    "sskd_index_search_screened_claim": (
+        _i, [_vp, _vp, _i64, _vp, _i, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]
+    ),
     "sskd_index_screen_band_scratch_bytes": (_sz, [_i]),
     "sskd_index_screen_band": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
     "sskd_index_search_onepass_workspace_bytes": (_sz, [_i64, _i, _i]),

@@ -183,7 +183,10 @@ constexpr float SCREEN_MIN_BAND = 0x1p-100f, SCREEN_MAX_BAND = 0x1p+100f;
 __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restrict__ queries, int nq,
                                                            const int* __restrict__ max_norm2, float* __restrict__ eps2,
                                                            int* __restrict__ tau, int* __restrict__ fb_count,
-                                                           int* __restrict__ d_status) {
+                                                           int* __restrict__ d_status, int* __restrict__ cursors,
+                                                           int n_cursors) {
+  // the tile cursors of the screening kernel (screen_tiles): zero before every launch (none: sskd_index_screen_band)
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n_cursors; i += gridDim.x * 256) cursors[i] = 0;
   if (threadIdx.x < 44) {   // this block's 4 queries x 11 words
     const int64_t i = (int64_t)blockIdx.x * 44 + threadIdx.x;
     if (i < (int64_t)nq * 11) tau[i] = (int)0x80000000;
@@ -356,6 +359,27 @@ constexpr int SCREEN_PRE_TILES = SSKD_SCREEN_PRE_TILES;   // rows / 32 of the bo
 constexpr int SCREEN_FIN_ENTRIES = SSKD_SCREEN_FIN_ENTRIES;
 static_assert(SCREEN_FIN_ENTRIES >= 640, "the streaming path of the finalize kernel parks 64 x 10 scores in the stage");
 
+// Tiles of the slice phase are CLAIMED, not dealt: a wave takes SCREEN_CLAIM_TILES consecutive tiles at a time with one
+// returning atomicAdd on the cursor of (query block, slice).  Measured at 4 / 8 / 16: profiles/r06/README.md.
+#ifndef SSKD_SCREEN_CLAIM_TILES
+#define SSKD_SCREEN_CLAIM_TILES 8
+#endif
+constexpr int SCREEN_CLAIM_TILES = SSKD_SCREEN_CLAIM_TILES;
+// where screen_plan claims: slices of at least MIN_CHUNKS chunks per wave, launches of at least MIN_QBLOCKS query blocks
+#ifndef SSKD_SCREEN_CLAIM_MIN_CHUNKS
+#define SSKD_SCREEN_CLAIM_MIN_CHUNKS 2
+#endif
+#ifndef SSKD_SCREEN_CLAIM_MIN_QBLOCKS
+#define SSKD_SCREEN_CLAIM_MIN_QBLOCKS 32
+#endif
+constexpr int SCREEN_CLAIM_MIN_CHUNKS = SSKD_SCREEN_CLAIM_MIN_CHUNKS, SCREEN_CLAIM_MIN_QBLOCKS = SSKD_SCREEN_CLAIM_MIN_QBLOCKS;
+static_assert(SCREEN_CLAIM_TILES >= 2, "the claim for the next chunk is issued one whole tile before the chunk in hand ends");
+#ifdef SSKD_SCREEN_NO_STEAL   // A/B build: claim inside the workgroup's own slice only
+constexpr bool SCREEN_STEAL = false;
+#else
+constexpr bool SCREEN_STEAL = true;
+#endif
+
 struct ScreenAppendParams {
   const sbf16x8* tiled;     // bf16 tiles
   const float* queries;     // fp32 [nq][384] (rounded to bf16 while staging)
@@ -364,6 +388,7 @@ struct ScreenAppendParams {
   int* cand_cnt;            // [nq][lists_per_query]: rows that reached the bound (> SCREEN_CAP: the run overflowed)
   int* tau;
   int* gpool;
+  int* cursors;             // [n_qblocks][n_slices], zero at launch: chunks of the slice handed out so far (screen_tiles)
   int64_t n_rows;
   int n_tiles;
   int nq;
@@ -372,7 +397,11 @@ struct ScreenAppendParams {
   int lists_per_query;
   int pre_tiles;            // the sample: the shard's first tiles, pre_tps of them per slice (0: no sample phase)
   int pre_tps;
+  int claim;                // slice phase: tiles are claimed from the cursors (screen_plan: slices long enough), not dealt
   const uint32_t* row_mask; // MASKED kernels only (as ScanParams::row_mask)
+#ifdef SSKD_SCREEN_STAMPS   // diagnostic build (tools/ab_search.py, AB_STAMPS): never in the shipped library
+  unsigned long long* stamps;   // [workgroups][WAVES][3]: s_memrealtime at entry, after the sample phase, after the tile loop
+#endif
 };
 
 // out of line: the cold path must not cost the screening loop registers
@@ -386,7 +415,21 @@ __device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* 
 }
 
 // One phase of the screening kernel: the tiles [t_begin, t_end) of this workgroup, one tile per wave at a time.
-// BOUND_ONLY: nothing is appended and nothing exchanged - one pool offer per lane and tile (the sample phase).
+// BOUND_ONLY: nothing is appended and nothing exchanged - one pool offer per lane and tile (the sample phase); wave w
+// takes tiles t_begin + w + WAVES i, as it does in a slice phase whose slices are short (p.claim == 0: screen_plan).
+// Otherwise the slice phase CLAIMS its tiles (dealt tiles let the waves of a workgroup end a quarter of the launch
+// apart: three waves share a SIMD's matrix pipe and nothing makes them progress evenly - stamps in profiles/r06,
+// DESIGN.md 3.1b).  The slice is cut into chunks of
+// CH = SCREEN_CLAIM_TILES tiles; chunk w < WAVES belongs to wave w of the slice's own workgroup, chunk WAVES + c to
+// whoever draws c from the slice's cursor (one returning atomicAdd of lane 0, agent scope; the set-up kernel zeroed
+// it).  A chunk at or past the slice's end means the slice is exhausted: the wave then draws from the sibling slices
+// of its query block (slice + 1, ... cyclically) until each is exhausted, and ends.  Nobody waits for anybody: no
+// spins, no barriers, an exhausted cursor is only ever incremented (by at most one draw per wave of the query block).
+// The draw for the next chunk is issued at the head of the SECOND-TO-LAST tile of the chunk in hand and read (one
+// readfirstlane) at the head of its last tile - a whole tile, ~10 us, later - so the prefetch ring always knows the
+// next tile's address; only a chunk that the slice's end cut down to one tile, and the hop to a sibling, draw and read
+// on the spot.  Every tile is still processed exactly once per query block, by a workgroup that appends to its OWN runs
+// (my_list); the pool invariant (distinct rows) is kept by the caller.
 // MASKED: the row allow-mask (tile_mask_word).  Why the proof survives it: a masked row scores -inf right after the MFMAs,
 // and gthr starts at -FLT_MAX, so it never passes "x >= gthr" (no append), and every pool offer is either a row that passed
 // that test or the lane's best row m of a tile only when m >= gthr (the sample phase, LIGHT) or when some row was taken
@@ -396,7 +439,8 @@ __device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* 
 // k allowed rows no pool ever fills, nothing is pruned, and the finalize kernel takes every appended row (tau = -inf).
 // The in-call exact fallback scans with the same mask.
 template <int K, int QB, int WAVES, bool BOUND_ONLY, bool LIGHT, int BG, int RG, bool MASKED = false>
-__device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_begin, int t_end, int wave, int j, int h, int q0,
+__device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_begin, int t_end, int slice, int* cursors,
+                                             int wave, int j, int h, int q0,
                                              const sbf16x8* __restrict__ qlane,
                                              int* __restrict__ pool, int* __restrict__ wthr, uint2* run0, int64_t run_stride,
                                              bool ragged, float (&gthr)[QB], const float (&band)[QB], int (&cnt)[QB]) {
@@ -414,14 +458,70 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
   // a compare per use instead of QB flags held across the MFMA burst
   int n_real = p.nq - q0 - j;
   asm volatile("" : "+v"(n_real));
-  int t = t_begin + wave;
-  if (t < t_end) {
+  constexpr int CH = SCREEN_CLAIM_TILES;
+  // all wave-uniform (scalar registers) but `drawn`: the tile in hand (-1: none), the end of its chunk, the slice drawn
+  // from [s_begin, s_end) and the siblings not yet tried, the draw in flight (lane 0) and whether there is one
+  int t, next_t, c_end = 0, next_end = 0, sl = slice, s_begin = t_begin, s_end = t_end, left = p.n_slices - 1, drawn = 0;
+  bool in_flight = false;
+  const auto draw = [&]() {
+    drawn = 0;
+    // The cursor's index goes through a vector register the optimiser cannot see into: on a wave-uniform address
+    // LLVM's atomic optimiser rewrites the add into "one lane adds the popcount, readfirstlane, add the lane's rank",
+    // and that readfirstlane waits for the atomic (vmcnt(0)) right here instead of a tile later.  (The index, not the
+    // pointer: a laundered pointer loses its address space, and a FLAT atomic in flight turns every counted wait of
+    // the ring into vmcnt(0).)
+    int at = sl;
+    asm volatile("" : "+v"(at));
+    if (j + 32 * h == 0) drawn = __hip_atomic_fetch_add(cursors + at, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    in_flight = true;
+  };
+  // first tile of the chunk drawn (its end: next_end), or -1 when the query block has no tile left for this wave
+  const auto drawn_chunk = [&]() -> int {
+    for (;;) {
+      if (!in_flight) draw();
+      in_flight = false;
+      const int c = __builtin_amdgcn_readfirstlane(drawn);
+      // (c <= tiles / CH + one draw per wave of the query block, and a shard holds < 2^26 tiles: no overflow)
+      const int nt = s_begin + (c + WAVES) * CH;
+      if (nt < s_end) {
+        next_end = min(nt + CH, s_end);
+        return nt;
+      }
+      if (!SCREEN_STEAL || left == 0) return -1;
+      --left;
+      sl = sl + 1 == p.n_slices ? 0 : sl + 1;
+      s_begin = sl * p.tiles_per_slice;
+      s_end = min(s_begin + p.tiles_per_slice, p.n_tiles);
+    }
+  };
+  const bool dealt = BOUND_ONLY || !p.claim;   // wave w takes tiles t_begin + w + WAVES i
+  if (dealt) {
+    t = t_begin + wave < t_end ? t_begin + wave : -1;
+  } else {
+    t = t_begin + wave * CH;
+    c_end = min(t + CH, t_end);
+    if (t >= t_end) {   // a slice of fewer chunks than waves
+      t = drawn_chunk();
+      c_end = next_end;
+    }
+  }
+  if (t >= 0) {
 #pragma unroll
     for (int g = 0; g + 1 < RG; ++g) load_bgroup<BG>(buf[g], p.tiled + (int64_t)t * BTILE_VEC + g * BG * 64, lane_off);
   }
 
-  int tiles_done = 0;
-  for (; t < t_end; t += WAVES, ++tiles_done) {
+  for (int tiles_done = 0; t >= 0; t = next_t, ++tiles_done) {
+    if (dealt) {
+      next_t = t + WAVES < t_end ? t + WAVES : -1;
+    } else {
+      const int rem = c_end - t;   // tiles of the chunk still to compute, this one included
+      if (rem == 2) draw();        // ahead of this tile's loads: it returns (in order) before the ring's next group is due
+      next_t = t + 1;
+      if (rem == 1) {
+        next_t = drawn_chunk();
+        c_end = next_end;
+      }
+    }
     const sbf16x8* tile = p.tiled + (int64_t)t * BTILE_VEC;   // wave-uniform
     uint32_t mword = 0xFFFFFFFFu;
     if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
@@ -443,8 +543,9 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
 
-    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tile, qbase, qfrag, acc, t + WAVES < t_end,
-                                                             (int64_t)WAVES * BTILE_VEC, lane_off);
+    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tile, qbase, qfrag, acc, next_t >= 0,
+                                                             BOUND_ONLY ? (int64_t)WAVES * BTILE_VEC
+                                                                        : (int64_t)(next_t - t) * BTILE_VEC, lane_off);
 
     const int rowbase = t * TILE_ROWS + 4 * h;
     if (ragged && (int64_t)(t + 1) * TILE_ROWS > p.n_rows) {
@@ -475,8 +576,13 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 #pragma unroll
           for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
           const int xi = float_to_ordered(m);
-          if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi))
-            bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
+          if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi)) {
+            // (the bucket address is formed here, on the rare path: hoisted out of the tile loop, the QB 64-bit
+            // addresses were spilled in the 160-query kernels)
+            int qa = q0 + qq * 32 + j;
+            asm volatile("" : "+v"(qa));
+            bucket_forward<K>(p.gpool, qa, xid, xi);
+          }
           gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
         }
       } else
@@ -557,6 +663,10 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   const int slice = logical / n_qblocks;
   const int qblk = logical % n_qblocks;
   const int q0 = qblk * (32 * QB);
+#ifdef SSKD_SCREEN_STAMPS
+  unsigned long long* const stamp = p.stamps + ((int64_t)blockIdx.x * WAVES + wave) * 3;
+  if (lane == 0) stamp[0] = __builtin_amdgcn_s_memrealtime();
+#endif
 
   for (int idx = tid; idx < QB * BSTEPS * 64; idx += WAVES * 64) {
     const int l = idx & 63, sidx = (idx >> 6) % BSTEPS, qq = idx / (64 * BSTEPS);
@@ -608,7 +718,7 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   if (p.pre_tps > 0) {
     const int s_begin = slice * p.pre_tps;
     const int s_end = min(s_begin + p.pre_tps, p.pre_tiles);
-    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, wave, j, h, q0, qlane,
+    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, slice, nullptr, wave, j, h, q0, qlane,
                                              pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
     // what this workgroup learned from its share of the sample; everybody's offers are in before phase 1
 #pragma unroll
@@ -622,18 +732,31 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
     // would be pruned silently (round 3 shipped that hole: VERDICT r3 weak 1).  So such a workgroup empties its slots
     // here.  wthr stays: it is the minimum of a full pool of distinct SAMPLE rows, a valid bound on its own, and only
     // ever rises to minima of full pools, which from here on hold phase-1 rows only.  Rows of other slices' sample
-    // shares never return in this workgroup's slice, so its pool keeps them.
-    if (s_begin < t_end && t_begin < s_end) {
+    // shares never return in this workgroup's slice - but a wave that has run out of tiles there goes on to draw from
+    // the sibling slices (screen_tiles), the sample's among them, so EVERY workgroup of a launch that claims its
+    // tiles empties its slots; where tiles are dealt (short slices, or a build without stealing) the workgroups whose
+    // share lies outside their slice keep their pools.
+    if ((SCREEN_STEAL && p.claim) || (s_begin < t_end && t_begin < s_end)) {
       for (int i = tid; i < QB * 32 * K; i += WAVES * 64) pool[i] = (int)0x80000000;
       __syncthreads();
     }
   }
-  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, wave, j, h, q0,
-                                            qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
+#ifdef SSKD_SCREEN_STAMPS
+  if (lane == 0) stamp[1] = __builtin_amdgcn_s_memrealtime();
+#endif
+  screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, slice, p.cursors + (int64_t)qblk * p.n_slices,
+                                            wave, j, h, q0, qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
+#ifdef SSKD_SCREEN_STAMPS
+  if (lane == 0) stamp[2] = __builtin_amdgcn_s_memrealtime();
+#endif
 
+  // (the query numbers and "real" tests are formed again here from a lane number the optimiser cannot follow: kept
+  // from the kernel's head they were five registers and five exec masks alive - and spilled - across both tile loops)
+  int jt = j;
+  asm volatile("" : "+v"(jt));
 #pragma unroll
   for (int qq = 0; qq < QB; ++qq) {
-    const int q = q0 + qq * 32 + j;
+    const int q = q0 + qq * 32 + jt;
     if (q < p.nq) p.cand_cnt[(int64_t)q * p.lists_per_query + my_list] = cnt[qq];
   }
 }
@@ -901,6 +1024,7 @@ struct ScreenPlan {
   int QB, LK, n_qblocks, n_slices, tiles_per_slice, n_tiles, lists_per_query;
   int pre_tiles, pre_slices, pre_tps;   // the bound-only sample phase over the first rows
   bool light;                           // short slices: one pool offer per lane and tile (screen_tiles<LIGHT>)
+  bool claim;                           // waves claim the slice's tiles in chunks (screen_tiles) instead of every WAVES-th
   size_t part_elems;
 };
 
@@ -953,6 +1077,16 @@ bool screen_plan(int64_t n_rows, int nq, int k, ScreenPlan* sp) {
   // by slice length, not shard size: 1 000 queries cut 1 M rows into 32 slices of 81 tiles per wave (-7 % in the light
   // form), 10 000 queries into 4 of 651 (+1 %)
   pl.light = pl.tiles_per_slice <= SCREEN_LIGHT_MAX_TILES_PER_WAVE * SCREEN_WAVES;
+  // Claimed chunks even out the waves' finish times (a quarter of the launch apart at 651 tiles per wave: profiles/r06)
+  // at the price of whole chunks: a slice of T tiles ends after CH x ceil(T / (WAVES x CH)) tiles of its slowest wave
+  // instead of ceil(T / WAVES).  Both thresholds below are SET, not derived, from the few shapes that were timed
+  // (profiles/r06/README.md, "The gates"): 64-tile slices run 0.225 ms claimed against 0.156 dealt, and two chunks per
+  // wave is simply the least at which most draws can be issued ahead; a launch of 8 query blocks lost 3 % claimed, one
+  // of 16 GAINED 3 %, those of 63 and more 4-9 %, so 32 is on the safe side and leaves the 16-block gain unused.  What
+  // the 8-block launch loses was not isolated.
+  // -DSSKD_SCREEN_CLAIM_MIN_CHUNKS / _MIN_QBLOCKS move them for an A/B (tools/ab_build.py).
+  pl.claim = pl.tiles_per_slice >= SCREEN_CLAIM_MIN_CHUNKS * SCREEN_WAVES * SCREEN_CLAIM_TILES &&
+             pl.n_qblocks >= SCREEN_CLAIM_MIN_QBLOCKS;
   pl.pre_tiles = std::min(SCREEN_PRE_TILES, pl.n_tiles / 8);
   pl.pre_slices = pl.n_slices;
   pl.pre_tps = (int)sskd::ceil_div(pl.pre_tiles, pl.n_slices);
@@ -967,6 +1101,7 @@ struct ScreenWs {
   int* tau;          // [nq] + gpool [nq * 10]
   float* eps2;
   int* fb_count;     // [2]: count, spare
+  int* cursors;      // [n_qblocks][n_slices]: tile cursors of the screening kernel
   int* fb_qid;
   float* fb_queries;
   float* fb_scores;
@@ -975,6 +1110,9 @@ struct ScreenWs {
   size_t exact_bytes;
   void* exact_ws2;     // tier 2 (the rest; absent when nq <= SCREEN_FALLBACK_TIER1)
   size_t exact_bytes2;
+#ifdef SSKD_SCREEN_STAMPS
+  unsigned long long* stamps;   // the LAST 3 x 8 bytes x waves x workgroups of the workspace (256-byte rounding aside)
+#endif
   size_t bytes;
 };
 
@@ -987,6 +1125,7 @@ ScreenWs screen_carve(void* base, const ScreenPlan& pl, int64_t n_rows, int nq, 
   w.tau = c.take<int>((size_t)nq * 11);
   w.eps2 = c.take<float>(nq);
   w.fb_count = c.take<int>(64);
+  w.cursors = c.take<int>((size_t)pl.n_qblocks * pl.n_slices);
   // the in-call exact fallback is sized for EVERY query: however many candidate bands cannot be proven
   // complete, the call answers them itself (its launches read the actual count from device memory)
   w.fb_qid = c.take<int>(nq);
@@ -998,6 +1137,9 @@ ScreenWs screen_carve(void* base, const ScreenPlan& pl, int64_t n_rows, int nq, 
   w.exact_ws = c.take<char>(w.exact_bytes);
   w.exact_bytes2 = nq > tier1 ? sskd::exact_workspace_bytes(n_rows, nq - tier1, k) : 0;
   w.exact_ws2 = w.exact_bytes2 ? c.take<char>(w.exact_bytes2) : nullptr;
+#ifdef SSKD_SCREEN_STAMPS
+  w.stamps = c.take<unsigned long long>((size_t)pl.n_qblocks * pl.n_slices * SCREEN_WAVES * 3);
+#endif
   w.bytes = c.bytes();
   return w;
 }
@@ -1009,9 +1151,9 @@ static inline size_t sidecar_rows_offset(int64_t n_rows) { return sidecar_norm_o
 
 // the one launch of screen_setup_kernel: the search's first launch, and all that sskd_index_screen_band does
 static inline void launch_screen_setup(const int* max_norm2, const float* d_queries, int nq, float* eps2, int* tau,
-                                       int* fb_count, int* d_status, hipStream_t st) {
+                                       int* fb_count, int* d_status, int* cursors, int n_cursors, hipStream_t st) {
   hipLaunchKernelGGL(screen_setup_kernel, dim3((unsigned)sskd::ceil_div(nq, 4)), dim3(256), 0, st, d_queries, nq, max_norm2,
-                     eps2, tau, fb_count, d_status);
+                     eps2, tau, fb_count, d_status, cursors, n_cursors);
 }
 
 size_t sskd_index_bf16_bytes(int64_t n_rows) {
@@ -1059,7 +1201,7 @@ int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_qu
   int* const status = c.take<int>(2);
   if ((rc = sskd::require_workspace("index_screen_band", d_scratch, scratch_bytes, c.bytes())) != SSKD_OK) return rc;
   const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
-  launch_screen_setup(max_norm2, d_queries, nq, d_eps2_out, tau, fb_count, status, sskd::as_stream(stream));
+  launch_screen_setup(max_norm2, d_queries, nq, d_eps2_out, tau, fb_count, status, nullptr, 0, sskd::as_stream(stream));
   return sskd::check_launch("screen_setup_kernel");
 }
 
@@ -1092,6 +1234,23 @@ int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16
                                         int nq, int k, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
                                         int64_t* d_out_ids, int* d_status, void* d_workspace, size_t workspace_bytes,
                                         void* stream, void* ev_scan_begin, void* ev_scan_end) {
+  return sskd_index_search_screened_claim(d_tiled, d_bf16, n_rows, d_queries, nq, k, id_offset, d_row_mask, -1, d_out_scores,
+                                          d_out_ids, d_status, d_workspace, workspace_bytes, stream, ev_scan_begin, ev_scan_end);
+}
+
+int sskd_index_search_screened_plan_claims(int64_t n_rows, int nq, int k, int* claims) {
+  ScreenPlan pl{};
+  if (!screen_plan(n_rows, nq, k, &pl)) return sskd::fail(SSKD_ERR_UNSUPPORTED, "index_search_screened_plan_claims: shape not served");
+  if (claims) *claims = pl.claim ? 1 : 0;
+  return SSKD_OK;
+}
+
+// test hook (and the whole of the screened search): claim < 0 leaves the tiles of the slice phase to the plan, 0 deals
+// them, 1 has them claimed whatever the geometry
+int sskd_index_search_screened_claim(const float* d_tiled, const void* d_bf16, int64_t n_rows, const float* d_queries,
+                                     int nq, int k, int64_t id_offset, const uint32_t* d_row_mask, int claim,
+                                     float* d_out_scores, int64_t* d_out_ids, int* d_status, void* d_workspace,
+                                     size_t workspace_bytes, void* stream, void* ev_scan_begin, void* ev_scan_end) {
   ScreenPlan pl{};
   if (!screen_plan(n_rows, nq, k, &pl))
     return sskd::fail(SSKD_ERR_UNSUPPORTED,
@@ -1101,13 +1260,14 @@ int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16
   if (rc != SSKD_OK) return rc;
   SSKD_REQUIRE(d_tiled && d_bf16 && d_queries && d_out_scores && d_out_ids && d_status,
                "index_search_screened: null pointer");
+  if (claim >= 0) pl.claim = claim != 0;
   const ScreenWs w = screen_carve(d_workspace, pl, n_rows, nq, k);
   if ((rc = sskd::require_workspace("index_search_screened", d_workspace, workspace_bytes, w.bytes)) != SSKD_OK) return rc;
   hipStream_t st = sskd::as_stream(stream);
   const int64_t tiles = sskd::ceil_div(n_rows, TILE_ROWS);
   const int* max_norm2 = reinterpret_cast<const int*>(static_cast<const char*>(d_bf16) + sidecar_norm_offset(n_rows));
 
-  launch_screen_setup(max_norm2, d_queries, nq, w.eps2, w.tau, w.fb_count, d_status, st);
+  launch_screen_setup(max_norm2, d_queries, nq, w.eps2, w.tau, w.fb_count, d_status, w.cursors, pl.n_qblocks * pl.n_slices, st);
 
   static_assert((SCREEN_CAP * sizeof(float)) % 256 == 0, "the runs span part_scores and part_ids back to back");
   ScreenAppendParams sp{};
@@ -1118,10 +1278,15 @@ int sskd_index_search_screened_filtered(const float* d_tiled, const void* d_bf16
   sp.cand_cnt = w.cand_cnt;
   sp.tau = w.tau;
   sp.gpool = w.tau + nq;
+  sp.cursors = w.cursors;
   sp.n_rows = n_rows;
   sp.nq = nq;
   sp.lists_per_query = pl.lists_per_query;
+  sp.claim = pl.claim ? 1 : 0;
   sp.row_mask = d_row_mask;
+#ifdef SSKD_SCREEN_STAMPS
+  sp.stamps = w.stamps;
+#endif
   const size_t lds = (size_t)pl.QB * BSTEPS * 64 * 16 + (size_t)pl.QB * 32 * 11 * sizeof(int);
   const void* kern = nullptr;
   switch (pl.QB) {
