@@ -416,6 +416,53 @@ int sskd_bm25_search(const int64_t* d_term_offsets, const int32_t* d_post_rows, 
                      const int32_t* d_q_terms, int nq, int k, double* d_out_scores, int64_t* d_out_ids,
                      void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Hybrid fusion: one dense ranking and one BM25 ranking per query joined into one (rrf / linear)
+ *   reference: the hybrid block of configs/service.yaml:43-49 (bm25_weight, semantic_weight, fusion_method "rrf" |
+ *   "linear"); the reference has no code behind those keys, so the rule below is this library's definition.
+ * Inputs per query q: the dense ranking d_dense_scores fp32 / d_dense_ids int64 [nq, kd] as the searches above write it
+ * with id_offset 0 (LOCAL rows, score descending then lower row, padded with id -1), and the BM25 ranking
+ * d_bm25_scores fp64 / d_bm25_ids int64 [nq, kb] as sskd_bm25_search writes it (padded with (-inf, -1)).  Both number
+ * the same rows 0 .. n_rows - 1, and a list holds a row at most once.
+ *   - candidates: a dense entry unless its id is -1 or outside [0, n_rows); a BM25 entry unless its id is -1 or outside
+ *     [0, n_rows), its score is exactly +0.0 or -0.0 (the row matched no query word: sskd_bm25_search returns such rows
+ *     only to fill k), or d_mask (DEVICE allow-mask words as in "Row filters", NULL = off) clears its row.  Each walk
+ *     stops at the first id -1.  Ranks are the 1-based positions among the surviving entries of each list, so a mask
+ *     gives the ranks a BM25 search over the allowed rows alone would give.  The dense side is expected to have been
+ *     searched under the same mask.
+ *   - the union holds one entry per distinct row (at most kd + kb <= 512).
+ *   - method 0, rrf: fused = w_semantic * (1.0 / (rrf_k + rank_s)) + w_bm25 * (1.0 / (rrf_k + rank_b)); a side the row
+ *     is absent from contributes exactly +0.0.
+ *   - method 1, linear: first every union row gets both scores.  A row the dense list lacks is scored against
+ *     d_queries[q] (the PREPARED query: normalised when the metric is cosine, the tensor the search used) with the fp32
+ *     fma chain of the exact scan - the bits a search returns for that row, as in sskd_index_mine_select.  A row the
+ *     BM25 list lacks is scored as sskd_bm25_search scores it: over d_q_terms[d_q_lims[q] .. d_q_lims[q + 1]) in query
+ *     order, repeats included, from +0.0, adding idf[t] * w(t, row) for every token whose posting list holds the row
+ *     (product rounded, then the sum; a term id outside [0, n_terms) is skipped; the lists ascend by row, so the lookup
+ *     is a binary search per (token, row)).  Then ns = (s - s_min) / (s_max - s_min) over the union, s widened to fp64,
+ *     ns = 0.0 for every row when s_max == s_min; nb likewise over the BM25 scores; fused = w_semantic * ns +
+ *     w_bm25 * nb.  (Where +0.0 and -0.0 both occur, -0.0 is the minimum and +0.0 the maximum.)
+ *   - all fusion arithmetic is fp64; every division, product and sum is rounded once (no fma).
+ *   - output: the best k of the union under (fused descending, row ascending) to d_out_scores fp64 / d_out_ids int64
+ *     [nq, k] (row + id_offset), the tail padded with (-inf, -1); d_out_counts int32 [nq] = the union's size before the
+ *     cut.  Optional per-result components d_out_dense fp32 / d_out_bm25 fp64 [nq, k] (either may be NULL): the row's
+ *     dense and BM25 score; under rrf a side the row was absent from is a quiet NaN, linear always has both; the
+ *     padded tail is NaN.
+ * Queries, scores and index tables are finite: the call does not check that (it never synchronises).
+ * One workgroup of 256 threads per query, the union in LDS.  Limits: 1 <= kd, kb <= SSKD_K_MAX with kd + kb <= 512;
+ * 1 <= k <= kd + kb; rrf_k > 0; both weights finite and >= 0; method 0 or 1; n_rows < 2^31 - 64.  Under rrf nothing is
+ * completed and the index-side pointers (d_tiled, d_queries, the postings, d_idf, d_q_lims, d_q_terms) may be NULL;
+ * under linear they are required, d_tiled and d_queries 16-byte aligned.  Stream-ordered, no host sync, no workspace,
+ * allocates nothing; arguments are checked before the launch (SSKD_ERR_INVALID); nq = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_hybrid_fuse(const float* d_tiled, int64_t n_rows, const float* d_queries, const float* d_dense_scores,
+                     const int64_t* d_dense_ids, int kd, const int64_t* d_term_offsets, const int32_t* d_post_rows,
+                     const double* d_post_w, const double* d_idf, int64_t n_terms, const int64_t* d_q_lims,
+                     const int32_t* d_q_terms, const double* d_bm25_scores, const int64_t* d_bm25_ids, int kb,
+                     const uint32_t* d_mask, int method, double w_semantic, double w_bm25, double rrf_k, int nq, int k,
+                     int64_t id_offset, double* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
+                     float* d_out_dense, double* d_out_bm25, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

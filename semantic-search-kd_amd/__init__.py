@@ -14,6 +14,7 @@ from .encoder import Mi355xSentenceEncoder, build_wordpiece_tokenizer  # noqa: F
 from .student import StudentModel  # noqa: F401
 from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELoss  # noqa: F401
 from .bm25 import BM25Index, build_bm25_index  # noqa: F401
+from .hybrid import HybridIndex  # noqa: F401
 from .mining import ANCEMiner, BM25Miner, TeacherMiner, build_mining_curriculum  # noqa: F401
 from .teacher import TeacherConfig, TeacherModel  # noqa: F401
 from .bench_support import bench_encode  # noqa: F401
@@ -25,6 +26,7 @@ __all__ = [
     "BM25Index",
     "BM25Miner",
     "build_bm25_index",
+    "HybridIndex",
     "build_mining_curriculum",
     "TeacherMiner",
     "TeacherConfig",

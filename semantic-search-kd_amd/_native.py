@@ -180,6 +180,10 @@ SIGNATURES = {
     "sskd_bm25_search_workspace_bytes": (_sz, [_i64, _i, _i]),
     "sskd_bm25_search_plan": (_i, [_i64, _i, _i, _ip, _ip, _ip]),
     "sskd_bm25_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sskd_hybrid_fuse": (
+        _i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i, C.c_double,
+             C.c_double, C.c_double, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

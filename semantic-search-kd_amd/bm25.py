@@ -220,31 +220,48 @@ class BM25Index:
                                    up(post.post_w, np.float64), up(post.idf, np.float64))
         return self._device_tables
 
-    def search_device(self, queries: Sequence[str], top_k: int = 100, max_workspace_bytes: Optional[int] = None):
-        """``(D float64 [nq, top_k], I int64 [nq, top_k])`` device tensors: rows of the corpus, best first (score
-        descending, then lower row), padded with ``(-inf, -1)`` when ``top_k`` exceeds the corpus.  One device call;
-        ``max_workspace_bytes`` caps its scratch buffer (never below what one query needs): the call then works
-        through the queries in chunks that fit, with the same result."""
+    def query_csr(self, queries: Sequence[str]):
+        """The queries' term ids as the device CSR the kernels read: ``(lims int64 [nq + 1], terms int32)`` device
+        tensors, tokens in query order, repeats kept, out-of-vocabulary tokens dropped.  Made once per batch and shared
+        by every call that scores it (``search_device``, ``HybridIndex``)."""
         import torch
 
         post = self._require_built()
-        top_k = int(top_k)
-        if not 1 <= top_k <= K_MAX:
-            raise ValueError(f"top_k={top_k} outside [1, {K_MAX}]")
-        dev, offsets, rows, w, idf = self._tables()
-        lib = _native.load()
+        dev = self._tables()[0]
         nq = len(queries)
-        scores = torch.empty((nq, top_k), dtype=torch.float64, device=dev)
-        ids = torch.empty((nq, top_k), dtype=torch.int64, device=dev)
-        if nq == 0:
-            return scores, ids
         q_ids = [post.term_ids(self._tokenize(q)) for q in queries]
         lims = np.zeros(nq + 1, dtype=np.int64)
         np.cumsum(np.fromiter(map(len, q_ids), dtype=np.int64, count=nq), out=lims[1:])
         flat = np.fromiter(chain.from_iterable(q_ids), dtype=np.int32, count=int(lims[-1]))
         if flat.size == 0:
             flat = np.zeros(1, dtype=np.int32)
-        d_lims, d_terms = torch.from_numpy(lims).to(dev), torch.from_numpy(flat).to(dev)
+        return torch.from_numpy(lims).to(dev), torch.from_numpy(flat).to(dev)
+
+    def search_device(self, queries: Sequence[str], top_k: int = 100, max_workspace_bytes: Optional[int] = None):
+        """``(D float64 [nq, top_k], I int64 [nq, top_k])`` device tensors: rows of the corpus, best first (score
+        descending, then lower row), padded with ``(-inf, -1)`` when ``top_k`` exceeds the corpus.  One device call;
+        ``max_workspace_bytes`` caps its scratch buffer (never below what one query needs): the call then works
+        through the queries in chunks that fit, with the same result."""
+        self._require_built()
+        top_k = int(top_k)
+        if not 1 <= top_k <= K_MAX:
+            raise ValueError(f"top_k={top_k} outside [1, {K_MAX}]")
+        nq = len(queries)
+        csr = self.query_csr(queries) if nq else None
+        return self._search_csr(csr, nq, top_k, max_workspace_bytes)
+
+    def _search_csr(self, csr, nq: int, top_k: int, max_workspace_bytes: Optional[int] = None):
+        """``search_device`` for queries already tokenised by ``query_csr`` (``csr`` is not read when ``nq`` is 0)."""
+        import torch
+
+        post = self._require_built()
+        dev, offsets, rows, w, idf = self._tables()
+        lib = _native.load()
+        scores = torch.empty((nq, top_k), dtype=torch.float64, device=dev)
+        ids = torch.empty((nq, top_k), dtype=torch.int64, device=dev)
+        if nq == 0:
+            return scores, ids
+        d_lims, d_terms = csr
         need = int(lib.sskd_bm25_search_workspace_bytes(post.corpus_size, nq, top_k))
         if max_workspace_bytes is not None:
             one_query = int(lib.sskd_bm25_search_workspace_bytes(post.corpus_size, 1, top_k))

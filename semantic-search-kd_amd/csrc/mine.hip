@@ -67,16 +67,7 @@ __global__ __launch_bounds__(MINE_WAVES * 64) void mine_select_kernel(MineParams
     const bool valid = row >= 0 && row < p.n_rows;
     if (valid) {
       const float4* src = reinterpret_cast<const float4*>(p.rows) + row * CHUNKS;
-      float acc = 0.f;
-#pragma unroll 16
-      for (int u = 0; u < STEPS; ++u) {
-        const float4 a = src[2 * u], c = src[2 * u + 1];
-        const float4 qa = *reinterpret_cast<const float4*>(&qv[8 * u]), qc = *reinterpret_cast<const float4*>(&qv[8 * u + 4]);
-        acc = fmaf(a.x, qa.x, acc); acc = fmaf(c.x, qc.x, acc);
-        acc = fmaf(a.y, qa.y, acc); acc = fmaf(c.y, qc.y, acc);
-        acc = fmaf(a.z, qa.z, acc); acc = fmaf(c.z, qc.z, acc);
-        acc = fmaf(a.w, qa.w, acc); acc = fmaf(c.w, qc.w, acc);
-      }
+      const float acc = row_score_fma(src, qv);
       if (acc != acc) any_nan = true;
       best = fmaxf(best, acc);
     }

@@ -1,5 +1,5 @@
 // Index layout and the device helpers that more than one search translation unit uses (internal: not installed).
-// Included by search.hip, index_rows.hip, screen.hip, range.hip and mine.hip; what only one of them uses stays there.
+// Included by search.hip, index_rows.hip, screen.hip, range.hip, mine.hip and hybrid.hip; what only one of them uses stays there.
 #pragma once
 #include "common.h"
 
@@ -28,6 +28,24 @@ constexpr int STEP_FLOATS = 8;                // a k-step = the next 8 columns o
 __host__ __device__ inline int tile_idx4(int r, int c) { return r * (DIM / 4) + c; }
 // D layout of both 32x32 MFMAs: accumulator register r of lane l holds column l & 31 and row acc_row(r) + 4 (l >> 5)
 __host__ __device__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
+
+// score(q, row) of the exact re-scoring: ONE fp32 accumulator from +0.0f, fma over the columns in the order 0, 4, 1, 5, 2,
+// 6, 3, 7 of every 8-column k-step - bit for bit the value a search returns for the row.  `src` = the row (96 float4),
+// `qv` = the prepared query (384 floats, 16-byte aligned; LDS in the callers).  mine.hip scores positives with it,
+// hybrid.hip the rows a ranking lacks.
+__device__ inline float row_score_fma(const float4* src, const float* qv) {
+  float acc = 0.f;
+#pragma unroll 16
+  for (int u = 0; u < STEPS; ++u) {
+    const float4 a = src[2 * u], c = src[2 * u + 1];
+    const float4 qa = *reinterpret_cast<const float4*>(&qv[8 * u]), qc = *reinterpret_cast<const float4*>(&qv[8 * u + 4]);
+    acc = fmaf(a.x, qa.x, acc); acc = fmaf(c.x, qc.x, acc);
+    acc = fmaf(a.y, qa.y, acc); acc = fmaf(c.y, qc.y, acc);
+    acc = fmaf(a.z, qa.z, acc); acc = fmaf(c.z, qc.z, acc);
+    acc = fmaf(a.w, qa.w, acc); acc = fmaf(c.w, qc.w, acc);
+  }
+  return acc;
+}
 
 // sum over the lanes of one wave
 template <typename T>

@@ -569,6 +569,12 @@ class FAISSIndexBuilder:
                                             self._mask_scratch.data_ptr(), _stream(self.device)))
         return self._mask_scratch
 
+    def search_mask(self, allow=None) -> Optional[torch.Tensor]:
+        """The device mask words a search under ``allow`` honours (``allow AND NOT removed``; None: no row is hidden),
+        for a kernel that must filter by the very mask the search used.  The tensor may be a scratch buffer that the
+        next filtered call overwrites: use it in stream order, before that call."""
+        return self._effective_mask(allow)
+
     # ------------------------------------------------------------------- search
     def search_device(
         self,

@@ -41,6 +41,13 @@ from .schemas import (
 VERSION = "1.1.0"  # API version of the reference this surface is wire-compatible with (app.py:41)
 
 
+def _env_bool(value: Optional[str], default: bool) -> bool:
+    """An environment flag as pydantic-settings reads one (the reference's loader): 1 / true / yes / on, any case."""
+    if value is None or not value.strip():
+        return default
+    return value.strip().lower() in ("1", "true", "t", "yes", "y", "on")
+
+
 @dataclass
 class ServeSettings:
     """The few settings the path reads (reference: src/config.py:22-32,223-233; env prefix
@@ -51,6 +58,13 @@ class ServeSettings:
     index_dir: Optional[str] = None
     environment: str = "development"
     extra: Dict[str, Any] = field(default_factory=dict)
+    # the ``hybrid:`` block of the reference's configs/service.yaml:43-49, names and defaults kept (the reference reads
+    # the keys and has no code behind them): /search fuses the dense ranking with a BM25 ranking (hybrid.HybridIndex)
+    hybrid_enabled: bool = False
+    bm25_index_path: str = "./artifacts/indexes/bm25"
+    bm25_weight: float = 0.3
+    semantic_weight: float = 0.7
+    fusion_method: str = "rrf"   # rrf (reciprocal rank fusion), linear
 
     @staticmethod
     def from_env() -> "ServeSettings":
@@ -60,6 +74,11 @@ class ServeSettings:
             student_device=e.get("SEMANTIC_KD_STUDENT__DEVICE", "cuda"),
             index_dir=e.get("SEMANTIC_KD_INDEX__DIR"),
             environment=e.get("SEMANTIC_KD_ENVIRONMENT", "development"),
+            hybrid_enabled=_env_bool(e.get("SEMANTIC_KD_HYBRID__ENABLED"), ServeSettings.hybrid_enabled),
+            bm25_index_path=e.get("SEMANTIC_KD_HYBRID__BM25_INDEX_PATH", ServeSettings.bm25_index_path),
+            bm25_weight=float(e.get("SEMANTIC_KD_HYBRID__BM25_WEIGHT", ServeSettings.bm25_weight)),
+            semantic_weight=float(e.get("SEMANTIC_KD_HYBRID__SEMANTIC_WEIGHT", ServeSettings.semantic_weight)),
+            fusion_method=e.get("SEMANTIC_KD_HYBRID__FUSION_METHOD", ServeSettings.fusion_method),
         )
 
     def is_production(self) -> bool:
@@ -77,6 +96,7 @@ class AppState:
         self.doc_texts: Optional[Dict[str, str]] = None
         self.settings: Optional[ServeSettings] = None
         self.ready: bool = False
+        self.hybrid = None   # hybrid.HybridIndex over index_builder when hybrid retrieval is on and its BM25 index fits
 
     def is_ready(self) -> bool:
         return self.ready and self.student is not None
@@ -97,7 +117,31 @@ def _load_index_dir(index_dir: Path) -> Dict[str, Any]:
             app_state.doc_texts = json.load(f)
     elif builder.doc_texts:
         app_state.doc_texts = builder.doc_texts
+    app_state.hybrid = _load_hybrid(builder, app_state.settings)
     return {"status": "loaded", "index_path": str(index_dir), "num_documents": len(app_state.doc_ids)}
+
+
+def _load_hybrid(builder, settings: Optional["ServeSettings"]):
+    """The ``HybridIndex`` /search retrieves through, or None (dense-only): hybrid retrieval is off, the index is
+    row-sharded (``ShardedIndex`` stays dense-only: fusing over shards needs the union across ranks), or the BM25
+    index does not load or does not describe the dense index's rows - then a warning is logged and the service answers
+    dense-only, the reference's rule for a teacher that fails to load (app.py:96-107)."""
+    if settings is None or not settings.hybrid_enabled:
+        return None
+    if not isinstance(builder, FAISSIndexBuilder):
+        logger.warning("Hybrid retrieval is enabled but the index is not a single-GPU dense index: serving dense-only")
+        return None
+    try:
+        from ..bm25 import BM25Index
+        from ..hybrid import HybridIndex
+
+        bm25 = BM25Index(settings.bm25_index_path, device=str(builder.device))
+        bm25.load()
+        return HybridIndex(builder, bm25, semantic_weight=settings.semantic_weight, bm25_weight=settings.bm25_weight,
+                           fusion_method=settings.fusion_method)
+    except Exception as exc:  # noqa: BLE001
+        logger.warning("Failed to load the BM25 index (hybrid retrieval disabled, serving dense-only): %s", exc)
+        return None
 
 
 def create_app(
@@ -182,7 +226,13 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
         try:
             query_emb = app_state.student.encode_queries([request.query])
             k_retrieve = request.rerank_top_k if request.rerank else request.k
-            distances, indices = app_state.index_builder.search(query_emb, k=k_retrieve)
+            hybrid = app_state.hybrid
+            if hybrid is not None and hybrid.dense is app_state.index_builder:
+                # both sides contribute at least k rows; the fused score is the result's score
+                depth = hybrid.clip_depth(max(hybrid.depth, k_retrieve))
+                distances, indices = hybrid.search([request.query], query_emb, k=min(k_retrieve, 2 * depth), depth=depth)
+            else:
+                distances, indices = app_state.index_builder.search(query_emb, k=k_retrieve)
             results: List[SearchResult] = []
             for rank, (dist, idx) in enumerate(zip(distances[0], indices[0]), 1):
                 if idx < 0 or (app_state.doc_ids and idx >= len(app_state.doc_ids)):
