@@ -624,6 +624,10 @@ int sskd_encoder_forward_packed(const sskd_encoder_config* cfg, const sskd_encod
  * Row-major activations; hidden <= 1024; head width, hidden, intermediate multiples of 32;
  * S a multiple of 32 (pad with mask 0).  Weights bf16 row-major [out, in]; the `_t` members are
  * the transposes [in, out] (needed by the backward pass only, may be NULL for inference).
+ * Inference (training == 0, and the teacher) runs the fused attention kernel, which serves head widths
+ * 32, 64 and 128 with S * width <= 36 864 (width 128: S <= 288); training serves every width that is a
+ * multiple of 32.  Arguments are checked before the first launch: a call that is refused (SSKD_ERR_INVALID,
+ * SSKD_ERR_WORKSPACE) has enqueued nothing, and the size queries return 0 for a shape the call rejects.
  * ------------------------------------------------------------------------- */
 typedef struct sskd_generic_config {
   int32_t vocab_size;

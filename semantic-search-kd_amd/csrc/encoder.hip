@@ -1331,7 +1331,8 @@ int check_cfg(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, int
   return SSKD_OK;
 }
 
-// runs embeddings + all layers; returns the (fragment-order) buffer holding the final hidden states
+// runs embeddings + all layers of a call that prepare() has validated; returns the (fragment-order) buffer holding the
+// final hidden states
 int run_layers(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, const int32_t* d_ids,
                const int32_t* d_mask, int B, int S, const Workspace& ws, hipStream_t st,
                __bf16** final_hidden, const int32_t* d_seg = nullptr) {
@@ -1348,9 +1349,6 @@ int run_layers(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, co
   __bf16* x = ws.xa;  // layer input; the fused MLP writes the layer output over it (row-local, in place)
   for (int li = 0; li < cfg->layers; ++li) {
     const sskd_encoder_layer_weights& lw = w->layers[li];
-    SSKD_REQUIRE(lw.wqkv && lw.bqkv && lw.wo && lw.bo && lw.ln1_g && lw.ln1_b && lw.w1 && lw.b1 &&
-                     lw.w2 && lw.b2 && lw.ln2_g && lw.ln2_b,
-                 "encoder: layer %d has a null weight pointer", li);
     QkvAttnParams qa{};
     qa.x = reinterpret_cast<const bf16x8*>(x);
     qa.wqkv = static_cast<const bf16x8*>(lw.wqkv);
@@ -1410,6 +1408,45 @@ int run_layers(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, co
   return SSKD_OK;
 }
 
+// Everything an entry point checks about cfg, w and the workspace, before it enqueues anything: after this a call fails
+// only on a HIP error.  B == 0 passes with the layers and the workspace not looked at: the caller returns.
+int prepare(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, int B, int S,
+            void* d_workspace, size_t workspace_bytes, Workspace* ws) {
+  int rc = check_cfg(cfg, w, B, S);
+  if (rc != SSKD_OK) return rc;
+  if (B == 0) return SSKD_OK;
+  *ws = carve(d_workspace, B, S);
+  if ((rc = sskd::require_workspace("encoder", d_workspace, workspace_bytes, ws->bytes)) != SSKD_OK) return rc;
+  for (int li = 0; li < cfg->layers; ++li) {
+    const sskd_encoder_layer_weights& lw = w->layers[li];
+    SSKD_REQUIRE(lw.wqkv && lw.bqkv && lw.wo && lw.bo && lw.ln1_g && lw.ln1_b && lw.w1 && lw.b1 &&
+                     lw.w2 && lw.b2 && lw.ln2_g && lw.ln2_b,
+                 "encoder: layer %d has a null weight pointer", li);
+  }
+  return SSKD_OK;
+}
+
+// row-major bf16 [B, S, H] out of a fragment-order token buffer
+int untile(const __bf16* frag, int B, int S, void* d_rows_bf16, hipStream_t st) {
+  const int64_t total = (int64_t)B * S * H;
+  int64_t blocks = sskd::ceil_div(total, 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(untile_hidden_kernel, dim3((unsigned)blocks), dim3(256), 0, st, frag, B, S,
+                     s_pad_of(S) / 32, static_cast<__bf16*>(d_rows_bf16));
+  return sskd::check_launch("untile_hidden_kernel");
+}
+
+// Parts (streams) that `n_rows` rows of `tokens_per_row` tokens run as: SSKD_FORWARD_STREAMS (default 2), fewer until
+// every part fills the chip twice over (>= 2 groups of 128 tokens per CU: the measured configuration; four parts of one
+// round each measured +1.5 % where two parts gave +4.8 %) and starts on a 256-row boundary of the token buffers.
+int forward_parts(int n_rows, int tokens_per_row) {
+  int parts = sskd::forward_stream_parts();
+  while (parts > 1 && !(n_rows % parts == 0 && ((int64_t)(n_rows / parts) * tokens_per_row) % 256 == 0 &&
+                        (int64_t)(n_rows / parts) * tokens_per_row / 128 >= 2 * sskd::cu_count()))
+    --parts;
+  return parts;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1419,23 +1456,6 @@ size_t sskd_encoder_workspace_bytes(const sskd_encoder_config* cfg, int B, int S
   if (B <= 0 || S <= 0) return 0;
   return carve(nullptr, B, S).bytes;
 }
-
-}  // extern "C"
-
-namespace {
-
-int prepare(const sskd_encoder_config* cfg, const sskd_encoder_weights* w, int B, int S,
-            void* d_workspace, size_t workspace_bytes, Workspace* ws) {
-  int rc = check_cfg(cfg, w, B, S);
-  if (rc != SSKD_OK) return rc;
-  if (B == 0) return SSKD_OK;
-  *ws = carve(d_workspace, B, S);
-  return sskd::require_workspace("encoder", d_workspace, workspace_bytes, ws->bytes);
-}
-
-}  // namespace
-
-extern "C" {
 
 int sskd_encoder_hidden(const sskd_encoder_config* cfg, const sskd_encoder_weights* w,
                         const int32_t* d_ids, const int32_t* d_mask, int B, int S,
@@ -1449,12 +1469,7 @@ int sskd_encoder_hidden(const sskd_encoder_config* cfg, const sskd_encoder_weigh
   __bf16* fin = nullptr;
   rc = run_layers(cfg, w, d_ids, d_mask, B, S, ws, st, &fin);
   if (rc != SSKD_OK) return rc;
-  const int64_t total = (int64_t)B * S * H;
-  int64_t blocks = sskd::ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(untile_hidden_kernel, dim3((unsigned)blocks), dim3(256), 0, st, fin, B, S,
-                     s_pad_of(S) / 32, static_cast<__bf16*>(d_hidden_bf16));
-  return sskd::check_launch("untile_hidden_kernel");
+  return untile(fin, B, S, d_hidden_bf16, st);
 }
 
 // Host-only test hook: `cfg->layers` layers (0 = the embedding LayerNorm alone), then BOTH workspace buffers un-tiled:
@@ -1473,15 +1488,8 @@ int sskd_encoder_probe(const sskd_encoder_config* cfg, const sskd_encoder_weight
   __bf16* fin = nullptr;
   rc = run_layers(cfg, w, d_ids, d_seg ? nullptr : d_mask, B, S, ws, st, &fin, d_seg);
   if (rc != SSKD_OK) return rc;
-  const int64_t total = (int64_t)B * S * H;
-  int64_t blocks = sskd::ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(untile_hidden_kernel, dim3((unsigned)blocks), dim3(256), 0, st, fin, B, S,
-                     s_pad_of(S) / 32, static_cast<__bf16*>(d_hidden_bf16));
-  if ((rc = sskd::check_launch("untile_hidden_kernel")) != SSKD_OK) return rc;
-  hipLaunchKernelGGL(untile_hidden_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ws.ctx, B, S,
-                     s_pad_of(S) / 32, static_cast<__bf16*>(d_context_bf16));
-  return sskd::check_launch("untile_hidden_kernel");
+  if ((rc = untile(fin, B, S, d_hidden_bf16, st)) != SSKD_OK) return rc;
+  return untile(ws.ctx, B, S, d_context_bf16, st);
 }
 
 namespace {
@@ -1512,12 +1520,7 @@ int sskd_encoder_forward(const sskd_encoder_config* cfg, const sskd_encoder_weig
   if (rc != SSKD_OK || B == 0) return rc;
   SSKD_REQUIRE(d_ids && d_mask && d_out, "encoder_forward: null pointer");
   hipStream_t st = sskd::as_stream(stream);
-  // every part must fill the chip twice over (>= 2 groups of 128 tokens per CU: the measured configuration; four parts of one
-  // round each measured +1.5 % where two parts gave +4.8 %) and start on a 256-row boundary
-  int parts = sskd::forward_stream_parts();
-  while (parts > 1 && !(B % parts == 0 && ((int64_t)(B / parts) * s_pad_of(S)) % 256 == 0 &&
-                        (int64_t)(B / parts) * s_pad_of(S) / 128 >= 2 * sskd::cu_count()))
-    --parts;
+  const int parts = forward_parts(B, s_pad_of(S));
   const int Bp = B / parts;
   const int64_t Tp = (int64_t)Bp * s_pad_of(S);   // rows of one part in the token buffers
   return sskd::run_parts_on_streams(parts, st, [&](int i, hipStream_t s) {
@@ -1599,10 +1602,7 @@ int sskd_encoder_forward_packed(const sskd_encoder_config* cfg, const sskd_encod
   hipStream_t st = sskd::as_stream(stream);
   // the layers in two branches like sskd_encoder_forward (packed rows do not interact either); the pooling reads rows of
   // both parts and runs behind the join
-  int parts = sskd::forward_stream_parts();
-  while (parts > 1 && !(n_rows % parts == 0 && ((int64_t)(n_rows / parts) * capacity) % 256 == 0 &&
-                        (int64_t)(n_rows / parts) * capacity / 128 >= 2 * sskd::cu_count()))
-    --parts;
+  const int parts = forward_parts(n_rows, capacity);
   const int Rp = n_rows / parts;
   const int64_t Tp = (int64_t)Rp * capacity;
   __bf16* fins[sskd::MAX_STREAM_PARTS] = {};

@@ -1,5 +1,5 @@
 // Dimension-generic bf16 building blocks (row-major activations) shared by the student
-// forward/backward step (train.hip) and the teacher cross-encoder (teacher.hip).
+// forward/backward step and the teacher cross-encoder's forward (both in train.hip).
 // The inference encoder (encoder.hip) is specialised for hidden 384 and keeps its own
 // fragment-order layouts; these kernels trade some of that speed for arbitrary shapes.
 #pragma once

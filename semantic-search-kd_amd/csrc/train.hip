@@ -8,6 +8,13 @@
 // gradients.  Dimension-generic (hidden <= 1024, any head count / width that are multiples of 32):
 // the teacher cross-encoder (XLM-R-large shape) runs the same forward.
 //
+// Attention takes one of three routes, decided once per call by check() (Dims::attn):
+//   inference (training == 0): the fused forward.  It serves head widths 32, 64 and 128 with
+//     S * DH <= 36 864 (ATT_FWD_MAX_SDH; width 128: S <= 288); any other shape is refused;
+//   training, attention_bwd_supported(S, DH): the fused forward / backward pair (keeps lse);
+//   training, any other shape: the unfused path (scores materialised), every width that is a multiple of 32.
+// A call is validated as a whole - shape, route, workspace, every pointer it will read - and only then enqueued.
+//
 // Activations are ROW-MAJOR [tokens, features] here (the inference encoder's fragment order is
 // tied to hidden 384).  Every GEMM is the one NT kernel of generic.hip; operands whose reduction
 // dimension is not contiguous are transposed first by a bandwidth-bound kernel.
@@ -20,16 +27,19 @@ using namespace sskd_generic;
 
 namespace {
 
+enum class Attn { FusedInference, FusedTraining, Unfused };
+
 struct Dims {
   int B, S, H, NH, DH, F, L;
   int64_t M;
   bool training;  // false: nothing is kept for a backward pass (fused attention, GELU in the GEMM epilogue)
+  Attn attn;      // a function of (training, S, DH) alone: the halves of a batch take the route of the whole
 };
 
 struct LayerSaved {
   bf16_t *qkv, *P, *ctx, *z1, *x1, *u, *hmid, *z2, *x2;
   float *mean1, *rstd1, *mean2, *rstd2;
-  float* lse;  // fused attention (training): log-sum-exp per (row, head, query) instead of P
+  float* lse;  // Attn::FusedTraining: log-sum-exp per (row, head, query) instead of P
 };
 
 struct Saved {
@@ -42,15 +52,14 @@ struct Saved {
 };
 
 // carve the workspace; `layers_out` must hold cfg->layers entries (host memory)
-Saved carve(void* base, const Dims& d, LayerSaved* layers_out, bool training) {
+Saved carve(void* base, const Dims& d, LayerSaved* layers_out) {
   sskd::Carver c(base);
   auto take_b = [&](size_t elems) { return c.take<bf16_t>(elems); };
   auto take_f = [&](size_t elems) { return c.take<float>(elems); };
   const size_t M = (size_t)d.M, MH = M * d.H, MF = M * d.F, PP = (size_t)d.B * d.NH * d.S * d.S;
+  const bool training = d.training, unfused = d.attn == Attn::Unfused;
   Saved s{};
   s.layer = layers_out;
-  // training with the fused attention kernels keeps lse [B, heads, S] instead of the S x S probabilities
-  const bool flash = training && attention_bwd_supported(d.S, d.DH);
   s.z0 = take_b(MH);
   s.x0 = take_b(MH);
   s.mean0 = take_f(M);
@@ -60,8 +69,8 @@ Saved carve(void* base, const Dims& d, LayerSaved* layers_out, bool training) {
   for (int l = 0; l < nl; ++l) {
     LayerSaved& ls = layers_out[l];
     ls.qkv = take_b(3 * MH);
-    ls.P = (training && !flash) ? take_b(PP) : nullptr;  // fused attention: no score matrix
-    ls.lse = flash ? take_f((size_t)d.B * d.NH * d.S) : nullptr;
+    ls.P = unfused ? take_b(PP) : nullptr;  // fused attention: no score matrix
+    ls.lse = d.attn == Attn::FusedTraining ? take_f((size_t)d.B * d.NH * d.S) : nullptr;
     ls.ctx = take_b(MH);
     ls.z1 = training ? take_b(MH) : nullptr;
     ls.x1 = take_b(MH);
@@ -88,8 +97,8 @@ Saved carve(void* base, const Dims& d, LayerSaved* layers_out, bool training) {
     s.tH1 = take_b(MH);
     s.tH2 = take_b(MH);
     s.tF0 = take_b(MF);
-    s.tP0 = flash ? nullptr : take_b(PP);
-    s.tP1 = flash ? nullptr : take_b(PP);
+    s.tP0 = unfused ? take_b(PP) : nullptr;
+    s.tP1 = unfused ? take_b(PP) : nullptr;
     const size_t wide = (size_t)(3 * d.H > d.F ? 3 * d.H : d.F);
     s.tA = take_b(wide * M);
     s.tB = take_b((size_t)(d.H > d.F ? d.H : d.F) * M);
@@ -99,8 +108,9 @@ Saved carve(void* base, const Dims& d, LayerSaved* layers_out, bool training) {
   return s;
 }
 
-int check(const sskd_generic_config* cfg, const sskd_generic_weights* w, int B, int S, Dims* d) {
-  SSKD_REQUIRE(cfg && w, "generic encoder: null config / weights");
+// config, shape and attention route of a call: everything that does not depend on the caller's pointers
+int check(const sskd_generic_config* cfg, int B, int S, int training, Dims* d) {
+  SSKD_REQUIRE(cfg, "generic encoder: null config / weights");
   SSKD_REQUIRE(cfg->hidden > 0 && cfg->hidden % 32 == 0 && cfg->hidden <= 1024,
                "generic encoder: hidden=%d must be a multiple of 32, at most 1024", cfg->hidden);
   SSKD_REQUIRE(cfg->heads > 0 && cfg->hidden % cfg->heads == 0 && (cfg->hidden / cfg->heads) % 32 == 0,
@@ -118,12 +128,20 @@ int check(const sskd_generic_config* cfg, const sskd_generic_weights* w, int B, 
   d->F = cfg->intermediate;
   d->L = cfg->layers;
   d->M = (int64_t)B * S;
+  d->training = training != 0;
+  d->attn = !d->training ? Attn::FusedInference : attention_bwd_supported(S, d->DH) ? Attn::FusedTraining : Attn::Unfused;
+  if (d->attn == Attn::FusedInference && B > 0) {   // what launch_attention_fwd would refuse, before anything is enqueued
+    const int DH = d->DH;
+    SSKD_REQUIRE(DH == 32 || DH == 64 || DH == 128, "attention_fwd: head width %d not in {32, 64, 128}", DH);
+    SSKD_REQUIRE(attention_fwd_supported(S, DH), "attention_fwd: S=%d x head width %d does not fit in LDS (S * DH <= %d)", S,
+                 DH, ATT_FWD_MAX_SDH);
+  }
   return SSKD_OK;
 }
 
-// C[M, N] = A[M, K] B[N, K]^T (+ bias), plain 2-D
+// C[M, N] = A[M, K] B[N, K]^T (+ bias), plain 2-D; act = 1: erf-GELU in the epilogue (bf16 output)
 int gemm(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int N, int K,
-         const float* bias, bool c_f32, bool acc, hipStream_t st) {
+         const float* bias, bool c_f32, bool acc, hipStream_t st, int act = 0) {
   GemmArgs g{};
   g.A = A;
   g.B = B;
@@ -139,6 +157,7 @@ int gemm(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, in
   g.alpha = 1.0f;
   g.c_is_f32 = c_f32;
   g.accumulate = acc;
+  g.act = act;
   // weight-gradient products (few output tiles, K = every token of the step): cut K over enough
   // workgroups to fill the chip; the slices meet through fp32 atomics
   if (acc && c_f32 && !bias) {
@@ -168,9 +187,6 @@ int transpose2d(const bf16_t* in, int64_t R, int C, int64_t ld_in, bf16_t* out, 
   return launch_transpose(t, st);
 }
 
-int gemm(const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int N, int K,
-         const float* bias, bool c_f32, bool acc, hipStream_t st);
-
 // dW[M, N] += dY[T, M]^T X[T, N] and db[M] += column sums of dY.  The student's shapes go to the TN kernel, which
 // reads both operands as they lie in memory; others are transposed into tA / tB and take the NT kernel.
 int weight_grad(const bf16_t* dY, int M, const bf16_t* X, int N, int64_t T, float* dW, float* db, bf16_t* tA, bf16_t* tB,
@@ -195,111 +211,94 @@ int weight_grad(const bf16_t* dY, int M, const bf16_t* X, int N, int64_t T, floa
     if (rc_ != SSKD_OK) return rc_;   \
   } while (0)
 
-// ---- forward of one layer: x -> ls.x2, saving what the backward needs -------------------------
-// everything after attention of a TRAINING forward (activations saved): out-projection, LN, FFN, LN
-int layer_forward_tail(const Dims& d, const sskd_generic_layer_weights& lw, float eps, const bf16_t* x, LayerSaved& ls,
-                       Saved& sv, hipStream_t st) {
-  const int H = d.H, F = d.F;
-  const int64_t M = d.M;
-  TRY(gemm(ls.ctx, H, static_cast<const bf16_t*>(lw.wo), H, sv.tH0, H, M, H, H, lw.bo, false, false, st));
-  TRY(launch_add_ln_fwd(x, sv.tH0, lw.ln1_g, lw.ln1_b, eps, M, H, ls.x1, ls.z1, ls.mean1, ls.rstd1, st));
-  TRY(gemm(ls.x1, H, static_cast<const bf16_t*>(lw.w1), H, ls.u, F, M, F, H, lw.b1, false, false, st));
-  TRY(launch_gelu_fwd(ls.u, ls.hmid, M * F, st));
-  TRY(gemm(ls.hmid, F, static_cast<const bf16_t*>(lw.w2), F, sv.tH0, H, M, H, F, lw.b2, false, false, st));
-  TRY(launch_add_ln_fwd(ls.x1, sv.tH0, lw.ln2_g, lw.ln2_b, eps, M, H, ls.x2, ls.z2, ls.mean2, ls.rstd2, st));
-  return SSKD_OK;
+// ---- unfused attention: one product per (batch row, head) over strided views of the step's buffers ----
+// Element (r, c) of batch row b, head h lies at p[b * sb + h * sh + r * ld + c].
+struct View {
+  bf16_t* p;
+  int64_t ld, sb, sh;
+};
+// head h = columns [h * DH, (h + 1) * DH) of a row-major [B * S, width] matrix (a third of qkv, ctx)
+View head_cols(const Dims& d, bf16_t* p, int width) { return {p, width, (int64_t)d.S * width, d.DH}; }
+// head h = rows [h * DH, (h + 1) * DH) of a transposed [B, rows, S] buffer
+View head_rows(const Dims& d, bf16_t* p, int rows) { return {p, d.S, (int64_t)rows * d.S, (int64_t)d.DH * d.S}; }
+// a [B, heads, S, S] matrix (scores, probabilities and their gradients)
+View head_sq(const Dims& d, bf16_t* p) { return {p, d.S, (int64_t)d.NH * d.S * d.S, (int64_t)d.S * d.S}; }
+
+// C_bh[M, N] = A_bh[M, K] B_bh[N, K]^T for every (batch row, head)
+int head_gemm(const Dims& d, View A, View B, View C, int M, int N, int K, hipStream_t st) {
+  GemmArgs g{};
+  g.A = A.p, g.lda = A.ld, g.sA1 = A.sb, g.sA2 = A.sh;
+  g.B = B.p, g.ldb = B.ld, g.sB1 = B.sb, g.sB2 = B.sh;
+  g.C = C.p, g.ldc = C.ld, g.sC1 = C.sb, g.sC2 = C.sh;
+  g.M = M, g.N = N, g.K = K;
+  g.batch1 = d.B, g.batch2 = d.NH;
+  g.alpha = 1.0f;
+  return launch_gemm_nt(g, st);
 }
 
+// out_bh[C, R] = in_bh[R, C]^T for every (batch row, head); heads == 1: whole batch rows, the head strides are not passed
+int head_transpose(const Dims& d, int heads, View in, View out, int R, int C, hipStream_t st) {
+  TransposeArgs t{};
+  t.in = in.p, t.ld_in = in.ld, t.sI1 = in.sb, t.sI2 = heads > 1 ? in.sh : 0;
+  t.out = out.p, t.ld_out = out.ld, t.sO1 = out.sb, t.sO2 = heads > 1 ? out.sh : 0;
+  t.R = R, t.C = C;
+  t.batch1 = d.B, t.batch2 = heads;
+  return launch_transpose(t, st);
+}
+
+int attention_unfused_fwd(const Dims& d, const int32_t* mask, LayerSaved& ls, Saved& sv, hipStream_t st) {
+  const int S = d.S, DH = d.DH, H = d.H;
+  const View Q = head_cols(d, ls.qkv, 3 * H), K = head_cols(d, ls.qkv + H, 3 * H), V = head_cols(d, ls.qkv + 2 * H, 3 * H);
+  const View P = head_sq(d, ls.P), Vt = head_rows(d, sv.vt, H);
+  TRY(head_gemm(d, Q, K, P, S, S, DH, st));                                                  // P = Q K^T
+  TRY(launch_softmax_fwd(ls.P, mask, d.B, d.NH, S, 1.0f / sqrtf((float)DH), st));            // P = softmax(scale P + mask)
+  TRY(head_transpose(d, d.NH, V, Vt, S, DH, st));                                            // V^T [DH, S]
+  return head_gemm(d, P, Vt, head_cols(d, ls.ctx, H), S, DH, S, st);                         // ctx = P V
+}
+
+// dqkv [B * S, 3H] = dQ | dK | dV from dctx; uses tP0, tP1 [B, heads, S, S], vt [B, H, S] and tA [B, 3H, S]
+int attention_unfused_bwd(const Dims& d, const LayerSaved& ls, Saved& sv, bf16_t* dctx, bf16_t* dqkv, hipStream_t st) {
+  const int S = d.S, DH = d.DH, H = d.H, NH = d.NH;
+  const View V = head_cols(d, ls.qkv + 2 * H, 3 * H), dO = head_cols(d, dctx, H);
+  const View dQ = head_cols(d, dqkv, 3 * H), dK = head_cols(d, dqkv + H, 3 * H), dV = head_cols(d, dqkv + 2 * H, 3 * H);
+  const View P = head_sq(d, ls.P), dP = head_sq(d, sv.tP0), T = head_sq(d, sv.tP1);   // dP becomes dS in place
+  const View dOt = head_rows(d, sv.vt, H);                                             // dctx^T [B, H, S]
+  const View Qt = head_rows(d, sv.tA, 3 * H), Kt = head_rows(d, sv.tA + (int64_t)H * S, 3 * H);   // of qkv^T [B, 3H, S]
+  TRY(head_gemm(d, dO, V, dP, S, S, DH, st));                                                // dP = dctx V^T
+  TRY(head_transpose(d, NH, P, T, S, S, st));                                                // T = P^T
+  TRY(head_transpose(d, 1, dO, dOt, S, H, st));                                              // dctx^T, every head at once
+  TRY(head_gemm(d, T, dOt, dV, S, DH, S, st));                                               // dV = P^T dctx
+  TRY(launch_softmax_bwd(sv.tP0, ls.P, (int64_t)d.B * NH * S, S, 1.0f / sqrtf((float)DH), st));   // dS = scale P (dP - rowsum(dP P))
+  TRY(head_transpose(d, 1, head_cols(d, ls.qkv, 3 * H), Qt, S, 3 * H, st));                  // Q^T, K^T, V^T of every row
+  TRY(head_gemm(d, dP, Kt, dQ, S, DH, S, st));                                               // dQ = dS K
+  TRY(head_transpose(d, NH, dP, T, S, S, st));                                               // T = dS^T
+  return head_gemm(d, T, Qt, dK, S, DH, S, st);                                              // dK = dS^T Q
+}
+
+// ---- forward of one layer: x -> ls.x2, saving what the backward needs when training -------------------------
 int layer_forward(const Dims& d, const sskd_generic_layer_weights& lw, float eps, const bf16_t* x, const int32_t* mask,
                   LayerSaved& ls, Saved& sv, hipStream_t st) {
-  const int H = d.H, S = d.S, DH = d.DH, NH = d.NH, F = d.F;
+  const int H = d.H, F = d.F;
   const int64_t M = d.M;
+  const bool keep = d.training;   // inference: no z / mean / rstd saved, GELU inside FFN1's epilogue (no u)
   TRY(gemm(x, H, static_cast<const bf16_t*>(lw.wqkv), H, ls.qkv, 3 * H, M, 3 * H, H, lw.bqkv, false, false, st));
-  if (!d.training) {
-    // inference: scores, softmax and P V in one kernel (no [B, heads, S, S] matrix), GELU inside FFN1's epilogue
-    TRY(launch_attention_fwd(ls.qkv, mask, d.B, S, NH, DH, 1.0f / sqrtf((float)DH), ls.ctx, nullptr, st));
-    TRY(gemm(ls.ctx, H, static_cast<const bf16_t*>(lw.wo), H, sv.tH0, H, M, H, H, lw.bo, false, false, st));
-    TRY(launch_add_ln_fwd(x, sv.tH0, lw.ln1_g, lw.ln1_b, eps, M, H, ls.x1, nullptr, nullptr, nullptr, st));
-    GemmArgs f1{};
-    f1.A = ls.x1;
-    f1.B = static_cast<const bf16_t*>(lw.w1);
-    f1.C = ls.hmid;
-    f1.bias = lw.b1;
-    f1.M = (int)M;
-    f1.N = F;
-    f1.K = H;
-    f1.lda = H;
-    f1.ldb = H;
-    f1.ldc = F;
-    f1.batch1 = f1.batch2 = 1;
-    f1.alpha = 1.0f;
-    f1.act = 1;
-    TRY(launch_gemm_nt(f1, st));
-    TRY(gemm(ls.hmid, F, static_cast<const bf16_t*>(lw.w2), F, sv.tH0, H, M, H, F, lw.b2, false, false, st));
-    TRY(launch_add_ln_fwd(ls.x1, sv.tH0, lw.ln2_g, lw.ln2_b, eps, M, H, ls.x2, nullptr, nullptr, nullptr, st));
-    return SSKD_OK;
+  if (d.attn == Attn::Unfused)
+    TRY(attention_unfused_fwd(d, mask, ls, sv, st));
+  else   // scores, softmax and P V in one kernel (no [B, heads, S, S] matrix); lse is null on the inference route
+    TRY(launch_attention_fwd(ls.qkv, mask, d.B, d.S, d.NH, d.DH, 1.0f / sqrtf((float)d.DH), ls.ctx, ls.lse, st));
+  TRY(gemm(ls.ctx, H, static_cast<const bf16_t*>(lw.wo), H, sv.tH0, H, M, H, H, lw.bo, false, false, st));
+  TRY(launch_add_ln_fwd(x, sv.tH0, lw.ln1_g, lw.ln1_b, eps, M, H, ls.x1, ls.z1, keep ? ls.mean1 : nullptr,
+                        keep ? ls.rstd1 : nullptr, st));
+  if (keep) {
+    TRY(gemm(ls.x1, H, static_cast<const bf16_t*>(lw.w1), H, ls.u, F, M, F, H, lw.b1, false, false, st));
+    TRY(launch_gelu_fwd(ls.u, ls.hmid, M * F, st));
+  } else {
+    TRY(gemm(ls.x1, H, static_cast<const bf16_t*>(lw.w1), H, ls.hmid, F, M, F, H, lw.b1, false, false, st, 1));
   }
-  if (ls.lse) {
-    // fused attention that keeps the log-sum-exp for the fused backward
-    TRY(launch_attention_fwd(ls.qkv, mask, d.B, S, NH, DH, 1.0f / sqrtf((float)DH), ls.ctx, ls.lse, st));
-    return layer_forward_tail(d, lw, eps, x, ls, sv, st);
-  }
-  // scores[b, h] = Q_bh K_bh^T
-  GemmArgs g{};
-  g.A = ls.qkv;
-  g.B = ls.qkv + H;
-  g.C = ls.P;
-  g.M = S;
-  g.N = S;
-  g.K = DH;
-  g.lda = g.ldb = 3 * H;
-  g.ldc = S;
-  g.batch1 = d.B;
-  g.batch2 = NH;
-  g.sA1 = g.sB1 = (int64_t)S * 3 * H;
-  g.sA2 = g.sB2 = DH;
-  g.sC1 = (int64_t)NH * S * S;
-  g.sC2 = (int64_t)S * S;
-  g.alpha = 1.0f;
-  TRY(launch_gemm_nt(g, st));
-  TRY(launch_softmax_fwd(ls.P, mask, d.B, NH, S, 1.0f / sqrtf((float)DH), st));
-  // V_bh^T [DH, S]
-  TransposeArgs t{};
-  t.in = ls.qkv + 2 * H;
-  t.out = sv.vt;
-  t.R = S;
-  t.C = DH;
-  t.ld_in = 3 * H;
-  t.ld_out = S;
-  t.batch1 = d.B;
-  t.batch2 = NH;
-  t.sI1 = (int64_t)S * 3 * H;
-  t.sI2 = DH;
-  t.sO1 = (int64_t)NH * DH * S;
-  t.sO2 = (int64_t)DH * S;
-  TRY(launch_transpose(t, st));
-  // ctx_bh = P_bh V_bh
-  GemmArgs c{};
-  c.A = ls.P;
-  c.B = sv.vt;
-  c.C = ls.ctx;
-  c.M = S;
-  c.N = DH;
-  c.K = S;
-  c.lda = S;
-  c.ldb = S;
-  c.ldc = H;
-  c.batch1 = d.B;
-  c.batch2 = NH;
-  c.sA1 = (int64_t)NH * S * S;
-  c.sA2 = (int64_t)S * S;
-  c.sB1 = (int64_t)NH * DH * S;
-  c.sB2 = (int64_t)DH * S;
-  c.sC1 = (int64_t)S * H;
-  c.sC2 = DH;
-  c.alpha = 1.0f;
-  TRY(launch_gemm_nt(c, st));
-  return layer_forward_tail(d, lw, eps, x, ls, sv, st);
+  TRY(gemm(ls.hmid, F, static_cast<const bf16_t*>(lw.w2), F, sv.tH0, H, M, H, F, lw.b2, false, false, st));
+  TRY(launch_add_ln_fwd(ls.x1, sv.tH0, lw.ln2_g, lw.ln2_b, eps, M, H, ls.x2, ls.z2, keep ? ls.mean2 : nullptr,
+                        keep ? ls.rstd2 : nullptr, st));
+  return SSKD_OK;
 }
 
 int forward_all(const sskd_generic_config* cfg, const sskd_generic_weights* w, const Dims& d, const int32_t* ids,
@@ -317,24 +316,12 @@ int forward_all(const sskd_generic_config* cfg, const sskd_generic_weights* w, c
   return SSKD_OK;
 }
 
-// last stage of a layer's backward: qkv = x Wqkv^T + bqkv.  The layer's input gradient is sv.tH1 + dz1 (dz1 = the
-// residual branch of LN1, in sv.tH0): the SUM is formed by the consumer - the LayerNorm backward that opens the layer
-// below (or the embedding LayerNorm's) - not by a pass of its own.
-int layer_backward_qkv(const Dims& d, const sskd_generic_layer_weights& lw, const sskd_generic_layer_grads& gw,
-                       const bf16_t* x_in, Saved& sv, bf16_t* dqkv, hipStream_t st) {
-  const int H = d.H;
-  const int64_t M = d.M;
-  TRY(weight_grad(dqkv, 3 * H, x_in, H, M, gw.wqkv, gw.bqkv, sv.tA, sv.tB, st));
-  TRY(gemm(dqkv, 3 * H, static_cast<const bf16_t*>(lw.wqkv_t), 3 * H, sv.tH1, H, M, H, 3 * H, nullptr, false, false, st));
-  return SSKD_OK;
-}
-
 // ---- backward of one layer: dx2 + dx2b (gradient of the layer output; dx2b optional) -> gradient of its input ----
 // The result is sv.tH1 + sv.tH0 (the caller hands both to the next consumer).
 int layer_backward(const Dims& d, const sskd_generic_layer_weights& lw, const sskd_generic_layer_grads& gw,
                    const bf16_t* x_in, const int32_t* mask, const LayerSaved& ls, Saved& sv, const bf16_t* dx2,
                    const bf16_t* dx2b, hipStream_t st) {
-  const int H = d.H, S = d.S, DH = d.DH, NH = d.NH, F = d.F;
+  const int H = d.H, F = d.F;
   const int64_t M = d.M;
   bf16_t* dz2 = sv.tH0;   // may alias dx2b: ln_bwd reads a row before it writes it
   TRY(launch_ln_bwd(dx2, ls.z2, ls.mean2, ls.rstd2, lw.ln2_g, M, H, dz2, gw.ln2_g, gw.ln2_b, st, gw.b2, dx2b));  // + db2
@@ -352,128 +339,19 @@ int layer_backward(const Dims& d, const sskd_generic_layer_weights& lw, const ss
   TRY(weight_grad(dz1, H, ls.ctx, H, M, gw.wo, nullptr, sv.tA, sv.tB, st));
   bf16_t* dctx = sv.tH2;
   TRY(gemm(dz1, H, static_cast<const bf16_t*>(lw.wo_t), H, dctx, H, M, H, H, nullptr, false, false, st));
-
-  // ---- attention, per (batch row, head) ----
-  if (ls.lse) {
-    bf16_t* dqkv_f = sv.t3H;
-    TRY(launch_attention_bwd(ls.qkv, mask, ls.ctx, dctx, ls.lse, d.B, S, NH, DH, 1.0f / sqrtf((float)DH), dqkv_f, st));
-    return layer_backward_qkv(d, lw, gw, x_in, sv, dqkv_f, st);
-  }
-  const int64_t bS3H = (int64_t)S * 3 * H, bPP = (int64_t)NH * S * S, hPP = (int64_t)S * S;
-  // dP = dctx_bh V_bh^T
-  GemmArgs g{};
-  g.A = dctx;
-  g.lda = H;
-  g.sA1 = (int64_t)S * H;
-  g.sA2 = DH;
-  g.B = ls.qkv + 2 * H;
-  g.ldb = 3 * H;
-  g.sB1 = bS3H;
-  g.sB2 = DH;
-  g.C = sv.tP0;
-  g.ldc = S;
-  g.sC1 = bPP;
-  g.sC2 = hPP;
-  g.M = S;
-  g.N = S;
-  g.K = DH;
-  g.batch1 = d.B;
-  g.batch2 = NH;
-  g.alpha = 1.0f;
-  TRY(launch_gemm_nt(g, st));
-  // dV_bh = P_bh^T dctx_bh: needs P^T [S(j), S(i)] and dctx_bh^T [DH, S(i)]
-  TransposeArgs t{};
-  t.in = ls.P;
-  t.out = sv.tP1;
-  t.R = S;
-  t.C = S;
-  t.ld_in = t.ld_out = S;
-  t.batch1 = d.B;
-  t.batch2 = NH;
-  t.sI1 = t.sO1 = bPP;
-  t.sI2 = t.sO2 = hPP;
-  TRY(launch_transpose(t, st));
-  TransposeArgs tc{};
-  tc.in = dctx;
-  tc.out = sv.vt;  // [B, H, S]
-  tc.R = S;
-  tc.C = H;
-  tc.ld_in = H;
-  tc.ld_out = S;
-  tc.batch1 = d.B;
-  tc.batch2 = 1;
-  tc.sI1 = (int64_t)S * H;
-  tc.sO1 = (int64_t)H * S;
-  TRY(launch_transpose(tc, st));
+  // attention, per (batch row, head)
   bf16_t* dqkv = sv.t3H;
-  GemmArgs gv{};
-  gv.A = sv.tP1;
-  gv.lda = S;
-  gv.sA1 = bPP;
-  gv.sA2 = hPP;
-  gv.B = sv.vt;
-  gv.ldb = S;
-  gv.sB1 = (int64_t)H * S;
-  gv.sB2 = (int64_t)DH * S;
-  gv.C = dqkv + 2 * H;
-  gv.ldc = 3 * H;
-  gv.sC1 = bS3H;
-  gv.sC2 = DH;
-  gv.M = S;
-  gv.N = DH;
-  gv.K = S;
-  gv.batch1 = d.B;
-  gv.batch2 = NH;
-  gv.alpha = 1.0f;
-  TRY(launch_gemm_nt(gv, st));
-  // dS = scale * P * (dP - rowsum(dP P))
-  TRY(launch_softmax_bwd(sv.tP0, ls.P, (int64_t)d.B * NH * S, S, 1.0f / sqrtf((float)DH), st));
-  // Q^T, K^T, V^T of every row: qkv [S, 3H] -> [3H, S]
-  TransposeArgs tq{};
-  tq.in = ls.qkv;
-  tq.out = sv.tA;  // [B, 3H, S]
-  tq.R = S;
-  tq.C = 3 * H;
-  tq.ld_in = 3 * H;
-  tq.ld_out = S;
-  tq.batch1 = d.B;
-  tq.batch2 = 1;
-  tq.sI1 = bS3H;
-  tq.sO1 = (int64_t)3 * H * S;
-  TRY(launch_transpose(tq, st));
-  // dQ_bh = dS K_bh  (B operand = K_bh^T [DH, S])
-  GemmArgs gq{};
-  gq.A = sv.tP0;
-  gq.lda = S;
-  gq.sA1 = bPP;
-  gq.sA2 = hPP;
-  gq.B = sv.tA + (int64_t)H * S;
-  gq.ldb = S;
-  gq.sB1 = (int64_t)3 * H * S;
-  gq.sB2 = (int64_t)DH * S;
-  gq.C = dqkv;
-  gq.ldc = 3 * H;
-  gq.sC1 = bS3H;
-  gq.sC2 = DH;
-  gq.M = S;
-  gq.N = DH;
-  gq.K = S;
-  gq.batch1 = d.B;
-  gq.batch2 = NH;
-  gq.alpha = 1.0f;
-  TRY(launch_gemm_nt(gq, st));
-  // dK_bh = dS^T Q_bh  (A = dS^T, B operand = Q_bh^T [DH, S])
-  TransposeArgs ts = t;
-  ts.in = sv.tP0;
-  ts.out = sv.tP1;
-  TRY(launch_transpose(ts, st));
-  GemmArgs gk = gq;
-  gk.A = sv.tP1;
-  gk.B = sv.tA;
-  gk.C = dqkv + H;
-  TRY(launch_gemm_nt(gk, st));
-  return layer_backward_qkv(d, lw, gw, x_in, sv, dqkv, st);
+  if (d.attn == Attn::Unfused)
+    TRY(attention_unfused_bwd(d, ls, sv, dctx, dqkv, st));
+  else
+    TRY(launch_attention_bwd(ls.qkv, mask, ls.ctx, dctx, ls.lse, d.B, d.S, d.NH, d.DH, 1.0f / sqrtf((float)d.DH), dqkv, st));
+  // qkv = x Wqkv^T + bqkv.  The layer's input gradient is sv.tH1 + dz1 (dz1 = the residual branch of LN1, in sv.tH0):
+  // the SUM is formed by the consumer - the LayerNorm backward that opens the layer below (or the embedding
+  // LayerNorm's) - not by a pass of its own.
+  TRY(weight_grad(dqkv, 3 * H, x_in, H, M, gw.wqkv, gw.bqkv, sv.tA, sv.tB, st));
+  return gemm(dqkv, 3 * H, static_cast<const bf16_t*>(lw.wqkv_t), 3 * H, sv.tH1, H, M, H, 3 * H, nullptr, false, false, st);
 }
+
 
 // Cross-encoder head, one workgroup per sequence, ALL in fp32 (RobertaClassificationHead with one label):
 //   logit = out_w . tanh(dense_w . h[<s>] + dense_b) + out_b
@@ -523,16 +401,14 @@ __global__ __launch_bounds__(HEAD_WAVES * 64) void teacher_head_kernel(const bf1
   }
 }
 
-}  // namespace
 
-extern "C" {
+// ---- the call path shared by the three entry points: size, validate, then run whole or as two halves ----
 
-static size_t workspace_one_part(const sskd_generic_config* cfg, int B, int S, int training) {
+size_t workspace_one_part(const sskd_generic_config* cfg, int B, int S, int training) {
   Dims d{};
-  sskd_generic_weights dummy{};
-  if (!cfg || B <= 0 || check(cfg, &dummy, B, S, &d) != SSKD_OK) return 0;
+  if (B <= 0 || check(cfg, B, S, training, &d) != SSKD_OK) return 0;
   std::vector<LayerSaved> tmp((size_t)(d.L > 0 ? d.L : 1));
-  return carve(nullptr, d, tmp.data(), training != 0).bytes;
+  return carve(nullptr, d, tmp.data()).bytes;
 }
 
 // Batches of >= 2 x 16 384 tokens run as TWO halves on two streams (sskd::run_parts_on_streams: a side stream forked from /
@@ -540,7 +416,8 @@ static size_t workspace_one_part(const sskd_generic_config* cfg, int B, int S, i
 // saves activations and the backward that reads them cut the batch - and the workspace - the same way.  Each half keeps
 // its token count a multiple of 256 (the 256-row GEMM tiles).  Training splits only where every weight gradient goes
 // through the atomically accumulating product (gemm_tn_supported): the halves add into the same gradient buffers.
-static int generic_parts(const sskd_generic_config* cfg, int B, int S, int training) {
+// (Teacher: + 1.5 ... 2.7 % at 128 pairs x 256 tokens, tools/two_stream_teacher_probe.py; bit-identical.)
+int generic_parts(const sskd_generic_config* cfg, int B, int S, int training) {
   if (sskd::forward_stream_parts() < 2 || !cfg || B < 2 || B % 2 != 0) return 1;
   const int64_t T = (int64_t)(B / 2) * S;
   if (T % 256 != 0 || T < 16384) return 1;
@@ -552,174 +429,152 @@ static int generic_parts(const sskd_generic_config* cfg, int B, int S, int train
   }
   return 2;
 }
-static size_t part_stride(const sskd_generic_config* cfg, int B, int S, int training) {   // bytes between the halves
+size_t part_stride(const sskd_generic_config* cfg, int B, int S, int training) {   // bytes between the halves
   return sskd::align256(workspace_one_part(cfg, B / 2, S, training));
 }
 
-size_t sskd_generic_workspace_bytes(const sskd_generic_config* cfg, int B, int S, int training) {
+size_t workspace_bytes_of(const sskd_generic_config* cfg, int B, int S, int training) {
   const size_t whole = workspace_one_part(cfg, B, S, training);
   if (whole == 0 || generic_parts(cfg, B, S, training) == 1) return whole;
   const size_t split = 2 * part_stride(cfg, B, S, training);
   return split > whole ? split : whole;
 }
 
-static int prepare(const sskd_generic_config* cfg, const sskd_generic_weights* w, int B, int S, int training,
-                   void* d_workspace, size_t workspace_bytes, Dims* d, std::vector<LayerSaved>* layers, Saved* sv) {
-  int rc = check(cfg, w, B, S, d);
+// What every entry point checks before it enqueues anything: config, shape and route (check), the workspace of the
+// whole call, the weight table.  B == 0 passes with nothing else looked at: the caller returns.
+int validate(const char* what, const sskd_generic_config* cfg, const sskd_generic_weights* w, int B, int S, int training,
+             const void* d_workspace, size_t workspace_bytes, Dims* d) {
+  SSKD_REQUIRE(cfg && w, "generic encoder: null config / weights");
+  int rc = check(cfg, B, S, training, d);
+  if (rc != SSKD_OK || B == 0) return rc;
+  rc = sskd::require_workspace(what, d_workspace, workspace_bytes, workspace_bytes_of(cfg, B, S, training));
   if (rc != SSKD_OK) return rc;
-  d->training = training != 0;
   SSKD_REQUIRE(w->word_emb && w->pos_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b && (cfg->layers == 0 || w->layers),
                "generic encoder: null weight pointer");
-  if (B == 0) return SSKD_OK;
-  layers->resize((size_t)(d->L > 0 ? d->L : 1));
-  *sv = carve(d_workspace, *d, layers->data(), training != 0);
-  return sskd::require_workspace("generic encoder", d_workspace, workspace_bytes, sv->bytes);
-}
-
-static int generic_forward_rows(const sskd_generic_config* cfg, const sskd_generic_weights* w, const int32_t* d_ids,
-                                const int32_t* d_mask, int B, int S, int training, int pool, int normalize, void* d_out,
-                                void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-  Dims d{};
-  std::vector<LayerSaved> layers;
-  Saved sv{};
-  int rc = prepare(cfg, w, B, S, training, d_workspace, workspace_bytes, &d, &layers, &sv);
-  if (rc != SSKD_OK || B == 0) return rc;
-  const bf16_t* fin = nullptr;
-  TRY(forward_all(cfg, w, d, d_ids, d_mask, sv, st, &fin));
-  if (pool) return launch_pool_fwd(fin, d_mask, B, S, d.H, normalize, static_cast<float*>(d_out), sv.pooled, st);
-  // raw final hidden states, bf16 [B, S, H]
-  if (hipMemcpyAsync(d_out, fin, (size_t)d.M * d.H * sizeof(bf16_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return sskd::fail(SSKD_ERR_HIP, "generic_forward: copy of the hidden states failed");
   return SSKD_OK;
 }
 
-int sskd_generic_forward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const int32_t* d_ids,
-                         const int32_t* d_mask, int B, int S, int training, int pool, int normalize, void* d_out,
-                         void* d_workspace, size_t workspace_bytes, void* stream) {
-  {   // validation of the whole call (and its workspace) before anything is enqueued
-    Dims d{};
-    int rc = check(cfg, w, B, S, &d);
-    if (rc != SSKD_OK || B == 0) return rc;
-    const size_t need = sskd_generic_workspace_bytes(cfg, B, S, training);
-    if ((rc = sskd::require_workspace("generic encoder", d_workspace, workspace_bytes, need)) != SSKD_OK) return rc;
-  }
-  SSKD_REQUIRE(d_ids && d_mask && d_out, "generic_forward: null pointer");
-  hipStream_t st = sskd::as_stream(stream);
-  const int parts = generic_parts(cfg, B, S, training);
-  if (parts == 1)
-    return generic_forward_rows(cfg, w, d_ids, d_mask, B, S, training, pool, normalize, d_out, d_workspace, workspace_bytes, st);
-  const int Bp = B / 2;
-  const size_t stride = part_stride(cfg, B, S, training);
-  const size_t out_row = pool ? (size_t)cfg->hidden * sizeof(float) : (size_t)S * cfg->hidden * sizeof(bf16_t);
+// Runs a validated call: part(i, rows, workspace, stream) once over the whole batch, or over its two halves on two
+// streams, each with its own slice of the workspace.  Part i starts at batch row i * rows.
+template <class F>
+int run_whole_or_halves(const sskd_generic_config* cfg, const Dims& d, void* d_workspace, hipStream_t st, F&& part) {
+  if (generic_parts(cfg, d.B, d.S, d.training) == 1) return part(0, d.B, d_workspace, st);
+  const size_t stride = part_stride(cfg, d.B, d.S, d.training);
   return sskd::run_parts_on_streams(2, st, [&](int i, hipStream_t s) {
-    return generic_forward_rows(cfg, w, d_ids + (int64_t)i * Bp * S, d_mask + (int64_t)i * Bp * S, Bp, S, training, pool,
-                                normalize, static_cast<char*>(d_out) + (size_t)i * Bp * out_row,
-                                static_cast<char*>(d_workspace) + i * stride, stride, s);
+    return part(i, d.B / 2, static_cast<char*>(d_workspace) + i * stride, s);
   });
 }
 
-static int generic_backward_rows(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
-                                 const int32_t* d_ids, const int32_t* d_mask, int B, int S, int normalize, const float* d_dout,
-                                 void* d_workspace, size_t workspace_bytes, hipStream_t st) {
-  Dims d{};
+// the buffers of `rows` batch rows of a validated call, laid out in `d_workspace`
+struct Rows {
+  Dims d;
   std::vector<LayerSaved> layers;
-  Saved sv{};
-  int rc = prepare(cfg, w, B, S, 1, d_workspace, workspace_bytes, &d, &layers, &sv);
-  if (rc != SSKD_OK || B == 0) return rc;
-  SSKD_REQUIRE(grads && d_ids && d_mask && d_dout, "generic_backward: null pointer");
-  SSKD_REQUIRE(grads->word_emb && grads->pos_emb && grads->type_emb && grads->emb_ln_g && grads->emb_ln_b &&
-                   (cfg->layers == 0 || grads->layers),
-               "generic_backward: null gradient pointer");
+  Saved sv;
+  Rows(const Dims& whole, int rows, void* d_workspace) : d(whole), layers((size_t)(whole.L > 0 ? whole.L : 1)) {
+    d.B = rows;
+    d.M = (int64_t)rows * d.S;
+    sv = carve(d_workspace, d, layers.data());
+  }
+};
+
+int backward_rows(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads, Rows& r,
+                  const int32_t* d_ids, const int32_t* d_mask, int normalize, const float* d_dout, hipStream_t st) {
+  const Dims& d = r.d;
+  Saved& sv = r.sv;
   // gradient flowing into the current layer's output = dx + dxb (dxb: the residual share, null at the top)
   const bf16_t* dx = sv.tH2;
   const bf16_t* dxb = nullptr;
-  TRY(launch_pool_bwd(d_dout, sv.pooled, d_mask, B, S, d.H, normalize, sv.tH2, st));
+  TRY(launch_pool_bwd(d_dout, sv.pooled, d_mask, d.B, d.S, d.H, normalize, sv.tH2, st));
   for (int l = d.L - 1; l >= 0; --l) {
-    const sskd_generic_layer_weights& lw = w->layers[l];
-    SSKD_REQUIRE(lw.wqkv_t && lw.wo_t && lw.w1_t && lw.w2_t, "generic_backward: layer %d lacks transposed weights", l);
     const bf16_t* x_in = l == 0 ? sv.x0 : sv.layer[l - 1].x2;
-    TRY(layer_backward(d, lw, grads->layers[l], x_in, d_mask, sv.layer[l], sv, dx, dxb, st));
+    TRY(layer_backward(d, w->layers[l], grads->layers[l], x_in, d_mask, sv.layer[l], sv, dx, dxb, st));
     // the layer's input gradient is tH1 + tH0: the layer below consumes both in its first kernel (which only READS tH1
     // and rewrites tH0 row by row), so nothing is copied and nothing is added in a pass of its own
     dx = sv.tH1;
     dxb = sv.tH0;
   }
   TRY(launch_ln_bwd(dx, sv.z0, sv.mean0, sv.rstd0, w->emb_ln_g, d.M, d.H, sv.tH0, grads->emb_ln_g, grads->emb_ln_b, st, nullptr, dxb));
-  return launch_embed_bwd(d_ids, d_mask, sv.tH0, B, S, d.H, cfg->vocab_size, cfg->pos_offset, grads->word_emb,
+  return launch_embed_bwd(d_ids, d_mask, sv.tH0, d.B, d.S, d.H, cfg->vocab_size, cfg->pos_offset, grads->word_emb,
                           grads->pos_emb, grads->type_emb, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sskd_generic_workspace_bytes(const sskd_generic_config* cfg, int B, int S, int training) {
+  return workspace_bytes_of(cfg, B, S, training);
+}
+
+int sskd_generic_forward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const int32_t* d_ids,
+                         const int32_t* d_mask, int B, int S, int training, int pool, int normalize, void* d_out,
+                         void* d_workspace, size_t workspace_bytes, void* stream) {
+  Dims d{};
+  int rc = validate("generic encoder", cfg, w, B, S, training, d_workspace, workspace_bytes, &d);
+  if (rc != SSKD_OK || B == 0) return rc;
+  SSKD_REQUIRE(d_ids && d_mask && d_out, "generic_forward: null pointer");
+  const size_t out_row = pool ? (size_t)d.H * sizeof(float) : (size_t)S * d.H * sizeof(bf16_t);
+  return run_whole_or_halves(cfg, d, d_workspace, sskd::as_stream(stream), [&](int i, int rows, void* ws, hipStream_t st) {
+    Rows r(d, rows, ws);
+    const int64_t row0 = (int64_t)i * rows;
+    void* out = static_cast<char*>(d_out) + row0 * out_row;
+    const int32_t* mask = d_mask + row0 * S;
+    const bf16_t* fin = nullptr;
+    TRY(forward_all(cfg, w, r.d, d_ids + row0 * S, mask, r.sv, st, &fin));
+    if (pool) return launch_pool_fwd(fin, mask, rows, S, d.H, normalize, static_cast<float*>(out), r.sv.pooled, st);
+    // raw final hidden states, bf16 [B, S, H]
+    if (hipMemcpyAsync(out, fin, (size_t)r.d.M * d.H * sizeof(bf16_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return sskd::fail(SSKD_ERR_HIP, "generic_forward: copy of the hidden states failed");
+    return SSKD_OK;
+  });
 }
 
 int sskd_generic_backward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
                           const int32_t* d_ids, const int32_t* d_mask, int B, int S, int normalize, const float* d_dout,
                           void* d_workspace, size_t workspace_bytes, void* stream) {
-  {
-    Dims d{};
-    int rc = check(cfg, w, B, S, &d);
-    if (rc != SSKD_OK || B == 0) return rc;
-    const size_t need = sskd_generic_workspace_bytes(cfg, B, S, 1);
-    if ((rc = sskd::require_workspace("generic encoder", d_workspace, workspace_bytes, need)) != SSKD_OK) return rc;
+  Dims d{};
+  int rc = validate("generic encoder", cfg, w, B, S, 1, d_workspace, workspace_bytes, &d);
+  if (rc != SSKD_OK || B == 0) return rc;
+  SSKD_REQUIRE(grads && d_ids && d_mask && d_dout, "generic_backward: null pointer");
+  SSKD_REQUIRE(grads->word_emb && grads->pos_emb && grads->type_emb && grads->emb_ln_g && grads->emb_ln_b &&
+                   (cfg->layers == 0 || grads->layers),
+               "generic_backward: null gradient pointer");
+  for (int l = d.L - 1; l >= 0; --l) {
+    const sskd_generic_layer_weights& lw = w->layers[l];
+    SSKD_REQUIRE(lw.wqkv_t && lw.wo_t && lw.w1_t && lw.w2_t, "generic_backward: layer %d lacks transposed weights", l);
   }
-  hipStream_t st = sskd::as_stream(stream);
-  const int parts = generic_parts(cfg, B, S, 1);
-  if (parts == 1)
-    return generic_backward_rows(cfg, w, grads, d_ids, d_mask, B, S, normalize, d_dout, d_workspace, workspace_bytes, st);
-  // the halves ADD into the same gradient buffers: every accumulation of the backward is atomic (generic_parts)
-  const int Bp = B / 2;
-  const size_t stride = part_stride(cfg, B, S, 1);
-  return sskd::run_parts_on_streams(2, st, [&](int i, hipStream_t s) {
-    return generic_backward_rows(cfg, w, grads, d_ids + (int64_t)i * Bp * S, d_mask + (int64_t)i * Bp * S, Bp, S, normalize,
-                                 d_dout + (int64_t)i * Bp * cfg->hidden, static_cast<char*>(d_workspace) + i * stride, stride, s);
+  // two halves ADD into the same gradient buffers: every accumulation of the backward is atomic (generic_parts)
+  return run_whole_or_halves(cfg, d, d_workspace, sskd::as_stream(stream), [&](int i, int rows, void* ws, hipStream_t st) {
+    Rows r(d, rows, ws);
+    const int64_t row0 = (int64_t)i * rows;
+    return backward_rows(cfg, w, grads, r, d_ids + row0 * S, d_mask + row0 * S, normalize, d_dout + row0 * d.H, st);
   });
 }
 
 size_t sskd_teacher_workspace_bytes(const sskd_generic_config* cfg, int B, int S) {
-  return sskd_generic_workspace_bytes(cfg, B, S, 0);
+  return workspace_bytes_of(cfg, B, S, 0);
 }
 
 // Cross-encoder score: generic encoder -> hidden state of token 0 (<s>) -> dense + tanh -> out_proj
 // (XLMRobertaForSequenceClassification's RobertaClassificationHead with num_labels = 1); the head runs in fp32.
-static int teacher_score_rows(const sskd_generic_config* cfg, const sskd_generic_weights* w, const float* d_head_dense_w,
-                              const float* d_head_dense_b, const float* d_head_out_w, const float* d_head_out_b,
-                              const int32_t* d_ids, const int32_t* d_mask, int B, int S, float* d_logits, void* d_workspace,
-                              size_t workspace_bytes, hipStream_t st) {
-  Dims d{};
-  std::vector<LayerSaved> layers;
-  Saved sv{};
-  int rc = prepare(cfg, w, B, S, 0, d_workspace, workspace_bytes, &d, &layers, &sv);
-  if (rc != SSKD_OK) return rc;
-  const bf16_t* fin = nullptr;
-  TRY(forward_all(cfg, w, d, d_ids, d_mask, sv, st, &fin));
-  hipLaunchKernelGGL(teacher_head_kernel, dim3(B), dim3(HEAD_WAVES * 64), 0, st, fin, S, d.H, d_head_dense_w, d_head_dense_b,
-                     d_head_out_w, d_head_out_b, d_logits);
-  return sskd::check_launch("teacher_head_kernel");
-}
-
-// Batches of >= 2 x 16 384 tokens run as two halves on two streams (generic_parts above: + 1.5 ... 2.7 % at 128 pairs x 256
-// tokens, tools/two_stream_teacher_probe.py; a pair's score does not depend on its batch-mates: bit-identical).
+// A pair's score does not depend on its batch-mates, so the two-halves run is bit-identical to the whole.
 int sskd_teacher_score(const sskd_generic_config* cfg, const sskd_generic_weights* w, const float* d_head_dense_w,
                        const float* d_head_dense_b, const float* d_head_out_w, const float* d_head_out_b,
                        const int32_t* d_ids, const int32_t* d_mask, int B, int S, float* d_logits, void* d_workspace,
                        size_t workspace_bytes, void* stream) {
-  {   // validation of the whole call (and its workspace) before anything is enqueued
-    Dims d{};
-    int rc = check(cfg, w, B, S, &d);
-    if (rc != SSKD_OK || B == 0) return rc;
-    const size_t need = sskd_teacher_workspace_bytes(cfg, B, S);
-    if ((rc = sskd::require_workspace("teacher_score", d_workspace, workspace_bytes, need)) != SSKD_OK) return rc;
-  }
+  Dims d{};
+  int rc = validate("teacher_score", cfg, w, B, S, 0, d_workspace, workspace_bytes, &d);
+  if (rc != SSKD_OK || B == 0) return rc;
   SSKD_REQUIRE(d_head_dense_w && d_head_dense_b && d_head_out_w && d_head_out_b && d_ids && d_mask && d_logits,
                "teacher_score: null pointer");
-  hipStream_t st = sskd::as_stream(stream);
-  const int parts = generic_parts(cfg, B, S, 0);
-  const int Bp = B / 2;
-  const size_t part_bytes = parts == 2 ? part_stride(cfg, B, S, 0) : 0;
-  if (parts == 1)
-    return teacher_score_rows(cfg, w, d_head_dense_w, d_head_dense_b, d_head_out_w, d_head_out_b, d_ids, d_mask, B, S,
-                              d_logits, d_workspace, workspace_bytes, st);
-  return sskd::run_parts_on_streams(2, st, [&](int i, hipStream_t s) {
-    return teacher_score_rows(cfg, w, d_head_dense_w, d_head_dense_b, d_head_out_w, d_head_out_b,
-                              d_ids + (int64_t)i * Bp * S, d_mask + (int64_t)i * Bp * S, Bp, S, d_logits + (int64_t)i * Bp,
-                              static_cast<char*>(d_workspace) + i * part_bytes, part_bytes, s);
+  return run_whole_or_halves(cfg, d, d_workspace, sskd::as_stream(stream), [&](int i, int rows, void* ws, hipStream_t st) {
+    Rows r(d, rows, ws);
+    const int64_t row0 = (int64_t)i * rows;
+    const bf16_t* fin = nullptr;
+    TRY(forward_all(cfg, w, r.d, d_ids + row0 * S, d_mask + row0 * S, r.sv, st, &fin));
+    hipLaunchKernelGGL(teacher_head_kernel, dim3(rows), dim3(HEAD_WAVES * 64), 0, st, fin, S, d.H, d_head_dense_w,
+                       d_head_dense_b, d_head_out_w, d_head_out_b, d_logits + row0);
+    return sskd::check_launch("teacher_head_kernel");
   });
 }
 
