@@ -278,3 +278,38 @@ def current_stream_ptr(device=None) -> int:
     import torch
 
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def grown(buf, need_bytes: int, device):
+    """``buf`` (a uint8 workspace tensor or None) when it holds ``need_bytes``, else a new one that does: never shrinks,
+    at least one byte.  Written ``x = grown(x, need, device)``: the old tensor goes back to the allocator when ``x`` is
+    rebound, and nothing that was enqueued on it is disturbed (the caching allocator reuses a block in stream order)."""
+    import torch
+
+    if buf is not None and buf.numel() >= need_bytes:
+        return buf
+    return torch.empty(max(int(need_bytes), 1), dtype=torch.uint8, device=device)
+
+
+def as_device_i32(x, device):
+    """tensor / array / nested list -> int32 tensor on ``device``"""
+    import numpy as np
+    import torch
+
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    return t.to(device=device, dtype=torch.int32)
+
+
+def padded_ids_mask(input_ids, attention_mask, device, pad_id: int = 0):
+    """``[B, S]`` ids / mask (None: all ones) -> contiguous device int32 tensors whose S is padded up to a multiple of
+    32 (the generic kernels' row tile): ids with ``pad_id``, the mask with 0."""
+    import torch
+
+    ids = as_device_i32(input_ids, device)
+    mask = torch.ones_like(ids) if attention_mask is None else as_device_i32(attention_mask, device)
+    S = ids.shape[1]
+    Sp = max(32, -(-S // 32) * 32)
+    if Sp != S:
+        ids = torch.nn.functional.pad(ids, (0, Sp - S), value=pad_id)
+        mask = torch.nn.functional.pad(mask, (0, Sp - S))
+    return ids.contiguous(), mask.contiguous()

@@ -83,7 +83,7 @@ def hip_range_merge_packed(records: torch.Tensor, g: int, nq: int, cap: int,
         lib.sskd_range_merge_packed(
             records.data_ptr(), g, nq, cap, lims.data_ptr(), scores.data_ptr() if total else None,
             ids.data_ptr() if total else None, total, ws.data_ptr(), ws.numel(),
-            int(torch.cuda.current_stream(dev).cuda_stream),
+            _native.current_stream_ptr(dev),
         )
     )
     return lims, scores, ids
@@ -97,7 +97,7 @@ def hip_merge_packed(records: torch.Tensor, g: int, nq: int, k_in: int, k_out: i
     _native.check(
         lib.sskd_topk_merge_packed(
             records.data_ptr(), g, nq, k_in, k_out, out_s.data_ptr(), out_i.data_ptr(),
-            int(torch.cuda.current_stream(records.device).cuda_stream),
+            _native.current_stream_ptr(records.device),
         )
     )
     return out_s, out_i

@@ -166,16 +166,11 @@ class Mi355xSentenceEncoder:
         self.max_seq_length = int(
             max_seq_length or st_max or min(512, self.config.max_position_embeddings)
         )
-        self._workspace: Optional[torch.Tensor] = None
-        self._workspace2: Optional[torch.Tensor] = None   # second half of a split batch (side stream)
-        self._side_stream: Optional[torch.cuda.Stream] = None
+        self._workspace: Optional[torch.Tensor] = None   # shared by every eager forward, grown on demand
         self._copy_stream: Optional[torch.cuda.Stream] = None
-        # large batches / alternate launches over two HIP streams: gave 4 % while the output projection
-        # was a separate load/store-bound kernel; with it fused into the MLP prologue it is neutral (off)
-        self.split_streams = False
         self._staging: List[_Staging] = []
         self._stage_next = 0
-        self._rows: list = [None, None]   # per stream lane: (packed ids, segment words)
+        self._rows: Optional[tuple] = None   # encode_ragged's (packed ids, segment words)
         self._tok_pool: Optional[ThreadPoolExecutor] = None
         self.last_encode_stats: Dict[str, float] = {}
 
@@ -268,18 +263,14 @@ class Mi355xSentenceEncoder:
             mask[i, : len(r)] = 1
         return {"input_ids": ids, "attention_mask": mask}
 
-    def _splits(self, B: int, S: int) -> bool:
-        """Whether ``encode_token_ids`` runs a ``[B, S]`` batch as two halves on two HIP streams."""
-        return self.split_streams and B >= 512 and B % 2 == 0 and S <= 256
-
     def encode_token_ids(
         self, input_ids, attention_mask=None, normalize: bool = True, out: Optional[torch.Tensor] = None,
-        _workspaces: Optional[Sequence[torch.Tensor]] = None,
+        _workspace: Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
         """One forward pass over pre-tokenised ``[B, S]`` int32 ids; returns fp32 ``[B, 384]`` on device.
 
-        Everything is enqueued on the current stream; no host synchronisation.  ``_workspaces`` (a captured forward's
-        own buffers, one per half when the batch splits) replaces the encoder's shared, growing workspace.
+        Everything is enqueued on the current stream; no host synchronisation.  ``_workspace`` (a captured forward's
+        own buffer) replaces the encoder's shared, growing workspace.
         """
         lib = _native.load()
         self.sync_inference_weights()
@@ -294,23 +285,7 @@ class Mi355xSentenceEncoder:
             out = torch.empty((B, self.config.hidden_size), dtype=torch.float32, device=self.device)
         if B == 0:
             return out
-        own = list(_workspaces) if _workspaces is not None else [None, None]
-        if self._splits(B, S):
-            # Two halves on two HIP streams: the load/store-bound output projection of one half runs
-            # beside the matrix-bound fused MLP of the other (same work, 5-6 % less time at 512 x 256).
-            # Fork / join with events: the caller's stream semantics are unchanged.
-            h = B // 2
-            main = torch.cuda.current_stream(self.device)
-            if self._side_stream is None:
-                self._side_stream = torch.cuda.Stream(self.device)
-            side = self._side_stream
-            side.wait_stream(main)
-            self._forward_rows(lib, ids[:h], mask[:h], normalize, out[:h], main, "_workspace", own[0])
-            with torch.cuda.stream(side):
-                self._forward_rows(lib, ids[h:], mask[h:], normalize, out[h:], side, "_workspace2", own[1])
-            main.wait_stream(side)
-            return out
-        self._forward_rows(lib, ids, mask, normalize, out, torch.cuda.current_stream(self.device), "_workspace", own[0])
+        self._forward_rows(lib, ids, mask, normalize, out, _workspace)
         return out
 
     def capture_forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
@@ -327,31 +302,21 @@ class Mi355xSentenceEncoder:
             out = torch.empty((ids.shape[0], self.config.hidden_size), dtype=torch.float32, device=self.device)
         return GraphedForward(self, ids, mask, bool(normalize), out)
 
-    def _forward_rows(self, lib, ids, mask, normalize, out, stream, ws_name: str,
-                      own_ws: Optional[torch.Tensor] = None) -> None:
+    def _shared_workspace(self, need: int) -> torch.Tensor:
+        self._workspace = _native.grown(self._workspace, need, self.device)
+        return self._workspace
+
+    def _forward_rows(self, lib, ids, mask, normalize, out, own_ws: Optional[torch.Tensor] = None) -> None:
+        """One ``sskd_encoder_forward`` on the current stream, in ``own_ws`` or (None) the shared workspace."""
         B, S = ids.shape
         need = int(lib.sskd_encoder_workspace_bytes(self.weights.cstruct_cfg, B, S))
-        ws = own_ws if own_ws is not None else getattr(self, ws_name)
-        if own_ws is not None:
-            if ws.numel() < need:
-                raise ValueError(f"workspace of {ws.numel()} bytes given, [{B}, {S}] needs {need}")
-        elif ws is None or ws.numel() < need:
-            setattr(self, ws_name, None)
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            setattr(self, ws_name, ws)
+        if own_ws is not None and own_ws.numel() < need:
+            raise ValueError(f"workspace of {own_ws.numel()} bytes given, [{B}, {S}] needs {need}")
+        ws = own_ws if own_ws is not None else self._shared_workspace(need)
         _native.check(
             lib.sskd_encoder_forward(
-                self.weights.cstruct_cfg,
-                self.weights.struct,
-                ids.data_ptr(),
-                mask.data_ptr(),
-                B,
-                S,
-                int(bool(normalize)),
-                out.data_ptr(),
-                ws.data_ptr(),
-                ws.numel(),
-                int(stream.cuda_stream),
+                self.weights.cstruct_cfg, self.weights.struct, ids.data_ptr(), mask.data_ptr(), B, S,
+                int(bool(normalize)), out.data_ptr(), ws.data_ptr(), ws.numel(), _native.current_stream_ptr(self.device),
             )
         )
 
@@ -390,59 +355,47 @@ class Mi355xSentenceEncoder:
         np.cumsum(lengths, out=cu[1:])
         if int(cu[-1]) != flat_ids.shape[0]:
             raise ValueError("encode_ragged: flat_ids does not hold sum(lengths) tokens")
-        # launches alternate between the caller's stream and a side stream (fork / join with events):
-        # the load/store-bound kernels of one launch run beside the matrix-bound ones of the other
-        main = torch.cuda.current_stream(self.device)
-        if self._side_stream is None:
-            self._side_stream = torch.cuda.Stream(self.device)
-        lanes = [main, self._side_stream if self.split_streams else main]
-        self._side_stream.wait_stream(main)
+        # every launch goes to the current stream and reuses ONE workspace and ONE pair of packed-row buffers: stream
+        # order keeps launch i + 1 off them until launch i is through (only the staging blocks, which the HOST writes,
+        # need a ring)
         budget = int(LAUNCH_TOKENS * 0.97)
         padded_tokens = 0
         s0 = 0
-        launch = 0
-        while s0 < n:
-            s1 = int(np.searchsorted(cu, cu[s0] + budget, side="right")) - 1
-            s1 = min(max(s1, s0 + 1), n)
-            m, t0, t1 = s1 - s0, int(cu[s0]), int(cu[s1])
-            total = t1 - t0
-            cap = ROW_CAPACITY if total >= ROW_CAPACITY else -(-total // 32) * 32
-            # staging layout (int32 words): [tokens | cu_seqlens (m + 1) | pad to 4 words | table (4 per sequence)]; the
-            # kernels read table entries as 16-byte vectors, so the table starts on a 16-byte boundary
-            tab0 = -(-(total + m + 1) // 4) * 4
-            st = self._stage(tab0 + 4 * m)
-            a = st.np
-            a[:total] = flat_ids[t0:t1]
-            a[total : total + m + 1] = cu[s0 : s1 + 1] - t0
-            table = a[tab0 : tab0 + 4 * m]
-            n_rows = ctypes.c_int(0)
-            _native.check(lib.sskd_pack_plan(lengths[s0:s1].ctypes.data, m, cap, table.ctypes.data, n_rows))
-            rows = n_rows.value
-            words = tab0 + 4 * m
-            lane = launch & 1
-            with torch.cuda.stream(lanes[lane]):
-                stream = int(lanes[lane].cuda_stream)
+        with torch.cuda.device(self.device):   # the library forks its side streams on the CURRENT device
+            stream = _native.current_stream_ptr(self.device)
+            while s0 < n:
+                s1 = int(np.searchsorted(cu, cu[s0] + budget, side="right")) - 1
+                s1 = min(max(s1, s0 + 1), n)
+                m, t0, t1 = s1 - s0, int(cu[s0]), int(cu[s1])
+                total = t1 - t0
+                cap = ROW_CAPACITY if total >= ROW_CAPACITY else -(-total // 32) * 32
+                # staging layout (int32 words): [tokens | cu_seqlens (m + 1) | pad to 4 words | table (4 per sequence)]; the
+                # kernels read table entries as 16-byte vectors, so the table starts on a 16-byte boundary
+                tab0 = -(-(total + m + 1) // 4) * 4
+                st = self._stage(tab0 + 4 * m)
+                a = st.np
+                a[:total] = flat_ids[t0:t1]
+                a[total : total + m + 1] = cu[s0 : s1 + 1] - t0
+                table = a[tab0 : tab0 + 4 * m]
+                n_rows = ctypes.c_int(0)
+                _native.check(lib.sskd_pack_plan(lengths[s0:s1].ctypes.data, m, cap, table.ctypes.data, n_rows))
+                rows = n_rows.value
+                words = tab0 + 4 * m
                 st.dev[:words].copy_(st.host[:words], non_blocking=True)
-                st.done.record(lanes[lane])
+                st.done.record(torch.cuda.current_stream(self.device))
                 st.used = True
                 need_rows = rows * cap
-                if self._rows[lane] is None or self._rows[lane][0].numel() < need_rows:
+                if self._rows is None or self._rows[0].numel() < need_rows:
                     size = max(need_rows, LAUNCH_TOKENS + 16 * ROW_CAPACITY)
-                    self._rows[lane] = (torch.empty(size, dtype=torch.int32, device=self.device),
-                                        torch.empty(size, dtype=torch.int32, device=self.device))
-                rows_ids, rows_seg = self._rows[lane]
+                    self._rows = (torch.empty(size, dtype=torch.int32, device=self.device),
+                                  torch.empty(size, dtype=torch.int32, device=self.device))
+                rows_ids, rows_seg = self._rows
                 base = st.dev.data_ptr()
                 d_cu, d_table = base + 4 * total, base + 4 * tab0
                 assert d_table % 16 == 0
                 _native.check(lib.sskd_pack_tokens(base, d_cu, d_table, m, rows, cap, rows_ids.data_ptr(),
                                                    rows_seg.data_ptr(), stream))
-                need = int(lib.sskd_encoder_workspace_bytes(self.weights.cstruct_cfg, rows, cap))
-                ws_name = "_workspace" if lane == 0 else "_workspace2"
-                ws = getattr(self, ws_name)
-                if ws is None or ws.numel() < need:
-                    setattr(self, ws_name, None)
-                    ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                    setattr(self, ws_name, ws)
+                ws = self._shared_workspace(int(lib.sskd_encoder_workspace_bytes(self.weights.cstruct_cfg, rows, cap)))
                 _native.check(
                     lib.sskd_encoder_forward_packed(
                         self.weights.cstruct_cfg, self.weights.struct, rows_ids.data_ptr(), rows_seg.data_ptr(),
@@ -450,10 +403,8 @@ class Mi355xSentenceEncoder:
                         ws.data_ptr(), ws.numel(), stream,
                     )
                 )
-            padded_tokens += rows * cap
-            s0 = s1
-            launch += 1
-        main.wait_stream(self._side_stream)
+                padded_tokens += rows * cap
+                s0 = s1
         self.last_encode_stats = {"real_tokens": float(cu[-1]), "padded_tokens": float(padded_tokens),
                                   "padding_overhead": padded_tokens / float(cu[-1]) - 1.0}
         return out
@@ -506,12 +457,11 @@ class Mi355xSentenceEncoder:
         B, S = ids.shape
         mask = torch.ones_like(ids) if attention_mask is None else _as_device_i32(attention_mask, self.device)
         out = torch.empty((B, S, self.config.hidden_size), dtype=torch.bfloat16, device=self.device)
-        need = int(lib.sskd_encoder_workspace_bytes(self.weights.cstruct_cfg, B, S))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        ws = _native.grown(None, int(lib.sskd_encoder_workspace_bytes(self.weights.cstruct_cfg, B, S)), self.device)
         _native.check(
             lib.sskd_encoder_hidden(
                 self.weights.cstruct_cfg, self.weights.struct, ids.data_ptr(), mask.data_ptr(), B, S,
-                out.data_ptr(), ws.data_ptr(), ws.numel(), int(torch.cuda.current_stream(self.device).cuda_stream),
+                out.data_ptr(), ws.data_ptr(), ws.numel(), _native.current_stream_ptr(self.device),
             )
         )
         return out
@@ -609,8 +559,7 @@ class Mi355xSentenceEncoder:
 
     def cleanup(self) -> None:
         self._workspace = None
-        self._workspace2 = None
-        self._staging, self._rows = [], [None, None]
+        self._staging, self._rows = [], None
         if self._tok_pool is not None:
             self._tok_pool.shutdown(wait=True)
             self._tok_pool = None
@@ -629,8 +578,7 @@ def _resolve_device(device: Optional[str]) -> torch.device:
 
 
 def _as_device_i32(x, device: torch.device) -> torch.Tensor:
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
-    return t.to(device=device, dtype=torch.int32).contiguous()
+    return _native.as_device_i32(x, device).contiguous()
 
 
 def _load_tokenizer(model_dir: Optional[Path]):
@@ -686,22 +634,20 @@ class GraphedForward:
         enc.sync_inference_weights()
         self._weights = enc.weights
         # The graph bakes in the workspace ADDRESS, and the encoder drops and reallocates its shared workspace whenever a
-        # later eager call needs more bytes: the captured launches get buffers this object owns (one per half when the
-        # forward splits), alive as long as the graph is.
+        # later eager call needs more bytes: the captured launches get a buffer this object owns, alive as long as the
+        # graph is.
         B, S = ids.shape
-        lib = _native.load()
-        parts = 2 if enc._splits(B, S) else 1
-        need = max(int(lib.sskd_encoder_workspace_bytes(enc.weights.cstruct_cfg, B // parts, S)), 1)
-        self.workspaces = [torch.empty(need, dtype=torch.uint8, device=enc.device) for _ in range(parts)]
+        need = int(_native.load().sskd_encoder_workspace_bytes(enc.weights.cstruct_cfg, B, S))
+        self.workspaces = [_native.grown(None, need, enc.device)]   # a list: tests/test_encoder_gpu.py reads [0]
         side = torch.cuda.Stream(enc.device)
         side.wait_stream(torch.cuda.current_stream(enc.device))
         with torch.cuda.stream(side):          # warm-up off the capture stream: code load, side-stream creation
-            enc.encode_token_ids(ids, mask, normalize=normalize, out=out, _workspaces=self.workspaces)
+            enc.encode_token_ids(ids, mask, normalize=normalize, out=out, _workspace=self.workspaces[0])
         torch.cuda.current_stream(enc.device).wait_stream(side)
         torch.cuda.synchronize(enc.device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            enc.encode_token_ids(ids, mask, normalize=normalize, out=out, _workspaces=self.workspaces)
+            enc.encode_token_ids(ids, mask, normalize=normalize, out=out, _workspace=self.workspaces[0])
 
     def replay(self) -> torch.Tensor:
         if self.enc.weights is not self._weights or self.enc.sync_inference_weights():

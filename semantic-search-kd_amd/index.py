@@ -228,7 +228,7 @@ class FAISSIndexBuilder:
         if tail:
             # rows cannot start mid-tile: re-pack the partial tail tile together with the new
             # rows as one contiguous [tail | new] block written at the tail tile's first row
-            stream = _stream(self.device)
+            stream = _native.current_stream_ptr(self.device)
             staged = torch.empty((tail + n_new, self.embedding_dim), dtype=torch.float32, device=self.device)
             _native.check(
                 lib.sskd_index_get_rows(self._tiled.data_ptr(), self._n - tail, tail, staged.data_ptr(), stream)
@@ -253,7 +253,7 @@ class FAISSIndexBuilder:
                     1 if self.metric == "cosine" else 0,
                     self._tiled.data_ptr(),
                     self._n,
-                    _stream(self.device),
+                    _native.current_stream_ptr(self.device),
                 )
             )
         self._n += n_new
@@ -441,7 +441,7 @@ class FAISSIndexBuilder:
             raise ValueError(f"ids outside [{self.id_offset}, {self.id_offset + self._n})")
         if rows.numel() == 0:
             return 0
-        stream = _stream(self.device)
+        stream = _native.current_stream_ptr(self.device)
         if self._live is None:
             self._live = torch.full((int(lib.sskd_row_mask_words(self._n)),), -1, dtype=torch.int32, device=self.device)
         rows = rows.contiguous()
@@ -487,7 +487,7 @@ class FAISSIndexBuilder:
         gone = self.removed_rows()
         n_live = n_old - gone.size
         with torch.cuda.device(self.device):
-            stream = _stream(self.device)
+            stream = _native.current_stream_ptr(self.device)
             prefix = torch.empty(int(lib.sskd_row_mask_words(n_old)) + 1, dtype=torch.int64, device=self.device)
             _native.check(lib.sskd_row_mask_rank(self._live.data_ptr(), n_old, prefix.data_ptr(), stream))
             new = torch.empty(int(lib.sskd_index_padded_rows(n_live)) * self.embedding_dim, dtype=torch.float32,
@@ -530,7 +530,7 @@ class FAISSIndexBuilder:
         n_words = int(lib.sskd_row_mask_words(n))
         words = torch.zeros(max(n_words, 1), dtype=torch.int32, device=self.device)
         if isinstance(allow, torch.Tensor) and allow.is_cuda:
-            stream = _stream(self.device)
+            stream = _native.current_stream_ptr(self.device)
             if allow.dtype == torch.bool or allow.dtype == torch.uint8:
                 if allow.numel() != n:
                     raise ValueError(f"a boolean filter needs one entry per row: {allow.numel()} for {n} rows")
@@ -566,7 +566,7 @@ class FAISSIndexBuilder:
         if self._mask_scratch is None or self._mask_scratch.numel() < words:
             self._mask_scratch = torch.empty(max(words, 1), dtype=torch.int32, device=self.device)
         _native.check(lib.sskd_row_mask_and(f.words.data_ptr(), self._live.data_ptr(), self._n,
-                                            self._mask_scratch.data_ptr(), _stream(self.device)))
+                                            self._mask_scratch.data_ptr(), _native.current_stream_ptr(self.device)))
         return self._mask_scratch
 
     def search_mask(self, allow=None) -> Optional[torch.Tensor]:
@@ -607,13 +607,12 @@ class FAISSIndexBuilder:
         if normalize_queries and q.shape[0]:
             q = q.clone()
             _native.check(_native.load().sskd_l2_normalize_rows(q.data_ptr(), q.shape[0], self.embedding_dim,
-                                                                _stream(self.device)))
+                                                                _native.current_stream_ptr(self.device)))
         return q
 
     def _workspace_for(self, need: int) -> torch.Tensor:
         """The shared search workspace, grown to at least ``need`` bytes."""
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        self._workspace = _native.grown(self._workspace, need, self.device)
         return self._workspace
 
     def _search_device_masked(self, queries, k, normalize_queries, out_scores, out_ids, mask, id_offset=None):
@@ -624,7 +623,7 @@ class FAISSIndexBuilder:
             raise ValueError(f"k={k} outside [1, {_native.SSKD_K_MAX}]")
         q = self._prepare_queries(queries, normalize_queries, "search_device")
         nq = q.shape[0]
-        stream = _stream(self.device)
+        stream = _native.current_stream_ptr(self.device)
         mask_ptr = None if mask is None else mask.data_ptr()
         if out_scores is None:
             out_scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
@@ -680,7 +679,7 @@ class FAISSIndexBuilder:
             lib.sskd_index_search_onepass_filtered(
                 self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, self.id_offset,
                 None if mask is None else mask.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr(), flag.data_ptr(),
-                ws.data_ptr(), ws.numel(), _stream(self.device),
+                ws.data_ptr(), ws.numel(), _native.current_stream_ptr(self.device),
             )
         )
         return out_scores, out_ids, flag
@@ -776,7 +775,7 @@ class FAISSIndexBuilder:
                 rank_scores.data_ptr(), rank_rows.data_ptr(), search_k, lims.data_ptr(),
                 rows.data_ptr() if rows.numel() else None, None if groups is None else groups.data_ptr(),
                 float(margin), top_k, self.id_offset, scores.data_ptr(), ids.data_ptr(), counts.data_ptr(),
-                max_pos.data_ptr(), _stream(self.device),
+                max_pos.data_ptr(), _native.current_stream_ptr(self.device),
             )
         )
         return scores, ids, counts, max_pos
@@ -850,7 +849,7 @@ class FAISSIndexBuilder:
                 0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, k, k_rows, self.id_offset,
                 None if mask is None else mask.data_ptr(), self._row_group_device().data_ptr(), scores.data_ptr(),
                 ids.data_ptr(), groups.data_ptr(), counts.data_ptr(), unproved.data_ptr(), n_unproved.data_ptr(),
-                ws.data_ptr(), ws.numel(), _stream(self.device),
+                ws.data_ptr(), ws.numel(), _native.current_stream_ptr(self.device),
             )
         )
         self.last_group_counts, self.last_group_n_unproved = counts, n_unproved
@@ -906,7 +905,7 @@ class FAISSIndexBuilder:
                 while True:
                     rows = torch.from_numpy(self._rows_of_groups(new)).to(self.device)
                     _native.check(lib.sskd_row_mask_update(m_q.data_ptr(), self._n, rows.data_ptr(), rows.numel(), 0,
-                                                           bad.data_ptr(), _stream(self.device)))
+                                                           bad.data_ptr(), _native.current_stream_ptr(self.device)))
                     d, i, g, c, u, _ = self._grouped_rounds(q[qi:qi + 1], k - found, m_q)
                     c0 = int(c[0])
                     D[qi, found:found + c0], I[qi, found:found + c0], G[qi, found:found + c0] = d[0, :c0], i[0, :c0], g[0, :c0]
@@ -944,7 +943,7 @@ class FAISSIndexBuilder:
                 0 if self._tiled is None else self._tiled.data_ptr(), self._n, q.data_ptr(), nq, thr.data_ptr(),
                 self.id_offset, None if mask is None else mask.data_ptr(), lims.data_ptr(),
                 None if scores is None else scores.data_ptr(), None if ids is None else ids.data_ptr(), max_results,
-                ws.data_ptr(), ws.numel(), _stream(self.device),
+                ws.data_ptr(), ws.numel(), _native.current_stream_ptr(self.device),
             )
         )
 
@@ -1037,7 +1036,8 @@ class FAISSIndexBuilder:
             for lo in range(0, self._n, batch_size):
                 b = min(batch_size, self._n - lo)
                 rows = torch.empty((b, self.embedding_dim), dtype=torch.float32, device=self.device)
-                _native.check(lib.sskd_index_get_rows(self._tiled.data_ptr(), lo, b, rows.data_ptr(), _stream(self.device)))
+                _native.check(lib.sskd_index_get_rows(self._tiled.data_ptr(), lo, b, rows.data_ptr(),
+                                                      _native.current_stream_ptr(self.device)))
                 lims, scores, ids = self.range_search_device(rows, float(threshold), normalize_queries=False)
                 p, s = pairs_from_ranges(lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy(),
                                          np.arange(lo, lo + b, dtype=np.int64) + self.id_offset, live[lo:lo + b])
@@ -1056,7 +1056,8 @@ class FAISSIndexBuilder:
         for j, r in enumerate(rows):
             if not 0 <= r < self._n:
                 raise IndexError(f"row {r} outside [0, {self._n})")
-            _native.check(lib.sskd_index_get_rows(self._tiled.data_ptr(), r, 1, out[j].data_ptr(), _stream(self.device)))
+            _native.check(lib.sskd_index_get_rows(self._tiled.data_ptr(), r, 1, out[j].data_ptr(),
+                                                  _native.current_stream_ptr(self.device)))
         return out.cpu().numpy()
 
     def to_numpy(self) -> np.ndarray:
@@ -1065,7 +1066,8 @@ class FAISSIndexBuilder:
         out = torch.empty((self._n, self.embedding_dim), dtype=torch.float32, device=self.device)
         if self._n:
             _native.check(
-                lib.sskd_index_get_rows(self._tiled.data_ptr(), 0, self._n, out.data_ptr(), _stream(self.device))
+                lib.sskd_index_get_rows(self._tiled.data_ptr(), 0, self._n, out.data_ptr(),
+                                        _native.current_stream_ptr(self.device))
             )
         return out.cpu().numpy()
 
@@ -1306,10 +1308,6 @@ def _resolve_device(device: Optional[str]) -> torch.device:
             "there is no CPU path"
         )
     return dev
-
-
-def _stream(device: torch.device) -> int:
-    return int(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _host_queries_to_device(query_emb, device: torch.device) -> torch.Tensor:

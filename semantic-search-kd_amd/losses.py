@@ -43,7 +43,7 @@ class _KDLossFunction(torch.autograd.Function):
         grad = torch.empty_like(s)
         rows = torch.empty(3 * b, dtype=torch.float32, device=s.device)
         with torch.cuda.device(s.device):
-            stream = int(torch.cuda.current_stream(s.device).cuda_stream)
+            stream = _native.current_stream_ptr(s.device)
             _native.check(
                 lib.sskd_kd_loss(
                     s.data_ptr(), t.data_ptr(), b, d, float(temperature), float(tau),

@@ -142,7 +142,7 @@ class StudentModel:
         _native.check(
             lib.sskd_similarity(
                 qd.data_ptr(), q.shape[0], dd.data_ptr(), d.shape[0], q.shape[1], out.data_ptr(),
-                int(torch.cuda.current_stream(dev).cuda_stream),
+                _native.current_stream_ptr(dev),
             )
         )
         return out.cpu().numpy()

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .weights import BertConfig, synthetic_state_dict, synthetic_tensor
+from .weights import EMBEDDING_FIELDS, LAYER_FIELDS, BertConfig, field_shape, synthetic_state_dict, synthetic_tensor
 
 
 @dataclass(frozen=True)
@@ -171,25 +171,20 @@ class TeacherModel:
         self.device, self.model_name, self.config, self.tokenizer = str(self.torch_device), "random-reranker", cfg, None
         self.max_length = cfg.max_position_embeddings - 2
         g = torch.Generator(device=self.torch_device).manual_seed(seed)
-        h, f = cfg.hidden_size, cfg.intermediate_size
+        h = cfg.hidden_size
 
         def mat(*shape):
             return (torch.randn(shape, generator=g, device=self.torch_device) * 0.02)
 
-        sd = {"embeddings.word_embeddings.weight": mat(cfg.vocab_size, h),
-              "embeddings.position_embeddings.weight": mat(cfg.max_position_embeddings, h),
-              "embeddings.token_type_embeddings.weight": mat(cfg.type_vocab_size, h),
-              "embeddings.LayerNorm.weight": torch.ones(h, device=self.torch_device),
-              "embeddings.LayerNorm.bias": torch.zeros(h, device=self.torch_device)}
+        def param(name: str, dims: str):   # matrices are drawn (in table order: the seed's meaning), vectors are constants
+            shape = field_shape(cfg, dims)
+            if len(dims) == 2:
+                return mat(*shape)
+            return (torch.ones if name.endswith("LayerNorm.weight") else torch.zeros)(shape, device=self.torch_device)
+
+        sd = {n: param(n, dims) for _, names, dims in EMBEDDING_FIELDS for n in names}
         for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layer.{i}."
-            for nm, shape in (("attention.self.query", (h, h)), ("attention.self.key", (h, h)), ("attention.self.value", (h, h)),
-                              ("attention.output.dense", (h, h)), ("intermediate.dense", (f, h)), ("output.dense", (h, f))):
-                sd[p + nm + ".weight"] = mat(*shape)
-                sd[p + nm + ".bias"] = torch.zeros(shape[0], device=self.torch_device)
-            for nm in ("attention.output.LayerNorm", "output.LayerNorm"):
-                sd[p + nm + ".weight"] = torch.ones(h, device=self.torch_device)
-                sd[p + nm + ".bias"] = torch.zeros(h, device=self.torch_device)
+            sd.update({f"encoder.layer.{i}.{n}": param(n, dims) for _, names, dims in LAYER_FIELDS for n in names})
         sd["classifier.dense.weight"], sd["classifier.dense.bias"] = mat(h, h), torch.zeros(h, device=self.torch_device)
         sd["classifier.out_proj.weight"], sd["classifier.out_proj.bias"] = mat(1, h), torch.zeros(1, device=self.torch_device)
         self._upload(sd)
@@ -214,23 +209,18 @@ class TeacherModel:
             keep.append(y)
             return y.data_ptr()
 
+        def upload(prefix: str, names, dims) -> int:
+            x = sd[prefix + names[0]] if len(names) == 1 else torch.cat([t(sd[prefix + n]) for n in names], dim=0)
+            return bf(x) if len(dims) == 2 else f32(x)
+
         L = cfg.num_hidden_layers
         layers = (_native.GenericLayerWeights * max(L, 1))()
         for i in range(L):
-            p = f"encoder.layer.{i}."
-            lw = layers[i]
-            lw.wqkv = bf(torch.cat([t(sd[p + f"attention.self.{n}.weight"]) for n in ("query", "key", "value")], dim=0))
-            lw.bqkv = f32(torch.cat([t(sd[p + f"attention.self.{n}.bias"]) for n in ("query", "key", "value")]))
-            lw.wo, lw.bo = bf(sd[p + "attention.output.dense.weight"]), f32(sd[p + "attention.output.dense.bias"])
-            lw.w1, lw.b1 = bf(sd[p + "intermediate.dense.weight"]), f32(sd[p + "intermediate.dense.bias"])
-            lw.w2, lw.b2 = bf(sd[p + "output.dense.weight"]), f32(sd[p + "output.dense.bias"])
-            lw.ln1_g, lw.ln1_b = f32(sd[p + "attention.output.LayerNorm.weight"]), f32(sd[p + "attention.output.LayerNorm.bias"])
-            lw.ln2_g, lw.ln2_b = f32(sd[p + "output.LayerNorm.weight"]), f32(sd[p + "output.LayerNorm.bias"])
+            for field, names, dims in LAYER_FIELDS:
+                setattr(layers[i], field, upload(f"encoder.layer.{i}.", names, dims))
         w = _native.GenericWeights()
-        w.word_emb = bf(sd["embeddings.word_embeddings.weight"])
-        w.pos_emb = bf(sd["embeddings.position_embeddings.weight"])
-        w.type_emb = bf(sd["embeddings.token_type_embeddings.weight"])
-        w.emb_ln_g, w.emb_ln_b = f32(sd["embeddings.LayerNorm.weight"]), f32(sd["embeddings.LayerNorm.bias"])
+        for field, names, dims in EMBEDDING_FIELDS:
+            setattr(w, field, upload("", names, dims))
         w.layers = layers
         # the classification head stays fp32 end to end (a reranker's product is the ORDER of its logits)
         self._head = (f32(sd["classifier.dense.weight"]), f32(sd["classifier.dense.bias"]),
@@ -245,12 +235,9 @@ class TeacherModel:
         """Raw logits fp32 ``[B]`` (device) for pre-tokenised pair sequences ``<s> q </s></s> d </s>``
         (right-padded with ``pad_token_id``).  Enqueued on the current stream."""
         lib = _native.load()
-        ids, mask = self._to_device_i32(input_ids, attention_mask)
-        B, S = ids.shape
-        Sp = max(32, -(-S // 32) * 32)
-        if Sp != S:
-            ids = torch.nn.functional.pad(ids, (0, Sp - S), value=self.config.pad_token_id)
-            mask = torch.nn.functional.pad(mask, (0, Sp - S))
+        ids, mask = _native.padded_ids_mask(*self._to_device_i32(input_ids, attention_mask), self.torch_device,
+                                            pad_id=self.config.pad_token_id)
+        B, Sp = ids.shape
         if out is None:
             out = torch.empty(B, dtype=torch.float32, device=self.torch_device)
         if B == 0:
@@ -264,17 +251,12 @@ class TeacherModel:
             ids = torch.cat([ids, ids[:1].expand(Bp - B, -1)])
             mask = torch.cat([mask, mask[:1].expand(Bp - B, -1)])
             user_out, out = out, torch.empty(Bp, dtype=torch.float32, device=self.torch_device)
-        ids, mask = ids.contiguous(), mask.contiguous()
-        B_launch = Bp
-        need = int(lib.sskd_teacher_workspace_bytes(self._cfg, B_launch, Sp))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.torch_device)
+        need = int(lib.sskd_teacher_workspace_bytes(self._cfg, Bp, Sp))
+        self._workspace = _native.grown(self._workspace, need, self.torch_device)
         with torch.cuda.device(self.torch_device):
             _native.check(lib.sskd_teacher_score(
-                self._cfg, self._w, *self._head, ids.data_ptr(), mask.data_ptr(), B_launch, Sp, out.data_ptr(),
-                self._workspace.data_ptr(), self._workspace.numel(),
-                int(torch.cuda.current_stream(self.torch_device).cuda_stream)))
+                self._cfg, self._w, *self._head, ids.data_ptr(), mask.data_ptr(), Bp, Sp, out.data_ptr(),
+                self._workspace.data_ptr(), self._workspace.numel(), _native.current_stream_ptr(self.torch_device)))
         if user_out is not None:
             user_out.copy_(out[:B])
             return user_out

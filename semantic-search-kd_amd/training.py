@@ -10,7 +10,6 @@ and supplies device memory.  bf16 compute, fp32 accumulation and gradients.  No 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -18,12 +17,7 @@ import torch
 from torch import nn
 
 from . import _native
-from .weights import BertConfig
-
-_LAYER_MATS = (
-    ("attention.self.query", "q"), ("attention.self.key", "k"), ("attention.self.value", "v"),
-    ("attention.output.dense", "o"), ("intermediate.dense", "w1"), ("output.dense", "w2"),
-)
+from .weights import EMBEDDING_FIELDS, LAYER_FIELDS, BertConfig, field_shape
 
 
 def _pname(hf_name: str) -> str:
@@ -43,7 +37,7 @@ class _EncoderFunction(torch.autograd.Function):
         with torch.cuda.device(ids.device):
             _native.check(lib.sskd_generic_forward(
                 module.cfg_struct, module.w_struct, ids.data_ptr(), mask.data_ptr(), B, S, 1, 1, int(normalize),
-                out.data_ptr(), ws.data_ptr(), ws.numel(), int(torch.cuda.current_stream(ids.device).cuda_stream)))
+                out.data_ptr(), ws.data_ptr(), ws.numel(), _native.current_stream_ptr(ids.device)))
         ctx.module, ctx.ws, ctx.normalize = module, ws, bool(normalize)
         ctx.save_for_backward(ids, mask)
         ctx.weights_version = module._weights_version
@@ -74,8 +68,7 @@ class _EncoderFunction(torch.autograd.Function):
         with torch.cuda.device(ids.device):
             _native.check(lib.sskd_generic_backward(
                 module.cfg_struct, module.w_struct, module.g_struct, ids.data_ptr(), mask.data_ptr(), B, S, int(ctx.normalize),
-                dout.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(),
-                int(torch.cuda.current_stream(ids.device).cuda_stream)))
+                dout.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), _native.current_stream_ptr(ids.device)))
         ctx.ws = None
         return (None, None, None, None) + (None,) * len(module.names)
 
@@ -97,15 +90,7 @@ class TrainableEncoder(nn.Module):
         self.pos_offset = pos_offset
         H, F, L = config.hidden_size, config.intermediate_size, config.num_hidden_layers
         # ---- layout (element offsets into the flat buffers) ----
-        layer_fields = [  # (hf suffix, shape)
-            ("attention.self.query.weight", (H, H)), ("attention.self.key.weight", (H, H)), ("attention.self.value.weight", (H, H)),
-            ("attention.self.query.bias", (H,)), ("attention.self.key.bias", (H,)), ("attention.self.value.bias", (H,)),
-            ("attention.output.dense.weight", (H, H)), ("attention.output.dense.bias", (H,)),
-            ("attention.output.LayerNorm.weight", (H,)), ("attention.output.LayerNorm.bias", (H,)),
-            ("intermediate.dense.weight", (F, H)), ("intermediate.dense.bias", (F,)),
-            ("output.dense.weight", (H, F)), ("output.dense.bias", (H,)),
-            ("output.LayerNorm.weight", (H,)), ("output.LayerNorm.bias", (H,)),
-        ]
+        layer_fields = [(n, field_shape(config, dims)) for _, names, dims in LAYER_FIELDS for n in names]
         self._field_off: Dict[str, int] = {}
         off = 0
         for suffix, shape in layer_fields:
@@ -117,10 +102,8 @@ class TrainableEncoder(nn.Module):
             for suffix, shape in layer_fields:
                 layout[f"encoder.layer.{i}.{suffix}"] = (i * self._layer_stride + self._field_off[suffix], shape)
         off = L * self._layer_stride
-        for name, shape in (("embeddings.word_embeddings.weight", (config.vocab_size, H)),
-                            ("embeddings.position_embeddings.weight", (config.max_position_embeddings, H)),
-                            ("embeddings.token_type_embeddings.weight", (config.type_vocab_size, H)),
-                            ("embeddings.LayerNorm.weight", (H,)), ("embeddings.LayerNorm.bias", (H,))):
+        for _, (name,), dims in EMBEDDING_FIELDS:
+            shape = field_shape(config, dims)
             layout[name] = (off, shape)
             off += int(np.prod(shape))
         if H % 8 or F % 8:
@@ -156,7 +139,8 @@ class TrainableEncoder(nn.Module):
         self._epoch = 0   # bumped by invalidate(): changes that torch's version counters do not see (HIP-graph replays)
         self._keep: list = []
         self.w_struct = None
-        self.g_struct, self._g_layers = self._grad_struct()
+        self.g_struct, self._g_layers = _native.GenericGrads(), (_native.GenericLayerGrads * max(L, 1))()
+        self._point(self.g_struct, self._g_layers, self._flat_grad.data_ptr(), 4)
 
     def p(self, hf_name: str) -> nn.Parameter:
         return getattr(self, _pname(hf_name))
@@ -202,65 +186,38 @@ class TrainableEncoder(nn.Module):
         versions = tuple(q._version for q in params)
         if versions == self._seen_versions and self.w_struct is not None:
             return
-        cfg = self.config
-        H, F, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+        L = self.config.num_hidden_layers
         self._flat_bf16.copy_(self._flat)                                   # ONE cast kernel for all parameters
-        bf_base, f_base = self._flat_bf16.data_ptr(), self._flat.data_ptr()
-
-        def transposed(suffix: str, rows: int, cols: int) -> torch.Tensor:   # [L, cols, rows], one launch for all layers
-            w = self._flat_bf16.as_strided((L, rows, cols), (self._layer_stride, cols, 1), self._field_off[suffix])
-            return w.transpose(1, 2).contiguous()
-
-        t_qkv = transposed("attention.self.query.weight", 3 * H, H)
-        t_o = transposed("attention.output.dense.weight", H, H)
-        t_1 = transposed("intermediate.dense.weight", F, H)
-        t_2 = transposed("output.dense.weight", H, F)
-        layers = (_native.GenericLayerWeights * max(L, 1))()
-        for i in range(L):
-            lw = layers[i]
-            bf = lambda sfx: bf_base + 2 * self._off(i, sfx)    # noqa: E731
-            f32 = lambda sfx: f_base + 4 * self._off(i, sfx)    # noqa: E731
-            lw.wqkv, lw.wqkv_t = bf("attention.self.query.weight"), t_qkv[i].data_ptr()
-            lw.bqkv = f32("attention.self.query.bias")
-            lw.wo, lw.wo_t, lw.bo = bf("attention.output.dense.weight"), t_o[i].data_ptr(), f32("attention.output.dense.bias")
-            lw.w1, lw.w1_t, lw.b1 = bf("intermediate.dense.weight"), t_1[i].data_ptr(), f32("intermediate.dense.bias")
-            lw.w2, lw.w2_t, lw.b2 = bf("output.dense.weight"), t_2[i].data_ptr(), f32("output.dense.bias")
-            lw.ln1_g, lw.ln1_b = f32("attention.output.LayerNorm.weight"), f32("attention.output.LayerNorm.bias")
-            lw.ln2_g, lw.ln2_b = f32("output.LayerNorm.weight"), f32("output.LayerNorm.bias")
-        w = _native.GenericWeights()
-        w.word_emb = bf_base + 2 * self._layout["embeddings.word_embeddings.weight"][0]
-        w.pos_emb = bf_base + 2 * self._layout["embeddings.position_embeddings.weight"][0]
-        w.type_emb = bf_base + 2 * self._layout["embeddings.token_type_embeddings.weight"][0]
-        w.emb_ln_g = f_base + 4 * self._layout["embeddings.LayerNorm.weight"][0]
-        w.emb_ln_b = f_base + 4 * self._layout["embeddings.LayerNorm.bias"][0]
-        w.layers = layers
-        self.w_struct, self._layers_struct, self._keep = w, layers, [t_qkv, t_o, t_1, t_2]
+        w, layers, keep = _native.GenericWeights(), (_native.GenericLayerWeights * max(L, 1))(), []
+        self._point(w, layers, self._flat_bf16.data_ptr(), 2, ndim=2)
+        self._point(w, layers, self._flat.data_ptr(), 4, ndim=1)
+        for field, names, dims in LAYER_FIELDS:   # the backward's W^T operands: [L, cols, rows], one launch for all layers
+            if len(dims) == 2:
+                rows, cols = field_shape(self.config, dims)
+                rows *= len(names)
+                wt = self._flat_bf16.as_strided((L, rows, cols), (self._layer_stride, cols, 1), self._field_off[names[0]])
+                wt = wt.transpose(1, 2).contiguous()
+                keep.append(wt)
+                for i in range(L):
+                    setattr(layers[i], field + "_t", wt[i].data_ptr())
+        self.w_struct, self._layers_struct, self._keep = w, layers, keep
         self._seen_versions = versions
         self._weights_version += 1
 
-    # -------------------------------------------------------------- gradients
-    def _grad_struct(self):
-        L = self.config.num_hidden_layers
-        g_base = self._flat_grad.data_ptr()
-        layers = (_native.GenericLayerGrads * max(L, 1))()
-        for i in range(L):
-            at = lambda sfx: g_base + 4 * self._off(i, sfx)    # noqa: E731
-            lg = layers[i]
-            lg.wqkv, lg.bqkv = at("attention.self.query.weight"), at("attention.self.query.bias")
-            lg.wo, lg.bo = at("attention.output.dense.weight"), at("attention.output.dense.bias")
-            lg.ln1_g, lg.ln1_b = at("attention.output.LayerNorm.weight"), at("attention.output.LayerNorm.bias")
-            lg.w1, lg.b1 = at("intermediate.dense.weight"), at("intermediate.dense.bias")
-            lg.w2, lg.b2 = at("output.dense.weight"), at("output.dense.bias")
-            lg.ln2_g, lg.ln2_b = at("output.LayerNorm.weight"), at("output.LayerNorm.bias")
-        s = _native.GenericGrads()
-        s.word_emb = g_base + 4 * self._layout["embeddings.word_embeddings.weight"][0]
-        s.pos_emb = g_base + 4 * self._layout["embeddings.position_embeddings.weight"][0]
-        s.type_emb = g_base + 4 * self._layout["embeddings.token_type_embeddings.weight"][0]
-        s.emb_ln_g = g_base + 4 * self._layout["embeddings.LayerNorm.weight"][0]
-        s.emb_ln_b = g_base + 4 * self._layout["embeddings.LayerNorm.bias"][0]
-        s.layers = layers
-        return s, layers
+    def _point(self, top, layers, base: int, size: int, ndim: Optional[int] = None) -> None:
+        """Point the table's fields of ``top`` (GenericWeights / GenericGrads) and of its ``layers`` at
+        ``base + size * offset`` of their (first) tensor in the flat layout; ``ndim`` restricts it to the matrices (2)
+        or the vectors (1)."""
+        top.layers = layers
+        for field, names, dims in EMBEDDING_FIELDS:
+            if ndim in (None, len(dims)):
+                setattr(top, field, base + size * self._layout[names[0]][0])
+        for i in range(self.config.num_hidden_layers):
+            for field, names, dims in LAYER_FIELDS:
+                if ndim in (None, len(dims)):
+                    setattr(layers[i], field, base + size * self._off(i, names[0]))
 
+    # -------------------------------------------------------------- gradients
     def _attach_grads(self) -> None:
         """Make every ``p.grad`` the matching view of the flat gradient buffer.  Gradients that were ``None`` (after
         ``zero_grad(set_to_none=True)`` or before the first step) start from ONE memset; gradients that already are our
@@ -287,18 +244,9 @@ class TrainableEncoder(nn.Module):
     def forward(self, input_ids, attention_mask=None, normalize: bool = True) -> torch.Tensor:
         """ids / mask ``[B, S]`` -> embeddings ``[B, hidden]`` (fp32, on device, differentiable with
         respect to every parameter).  S is padded to a multiple of 32 here."""
-        ids = torch.as_tensor(np.asarray(input_ids) if not isinstance(input_ids, torch.Tensor) else input_ids)
-        ids = ids.to(device=self.device, dtype=torch.int32)
-        mask = torch.ones_like(ids) if attention_mask is None else torch.as_tensor(
-            np.asarray(attention_mask) if not isinstance(attention_mask, torch.Tensor) else attention_mask
-        ).to(device=self.device, dtype=torch.int32)
-        B, S = ids.shape
-        Sp = max(32, -(-S // 32) * 32)
-        if Sp != S:
-            ids = torch.nn.functional.pad(ids, (0, Sp - S))
-            mask = torch.nn.functional.pad(mask, (0, Sp - S))
+        ids, mask = _native.padded_ids_mask(input_ids, attention_mask, self.device)
         params = [self.p(n) for n in self.names]
-        return _EncoderFunction.apply(self, ids.contiguous(), mask.contiguous(), normalize, *params)
+        return _EncoderFunction.apply(self, ids, mask, normalize, *params)
 
     def state_dict_numpy(self) -> Dict[str, np.ndarray]:
         return {n: self.p(n).detach().cpu().numpy() for n in self.names}

@@ -46,6 +46,44 @@ class BertConfig:
         return d
 
 
+# ------------------------------------------------------------------ struct fields <-> HF parameter names
+# (C struct field, HF parameter names, dimensions of EACH named tensor) for the layer / embedding structs of _native.py
+# (EncoderLayerWeights, GenericLayerWeights, GenericLayerGrads; EncoderWeights, GenericWeights, GenericGrads).  Several
+# names = those tensors concatenated along dim 0 (the fused QKV projection).  Layer names follow "encoder.layer.{i}.".
+# Dimensions: H hidden, F intermediate, V vocabulary, P positions, T token types.  The kernels read every matrix (two
+# dimensions) as bf16 and every vector as fp32.  The order - within a field, then field by field - is also the order
+# of the trainer's flat parameter buffer (training.TrainableEncoder).
+_QKV = ("query", "key", "value")
+LAYER_FIELDS = (
+    ("wqkv", tuple(f"attention.self.{n}.weight" for n in _QKV), "HH"),
+    ("bqkv", tuple(f"attention.self.{n}.bias" for n in _QKV), "H"),
+    ("wo", ("attention.output.dense.weight",), "HH"),
+    ("bo", ("attention.output.dense.bias",), "H"),
+    ("ln1_g", ("attention.output.LayerNorm.weight",), "H"),
+    ("ln1_b", ("attention.output.LayerNorm.bias",), "H"),
+    ("w1", ("intermediate.dense.weight",), "FH"),
+    ("b1", ("intermediate.dense.bias",), "F"),
+    ("w2", ("output.dense.weight",), "HF"),
+    ("b2", ("output.dense.bias",), "H"),
+    ("ln2_g", ("output.LayerNorm.weight",), "H"),
+    ("ln2_b", ("output.LayerNorm.bias",), "H"),
+)
+EMBEDDING_FIELDS = (
+    ("word_emb", ("embeddings.word_embeddings.weight",), "VH"),
+    ("pos_emb", ("embeddings.position_embeddings.weight",), "PH"),
+    ("type_emb", ("embeddings.token_type_embeddings.weight",), "TH"),
+    ("emb_ln_g", ("embeddings.LayerNorm.weight",), "H"),
+    ("emb_ln_b", ("embeddings.LayerNorm.bias",), "H"),
+)
+
+
+def field_shape(cfg, dims: str) -> tuple:
+    """``"FH"`` -> ``(intermediate, hidden)`` of ``cfg`` (a BertConfig or anything with its attribute names)."""
+    size = {"H": cfg.hidden_size, "F": cfg.intermediate_size, "V": cfg.vocab_size,
+            "P": cfg.max_position_embeddings, "T": cfg.type_vocab_size}
+    return tuple(size[d] for d in dims)
+
+
 # ------------------------------------------------------------------ synthetic weights
 _MASK = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -213,6 +251,11 @@ def bf16_round(x: np.ndarray) -> np.ndarray:
     return (f32_to_bf16_bits(x).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
+# the 384 encoder's matrices by struct field; the embedding tables stay row-major
+_TILINGS = {"wqkv": tile_weight_fragments, "wo": tile_weight_fragments, "w1": tile_weight_fragments,
+            "w2": tile_w2_chunked}
+
+
 class DeviceWeights:
     """bf16 / fp32 weight tensors resident in HBM plus the C structs that point at them."""
 
@@ -242,33 +285,20 @@ class DeviceWeights:
             self._keep.append(t)
             return t.data_ptr()
 
+        def upload(prefix: str, field: str, names, dims) -> int:
+            a = sd[prefix + names[0]] if len(names) == 1 else np.concatenate([sd[prefix + n] for n in names], axis=0)
+            if len(dims) == 1:
+                return f32(a)
+            return bf16(_TILINGS[field](a) if field in _TILINGS else a)
+
         L = cfg.num_hidden_layers
         self.layers = (_native.EncoderLayerWeights * max(L, 1))()
         for i in range(L):
-            p = f"encoder.layer.{i}."
-            wqkv = np.concatenate(
-                [sd[p + f"attention.self.{n}.weight"] for n in ("query", "key", "value")], axis=0
-            )
-            bqkv = np.concatenate([sd[p + f"attention.self.{n}.bias"] for n in ("query", "key", "value")])
-            lw = self.layers[i]
-            lw.wqkv = bf16(tile_weight_fragments(wqkv))
-            lw.bqkv = f32(bqkv)
-            lw.wo = bf16(tile_weight_fragments(sd[p + "attention.output.dense.weight"]))
-            lw.bo = f32(sd[p + "attention.output.dense.bias"])
-            lw.ln1_g = f32(sd[p + "attention.output.LayerNorm.weight"])
-            lw.ln1_b = f32(sd[p + "attention.output.LayerNorm.bias"])
-            lw.w1 = bf16(tile_weight_fragments(sd[p + "intermediate.dense.weight"]))
-            lw.b1 = f32(sd[p + "intermediate.dense.bias"])
-            lw.w2 = bf16(tile_w2_chunked(sd[p + "output.dense.weight"]))
-            lw.b2 = f32(sd[p + "output.dense.bias"])
-            lw.ln2_g = f32(sd[p + "output.LayerNorm.weight"])
-            lw.ln2_b = f32(sd[p + "output.LayerNorm.bias"])
+            for field, names, dims in LAYER_FIELDS:
+                setattr(self.layers[i], field, upload(f"encoder.layer.{i}.", field, names, dims))
         self.struct = _native.EncoderWeights()
-        self.struct.word_emb = bf16(sd["embeddings.word_embeddings.weight"])
-        self.struct.pos_emb = bf16(sd["embeddings.position_embeddings.weight"])
-        self.struct.type_emb = bf16(sd["embeddings.token_type_embeddings.weight"])
-        self.struct.emb_ln_g = f32(sd["embeddings.LayerNorm.weight"])
-        self.struct.emb_ln_b = f32(sd["embeddings.LayerNorm.bias"])
+        for field, names, dims in EMBEDDING_FIELDS:
+            setattr(self.struct, field, upload("", field, names, dims))
         self.struct.layers = self.layers
         self.cstruct_cfg = _native.EncoderConfig(
             cfg.vocab_size,
