@@ -463,6 +463,64 @@ int sskd_hybrid_fuse(const float* d_tiled, int64_t n_rows, const float* d_querie
                      int64_t id_offset, double* d_out_scores, int64_t* d_out_ids, int32_t* d_out_counts,
                      float* d_out_dense, double* d_out_bm25, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Retrieval evaluation: nDCG / MRR / recall / precision per cutoff, and the discordant pairs behind Kendall's tau
+ *   reference: ndcg_at_k / mrr_at_k / recall_at_k / precision_at_k / kendall_tau, src/utils/metrics.py:11-157;
+ *   KDEvaluator.evaluate_retrieval / _evaluate_model / evaluate_ranking_quality, src/kd/eval.py:42-265
+ * Per-cutoff arithmetic (both entry points).  Given a query's grades in rank order g[0 .. n) (int32), its judged grades
+ * and up to 8 cutoffs k_c (HOST array `cutoffs` int32 [n_cut], 1 <= n_cut <= 8, strictly increasing, 1 <= k_c <= 256;
+ * copied into the launch), with m = min(k_c, n):
+ *   - disc[i] = d_discounts[i], a DEVICE fp64 [256] table the caller fills with log2(i + 2).  It is an input so that its
+ *     bits are the caller's (NumPy's np.log2 for the reference's results), not the device's log2.
+ *   - DCG = sum over i < m of (double)g[i] / disc[i], added in the order np.sum adds a contiguous fp64 vector of length
+ *     m <= 256: for m < 8 left to right from 0.0; for 8 <= m <= 128 eight accumulators r[j] = a[j], r[j] += a[i + j] for
+ *     i = 8, 16, ... while i + 8 <= m, combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the tail left
+ *     to right; for m > 128 the vector is split at h = m/2 - (m/2) % 8, each part summed by this rule, the parts added.
+ *   - IDCG, ideal_mode 0 (the reference's): the same sum over the same m retrieved grades sorted descending.
+ *     ideal_mode 1 (trec-style): the same sum over the first min(k_c, n_judged) of ALL judged grades sorted descending.
+ *   - nDCG = IDCG == 0 ? 0.0 : DCG / IDCG (0.0 for m = 0).  MRR = 1.0 / (i + 1) for the first i < m with g[i] > 0, else
+ *     0.0.  recall = hits / n_relevant, hits = the entries with g > 0 among the first m, n_relevant = the judged entries
+ *     with grade > 0; 0.0 when n_relevant = 0.  precision = hits / k_c (k_c, not m, as the reference divides).
+ *   - all of it fp64, every division and sum rounded once (no fma).
+ *   - output: d_out_metrics fp64 [nq, n_cut, 4] = (ndcg, mrr, recall, precision).
+ *
+ * sskd_eval_judge judges a ranking a search wrote: d_rank_ids int64 [nq, k_rank], 1 <= k_rank <= SSKD_K_MAX; the row of
+ * an entry is id - id_offset; the walk stops at the first id -1 (only the first 256 places can reach a cutoff).  The
+ * judgements are a CSR: d_rel_lims int64 [nq + 1] non-decreasing with d_rel_lims[nq] <= n_rel, d_rel_rows int32
+ * ascending within a query (a row at most once: the lookup is a binary search), d_rel_grades int32 beside them.  A
+ * ranked row without a judgement has grade 0.  d_rel_rows == NULL: no query has judgements and every metric is 0.0.
+ * A query whose limits are negative, decreasing or beyond n_rel gets NaN metrics and reads nothing.
+ *
+ * sskd_eval_lists evaluates every query against its OWN candidate list: d_doc_lims int64 [nq + 1] non-decreasing,
+ * list q = entries [d_doc_lims[q], d_doc_lims[q + 1]) of the [total]-long arrays, 0 <= length <= 1024.  A query whose
+ * limits are negative, decreasing, beyond `total` or longer than 1024 gets NaN metrics; nothing else of it is read or
+ * written (lengths the host knows should be checked there).
+ *   - scores: d_scores_in fp32 [total] when given (teacher logits, precomputed scores).  When it is NULL they are
+ *     computed from d_queries fp32 [nq, dim] and d_docs fp32 [total, dim] (dim a multiple of 8, at most 2048, both
+ *     16-byte aligned) with the fp32 fma chain of the exact scan: the bits sskd_similarity returns for the pair.
+ *   - the list is ranked by score descending, then lower position within the list (the searches' rule with the position
+ *     as the id).  This departs from np.argsort(scores)[::-1] in two places: exactly equal scores (the reversal puts the
+ *     HIGHER position first) and NaN, which here ranks below every number, NaNs among themselves by position (the
+ *     reversal puts NaN first).  Callers pass finite scores; lists whose order matters should not hold ties.
+ *   - d_grades int32 [total] follow their documents; the judged set of a query is its whole list.
+ *   - outputs beside the metrics, each optional (NULL): d_out_scores fp32 [total], the scores used; d_out_order int32
+ *     [total], at d_doc_lims[q] + r the position within the list of the entry ranked r.
+ *   - d_ref_scores fp32 [total] (NULL = off; needs d_out_discordant int64 [nq]): a second score per entry, ranked by the
+ *     same rule.  d_out_discordant[q] = the number of unordered pairs of the list that the two rankings order
+ *     differently - both are permutations without ties, the count is exact, and Kendall's tau is
+ *     (n (n - 1) / 2 - 2 discordant) / (n (n - 1) / 2).  Without d_ref_scores d_out_discordant is not written.
+ * One workgroup of 256 threads per query.  Stream-ordered, no host sync, no workspace, allocates nothing; arguments are
+ * checked before the launch (SSKD_ERR_INVALID); nq = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_eval_judge(const int64_t* d_rank_ids, int nq, int k_rank, int64_t id_offset, const int64_t* d_rel_lims,
+                    const int32_t* d_rel_rows, const int32_t* d_rel_grades, int64_t n_rel, const double* d_discounts,
+                    const int32_t* cutoffs, int n_cut, int ideal_mode, double* d_out_metrics, void* stream);
+int sskd_eval_lists(const float* d_queries, const float* d_docs, int dim, const float* d_scores_in,
+                    const int64_t* d_doc_lims, int64_t total, const int32_t* d_grades, const float* d_ref_scores,
+                    const double* d_discounts, const int32_t* cutoffs, int n_cut, int ideal_mode, int nq,
+                    double* d_out_metrics, float* d_out_scores, int32_t* d_out_order, int64_t* d_out_discordant,
+                    void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -15,6 +15,18 @@ from .student import StudentModel  # noqa: F401
 from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELoss  # noqa: F401
 from .bm25 import BM25Index, build_bm25_index  # noqa: F401
 from .hybrid import HybridIndex  # noqa: F401
+from .evaluation import (  # noqa: F401
+    KDEvaluator,
+    compute_retrieval_metrics,
+    evaluate_lists,
+    evaluate_lists_device,
+    expected_calibration_error,
+    kendall_tau,
+    mrr_at_k,
+    ndcg_at_k,
+    precision_at_k,
+    recall_at_k,
+)
 from .mining import ANCEMiner, BM25Miner, TeacherMiner, build_mining_curriculum  # noqa: F401
 from .teacher import TeacherConfig, TeacherModel  # noqa: F401
 from .bench_support import bench_encode  # noqa: F401
@@ -27,6 +39,16 @@ __all__ = [
     "BM25Miner",
     "build_bm25_index",
     "HybridIndex",
+    "KDEvaluator",
+    "compute_retrieval_metrics",
+    "evaluate_lists",
+    "evaluate_lists_device",
+    "expected_calibration_error",
+    "kendall_tau",
+    "mrr_at_k",
+    "ndcg_at_k",
+    "precision_at_k",
+    "recall_at_k",
     "build_mining_curriculum",
     "TeacherMiner",
     "TeacherConfig",

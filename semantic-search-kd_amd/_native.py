@@ -184,6 +184,10 @@ SIGNATURES = {
         _i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i, C.c_double,
              C.c_double, C.c_double, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
     ),
+    "sskd_eval_judge": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp]),
+    "sskd_eval_lists": (
+        _i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

@@ -1,5 +1,5 @@
 // Index layout and the device helpers that more than one search translation unit uses (internal: not installed).
-// Included by search.hip, index_rows.hip, screen.hip, range.hip, mine.hip and hybrid.hip; what only one of them uses stays there.
+// Included by search.hip, index_rows.hip, screen.hip, range.hip, mine.hip, hybrid.hip and eval.hip; what only one of them uses stays there.
 #pragma once
 #include "common.h"
 
@@ -37,6 +37,22 @@ __device__ inline float row_score_fma(const float4* src, const float* qv) {
   float acc = 0.f;
 #pragma unroll 16
   for (int u = 0; u < STEPS; ++u) {
+    const float4 a = src[2 * u], c = src[2 * u + 1];
+    const float4 qa = *reinterpret_cast<const float4*>(&qv[8 * u]), qc = *reinterpret_cast<const float4*>(&qv[8 * u + 4]);
+    acc = fmaf(a.x, qa.x, acc); acc = fmaf(c.x, qc.x, acc);
+    acc = fmaf(a.y, qa.y, acc); acc = fmaf(c.y, qc.y, acc);
+    acc = fmaf(a.z, qa.z, acc); acc = fmaf(c.z, qc.z, acc);
+    acc = fmaf(a.w, qa.w, acc); acc = fmaf(c.w, qc.w, acc);
+  }
+  return acc;
+}
+
+// the same chain over a row of 8 * steps columns (any width that is a multiple of 8): the bits sskd_similarity returns
+// for the pair.  eval.hip scores a query's own candidate list with it.
+__device__ inline float row_score_fma(const float4* src, const float* qv, int steps) {
+  float acc = 0.f;
+#pragma unroll 4
+  for (int u = 0; u < steps; ++u) {
     const float4 a = src[2 * u], c = src[2 * u + 1];
     const float4 qa = *reinterpret_cast<const float4*>(&qv[8 * u]), qc = *reinterpret_cast<const float4*>(&qv[8 * u + 4]);
     acc = fmaf(a.x, qa.x, acc); acc = fmaf(c.x, qc.x, acc);

@@ -717,6 +717,41 @@ class FAISSIndexBuilder:
             raise RuntimeError("index is empty: call build_from_parquet/add/load first")
         return self._search_numpy(query_emb, k, normalize_queries=None, allow=allow)
 
+    # --------------------------------------------------------------- evaluation
+    def qrels_device(self, qrels, nq: int):
+        """Either form of qrels (``evaluation.qrels_to_csr``: the reference's dense ``relevance_labels``, ``{row: grade}``
+        dicts, or a ready CSR) as the device CSR ``evaluate_device`` takes - built once on the host, so a caller that
+        evaluates repeatedly (early stopping) uploads it once.  Rows are the ids ``search`` returns."""
+        from . import evaluation
+
+        lims, rows, grades = evaluation.qrels_to_csr(qrels, nq, self.id_offset)
+        return tuple(torch.from_numpy(a).to(self.device) for a in (lims, rows, grades))
+
+    def evaluate_device(self, queries: torch.Tensor, qrels_csr, k_values: Sequence[int] = (10, 50, 100), *, allow=None,
+                        ideal: str = "retrieved") -> torch.Tensor:
+        """Per-query retrieval metrics of device-resident queries: ONE ``search_device(max(k_values))`` and ONE
+        ``sskd_eval_judge``, both enqueued on the current stream, no host synchronisation.  Returns a device fp64
+        ``[nq, n_cut, 4]`` tensor = (ndcg, mrr, recall, precision) per ascending distinct cutoff (each at most 256).
+        ``qrels_csr``: what ``qrels_device`` returned (None: no judgements).  Removed rows and ``allow`` act through the
+        search; ``ideal``: ``"retrieved"`` (the reference's nDCG) or ``"judged"`` (ideal ranking over all judged rows)."""
+        from . import evaluation
+
+        ks, _ = evaluation._cutoffs(k_values)
+        _, ids = self.search_device(queries, ks[-1], allow=allow)
+        return evaluation.judge_device(ids, qrels_csr, ks, id_offset=self.id_offset, ideal=ideal)
+
+    def evaluate(self, query_emb: np.ndarray, qrels, k_values: Sequence[int] = (10, 50, 100), *, allow=None,
+                 ideal: str = "retrieved") -> dict:
+        """``{"ndcg@k", "mrr@k", "recall@k", "precision@k"}`` for every cutoff: the means over the queries of
+        ``evaluate_device``, taken with NumPy on the host (the reference's bits).  ``qrels``: per query the
+        reference's dense label list indexed by corpus position (shorter lists mean 0) or a ``{row: grade}`` dict."""
+        from . import evaluation
+
+        qd = _host_queries_to_device(query_emb, self.device)
+        with torch.cuda.device(self.device):
+            block = self.evaluate_device(qd, self.qrels_device(qrels, qd.shape[0]), k_values, allow=allow, ideal=ideal)
+            return evaluation.means_of(block.cpu().numpy(), sorted({int(k) for k in k_values}))
+
     # ------------------------------------------------------- hard-negative mining
     def mine_negatives_device(
         self,
