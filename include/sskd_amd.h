@@ -521,6 +521,52 @@ int sskd_eval_lists(const float* d_queries, const float* d_docs, int dim, const 
                     double* d_out_metrics, float* d_out_scores, int32_t* d_out_order, int64_t* d_out_discordant,
                     void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * IVF index: inverted lists over the flat index, nprobe search with exact scores
+ *   reference: the `ivf_pq` index type of configs/index.yaml:4, 13-19 (nlist, nprobe; "for >50M vectors") and its
+ *   validation block (recall_threshold 0.97), configs/index.yaml:51-56.  The reference has no code behind the type; the
+ *   rules below are this library's definition.  The PQ half (m, nbits) is not implemented: rows stay fp32.
+ * Layout.  The rows are the flat index, unchanged and not permuted (d_tiled, row-major fp32 [n_rows, 384]).  The lists
+ * are a CSR over row numbers: d_list_offsets DEVICE int64 [nlist + 1] (non-decreasing, from 0 to n_rows), d_list_rows
+ * DEVICE int32 [n_rows] (every row once, ascending within a list).  An empty list is two equal offsets.
+ *
+ * sskd_ivf_search.  d_probe DEVICE int64 [nq, nprobe] holds, per query, the lists to visit, exactly as a top-nprobe
+ * search over the centroid rows writes its ids (-1 = none; a number outside [0, nlist) is treated as -1; a list should
+ * not repeat).  Bit contract: the result of query q is what sskd_index_search_filtered returns for q under an allow-mask
+ * of the rows of its probed lists (AND d_row_mask when given: the format of "Filtered search", NULL = all rows) - every
+ * score the fp32 fma chain of the exact scan, order (score descending, then lower id), ids row + id_offset, the tail
+ * padded with (-FLT_MAX, -1).  With every list probed it is what sskd_index_search returns.
+ *   One workgroup per (part, query): the rows a query probes form one sequence of L_q = the sum of its lists' lengths,
+ * part p of P scans positions [p L_q / P, (p + 1) L_q / P) of it, found from a prefix sum over the list lengths, so the
+ * split is balanced however skewed the lists are.  Every part writes k (unsorted) records to the workspace and
+ * sskd_topk_merge joins them - more than 512 records of a query in two steps (p1 x p2 parts: p1 lists for each of the
+ * p2 nq (slot, query) pairs, then p2 lists per query), because that merge is one wave per query.  sskd_ivf_search_plan reports P (and the rows per chunk and the workgroups launched; any
+ * out pointer may be NULL) from host-known numbers only - nq, nprobe, k, the longest list, 256 compute units - and
+ * sskd_ivf_search_workspace_bytes is the workspace of that plan (0 for arguments the search rejects).  The search is
+ * not told the longest list: it runs as many parts as its workspace holds, at most the plan of a list that holds every
+ * row, so a workspace of exactly sskd_ivf_search_workspace_bytes(..) runs a plan of that size; any workspace that holds
+ * one part is accepted, a smaller one is refused.  The result does not depend on P.
+ * Limits: 1 <= k <= 256; 1 <= nprobe <= nlist <= 65 536; nq <= 65 535; id_offset >= 0; n_rows < 2^31 - 64; d_queries,
+ * d_tiled and the workspace 16-byte aligned.  Stream-ordered, no host sync (graph-capturable), allocates nothing; every
+ * argument is checked before anything is enqueued (SSKD_ERR_INVALID, a short workspace included); nq = 0 is a
+ * successful no-op.
+ *
+ * sskd_ivf_list_sums: the centroid update of the spherical k-means.  d_sums DEVICE fp64 [nlist, 384]: element (l, c) =
+ * the sum of column c over the rows of list l, added in CSR order into one fp64 accumulator from +0.0 (each fp32 value
+ * widened exactly, each addition rounded once).  One fixed order per element and no atomics: two calls give the same
+ * bits.  An empty list gives +0.0 everywhere.  The caller rounds to fp32 and normalises (sskd_l2_normalize_rows).
+ * Limits: 0 <= nlist <= 65 536.  Stream-ordered, no host sync, no workspace; nlist = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_ivf_search_plan(int nq, int nprobe, int k, int64_t n_rows, int64_t max_list_rows, int* parts, int* chunk_rows,
+                         int* workgroups);
+size_t sskd_ivf_search_workspace_bytes(int nq, int nprobe, int k, int64_t n_rows, int64_t max_list_rows);
+int sskd_ivf_search(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq, const int64_t* d_probe,
+                    int nprobe, const int64_t* d_list_offsets, const int32_t* d_list_rows, int nlist, int k,
+                    int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores, int64_t* d_out_ids,
+                    void* d_workspace, size_t workspace_bytes, void* stream);
+int sskd_ivf_list_sums(const float* d_tiled, int64_t n_rows, const int64_t* d_list_offsets, const int32_t* d_list_rows,
+                       int nlist, double* d_sums, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

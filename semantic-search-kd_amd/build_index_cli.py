@@ -5,6 +5,10 @@ Same flags as the reference's ``scripts/build_faiss_index.py:15-24`` (``--hnsw-*
 ignored: the index is an exact scan, there is no graph to build).
 Run as ``python -m semantic_search_kd_amd.build_index_cli ...``.
 
+``--index-type ivf`` trains inverted lists over the rows (``ivf.IVFIndex``: ``--nlist``, ``--nprobe``), checks recall@10
+of the IVF search against the exact search as the reference's ``validation:`` block prescribes (configs/index.yaml:51-56)
+and exits non-zero below ``--recall-threshold``; single-index builds only.
+
 Row-sharded build (BASELINE cfg 3): launch the same command under
 ``python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m semantic_search_kd_amd.build_index_cli ...``
 and rank r encodes rows ``shard_bounds(N, G, r)`` straight into its own HBM shard and writes
@@ -53,6 +57,12 @@ def main(argv=None) -> int:
     ap.add_argument("--group-column", type=str, default=None,
                     help="parquet column holding the group key of every row (for example doc_id): the saved index "
                          "then answers search_grouped with distinct documents; single-index builds only")
+    ap.add_argument("--index-type", type=str, choices=("flat", "ivf"), default="flat",
+                    help="flat = the exact scan; ivf = inverted lists over the same rows (nprobe search, exact scores)")
+    ap.add_argument("--nlist", type=_positive, default=None, help="ivf: number of lists (default round(sqrt(rows)))")
+    ap.add_argument("--nprobe", type=_positive, default=32, help="ivf: lists a query visits")
+    ap.add_argument("--recall-threshold", type=float, default=0.97,
+                    help="ivf: fail if recall@10 against the exact search is below this")
     args = ap.parse_args(argv)
     for flag, p in (("--model-path", args.model_path), ("--data-path", args.data_path)):
         if not Path(p).exists():
@@ -62,6 +72,8 @@ def main(argv=None) -> int:
     if world > 1 or args.shards == 1:
         if args.group_column:
             ap.error("--group-column: the row-sharded index has no grouped search yet")
+        if args.index_type == "ivf":
+            ap.error("--index-type ivf: the row-sharded index has no inverted lists yet")
         return _build_sharded(args, world)
 
     model = StudentModel(args.model_path, device=args.device)
@@ -75,7 +87,19 @@ def main(argv=None) -> int:
         hnsw_ef_construction=args.hnsw_ef_construction,
         group_column=args.group_column,
     )
-    builder.save(Path(args.output_dir))
+    if args.index_type == "ivf":
+        from .ivf import IVFIndex
+
+        ivf = IVFIndex(flat=builder, nlist=args.nlist, nprobe=args.nprobe)
+        ivf.train()
+        ivf.save(Path(args.output_dir))
+        recall = ivf.validate(num_queries=1000, k=10)
+        print(f"IVF lists: {ivf.nlist}, nprobe: {min(ivf.nprobe, ivf.nlist)}, recall@10 vs exact: {recall:.4f}")
+        if recall < args.recall_threshold:
+            print(f"recall@10 {recall:.4f} is below the threshold {args.recall_threshold}", file=sys.stderr)
+            return 1
+    else:
+        builder.save(Path(args.output_dir))
     print(f"Index saved to: {args.output_dir}")
     print(f"Total vectors: {index.ntotal}")
     return 0

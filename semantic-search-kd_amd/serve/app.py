@@ -65,6 +65,9 @@ class ServeSettings:
     bm25_weight: float = 0.3
     semantic_weight: float = 0.7
     fusion_method: str = "rrf"   # rrf (reciprocal rank fusion), linear
+    # ``index_type`` of the reference's configs/index.yaml:4 (hnsw | ivf_pq | flat): "ivf" retrieves through the inverted
+    # lists saved beside the index (ivf.IVFIndex) when the directory holds them; anything else is the exact scan
+    index_type: str = "flat"
 
     @staticmethod
     def from_env() -> "ServeSettings":
@@ -79,6 +82,7 @@ class ServeSettings:
             bm25_weight=float(e.get("SEMANTIC_KD_HYBRID__BM25_WEIGHT", ServeSettings.bm25_weight)),
             semantic_weight=float(e.get("SEMANTIC_KD_HYBRID__SEMANTIC_WEIGHT", ServeSettings.semantic_weight)),
             fusion_method=e.get("SEMANTIC_KD_HYBRID__FUSION_METHOD", ServeSettings.fusion_method),
+            index_type=(e.get("SEMANTIC_KD_INDEX__INDEX_TYPE") or ServeSettings.index_type).strip().lower(),
         )
 
     def is_production(self) -> bool:
@@ -97,6 +101,7 @@ class AppState:
         self.settings: Optional[ServeSettings] = None
         self.ready: bool = False
         self.hybrid = None   # hybrid.HybridIndex over index_builder when hybrid retrieval is on and its BM25 index fits
+        self.ivf = None      # ivf.IVFIndex over index_builder when the index type is "ivf" and the directory holds lists
 
     def is_ready(self) -> bool:
         return self.ready and self.student is not None
@@ -118,6 +123,7 @@ def _load_index_dir(index_dir: Path) -> Dict[str, Any]:
     elif builder.doc_texts:
         app_state.doc_texts = builder.doc_texts
     app_state.hybrid = _load_hybrid(builder, app_state.settings)
+    app_state.ivf = _load_ivf(builder, index_dir, app_state.settings)
     return {"status": "loaded", "index_path": str(index_dir), "num_documents": len(app_state.doc_ids)}
 
 
@@ -141,6 +147,27 @@ def _load_hybrid(builder, settings: Optional["ServeSettings"]):
                            fusion_method=settings.fusion_method)
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the BM25 index (hybrid retrieval disabled, serving dense-only): %s", exc)
+        return None
+
+
+def _load_ivf(builder, index_dir: Path, settings: Optional["ServeSettings"]):
+    """The ``IVFIndex`` /search retrieves through, or None (the exact scan): the index type is not "ivf", the directory
+    holds no ``ivf.json``, the index is row-sharded, or the lists do not load - then a warning is logged and the service
+    answers with the exact search."""
+    if settings is None or settings.index_type != "ivf":
+        return None
+    from ..ivf import IVFIndex, is_ivf_dir
+
+    if not isinstance(builder, FAISSIndexBuilder) or not is_ivf_dir(index_dir):
+        logger.warning("Index type is ivf but %s holds no inverted lists over a single-GPU index: serving the exact scan",
+                       index_dir)
+        return None
+    try:
+        ivf = IVFIndex(flat=builder)
+        ivf.load_lists(index_dir)
+        return ivf
+    except Exception as exc:  # noqa: BLE001
+        logger.warning("Failed to load the inverted lists (serving the exact scan): %s", exc)
         return None
 
 
@@ -231,6 +258,8 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
                 # both sides contribute at least k rows; the fused score is the result's score
                 depth = hybrid.clip_depth(max(hybrid.depth, k_retrieve))
                 distances, indices = hybrid.search([request.query], query_emb, k=min(k_retrieve, 2 * depth), depth=depth)
+            elif app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_retrieve <= 256:
+                distances, indices = app_state.ivf.search(query_emb, k=k_retrieve)
             else:
                 distances, indices = app_state.index_builder.search(query_emb, k=k_retrieve)
             results: List[SearchResult] = []
