@@ -525,7 +525,7 @@ int sskd_eval_lists(const float* d_queries, const float* d_docs, int dim, const 
  * IVF index: inverted lists over the flat index, nprobe search with exact scores
  *   reference: the `ivf_pq` index type of configs/index.yaml:4, 13-19 (nlist, nprobe; "for >50M vectors") and its
  *   validation block (recall_threshold 0.97), configs/index.yaml:51-56.  The reference has no code behind the type; the
- *   rules below are this library's definition.  The PQ half (m, nbits) is not implemented: rows stay fp32.
+ *   rules below are this library's definition.  The rows stay fp32 here; the PQ half (m, nbits) is "IVF-PQ" below.
  * Layout.  The rows are the flat index, unchanged and not permuted (d_tiled, row-major fp32 [n_rows, 384]).  The lists
  * are a CSR over row numbers: d_list_offsets DEVICE int64 [nlist + 1] (non-decreasing, from 0 to n_rows), d_list_rows
  * DEVICE int32 [n_rows] (every row once, ascending within a list).  An empty list is two equal offsets.
@@ -566,6 +566,70 @@ int sskd_ivf_search(const float* d_tiled, int64_t n_rows, const float* d_queries
                     void* d_workspace, size_t workspace_bytes, void* stream);
 int sskd_ivf_list_sums(const float* d_tiled, int64_t n_rows, const int64_t* d_list_offsets, const int32_t* d_list_rows,
                        int nlist, double* d_sums, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * IVF-PQ: product-quantisation codes over the inverted lists, ADC list scan, exact re-ranking
+ *   reference: the `ivf_pq` index type of configs/index.yaml (nlist, nprobe, m: 64, nbits: 8).  PQ decides WHICH rows
+ *   of the probed lists are re-scored; every score and order of a refined result is the exact scan's fp32 fma chain.
+ * Fixed: dim = 384; nbits = 8 (256 codes per subquantiser); m in {8, 16, 24, 32, 48, 64, 96}; dsub = 384 / m.
+ * d_codebooks DEVICE fp32 [m][256][dsub] (cb[j][c][d]); codes are uint8 [rows][m].  The arithmetic is chosen so that
+ * every step can be restated bit for bit with sequential IEEE operations:
+ *   Residual.  r = row - centroid[list(row)], one fp32 subtraction per element (d_assign DEVICE int64 [n] = the list of
+ *     every row, d_centroids fp32 [nlist, 384]; d_assign = NULL: r = row).  For the inner product
+ *     <q, row> ~ <q, c_list> + sum_j <q_j, cb[j][code_j]>: the look-up table does not depend on the list and the first
+ *     term is the probe's own score.
+ *   Encode (sskd_pq_encode).  code[row][j] = argmin over c of sum_d (r_d - cb[j][c][d])^2 over the dsub elements of
+ *     subspace j, ties to the lower c; the distance is fp64, summed over d ascending from +0.0, operands widened exactly,
+ *     every subtract, multiply and add rounded once and no fma formed.  d_codes DEVICE uint8 [n][m], row order.
+ *   Code sums (sskd_pq_code_sums, the k-means update).  d_sums DEVICE fp64 [m][256][dsub]: element (j, c, d) = the sum
+ *     of r_d over the rows grouped under code c of subspace j, added in the order d_group_rows lists them into one
+ *     accumulator from +0.0 (no atomics: two calls agree bit for bit).  d_group_offsets DEVICE int64 [m][257],
+ *     d_group_rows DEVICE int32 [m][n]: per subspace the rows sorted stably by code (ascending row within a code).
+ *     d_counts DEVICE int64 [m][256] = the group sizes.  The caller sets the new centroid to fl32(sum / count), the
+ *     division in fp64; an empty code (sum +0.0, count 0) keeps its centroid.
+ *   LUT (sskd_pq_lut).  lut[q][j][c] = fl32(sum_d (double) q_d (double) cb[j][c][d]), fp64 over d ascending (the
+ *     products are exact in fp64).  d_lut DEVICE fp32 [nq][m][256].
+ *   ADC score of a row.  s = the probe score of its list (d_probe_scores DEVICE fp32 [nq, nprobe]: the fp32 bits the
+ *     coarse search returned beside d_probe), then s = s + lut[j][code_j] for j = 0 .. m - 1, fp32 adds in that order.
+ *   Candidates.  The R = refine best probed rows in rank order (ADC score descending, then lower row).  Rows the
+ *     allow-mask hides are dropped BEFORE scoring and take no slot.
+ *   Result (sskd_pq_search).  refine = R > 0: bit for bit what sskd_index_search_filtered returns for the query under
+ *     an allow-mask of its R candidates - scores from the fp32 fma chain of the exact scan, order (score descending,
+ *     then lower id), ids row + id_offset, padding (-FLT_MAX, -1).  refine = 0: the top-k by ADC with the ADC scores, in
+ *     the same order rule.  d_out_candidates (NULL or DEVICE int64 [nq, R], refine > 0 only) receives the candidate ids
+ *     in ADC rank order, -1 padded.  The result does not depend on how the work is split.
+ * d_codes_csr DEVICE uint8 [n_rows][m] holds the codes IN CSR ORDER: entry p belongs to row d_list_rows[p], so a list
+ * is one contiguous byte range.  One workgroup per (part, query) scans the codes of its positions (partitioned as in
+ * sskd_ivf_search) with the query's LUT in LDS and keeps its R (or k) best; one workgroup per query then sorts the
+ * partial records, gathers the R candidates' rows, scores them exactly and sorts again.  sskd_pq_search_plan reports
+ * the parts, the fewest positions a part is planned for (its code bytes are several times its LUT bytes), the workgroups
+ * and the LUT bytes, from host-known numbers only; a query never has more than 4 096 partial records.  The workspace
+ * (sskd_pq_search_workspace_bytes; 0 for arguments the search rejects) holds the LUT - 1 KiB m per query, so callers
+ * batch a few thousand queries per call - and the records; as with sskd_ivf_search any workspace that holds one part
+ * is accepted and a smaller one refused.  The search is not told the longest list: it runs as many parts as its
+ * workspace holds, up to the plan of a list that holds every row.  So pass workspace_bytes =
+ * sskd_pq_search_workspace_bytes(.., max_list_rows) and no more: a larger figure buys shorter parts than the plan's,
+ * each of which still loads the whole LUT first (with nprobe = 1 at 1 M rows, up to 40 parts over a thousand positions).
+ * Limits: 1 <= k <= R <= 256 or R = 0; 1 <= nprobe <= nlist <= 65 536; nq <= 65 535; id_offset >= 0; n_rows < 2^31 - 64;
+ * d_queries, d_tiled, d_codes_csr and the workspace 16-byte aligned.  Every call is stream-ordered, does no host sync
+ * (graph-capturable) and allocates nothing; every argument is checked before anything is enqueued (SSKD_ERR_INVALID, a
+ * short workspace included); nq = 0 (n = 0) is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_pq_encode(const float* d_rows, int64_t n, const float* d_centroids, const int64_t* d_assign, int nlist,
+                   const float* d_codebooks, int m, uint8_t* d_codes, void* stream);
+int sskd_pq_code_sums(const float* d_rows, int64_t n, const float* d_centroids, const int64_t* d_assign, int nlist,
+                      const int64_t* d_group_offsets, const int32_t* d_group_rows, int m, double* d_sums,
+                      int64_t* d_counts, void* stream);
+int sskd_pq_lut(const float* d_queries, int nq, const float* d_codebooks, int m, float* d_lut, void* stream);
+int sskd_pq_search_plan(int nq, int nprobe, int k, int refine, int m, int64_t n_rows, int64_t max_list_rows, int* parts,
+                        int* min_part_rows, int* workgroups, size_t* lut_bytes);
+size_t sskd_pq_search_workspace_bytes(int nq, int nprobe, int k, int refine, int m, int64_t n_rows,
+                                      int64_t max_list_rows);
+int sskd_pq_search(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq, const int64_t* d_probe,
+                   const float* d_probe_scores, int nprobe, const int64_t* d_list_offsets, const int32_t* d_list_rows,
+                   int nlist, const uint8_t* d_codes_csr, const float* d_codebooks, int m, int k, int refine,
+                   int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores, int64_t* d_out_ids,
+                   int64_t* d_out_candidates, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward

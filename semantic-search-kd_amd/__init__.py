@@ -16,6 +16,7 @@ from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELo
 from .bm25 import BM25Index, build_bm25_index  # noqa: F401
 from .hybrid import HybridIndex  # noqa: F401
 from .ivf import IVFIndex  # noqa: F401
+from .pq import IVFPQIndex  # noqa: F401
 from .evaluation import (  # noqa: F401
     KDEvaluator,
     compute_retrieval_metrics,
@@ -41,6 +42,7 @@ __all__ = [
     "build_bm25_index",
     "HybridIndex",
     "IVFIndex",
+    "IVFPQIndex",
     "KDEvaluator",
     "compute_retrieval_metrics",
     "evaluate_lists",

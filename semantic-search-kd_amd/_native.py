@@ -192,6 +192,14 @@ SIGNATURES = {
     "sskd_ivf_search_workspace_bytes": (_sz, [_i, _i, _i, _i64, _i64]),
     "sskd_ivf_search": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sskd_ivf_list_sums": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp]),
+    "sskd_pq_encode": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "sskd_pq_code_sums": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sskd_pq_lut": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "sskd_pq_search_plan": (_i, [_i, _i, _i, _i, _i, _i64, _i64, _ip, _ip, _ip, C.POINTER(_sz)]),
+    "sskd_pq_search_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i64, _i64]),
+    "sskd_pq_search": (
+        _i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

@@ -7,7 +7,8 @@ Run as ``python -m semantic_search_kd_amd.build_index_cli ...``.
 
 ``--index-type ivf`` trains inverted lists over the rows (``ivf.IVFIndex``: ``--nlist``, ``--nprobe``), checks recall@10
 of the IVF search against the exact search as the reference's ``validation:`` block prescribes (configs/index.yaml:51-56)
-and exits non-zero below ``--recall-threshold``; single-index builds only.
+and exits non-zero below ``--recall-threshold``; single-index builds only.  ``--index-type ivf_pq`` adds product-quantisation
+codes over the same lists (``pq.IVFPQIndex``: ``--pq-m``, ``--pq-refine``) behind the same recall gate.
 
 Row-sharded build (BASELINE cfg 3): launch the same command under
 ``python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m semantic_search_kd_amd.build_index_cli ...``
@@ -57,10 +58,15 @@ def main(argv=None) -> int:
     ap.add_argument("--group-column", type=str, default=None,
                     help="parquet column holding the group key of every row (for example doc_id): the saved index "
                          "then answers search_grouped with distinct documents; single-index builds only")
-    ap.add_argument("--index-type", type=str, choices=("flat", "ivf"), default="flat",
-                    help="flat = the exact scan; ivf = inverted lists over the same rows (nprobe search, exact scores)")
+    ap.add_argument("--index-type", type=str, choices=("flat", "ivf", "ivf_pq"), default="flat",
+                    help="flat = the exact scan; ivf = inverted lists over the same rows (nprobe search, exact scores); "
+                         "ivf_pq = the lists scanned through product-quantisation codes, the best candidates re-scored exactly")
     ap.add_argument("--nlist", type=_positive, default=None, help="ivf: number of lists (default round(sqrt(rows)))")
     ap.add_argument("--nprobe", type=_positive, default=32, help="ivf: lists a query visits")
+    ap.add_argument("--pq-m", type=_positive, default=64, help="ivf_pq: subquantisers per row (8, 16, 24, 32, 48, 64 or 96)")
+    ap.add_argument("--pq-refine", type=int, default=None,
+                    help="ivf_pq: candidates re-scored exactly per query, at least; a search for more than N results re-scores "
+                         "that many (default: min(256, max(100, 4 k)) per search)")
     ap.add_argument("--recall-threshold", type=float, default=0.97,
                     help="ivf: fail if recall@10 against the exact search is below this")
     args = ap.parse_args(argv)
@@ -72,8 +78,8 @@ def main(argv=None) -> int:
     if world > 1 or args.shards == 1:
         if args.group_column:
             ap.error("--group-column: the row-sharded index has no grouped search yet")
-        if args.index_type == "ivf":
-            ap.error("--index-type ivf: the row-sharded index has no inverted lists yet")
+        if args.index_type != "flat":
+            ap.error(f"--index-type {args.index_type}: the row-sharded index has no inverted lists yet")
         return _build_sharded(args, world)
 
     model = StudentModel(args.model_path, device=args.device)
@@ -95,6 +101,27 @@ def main(argv=None) -> int:
         ivf.save(Path(args.output_dir))
         recall = ivf.validate(num_queries=1000, k=10)
         print(f"IVF lists: {ivf.nlist}, nprobe: {min(ivf.nprobe, ivf.nlist)}, recall@10 vs exact: {recall:.4f}")
+        if recall < args.recall_threshold:
+            print(f"recall@10 {recall:.4f} is below the threshold {args.recall_threshold}", file=sys.stderr)
+            return 1
+    elif args.index_type == "ivf_pq":
+        from .pq import PQ_CODES, PQ_M_ALLOWED, IVFPQIndex
+
+        if args.pq_m not in PQ_M_ALLOWED:
+            ap.error(f"--pq-m: must be one of {PQ_M_ALLOWED}")
+        if args.pq_refine is not None and not 1 <= args.pq_refine <= 256:
+            # 0 (raw ADC scores as the result) is left to callers of IVFPQIndex.search: a built index is served, and
+            # the service's scores are exact inner products
+            ap.error("--pq-refine: a number in [1, 256]")
+        if index.ntotal < PQ_CODES:
+            ap.error(f"--index-type ivf_pq: product quantisation trains on at least {PQ_CODES} rows, the corpus has {index.ntotal}")
+        ivf = IVFPQIndex(flat=builder, nlist=args.nlist, nprobe=args.nprobe, m=args.pq_m, refine=args.pq_refine)
+        ivf.train()
+        ivf.save(Path(args.output_dir))
+        recall = ivf.validate(num_queries=1000, k=10)
+        refine = "default" if ivf.refine is None else ivf.refine
+        print(f"IVF-PQ lists: {ivf.nlist}, nprobe: {min(ivf.nprobe, ivf.nlist)}, m: {ivf.m}, refine: {refine}, "
+              f"recall@10 vs exact: {recall:.4f}")
         if recall < args.recall_threshold:
             print(f"recall@10 {recall:.4f} is below the threshold {args.recall_threshold}", file=sys.stderr)
             return 1

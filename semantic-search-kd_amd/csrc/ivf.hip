@@ -1,7 +1,7 @@
 // Inverted-file search over the flat index (sskd_amd.h "IVF index").
 //
 // The reference names an `ivf_pq` index type in configs/index.yaml:4, 13-19 (nlist / nprobe, "for >50M vectors") beside the
-// HNSW one it builds; this file is the IVF half over uncompressed rows.  WHICH rows a query looks at is approximate (the
+// HNSW one it builds; this file is the IVF half over uncompressed rows (pq.hip is the PQ half, over the same lists).  WHICH rows a query looks at is approximate (the
 // rows of the nprobe lists whose centroids score best); every score and every order is exact: a row is scored by one lane
 // running row_score_fma, the fma chain of the exact scan, so an IVF search returns bit for bit what the exact search
 // returns under an allow-mask of the probed lists' rows.
@@ -25,7 +25,7 @@
 // ivf_list_sums_kernel: the centroid update of the k-means.  One wave per (list, 64 columns) adds the list's rows in CSR
 // order into one fp64 accumulator per column - one fixed order per output element and no atomics, so two runs agree bit
 // for bit.
-#include "search_device.h"
+#include "ivf_device.h"
 #include "search_host.h"
 
 #include <algorithm>
@@ -33,14 +33,9 @@
 
 namespace {
 
-constexpr int IVF_THREADS = 256;
 constexpr int IVF_ROWS = 32;                                   // rows per chunk
 constexpr int IVF_STRIDE4 = CHUNKS + 1;                        // LDS row stride in float4 (97: see above)
 constexpr int IVF_LOADS = IVF_ROWS * CHUNKS / IVF_THREADS;     // 12 float4 per thread and chunk
-constexpr int IVF_PROBES = 256;                                // probes per prefix block
-constexpr int IVF_K_MAX = 256;
-constexpr int IVF_NLIST_MAX = 65536;
-constexpr int IVF_CUS = 256;                                   // the plan is fixed from host-known numbers only
 constexpr int IVF_MAX_PARTS = 1024;
 constexpr int IVF_MERGE_CAND = 2048;                           // parts * k: the candidates of one query
 constexpr int IVF_MERGE_DIRECT = 512;                          // up to here one merge step joins them
@@ -60,6 +55,7 @@ struct IvfParams {
   int64_t* part_ids;
 };
 
+// (the prefix over the probed lists and the position -> row step are in ivf_device.h)
 // the running top-k of one workgroup; wave 0 owns it (count, worst are wave-uniform)
 struct IvfTop {
   float* s;
@@ -127,38 +123,9 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(IvfParams p) {
   const float4* rows4 = reinterpret_cast<const float4*>(p.rows);
   const int n_blocks = (p.nprobe + IVF_PROBES - 1) / IVF_PROBES;
 
+  const IvfPrefix pre{pre_s, off_s, wsum_s};
   // prefix of probe block pb into pre_s / off_s; returns the block's total (uniform).  Two barriers inside.
-  auto scan_block = [&](int pb) -> int64_t {
-    const int j = pb * IVF_PROBES + tid;
-    int64_t len = 0, off = 0;
-    if (j < p.nprobe) {
-      const int64_t l = probe[j];
-      if (l >= 0 && l < p.nlist) {
-        off = p.list_offsets[l];
-        len = p.list_offsets[l + 1] - off;
-        if (len < 0 || off < 0) len = 0;
-      }
-    }
-    int64_t x = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t y = __shfl_up(x, o);
-      if (lane >= o) x += y;
-    }
-    __syncthreads();   // nobody still reads the previous block's prefix
-    if (lane == 63) wsum_s[wave] = x;
-    __syncthreads();
-    int64_t base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < IVF_THREADS / 64; ++w) {
-      if (w < wave) base += wsum_s[w];
-      total += wsum_s[w];
-    }
-    pre_s[tid + 1] = base + x;
-    if (tid == 0) pre_s[0] = 0;
-    off_s[tid] = off;
-    return total;
-  };
+  auto scan_block = [&](int pb) -> int64_t { return ivf_prefix_block(pre, probe, p.nprobe, p.nlist, p.list_offsets, pb, tid); };
 
   int64_t Lq = 0;
   for (int pb = 0; pb < n_blocks; ++pb) Lq += scan_block(pb);
@@ -169,18 +136,7 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(IvfParams p) {
   // row number at position v of the current block (relative to the block's first position), -1 when there is none,
   // the row is outside the index or its mask bit is clear
   auto row_at = [&](int64_t v, int64_t end, int n_in_block) -> int {
-    if (v >= end) return -1;
-    int a = 0, b = n_in_block;   // first j in (a, b] with pre_s[j] > v; the list is j - 1
-    while (b - a > 1) {
-      const int mid = (a + b) >> 1;
-      if (pre_s[mid] > v) b = mid; else a = mid;
-    }
-    const int64_t at = off_s[a] + (v - pre_s[a]);
-    if (at < 0 || at >= p.n_rows) return -1;
-    const int r = p.list_rows[at];
-    if (r < 0 || r >= p.n_rows) return -1;
-    if (p.row_mask && ((p.row_mask[r >> 5] >> (r & 31)) & 1u) == 0u) return -1;
-    return r;
+    return ivf_row_at(pre, v, end, n_in_block, p.list_rows, p.row_mask, p.n_rows);
   };
   float4 regs[IVF_LOADS];
   auto load_chunk = [&](const int* rid) {

@@ -2,7 +2,7 @@
 
 The reference's ``configs/index.yaml`` names three index types - ``hnsw``, ``ivf_pq`` ("for >50M vectors", with
 ``nlist`` / ``nprobe``) and ``flat`` - and a validation gate (``recall_threshold: 0.97`` against brute force).  This is
-the IVF half over uncompressed rows (the PQ half, ``m`` / ``nbits``, is not implemented: rows stay fp32).
+the IVF half over uncompressed rows; the PQ half (``m`` / ``nbits``) is ``pq.IVFPQIndex``, which subclasses this index.
 
 * The rows are a ``FAISSIndexBuilder`` (``ivf.flat``), not permuted and not copied; the lists are a CSR over row numbers
   in HBM (``list_offsets`` int64 ``[nlist + 1]``, ``list_rows`` int32 ``[ntotal]``, ascending within a list) and the
@@ -365,7 +365,7 @@ class IVFIndex:
     PROBE_SCAN_MAX_NQ = 64
     PROBE_SCAN_NPROBE = (11, 32)
 
-    def _probe_by_scan(self, q: torch.Tensor, nprobe: int) -> torch.Tensor:
+    def _probe_by_scan(self, q: torch.Tensor, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
         lib = _native.load()
         nq, nlist, quant = q.shape[0], self.nlist, self.quantizer
         if self._all_lists is None or self._all_lists[1].numel() != nlist:
@@ -381,17 +381,30 @@ class IVFIndex:
             quant._tiled.data_ptr(), nlist, q.data_ptr(), nq, zero.data_ptr(), 1, offsets.data_ptr(), rows.data_ptr(), 1,
             nprobe, 0, None, scores.data_ptr(), ids.data_ptr(), self._probe_workspace.data_ptr(), need,
             _native.current_stream_ptr(self.device)))
-        return ids
+        return scores, ids
 
-    def _probe_prepared(self, q: torch.Tensor, nprobe: int) -> torch.Tensor:
+    def _probe_scored(self, q: torch.Tensor, nprobe: int, want_scores: bool = True):
+        """``(scores or None, lists)`` of the probe: the scores are the coarse search's own fp32 bits (the fma chain
+        over the centroid rows).  Probing every one of more than 1 024 lists has no search behind it; its scores, when
+        asked for, come from ``sskd_similarity`` (the same chain)."""
         lo, hi = self.PROBE_SCAN_NPROBE
         if 1 <= q.shape[0] <= self.PROBE_SCAN_MAX_NQ and lo <= nprobe <= hi:
             return self._probe_by_scan(q, nprobe)
         if nprobe <= _native.SSKD_K_MAX:
-            return self.quantizer.search_device(q, nprobe, normalize_queries=False)[1]
+            return self.quantizer.search_device(q, nprobe, normalize_queries=False)
         if nprobe < self.nlist:
             raise ValueError(f"nprobe={nprobe}: a partial probe takes at most {_native.SSKD_K_MAX} lists")
-        return torch.arange(self.nlist, dtype=torch.int64, device=self.device).expand(q.shape[0], -1).contiguous()
+        ids = torch.arange(self.nlist, dtype=torch.int64, device=self.device).expand(q.shape[0], -1).contiguous()
+        if not want_scores:
+            return None, ids
+        scores = torch.empty((q.shape[0], self.nlist), dtype=torch.float32, device=self.device)
+        _native.check(_native.load().sskd_similarity(q.data_ptr(), q.shape[0], self.quantizer._tiled.data_ptr(), self.nlist,
+                                                     self.embedding_dim, scores.data_ptr(),
+                                                     _native.current_stream_ptr(self.device)))
+        return scores, ids
+
+    def _probe_prepared(self, q: torch.Tensor, nprobe: int) -> torch.Tensor:
+        return self._probe_scored(q, nprobe, want_scores=False)[1]
 
     def probe_device(self, queries: torch.Tensor, nprobe: Optional[int] = None,
                      normalize_queries: Optional[bool] = None) -> torch.Tensor:

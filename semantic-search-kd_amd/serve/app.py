@@ -66,7 +66,8 @@ class ServeSettings:
     semantic_weight: float = 0.7
     fusion_method: str = "rrf"   # rrf (reciprocal rank fusion), linear
     # ``index_type`` of the reference's configs/index.yaml:4 (hnsw | ivf_pq | flat): "ivf" retrieves through the inverted
-    # lists saved beside the index (ivf.IVFIndex) when the directory holds them; anything else is the exact scan
+    # lists saved beside the index (ivf.IVFIndex), "ivf_pq" through the lists and their PQ codes (pq.IVFPQIndex), when
+    # the directory holds them; anything else is the exact scan
     index_type: str = "flat"
 
     @staticmethod
@@ -101,7 +102,7 @@ class AppState:
         self.settings: Optional[ServeSettings] = None
         self.ready: bool = False
         self.hybrid = None   # hybrid.HybridIndex over index_builder when hybrid retrieval is on and its BM25 index fits
-        self.ivf = None      # ivf.IVFIndex over index_builder when the index type is "ivf" and the directory holds lists
+        self.ivf = None      # ivf.IVFIndex / pq.IVFPQIndex over index_builder when the index type asks for it and the directory holds its files
 
     def is_ready(self) -> bool:
         return self.ready and self.student is not None
@@ -151,20 +152,26 @@ def _load_hybrid(builder, settings: Optional["ServeSettings"]):
 
 
 def _load_ivf(builder, index_dir: Path, settings: Optional["ServeSettings"]):
-    """The ``IVFIndex`` /search retrieves through, or None (the exact scan): the index type is not "ivf", the directory
-    holds no ``ivf.json``, the index is row-sharded, or the lists do not load - then a warning is logged and the service
-    answers with the exact search."""
-    if settings is None or settings.index_type != "ivf":
+    """The ``IVFIndex`` (index type "ivf") or ``IVFPQIndex`` ("ivf_pq") /search retrieves through, or None (the exact
+    scan): the index type is neither, the directory holds no ``ivf.json`` (for "ivf_pq": no ``pq.json``), the index is
+    row-sharded, or the files do not load - then a warning is logged and the service answers with the exact search."""
+    if settings is None or settings.index_type not in ("ivf", "ivf_pq"):
         return None
     from ..ivf import IVFIndex, is_ivf_dir
+    from ..pq import IVFPQIndex, is_pq_dir
 
-    if not isinstance(builder, FAISSIndexBuilder) or not is_ivf_dir(index_dir):
-        logger.warning("Index type is ivf but %s holds no inverted lists over a single-GPU index: serving the exact scan",
-                       index_dir)
+    want_pq = settings.index_type == "ivf_pq"
+    if not isinstance(builder, FAISSIndexBuilder) or not is_ivf_dir(index_dir) or (want_pq and not is_pq_dir(index_dir)):
+        logger.warning("Index type is %s but %s holds no %s over a single-GPU index: serving the exact scan",
+                       settings.index_type, index_dir, "inverted lists with PQ codes" if want_pq else "inverted lists")
         return None
     try:
-        ivf = IVFIndex(flat=builder)
+        ivf = IVFPQIndex(flat=builder) if want_pq else IVFIndex(flat=builder)
         ivf.load_lists(index_dir)
+        if want_pq and ivf.refine == 0:
+            # an index saved with refine = 0 answers with raw ADC scores; the service's scores are exact inner products
+            logger.warning("%s stores refine = 0 (raw ADC scores): serving with the default exact re-ranking", index_dir)
+            ivf.refine = None
         return ivf
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the inverted lists (serving the exact scan): %s", exc)

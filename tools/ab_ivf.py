@@ -1,14 +1,17 @@
-"""A/B of the IVF search against the exact search: same process, same corpus, same queries.
+"""A/B of the IVF and IVF-PQ searches against the exact search: same process, same corpus, same queries (DESIGN
+sections 18 and 19).
 
     python tools/ab_ivf.py [--rows 1000000] [--nlist 1024] [--nprobe 1 8 32 128] [--batches 1 64 10000]
-                           [--iterations 10] [--reps 5] [--out FILE]
+                           [--iterations 10] [--reps 5] [--pq-m 64] [--pq-refine 100] [--pq-iterations 10] [--out FILE]
 
 The corpus is clustered (`--topics` unit centres, rows = unit(centre + N(0, I) / sqrt(384))) and every query is a noisy
 copy of a row (unit(row + 0.5 N(0, I) / sqrt(384))), so a probe of a few lists can find a query's neighbours at all; on
 rows without structure no inverted file has recall to trade.  For every batch size the exact side is
 `flat.search_device` (and, up to 64 queries, the one-pass path `flat.search` takes for the online shape); the IVF side is
 `IVFIndex.search_device` (coarse top-nprobe search + list scan + merge) for every `--nprobe`, with recall@10 of its ids
-against the exact ids beside each timing.  Every call is timed twice: eagerly (device events over `--iters` back-to-back
+against the exact ids beside each timing.  With `--pq-m` other than 0 the index is an `IVFPQIndex` over the same lists and
+`IVFPQIndex.search_device` (probe with scores + LUT + ADC scan of the codes + exact re-scoring of `--pq-refine` candidates)
+is timed for the same cells, with `refine = 0` (raw ADC) beside it.  Every call is timed twice: eagerly (device events over `--iters` back-to-back
 calls: what a Python caller sees, launch overhead included) and as a replayed graph of one call (the device time
 alone); median of `--reps` rounds after a warm-up.  Prints one JSON object.
 """
@@ -24,7 +27,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from semantic_search_kd_amd import FAISSIndexBuilder, IVFIndex, _native  # noqa: E402
+from semantic_search_kd_amd import FAISSIndexBuilder, IVFIndex, IVFPQIndex, _native  # noqa: E402
 from semantic_search_kd_amd.ivf import recall_at_k  # noqa: E402
 
 
@@ -67,6 +70,9 @@ def main():
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--pq-m", type=int, default=64, help="0: no PQ side")
+    ap.add_argument("--pq-refine", type=int, default=100)
+    ap.add_argument("--pq-iterations", type=int, default=10)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -83,19 +89,26 @@ def main():
     flat = FAISSIndexBuilder(embedding_dim=384, metric="ip", device="cuda:0")
     flat.build_from_embeddings(corpus)
     del corpus
-    index = IVFIndex(flat=flat)
+    index = IVFPQIndex(flat=flat, m=args.pq_m) if args.pq_m else IVFIndex(flat=flat)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    index.train(nlist=args.nlist, iterations=args.iterations)
+    IVFIndex.train(index, nlist=args.nlist, iterations=args.iterations)
     torch.cuda.synchronize()
     train_s = time.perf_counter() - t0
+    pq_train_s = None
+    if args.pq_m:
+        t0 = time.perf_counter()
+        index.train_pq(pq_iterations=args.pq_iterations)
+        torch.cuda.synchronize()
+        pq_train_s = round(time.perf_counter() - t0, 2)
     sizes = np.diff(index.lists_numpy()[0])
 
     lib = _native.load()
     result = {
         "rows": args.rows, "nlist": index.nlist, "k": args.k, "kmeans_iterations": args.iterations,
         "train_s": round(train_s, 2), "list_rows_min_mean_max": [int(sizes.min()), round(float(sizes.mean()), 1), int(sizes.max())],
-        "empty_lists": int((sizes == 0).sum()), "device": torch.cuda.get_device_name(0), "runs": [],
+        "empty_lists": int((sizes == 0).sum()), "pq_m": args.pq_m, "pq_refine": args.pq_refine,
+        "pq_iterations": args.pq_iterations, "pq_train_s": pq_train_s, "device": torch.cuda.get_device_name(0), "runs": [],
     }
     for nq in args.batches:
         q = queries[:nq].contiguous()
@@ -109,11 +122,11 @@ def main():
                 lambda: flat._search_onepass_device(q, args.k, False), iters, args.reps)
         row["ivf"] = []
         for nprobe in args.nprobe:
-            found = index.search_device(q, args.k, nprobe=nprobe, normalize_queries=False)[1].cpu().numpy()
+            found = IVFIndex.search_device(index, q, args.k, nprobe=nprobe, normalize_queries=False)[1].cpu().numpy()
             p = C.c_int(0)
             lib.sskd_ivf_search_plan(nq, min(nprobe, index.nlist), args.k, flat.ntotal, index.max_list_rows, C.byref(p), None, None)
             parts = p.value
-            eager, graph = _measure(lambda: index.search_device(q, args.k, nprobe=nprobe, normalize_queries=False),
+            eager, graph = _measure(lambda: IVFIndex.search_device(index, q, args.k, nprobe=nprobe, normalize_queries=False),
                                     iters, args.reps)
             probe = index.probe_device(q, nprobe, normalize_queries=False).cpu().numpy()
             row["ivf"].append({
@@ -122,6 +135,23 @@ def main():
                 "rows_read_fraction": round(float(sizes[probe].sum(axis=1).mean()) / args.rows, 5),
                 "flat_graph_over_ivf_graph": round(row["flat_graph_ms"] / graph, 2),
             })
+        row["pq"] = []
+        for nprobe in (args.nprobe if args.pq_m else []):
+            cell = {"nprobe": nprobe}
+            for name, refine in (("refined", args.pq_refine), ("adc", 0)):
+                def call(refine=refine):
+                    return index.search_device(q, args.k, nprobe=nprobe, refine=refine, normalize_queries=False)
+                found = call()[1].cpu().numpy()
+                p = C.c_int(0)
+                lib.sskd_pq_search_plan(min(nq, 4096), min(nprobe, index.nlist), args.k, refine, args.pq_m, flat.ntotal,
+                                        index.max_list_rows, C.byref(p), None, None, None)
+                eager, graph = _measure(call, iters, args.reps)
+                cell[name] = {"refine": refine, "parts": p.value, "eager_ms": eager, "graph_ms": graph,
+                              "recall_at_k": round(recall_at_k(found, exact), 4)}
+            ivf_graph = next(c["graph_ms"] for c in row["ivf"] if c["nprobe"] == nprobe)
+            cell["ivf_graph_over_pq_graph"] = round(ivf_graph / cell["refined"]["graph_ms"], 2)
+            cell["flat_graph_over_pq_graph"] = round(row["flat_graph_ms"] / cell["refined"]["graph_ms"], 2)
+            row["pq"].append(cell)
         result["runs"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
     line = json.dumps(result)
