@@ -631,6 +631,60 @@ int sskd_pq_search(const float* d_tiled, int64_t n_rows, const float* d_queries,
                    int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores, int64_t* d_out_ids,
                    int64_t* d_out_candidates, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Graph index: a fixed-degree k-NN graph over the flat index, beam search with exact scores
+ *   reference: the `hnsw` index type of configs/index.yaml:4-11 (M 32, efConstruction 200, efSearch 64) and its
+ *   validation block (recall_threshold 0.97).  This is a single-layer graph, built from exact k-NN lists; the rules
+ *   below are this library's definition.  WHICH rows a query scores is approximate; every score is the fp32 fma chain
+ *   of the exact scan and every order is (score descending, then lower id).
+ * Layout.  The rows are the flat index, unchanged (d_tiled, row-major fp32 [n_rows, 384]).  d_graph DEVICE int32
+ * [n_rows, M]: the out-edges of every row, -1 = none.  M even, 4 <= M <= 64.  The search accepts any adjacency: -1,
+ * ids outside [0, n_rows), self loops and repeated edges are harmless.
+ *
+ * Build.  d_knn DEVICE int32 [n_rows, knn_k] holds every row's nearest rows in rank order without the row itself (-1
+ * where there are none), M <= knn_k <= 128.  An entry is valid when it is in [0, n_rows) and not the row itself.
+ *   sskd_graph_prune.  Let L_u be the list of row u.  The detour count of L_u[j] is the number of i < j, L_u[i] valid,
+ *     for which some p < j has L_{L_u[i]}[p] == L_u[j].  d_fwd DEVICE int32 [n_rows, M] = the valid entries of L_u
+ *     ordered by (detour count ascending, j ascending), the first M of them, -1 padded.
+ *   Reverse edges (the caller's, a stable sort): d_rev DEVICE int32 [n_rows, M / 2], rev[v] = the rows u that have v
+ *     among the first M / 2 entries of fwd[u], ordered by (position of v in fwd[u], u), the first M / 2, -1 padded.
+ *   sskd_graph_merge.  graph[u] = the first M / 2 entries of fwd[u], then the entries of rev[u], then the remaining
+ *     entries of fwd[u]; an entry that is not valid or equals an earlier one is skipped; cut to M, -1 padded.
+ *   Both are integer-only and write every element of their output exactly once: two calls give the same bits.
+ *
+ * sskd_graph_search, per query.  T = the ef best rows scored so far in rank order, whatever the mask says, each with
+ * an "expanded" flag; R = the k best scored rows whose bit of d_row_mask is set (NULL: all rows; the format of
+ * "Filtered search").  To OFFER a set of rows: drop -1 and ids outside [0, n_rows), score the rest, and for T, and
+ * for R among allowed rows, ignore a row the list holds, insert any other, cut the list to its capacity - the top-ef
+ * (top-k) of the union under a total order, so the outcome does not depend on the order inside the set.  Procedure:
+ * offer the seeds; then, at most max_iterations times: take the first `width` entries of T in rank order that are not
+ * expanded (none: stop), mark them, offer the union of their M out-edges.  Result: R in rank order, ids row +
+ * id_offset, padded with (-FLT_MAX, -1); d_out_iterations (NULL or DEVICE int32 [nq]) = the iterations that expanded
+ * at least one row.  Because the worst entry of T and of R only improves, offering a row again never changes a list:
+ * the kernel's visited table is an optimisation and cannot change a bit of the result.
+ *   d_seeds DEVICE int64 [nq, n_seeds].  With d_seed_rows = NULL a seed is a row number; otherwise a seed s in
+ * [0, n_seed_rows) stands for row d_seed_rows[s] (DEVICE int32), which lets the ids of a search over an entry index
+ * be passed as they are.  -1 and anything out of range is no seed; a seed may repeat.
+ *   One workgroup of 256 threads per query, its whole state in LDS (sskd_graph_search_plan reports the workgroups,
+ * the threads, the LDS bytes of one workgroup - two fit a compute unit - and the rows one iteration offers at most,
+ * width * M; any out pointer may be NULL).  There is no workspace: sskd_graph_search_workspace_bytes is 0 for every
+ * shape and exists so that callers can size the three index types alike.  One query occupies one compute unit.
+ * Limits: 1 <= k <= ef <= 256; 1 <= width <= 8; max_iterations >= 1; 1 <= n_seeds <= 256; id_offset >= 0; n_rows <
+ * 2^31 - 64; d_queries and d_tiled 16-byte aligned.  Every call of this section is stream-ordered, does no host sync
+ * (graph-capturable) and allocates nothing; every argument is checked before anything is enqueued (SSKD_ERR_INVALID);
+ * nq = 0 (n_rows = 0 for the build calls) is a successful no-op.  A query holding NaN returns without fault and its
+ * result is unspecified (as built: a NaN score enters neither list, so the query gets padding and 0 iterations).
+ * ------------------------------------------------------------------------- */
+int sskd_graph_prune(const int32_t* d_knn, int64_t n_rows, int knn_k, int M, int32_t* d_fwd, void* stream);
+int sskd_graph_merge(const int32_t* d_fwd, const int32_t* d_rev, int64_t n_rows, int M, int32_t* d_graph, void* stream);
+int sskd_graph_search_plan(int nq, int k, int ef, int width, int M, int n_seeds, int* workgroups, int* threads,
+                           int* lds_bytes, int* step_rows);
+size_t sskd_graph_search_workspace_bytes(int nq, int k, int ef, int width, int M, int n_seeds);
+int sskd_graph_search(const float* d_tiled, int64_t n_rows, const int32_t* d_graph, int M, const float* d_queries, int nq,
+                      const int64_t* d_seeds, int n_seeds, const int32_t* d_seed_rows, int64_t n_seed_rows, int k, int ef,
+                      int width, int max_iterations, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
+                      int64_t* d_out_ids, int32_t* d_out_iterations, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -15,6 +15,7 @@ from .student import StudentModel  # noqa: F401
 from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELoss  # noqa: F401
 from .bm25 import BM25Index, build_bm25_index  # noqa: F401
 from .hybrid import HybridIndex  # noqa: F401
+from .graph import GraphIndex  # noqa: F401
 from .ivf import IVFIndex  # noqa: F401
 from .pq import IVFPQIndex  # noqa: F401
 from .evaluation import (  # noqa: F401
@@ -41,6 +42,7 @@ __all__ = [
     "BM25Miner",
     "build_bm25_index",
     "HybridIndex",
+    "GraphIndex",
     "IVFIndex",
     "IVFPQIndex",
     "KDEvaluator",

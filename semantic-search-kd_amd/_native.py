@@ -200,6 +200,13 @@ SIGNATURES = {
     "sskd_pq_search": (
         _i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
     ),
+    "sskd_graph_prune": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
+    "sskd_graph_merge": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "sskd_graph_search_plan": (_i, [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),
+    "sskd_graph_search_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sskd_graph_search": (
+        _i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

@@ -2,13 +2,15 @@
 """Build a search index from a parquet corpus with the MI355X encoder.
 
 Same flags as the reference's ``scripts/build_faiss_index.py:15-24`` (``--hnsw-*`` are accepted and
-ignored: the index is an exact scan, there is no graph to build).
+ignored by every index type but ``graph``: the default index is an exact scan, there is no graph to build).
 Run as ``python -m semantic_search_kd_amd.build_index_cli ...``.
 
 ``--index-type ivf`` trains inverted lists over the rows (``ivf.IVFIndex``: ``--nlist``, ``--nprobe``), checks recall@10
 of the IVF search against the exact search as the reference's ``validation:`` block prescribes (configs/index.yaml:51-56)
 and exits non-zero below ``--recall-threshold``; single-index builds only.  ``--index-type ivf_pq`` adds product-quantisation
 codes over the same lists (``pq.IVFPQIndex``: ``--pq-m``, ``--pq-refine``) behind the same recall gate.
+``--index-type graph`` builds a k-NN graph over the rows (``graph.GraphIndex``: ``--hnsw-m`` is its degree, ``--ef-search``
+its beam), again behind the recall gate and for single-index builds only.
 
 Row-sharded build (BASELINE cfg 3): launch the same command under
 ``python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m semantic_search_kd_amd.build_index_cli ...``
@@ -50,7 +52,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-docs", type=_positive, default=None)
     ap.add_argument("--batch-size", type=_positive, default=32)
     ap.add_argument("--device", type=_device, default="cuda")
-    ap.add_argument("--hnsw-m", type=_positive, default=32, help="accepted for compatibility; unused")
+    ap.add_argument("--hnsw-m", type=_positive, default=32, help="graph: the degree (even, 4 .. 64); otherwise accepted for compatibility and unused")
     ap.add_argument("--hnsw-ef-construction", type=_positive, default=200, help="accepted for compatibility; unused")
     ap.add_argument("--shards", type=int, default=0,
                     help="0 = one shard per rank when launched under torch.distributed.run, plain single index otherwise; "
@@ -58,17 +60,19 @@ def main(argv=None) -> int:
     ap.add_argument("--group-column", type=str, default=None,
                     help="parquet column holding the group key of every row (for example doc_id): the saved index "
                          "then answers search_grouped with distinct documents; single-index builds only")
-    ap.add_argument("--index-type", type=str, choices=("flat", "ivf", "ivf_pq"), default="flat",
+    ap.add_argument("--index-type", type=str, choices=("flat", "ivf", "ivf_pq", "graph"), default="flat",
                     help="flat = the exact scan; ivf = inverted lists over the same rows (nprobe search, exact scores); "
-                         "ivf_pq = the lists scanned through product-quantisation codes, the best candidates re-scored exactly")
+                         "ivf_pq = the lists scanned through product-quantisation codes, the best candidates re-scored exactly; "
+                         "graph = a k-NN graph over the same rows (beam search, exact scores)")
     ap.add_argument("--nlist", type=_positive, default=None, help="ivf: number of lists (default round(sqrt(rows)))")
     ap.add_argument("--nprobe", type=_positive, default=32, help="ivf: lists a query visits")
     ap.add_argument("--pq-m", type=_positive, default=64, help="ivf_pq: subquantisers per row (8, 16, 24, 32, 48, 64 or 96)")
     ap.add_argument("--pq-refine", type=int, default=None,
                     help="ivf_pq: candidates re-scored exactly per query, at least; a search for more than N results re-scores "
                          "that many (default: min(256, max(100, 4 k)) per search)")
+    ap.add_argument("--ef-search", type=_positive, default=64, help="graph: rows a search keeps in its beam (at most 256)")
     ap.add_argument("--recall-threshold", type=float, default=0.97,
-                    help="ivf: fail if recall@10 against the exact search is below this")
+                    help="ivf, ivf_pq, graph: fail if recall@10 against the exact search is below this")
     args = ap.parse_args(argv)
     for flag, p in (("--model-path", args.model_path), ("--data-path", args.data_path)):
         if not Path(p).exists():
@@ -79,8 +83,19 @@ def main(argv=None) -> int:
         if args.group_column:
             ap.error("--group-column: the row-sharded index has no grouped search yet")
         if args.index_type != "flat":
-            ap.error(f"--index-type {args.index_type}: the row-sharded index has no inverted lists yet")
+            what = "graph" if args.index_type == "graph" else "inverted lists"
+            ap.error(f"--index-type {args.index_type}: the row-sharded index has no {what} yet")
         return _build_sharded(args, world)
+
+    if args.index_type == "graph":
+        from .graph import GRAPH_EF_MAX, check_degree
+
+        try:
+            check_degree(args.hnsw_m)
+        except ValueError as exc:
+            ap.error(f"--hnsw-m: {exc}")
+        if args.ef_search > GRAPH_EF_MAX or args.ef_search < 10:
+            ap.error(f"--ef-search: a number in [10, {GRAPH_EF_MAX}] (the recall gate searches for 10 results)")
 
     model = StudentModel(args.model_path, device=args.device)
     builder = FAISSIndexBuilder(embedding_dim=384, index_type="HNSW", metric="cosine", device=args.device)
@@ -122,6 +137,18 @@ def main(argv=None) -> int:
         refine = "default" if ivf.refine is None else ivf.refine
         print(f"IVF-PQ lists: {ivf.nlist}, nprobe: {min(ivf.nprobe, ivf.nlist)}, m: {ivf.m}, refine: {refine}, "
               f"recall@10 vs exact: {recall:.4f}")
+        if recall < args.recall_threshold:
+            print(f"recall@10 {recall:.4f} is below the threshold {args.recall_threshold}", file=sys.stderr)
+            return 1
+    elif args.index_type == "graph":
+        from .graph import GraphIndex
+
+        graph = GraphIndex(flat=builder, M=args.hnsw_m, ef=args.ef_search)
+        graph.build_graph()
+        graph.save(Path(args.output_dir))
+        recall = graph.validate(num_queries=1000, k=10)
+        print(f"Graph degree: {graph.M}, k-NN lists: {graph.knn_k}, entry rows: {graph.n_entry}, ef: {graph.ef}, "
+              f"width: {graph.width}, recall@10 vs exact: {recall:.4f}")
         if recall < args.recall_threshold:
             print(f"recall@10 {recall:.4f} is below the threshold {args.recall_threshold}", file=sys.stderr)
             return 1

@@ -67,7 +67,8 @@ class ServeSettings:
     fusion_method: str = "rrf"   # rrf (reciprocal rank fusion), linear
     # ``index_type`` of the reference's configs/index.yaml:4 (hnsw | ivf_pq | flat): "ivf" retrieves through the inverted
     # lists saved beside the index (ivf.IVFIndex), "ivf_pq" through the lists and their PQ codes (pq.IVFPQIndex), when
-    # the directory holds them; anything else is the exact scan
+    # the directory holds them, "graph" through the k-NN graph saved beside the index (graph.GraphIndex); anything else
+    # ("hnsw" included) is the exact scan
     index_type: str = "flat"
 
     @staticmethod
@@ -103,6 +104,7 @@ class AppState:
         self.ready: bool = False
         self.hybrid = None   # hybrid.HybridIndex over index_builder when hybrid retrieval is on and its BM25 index fits
         self.ivf = None      # ivf.IVFIndex / pq.IVFPQIndex over index_builder when the index type asks for it and the directory holds its files
+        self.graph = None    # graph.GraphIndex over index_builder, likewise (index type "graph", graph.json)
 
     def is_ready(self) -> bool:
         return self.ready and self.student is not None
@@ -125,6 +127,7 @@ def _load_index_dir(index_dir: Path) -> Dict[str, Any]:
         app_state.doc_texts = builder.doc_texts
     app_state.hybrid = _load_hybrid(builder, app_state.settings)
     app_state.ivf = _load_ivf(builder, index_dir, app_state.settings)
+    app_state.graph = _load_graph(builder, index_dir, app_state.settings)
     return {"status": "loaded", "index_path": str(index_dir), "num_documents": len(app_state.doc_ids)}
 
 
@@ -148,6 +151,26 @@ def _load_hybrid(builder, settings: Optional["ServeSettings"]):
                            fusion_method=settings.fusion_method)
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the BM25 index (hybrid retrieval disabled, serving dense-only): %s", exc)
+        return None
+
+
+def _load_graph(builder, index_dir: Path, settings: Optional["ServeSettings"]):
+    """The ``GraphIndex`` /search retrieves through, or None (the exact scan): the index type is not "graph", the
+    directory holds no ``graph.json``, the index is row-sharded, or the files do not load - then a warning is logged
+    and the service answers with the exact search."""
+    if settings is None or settings.index_type != "graph":
+        return None
+    from ..graph import GraphIndex, is_graph_dir
+
+    if not isinstance(builder, FAISSIndexBuilder) or not is_graph_dir(index_dir):
+        logger.warning("Index type is graph but %s holds no graph over a single-GPU index: serving the exact scan", index_dir)
+        return None
+    try:
+        graph = GraphIndex(flat=builder)
+        graph.load_graph(index_dir)
+        return graph
+    except Exception as exc:  # noqa: BLE001
+        logger.warning("Failed to load the graph (serving the exact scan): %s", exc)
         return None
 
 
@@ -267,6 +290,9 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
                 distances, indices = hybrid.search([request.query], query_emb, k=min(k_retrieve, 2 * depth), depth=depth)
             elif app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_retrieve <= 256:
                 distances, indices = app_state.ivf.search(query_emb, k=k_retrieve)
+            elif (app_state.graph is not None and app_state.graph.flat is app_state.index_builder
+                  and k_retrieve <= app_state.graph.ef):
+                distances, indices = app_state.graph.search(query_emb, k=k_retrieve)
             else:
                 distances, indices = app_state.index_builder.search(query_emb, k=k_retrieve)
             results: List[SearchResult] = []

@@ -1,0 +1,439 @@
+"""Graph index on the GPU: which rows a query scores is approximate, every score and every order is exact.
+
+The oracle of a search is ``graph_cases.beam_search_ref`` - the beam search of ``include/sskd_amd.h`` ("Graph index")
+restated in plain Python WITHOUT a visited set - over ``oracle.scores_fma`` (the scan's fma order, in C): ids are
+compared with ``np.array_equal``, scores by their bits, iteration counts exactly.  The build kernels are compared with
+``detours_ref`` / ``reverse_ref`` / ``merge_ref`` by exact integer equality."""
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import graph_cases as gc
+from oracle import search as oracle
+from semantic_search_kd_amd import FAISSIndexBuilder, GraphIndex, _native, graph as graph_mod, ivf as ivf_mod
+
+pytestmark = pytest.mark.gpu
+
+N, DIM, NQ = 3001, 384, 65   # 3001 rows: a ragged last tile
+
+
+def _flat(corpus, gpu):
+    index = FAISSIndexBuilder(embedding_dim=DIM, metric="ip", device=str(gpu))
+    index.build_from_embeddings(corpus)
+    return index
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def _same(got, ref, what):
+    assert np.array_equal(got[1], ref[1]), f"{what}: ids differ"
+    assert np.array_equal(_bits(got[0]), _bits(ref[0])), f"{what}: scores differ"
+
+
+def _over(flat, adjacency, **args):
+    """A GraphIndex over ``flat`` with ANY int32 adjacency (``from_graph`` would refuse out-of-range edges)."""
+    index = GraphIndex(flat=flat, M=adjacency.shape[1], **args)
+    index._from_host(adjacency, None)
+    return index
+
+
+def _search(index, queries, k, ef, width, max_iterations, seeds=None, allow=None):
+    """``(scores, ids, iterations)`` as host arrays; ``seeds`` = host row numbers ``[nq, n]`` or None (the entry index)."""
+    q = torch.from_numpy(np.ascontiguousarray(queries)).to(index.device)
+    s = None if seeds is None else torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.int64)).to(index.device)
+    out = index.search_device(q, k, ef=ef, width=width, max_iterations=max_iterations, seeds=s, allow=allow,
+                              normalize_queries=False, return_iterations=True)
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in out)
+
+
+def _check(got, ref, what):
+    _same(got, ref, what)
+    assert np.array_equal(got[2], ref[2]), f"{what}: iteration counts differ: {got[2]} != {ref[2]}"
+
+
+def _entry_seeds_ref(scores, entry_rows, ef):
+    """The seeds the entry index gives: its exact top-min(ef, 32, n_entry), as row numbers."""
+    n_seed = min(ef, 32, entry_rows.size)
+    return entry_rows[oracle.topk_of_scores(scores[:, entry_rows], n_seed)[1]]
+
+
+@pytest.fixture(scope="module")
+def world(gpu):
+    corpus = oracle.seeded_unit_rows(N, DIM, 1)
+    queries = oracle.seeded_unit_rows(NQ, DIM, 2)
+    rng = np.random.default_rng(3)
+    seeds = rng.integers(0, N, size=(NQ, 16)).astype(np.int64)
+    seeds[:, 3] = -1                      # no seed
+    seeds[:, 5] = seeds[:, 4]             # a seed twice
+    seeds[:, 7] = N + 11                  # outside the index
+    w = SimpleNamespace(corpus=corpus, queries=queries, flat=_flat(corpus, gpu), seeds=seeds,
+                        scores=oracle.scores_fma(queries, corpus), adjacency={}, index={})
+    for degree in (4, 32, 64):
+        w.adjacency[degree] = gc.random_adjacency(N, degree, 100 + degree)
+        w.index[degree] = _over(w.flat, w.adjacency[degree])
+
+    @functools.lru_cache(maxsize=None)
+    def ref(degree, ef, k, width, max_iterations):
+        return gc.beam_search_batch_ref(w.scores, w.adjacency[degree], seeds, ef, width, max_iterations, k)
+
+    w.ref = ref
+    return w
+
+
+# ------------------------------------------------------------------------------ the search against the restatement
+@pytest.mark.parametrize("max_iterations", [1, 3, "ef"])
+@pytest.mark.parametrize("degree", [4, 32, 64])
+@pytest.mark.parametrize("width", [1, 4, 8])
+@pytest.mark.parametrize("ef, k", [(16, 16), (64, 1), (64, 10), (256, 256)])
+@pytest.mark.parametrize("nq", [1, NQ])
+def test_search_equals_the_restatement_on_arbitrary_adjacency(world, nq, ef, k, width, degree, max_iterations):
+    """Random int32 adjacency (not a k-NN graph) with -1 pads, self loops, repeated edges and out-of-range ids."""
+    max_iterations = ef if max_iterations == "ef" else max_iterations
+    adjacency = world.adjacency[degree]
+    assert (adjacency == -1).any() and (adjacency >= N).any() and (adjacency < -1).any()
+    assert (adjacency[:, 0] == np.arange(N)).any() and (adjacency[:, -1] == adjacency[:, 1]).any()
+    got = _search(world.index[degree], world.queries[:nq], k, ef, width, max_iterations, world.seeds[:nq])
+    ref = tuple(a[:nq] for a in world.ref(degree, ef, k, width, max_iterations))
+    _check(got, ref, f"nq={nq} ef={ef} k={k} width={width} degree={degree} max_iterations={max_iterations}")
+
+
+def test_seeds_come_from_the_exact_search_of_the_entry_index(world):
+    index = world.index[32]
+    entry_rows = index.entry_rows_numpy()
+    assert np.array_equal(entry_rows, graph_mod.entry_rows_of(N, graph_mod.default_n_entry(N, 32))) and index.n_entry == 94
+    assert np.array_equal(_bits(index.entry.to_numpy()), _bits(world.corpus[entry_rows]))
+    for ef in (8, 64):
+        seeds = _entry_seeds_ref(world.scores, entry_rows, ef)
+        assert seeds.shape == (NQ, min(ef, 32))
+        got = _search(index, world.queries, min(ef, 10), ef, 4, ef)
+        _check(got, gc.beam_search_batch_ref(world.scores, world.adjacency[32], seeds, ef, 4, ef, min(ef, 10)), f"ef={ef}")
+    # the host call and its defaults (ef and width from the index, max_iterations = ef)
+    index.ef, index.width = 64, 2
+    host = index.search(world.queries, 10)
+    assert index.last_search_path == "graph"
+    seeds = _entry_seeds_ref(world.scores, entry_rows, 64)
+    _same(host, gc.beam_search_batch_ref(world.scores, world.adjacency[32], seeds, 64, 2, 64, 10), "search()")
+
+
+# ------------------------------------------------------------------------------------- anchor to the exact search
+def test_ring_with_a_beam_wider_than_the_index_is_the_exact_search(gpu):
+    n = 200
+    corpus = oracle.seeded_unit_rows(n, DIM, 11)
+    queries = oracle.seeded_unit_rows(NQ, DIM, 12)
+    flat = _flat(corpus, gpu)
+    index = GraphIndex.from_graph(flat, gc.ring_graph(n, 4))
+    for width in (1, 8):
+        for k in (1, 10, 200):
+            got = index.search(queries, k, ef=256, width=width, max_iterations=256)
+            _same(got, flat.search(queries, k), f"k={k} width={width} vs flat.search")
+            _same(got, oracle.topk_of_scores(oracle.scores_fma(queries, corpus), k), f"k={k} width={width} vs oracle")
+    D, I = index.search(queries, 256, ef=256, width=4, max_iterations=256)
+    _same((D[:, :200], I[:, :200]), flat.search(queries, 200), "k=256: the 200 rows")
+    assert (I[:, 200:] == -1).all() and (D[:, 200:] == oracle.NEG_PAD).all()
+
+
+# --------------------------------------------------------------------------- the visited filter cannot change bits
+def test_nearly_every_edge_points_at_a_visited_row(gpu):
+    n = 64
+    corpus = oracle.seeded_unit_rows(n, DIM, 21)
+    queries = oracle.seeded_unit_rows(NQ, DIM, 22)
+    adjacency = np.random.default_rng(23).integers(0, n, size=(n, 64)).astype(np.int32)
+    index = _over(_flat(corpus, gpu), adjacency)
+    scores = oracle.scores_fma(queries, corpus)
+    seeds = np.zeros((NQ, 1), dtype=np.int64)
+    for ef, k, width in ((64, 64, 8), (16, 10, 1), (256, 64, 4)):
+        got = _search(index, queries, k, ef, width, ef, seeds)
+        _check(got, gc.beam_search_batch_ref(scores, adjacency, seeds, ef, width, ef, k), f"ef={ef} width={width}")
+
+
+def test_far_more_rows_scored_than_the_visited_table_holds(world):
+    """ef 256, width 8, degree 64, 256 iterations at most: thousands of offers per query, several table resets."""
+    nq = 8
+    got = _search(world.index[64], world.queries[:nq], 256, 256, 8, 256, world.seeds[:nq])
+    ref = tuple(a[:nq] for a in world.ref(64, 256, 256, 8, 256))
+    assert (ref[2] * 8 * 64 > 4 * 2048).all()    # offers per query against the table's 2 048 slots
+    _check(got, ref, "table resets")
+
+
+# --------------------------------------------------------------------------------------------- edges of the contract
+def test_disconnected_graph_seeds_and_padding(gpu):
+    n = 200
+    corpus = oracle.seeded_unit_rows(n, DIM, 31)
+    queries = oracle.seeded_unit_rows(9, DIM, 32)
+    scores = oracle.scores_fma(queries, corpus)
+    adjacency = np.concatenate([gc.ring_graph(100, 4), 100 + gc.ring_graph(100, 4)])   # two rings that never meet
+    index = _over(_flat(corpus, gpu), adjacency)
+    low = np.full((9, 2), 5, dtype=np.int64)      # (a seed twice)
+    got = _search(index, queries, 150, 256, 4, 256, low)
+    _check(got, gc.beam_search_batch_ref(scores, adjacency, low, 256, 4, 256, 150), "one component")
+    assert (got[1][:, :100] >= 0).all() and (got[1][:, :100] < 100).all()          # the unreachable ring is never returned
+    assert (got[1][:, 100:] == -1).all() and (got[0][:, 100:] == oracle.NEG_PAD).all()
+    masked = np.where(np.arange(n)[None, :] < 100, scores, -np.inf)
+    _same(got[:2], oracle.topk_of_scores(masked, 150), "the reachable ring, exactly")
+    # no seed at all: nothing but padding, no iteration
+    none = np.full((9, 4), -1, dtype=np.int64)
+    s, i, it = _search(index, queries, 10, 64, 4, 64, none)
+    assert (i == -1).all() and (s == oracle.NEG_PAD).all() and (it == 0).all()
+    # a seed in each ring, one of them three times
+    both = np.tile(np.array([[7, 150, 150, 150, -1]], dtype=np.int64), (9, 1))
+    got = _search(index, queries, 200, 256, 8, 256, both)
+    _check(got, gc.beam_search_batch_ref(scores, adjacency, both, 256, 8, 256, 200), "both components")
+    _same(got[:2], oracle.topk_of_scores(scores, 200), "both components, exactly")
+
+
+def test_a_query_holding_nan_returns_padding(world):
+    """A NaN score ranks nowhere, so it enters no list: the query gets padding and no iteration, its neighbours in the
+    batch are untouched (the contract leaves such a query's result open; this is what the kernel does)."""
+    q = world.queries[:5].copy()
+    q[2, 17] = np.nan
+    for allow in (None, np.arange(0, N, 2)):
+        s, i, it = _search(world.index[32], q, 10, 64, 4, 64, world.seeds[:5], allow=allow)
+        assert (i[2] == -1).all() and (s[2] == oracle.NEG_PAD).all() and it[2] == 0
+        allowed = None if allow is None else np.isin(np.arange(N), allow)
+        ref = gc.beam_search_batch_ref(world.scores[:5], world.adjacency[32], world.seeds[:5], 64, 4, 64, 10, allowed)
+        keep = [0, 1, 3, 4]
+        _check(tuple(a[keep] for a in (s, i, it)), tuple(a[keep] for a in ref), "the other queries")
+
+
+def test_ties_come_out_in_ascending_id_order(gpu):
+    """40 vectors, each stored at three ids."""
+    n = 600
+    corpus = oracle.seeded_unit_rows(n, DIM, 41)
+    base = oracle.seeded_unit_rows(40, DIM, 42)
+    ids = np.random.default_rng(43).permutation(n)[:120].reshape(40, 3)
+    for j in range(40):
+        corpus[ids[j]] = base[j]
+    index = GraphIndex(flat=_flat(corpus, gpu), M=16)
+    index.build_graph()
+    queries = np.concatenate([base[:24], oracle.seeded_unit_rows(8, DIM, 45)])
+    scores = oracle.scores_fma(queries, corpus)
+    seeds = _entry_seeds_ref(scores, index.entry_rows_numpy(), 64)
+    got = _search(index, queries, 10, 64, 4, 64)
+    _check(got, gc.beam_search_batch_ref(scores, index.graph_numpy(), seeds, 64, 4, 64, 10), "ties")
+    D, I = got[:2]
+    equal = _bits(D)[:, 1:] == _bits(D)[:, :-1]
+    assert equal.any() and (I[:, 1:][equal] > I[:, :-1][equal]).all()
+
+
+def test_allow_masks_and_removed_rows(world, gpu):
+    flat = _flat(world.corpus, gpu)
+    index = _over(flat, world.adjacency[32])
+    rng = np.random.default_rng(51)
+    removed = rng.permutation(N)[:300]
+    assert index.remove_ids(removed) == 300
+    live = np.ones(N, dtype=np.bool_)
+    live[removed] = False
+    few = np.zeros(N, dtype=np.bool_)
+    few[rng.permutation(N)[:7]] = True
+    cases = {"no filter": None, "half": rng.random(N) < 0.5, "one percent": rng.random(N) < 0.01,
+             "none": np.zeros(N, dtype=np.bool_), "fewer than k": few}
+    for name, allow in cases.items():
+        allowed = live if allow is None else (allow & live)
+        for ef, k, width in ((64, 10, 4), (256, 256, 8)):
+            got = _search(index, world.queries, k, ef, width, ef, world.seeds, allow=allow)
+            ref = gc.beam_search_batch_ref(world.scores, world.adjacency[32], world.seeds, ef, width, ef, k, allowed)
+            _check(got, ref, f"{name} ef={ef}")
+            hit = got[1][got[1] >= 0]
+            assert allowed[hit].all(), f"{name}: a hidden row was returned"
+            # hidden rows are traversed all the same: the walk (its length) is the unmasked one
+            assert np.array_equal(got[2], world.ref(32, ef, k, width, ef)[2])
+    s, i, _ = _search(index, world.queries, 10, 64, 4, 64, world.seeds, allow=cases["none"])
+    assert (i == -1).all() and (s == oracle.NEG_PAD).all()
+    # an id array and a prepared RowFilter are the same filter
+    want = _search(index, world.queries, 10, 64, 4, 64, world.seeds, allow=cases["half"])
+    _check(_search(index, world.queries, 10, 64, 4, 64, world.seeds, allow=np.flatnonzero(cases["half"])), want, "id array")
+    _check(_search(index, world.queries, 10, 64, 4, 64, world.seeds, allow=flat.row_filter(cases["half"])), want, "RowFilter")
+
+
+# --------------------------------------------------------------------------------------------------------- build
+def _knn_ref(corpus, K0):
+    ids = oracle.topk_of_scores(oracle.scores_fma(corpus, corpus), K0 + 1)[1]
+    out = np.empty((corpus.shape[0], K0), dtype=np.int32)
+    for u, row in enumerate(ids):
+        own = np.flatnonzero(row == u)
+        out[u] = np.delete(row, own[0] if own.size else K0)
+    return out
+
+
+@pytest.mark.parametrize("n, K0, M", [(N, 64, 32), (50, 8, 4), (20, 32, 8)])
+def test_build_steps_against_the_restatements(world, gpu, n, K0, M):
+    corpus = world.corpus[:n]
+    index = GraphIndex(flat=world.flat if n == N else _flat(corpus, gpu), M=M)
+    with torch.cuda.device(index.device):
+        knn = index.knn_device(K0)
+        fwd = index.prune_device(knn, M)
+        rev = index.reverse_device(fwd)
+        merged = index.merge_device(fwd, rev)
+        torch.cuda.synchronize()
+    knn, fwd, rev, merged = (t.cpu().numpy() for t in (knn, fwd, rev, merged))
+    assert knn.dtype == np.int32 and np.array_equal(knn, _knn_ref(corpus, K0))
+    if n == 20:
+        assert (knn[:, 19:] == -1).all() and (knn[:, :19] >= 0).all()   # lists padded with -1
+    det, fwd_ref = gc.detours_ref(knn, M)
+    assert det.max() > 0
+    assert np.array_equal(fwd, fwd_ref), "sskd_graph_prune"
+    rev_ref = gc.reverse_ref(fwd_ref)
+    assert np.array_equal(rev, rev_ref), "reverse edges"
+    assert np.array_equal(merged, gc.merge_ref(fwd_ref, rev_ref)), "sskd_graph_merge"
+    # the whole build, twice: the same bits; no self edge, no edge twice
+    index.build_graph(M=M, knn_k=K0)
+    first = index.graph_numpy()
+    assert np.array_equal(first, merged) and index.M == M and index.knn_k == K0
+    index.build_graph(M=M, knn_k=K0)
+    assert np.array_equal(index.graph_numpy(), first)
+    for u, row in enumerate(first):
+        real = row[row >= 0]
+        assert u not in real and np.unique(real).size == real.size and (row[real.size:] == -1).all() and (real < n).all()
+
+
+def test_merge_skips_what_is_not_an_edge(gpu, native_lib):
+    """Straight through the C-ABI with hand-made lists: self edges, repeats, -1 and out-of-range entries."""
+    n, M = 37, 8
+    rng = np.random.default_rng(61)
+    fwd = rng.integers(-1, n + 2, size=(n, M)).astype(np.int32)
+    rev = rng.integers(-1, n + 2, size=(n, M // 2)).astype(np.int32)
+    fwd[:, 5] = fwd[:, 0]
+    rev[:, 1] = fwd[:, 2]
+    fwd[::3, 1] = np.arange(n)[::3]
+    d_fwd, d_rev = torch.from_numpy(fwd).to(gpu), torch.from_numpy(rev).to(gpu)
+    out = torch.full((n + 1, M), 77, dtype=torch.int32, device=gpu)
+    _native.check(native_lib.sskd_graph_merge(d_fwd.data_ptr(), d_rev.data_ptr(), n, M, out.data_ptr(),
+                                              _native.current_stream_ptr(gpu)))
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    assert (out[n] == 77).all()                                          # nothing written past the last row
+    assert np.array_equal(out[:n], gc.merge_ref(fwd, rev))
+
+
+def _unit(x):
+    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+
+
+def test_recall_gate(gpu):
+    """recall@10 >= 0.97 (recall_threshold of the reference's configs/index.yaml) against the index's own exact search
+    on the clustered corpus of test_ivf_gpu.py's gate: 64 unit centres, 20 000 rows unit(centre + N(0, I) / sqrt(384)),
+    500 queries unit(row + 0.5 N(0, I) / sqrt(384)) from 500 distinct rows.  Built with the defaults, searched at ef 64."""
+    rng = np.random.default_rng(0)
+    centres = _unit(rng.standard_normal((64, DIM)))
+    topic = rng.integers(0, 64, size=20000)
+    rows = _unit(centres[topic] + rng.standard_normal((20000, DIM)) / np.sqrt(DIM))
+    picked = rng.permutation(20000)[:500]
+    queries = _unit(rows[picked] + 0.5 * rng.standard_normal((500, DIM)) / np.sqrt(DIM))
+    index = GraphIndex(embedding_dim=DIM, metric="ip", device=str(gpu))
+    index.build_from_embeddings(rows)
+    assert index.ntotal == 20000 and index.M == 32 and index.knn_k == 64 and index.ef == 64 and index.n_entry == 625
+    truth = index.flat.search(queries, 10)[1]
+    recall = {ef: ivf_mod.recall_at_k(index.search(queries, 10, ef=ef)[1], truth) for ef in (16, 64, 256)}
+    print(f"recall@10 of 500 noisy queries by ef: {recall}; width {index.width}")
+    validated = index.validate(num_queries=1000, k=10, seed=0)
+    print(f"validate(): {validated:.4f}")
+    assert recall[64] >= 0.97
+    assert validated >= 0.97
+
+
+# ---------------------------------------------------------------------------------------------------- lifecycle
+@pytest.fixture(scope="module")
+def built(world, gpu):
+    index = GraphIndex(flat=_flat(world.corpus, gpu), M=16)
+    index.build_graph()
+    return index
+
+
+def _built_ref(index, corpus, queries, k, ef, width, allowed=None):
+    scores = oracle.scores_fma(queries, corpus)
+    seeds = _entry_seeds_ref(scores, index.entry_rows_numpy(), ef)
+    return gc.beam_search_batch_ref(scores, index.graph_numpy(), seeds, ef, width, ef, k, allowed)
+
+
+def test_add_rebuilds_the_graph_over_all_rows(world, gpu):
+    index = GraphIndex(flat=_flat(world.corpus[:2500], gpu), M=16)
+    index.build_graph()
+    index.add(world.corpus[2500:])
+    assert index.ntotal == N and index.graph_numpy().shape == (N, 16) and index.n_entry == graph_mod.default_n_entry(N, 16)
+    fresh = GraphIndex(flat=_flat(world.corpus, gpu), M=16)
+    fresh.build_graph()
+    assert np.array_equal(index.graph_numpy(), fresh.graph_numpy())
+    assert np.array_equal(index.entry_rows_numpy(), fresh.entry_rows_numpy())
+    _same(index.search(world.queries, 10, width=4), fresh.search(world.queries, 10, width=4), "after add")
+    D, I = index.search(world.corpus[2500:2564], 1, width=4)   # a new row finds itself
+    assert np.array_equal(I[:, 0], 2500 + np.arange(64))
+
+
+def test_remove_then_compact(world, gpu):
+    index = GraphIndex(flat=_flat(world.corpus, gpu), M=16)
+    index.build_graph()
+    gone = np.random.default_rng(71).permutation(N)[:400]
+    index.remove_ids(gone)
+    live = np.ones(N, dtype=np.bool_)
+    live[gone] = False
+    q = world.queries
+    got = _search(index, q, 10, 64, 4, 64)
+    _check(got, _built_ref(index, world.corpus, q, 10, 64, 4, live), "removed rows")
+    assert live[got[1][got[1] >= 0]].all()
+    old = index.graph_numpy()
+    kept = index.compact()
+    assert kept.size == N - 400 and index.ntotal == N - 400 and index.flat.n_removed == 0
+    assert np.array_equal(index.graph_numpy(), gc.remap_graph_ref(old, kept))
+    assert np.array_equal(index.entry_rows_numpy(), graph_mod.entry_rows_of(N - 400, graph_mod.default_n_entry(N - 400, 16)))
+    _check(_search(index, q, 10, 64, 4, 64), _built_ref(index, world.corpus[kept], q, 10, 64, 4), "after compact")
+    _same(index.flat.search(q, 10), oracle.topk_of_scores(oracle.scores_fma(q, world.corpus[kept]), 10), "flat after compact")
+
+
+def test_save_load(built, world, tmp_path):
+    q = world.queries
+    built.ef, built.width = 48, 2
+    before = built.search(q, 10)
+    built.save(tmp_path)
+    for name in ("index.faiss", "doc_ids.json", "graph.npy", "graph_entry_rows.npy", "graph.json"):
+        assert (tmp_path / name).exists(), name
+    again = GraphIndex(embedding_dim=DIM, metric="ip", device=str(built.device))
+    again.load(tmp_path)
+    assert again.ntotal == N and again.M == 16 and again.knn_k == 32 and again.ef == 48 and again.width == 2
+    assert np.array_equal(again.graph_numpy(), built.graph_numpy())
+    _same(again.search(q, 10), before, "after load")
+    # the flat loader ignores the extra files and still answers exactly
+    plain = FAISSIndexBuilder(embedding_dim=DIM, metric="ip", device=str(built.device))
+    plain.load(tmp_path)
+    _same(plain.search(q, 10), oracle.topk_of_scores(world.scores, 10), "FAISSIndexBuilder.load")
+
+
+def test_search_device_under_graph_capture(built, world):
+    q = torch.from_numpy(world.queries[:8].copy()).cuda()
+    ref = built.search(world.queries[:8], 10, ef=64, width=4)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        eager = built.search_device(q, 10, ef=64, width=4)   # sizes the entry search's workspace
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        captured = built.search_device(q, 10, ef=64, width=4)
+    g.replay()
+    torch.cuda.synchronize()
+    for name, got in (("eager", eager), ("graph", captured)):
+        _same(tuple(t.cpu().numpy() for t in got), ref, name)
+
+
+def test_python_argument_checks(built, world):
+    q = world.queries[:2]
+    for bad in (dict(k=0), dict(k=65), dict(k=10, ef=257), dict(k=10, ef=0), dict(k=10, width=0), dict(k=10, width=9),
+                dict(k=10, max_iterations=0)):
+        with pytest.raises(ValueError):
+            built.search(q, **bad)
+    fresh = GraphIndex(flat=built.flat)
+    with pytest.raises(RuntimeError):
+        fresh.search(q, 10)   # no graph yet
+    for bad in (dict(M=5), dict(M=66), dict(M=32, knn_k=16), dict(M=32, knn_k=129)):
+        with pytest.raises(ValueError):
+            fresh.build_graph(**bad)
+    with pytest.raises(ValueError):
+        GraphIndex.from_graph(built.flat, np.zeros((N, 7), np.int32))
+    with pytest.raises(ValueError):
+        GraphIndex.from_graph(built.flat, np.full((N, 8), N, np.int32))
