@@ -12,7 +12,7 @@ import torch
 import pq_cases as pc
 from capi_helpers import stream
 from oracle import search as oracle
-from semantic_search_kd_amd import FAISSIndexBuilder, IVFIndex, IVFPQIndex, _native, ivf as ivf_mod
+from semantic_search_kd_amd import FAISSIndexBuilder, IVFIndex, IVFPQIndex, _native, ivf as ivf_mod, pq
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +85,46 @@ def test_world_codes_are_the_restatement(world):
     assert world.index.codes_by_row.dtype == torch.uint8 and world.index.m == M
 
 
+# ------------------------------------------------------------------------------------------ one world per m
+# Every m is its own instance of pq_scan_kernel<M> and pq_encode_kernel<384 / M>: the worlds below share the corpus, the
+# queries and the lists of ``world`` and differ in the codebooks, the codes and the index.
+def world_seed(m):
+    """the codebook seed of the world of ``m`` (test_pq_host.py checks that m = 96 has no tied encoding distance with it)"""
+    return 100 + m
+
+
+@pytest.fixture(scope="module")
+def mworlds(world):
+    """m -> the world of that m, built on first use and kept; m = 64 keeps the codebooks, codes and index of ``world``"""
+    built = {M: SimpleNamespace(**vars(world), m=M)}
+
+    def get(m):
+        if m not in built:
+            cb = _sample_codebooks(world.resid, m, world_seed(m))
+            index = IVFPQIndex.from_codebooks(world.flat, world.centroids, world.assignment, cb)   # the device encodes
+            built[m] = SimpleNamespace(**{**vars(world), "cb": cb, "codes": pc.encode(world.resid, cb), "index": index}, m=m)
+        return built[m]
+
+    return get
+
+
+@pytest.fixture(scope="module", params=pq.PQ_M_ALLOWED)
+def mworld(mworlds, request):
+    return mworlds(request.param)
+
+
+@pytest.fixture(scope="module")
+def mranked(mworld):
+    """the restatement's rankings of the world of one m: every query at nprobe 1 and 16, eight at nprobe 4"""
+    return {p: _rankings(mworld, mworld.queries[:nq], p) for p, nq in ((1, 65), (4, 8), (16, 65))}
+
+
+def test_every_world_holds_the_restatements_codes(mworld):
+    assert np.array_equal(mworld.index.codes_numpy(), mworld.codes)
+    assert np.array_equal(mworld.index.codes_csr.cpu().numpy(), mworld.codes[mworld.rows])
+    assert mworld.index.m == mworld.m and mworld.index.codebooks_numpy().shape == (mworld.m, pc.CODES, DIM // mworld.m)
+
+
 # ------------------------------------------------------------------------------------------------------ encode
 def _encode(lib, w, n, cb, residual):
     m = cb.shape[0]
@@ -100,7 +140,7 @@ def _encode(lib, w, n, cb, residual):
 
 
 @pytest.mark.parametrize("residual", [True, False])
-@pytest.mark.parametrize("m", [8, 64, 96])
+@pytest.mark.parametrize("m", pq.PQ_M_ALLOWED)
 def test_encode(world, native_lib, m, residual):
     resid = world.resid if residual else world.corpus
     cb = world.cb if (m == M and residual) else _sample_codebooks(resid, m, 10 + m)
@@ -123,8 +163,7 @@ def test_encode_duplicated_entries_take_the_lower_code(world, native_lib):
 
 
 # --------------------------------------------------------------------------------------------------- code sums
-def test_code_sums(world):
-    m = 8
+def _code_sums_case(world, m):
     cb = _sample_codebooks(world.resid, m, 21)
     codes = pc.encode(world.resid, cb)
     codes[codes == 9] = 10   # code 9 is empty in every subspace
@@ -147,8 +186,17 @@ def test_code_sums(world):
     assert np.array_equal(pc.bits64(s3.cpu().numpy()), pc.bits64(ref3[0])) and np.array_equal(c3.cpu().numpy(), ref3[1])
 
 
+def test_code_sums(world):
+    _code_sums_case(world, 8)
+
+
+@pytest.mark.parametrize("m", [m for m in pq.PQ_M_ALLOWED if m != 8])
+def test_code_sums_every_other_m(world, m):
+    _code_sums_case(world, m)
+
+
 # --------------------------------------------------------------------------------------------------------- LUT
-@pytest.mark.parametrize("m", [8, 64, 96])
+@pytest.mark.parametrize("m", pq.PQ_M_ALLOWED)
 def test_lut(world, native_lib, m):
     cb = world.cb if m == M else _sample_codebooks(world.resid, m, 30 + m)
     nq = 65
@@ -193,6 +241,33 @@ def test_refined_search_is_the_exact_search_over_the_candidates(world, ranked, k
         assert np.array_equal(np.sort(cand[i][cand[i] >= 0]), np.sort(ref_rows))
         _same((D[i:i + 1], I[i:i + 1]), world.flat.search(q[i:i + 1], k, allow=cand[i][cand[i] >= 0]), f"query {i}")
     _same(world.index.search(q, k, nprobe=4, refine=R), (D, I), "search == search_with_candidates")
+
+
+# --------------------------------------------------------------------------------- the scan kernel of every m
+@pytest.mark.parametrize("k", [10, 256])
+@pytest.mark.parametrize("nprobe", [1, 16])
+@pytest.mark.parametrize("nq", [1, 65])
+def test_adc_search_without_refinement_every_m(mworld, mranked, nq, nprobe, k):
+    """pq_scan_kernel<m> against the restatement's ADC ranking, bit for bit.  nprobe = 1 is one list of about 190 rows (one
+    partial step, fewer rows than k = 256: the tail is padding); nprobe = 16 is all 3 001 rows: twelve steps, the last one
+    partial, and the pool of 1 024 records fills and is compacted."""
+    got = mworld.index.search(mworld.queries[:nq], k, nprobe=nprobe, refine=0)
+    _same(got, _adc_result(mranked[nprobe][:nq], k), f"m={mworld.m} nq={nq} nprobe={nprobe} k={k}")
+    if nprobe == 1 and k == 256:
+        for i, (_, rows) in enumerate(mranked[1][:nq]):
+            assert len(rows) < k and (got[1][i, len(rows):] == -1).all() and (got[0][i, len(rows):] == pc.NEG_PAD).all()
+
+
+@pytest.mark.parametrize("k, R", [(10, 100), (1, 1)])
+def test_refined_search_every_m(mworld, mranked, k, R):
+    """the candidates are the first R of the restatement's ADC ranking; the result is the exact search over them"""
+    w, q = mworld, mworld.queries[:8]
+    D, I, cand = w.index.search_with_candidates(q, k, nprobe=4, refine=R)
+    for i in range(8):
+        ref_rows = mranked[4][i][1][:R]
+        assert len(ref_rows) == R and np.array_equal(cand[i], ref_rows), f"m={w.m} query {i}: candidates not in ADC rank order"
+        _same((D[i:i + 1], I[i:i + 1]), w.flat.search(q[i:i + 1], k, allow=cand[i]), f"m={w.m} query {i}")
+    _same(w.index.search(q, k, nprobe=4, refine=R), (D, I), "search == search_with_candidates")
 
 
 def test_default_refine_and_exhaustive_refinement(world, gpu):
@@ -307,16 +382,14 @@ def test_capi_probe_with_minus_one_and_more_probes_than_a_prefix_block(world, na
         _same((S[i:i + 1], I[i:i + 1]), world.flat.search(q[i:i + 1], k, allow=cand[i]), f"capi refined {i}")
 
 
-def test_every_list_of_more_than_1024_probed(gpu, world):
-    """Probing ALL of more than 1 024 lists has no coarse search behind it: the lists come in list order and their scores
-    from ``sskd_similarity`` - the same fma chain, so the same bits as the coarse search would return."""
+def _every_list_of_1100(gpu, world, m):
     n = nlist = 1100
     corpus = oracle.seeded_unit_rows(n, DIM, 91)
     centroids = (oracle.seeded_unit_rows(nlist, DIM, 92) * np.float32(0.25)).astype(np.float32)
     assignment = np.random.default_rng(93).permutation(nlist)   # one row per list
     flat = _flat(corpus, gpu)
     resid = pc.residuals(corpus, centroids, assignment)
-    cb = _sample_codebooks(resid, 8, 94)
+    cb = _sample_codebooks(resid, m, 94)
     index = IVFPQIndex.from_codebooks(flat, centroids, assignment, cb)
     codes = pc.encode(resid, cb)
     assert np.array_equal(index.codes_numpy(), codes)
@@ -332,6 +405,51 @@ def test_every_list_of_more_than_1024_probed(gpu, world):
     for i in range(3):
         assert np.array_equal(cand[i], ranking[i][1][:256])
         _same((D[i:i + 1], I[i:i + 1]), flat.search(q[i:i + 1], 10, allow=cand[i]), f"1 100 lists, refined {i}")
+
+
+def test_every_list_of_more_than_1024_probed(gpu, world):
+    """Probing ALL of more than 1 024 lists has no coarse search behind it: the lists come in list order and their scores
+    from ``sskd_similarity`` - the same fma chain, so the same bits as the coarse search would return."""
+    _every_list_of_1100(gpu, world, 8)
+
+
+@pytest.mark.parametrize("m", [24, 96])
+def test_every_list_of_more_than_1024_probed_at_the_edge_variants(gpu, world, m):
+    """The same 1 100 one-row lists (five prefix blocks, a pool that fills and is compacted on the fourth step) through
+    pq_scan_kernel<24>, the 8-byte code loads with three loads per row, and <96>, the largest look-up table and the most
+    code registers per lane."""
+    _every_list_of_1100(gpu, world, m)
+
+
+@pytest.mark.parametrize("m", [24, 96])
+def test_four_parts_and_a_pool_compacted_many_times(gpu, native_lib, m):
+    """17 000 rows in four lists, all probed: four parts per query of about 4 250 positions each (17 steps, the pool
+    compacted again and again), the parts' records merged by the refine step.  The scan reads whatever codes the index
+    holds, so the codes are drawn at random instead of encoded: every code value in every subspace."""
+    import ctypes as C
+
+    n, nlist = 17000, 4
+    rng = np.random.default_rng(180 + m)
+    corpus = oracle.seeded_unit_rows(n, DIM, 81)
+    assignment = rng.integers(0, nlist, size=n)
+    centroids = (oracle.seeded_unit_rows(nlist, DIM, 83) * np.float32(0.25)).astype(np.float32)
+    codes = rng.integers(0, pc.CODES, size=(n, m)).astype(np.uint8)
+    flat = _flat(corpus, gpu)
+    index = IVFPQIndex.from_codebooks(flat, centroids, assignment, _sample_codebooks(corpus, m, 184), codes=codes)
+    offsets, rows = ivf_mod.csr_from_assignment(assignment, nlist)
+    q = oracle.seeded_unit_rows(3, DIM, 85)
+    parts = C.c_int(0)
+    longest = int(np.diff(offsets).max())
+    for cap in (100, 256):
+        assert native_lib.sskd_pq_search_plan(3, nlist, 10, cap, m, n, longest, C.byref(parts), None, None, None) == 0
+        assert parts.value == 4
+    w = SimpleNamespace()
+    ranking = _rankings(w, q, nlist, index=index, offsets=offsets, rows=rows, codes=codes, nlist=nlist)
+    _same(index.search(q, 256, nprobe=nlist, refine=0), _adc_result(ranking, 256), f"m={m}, four parts, adc")
+    D, I, cand = index.search_with_candidates(q, 10, nprobe=nlist, refine=100)
+    for i in range(3):
+        assert np.array_equal(cand[i], ranking[i][1][:100])
+        _same((D[i:i + 1], I[i:i + 1]), flat.search(q[i:i + 1], 10, allow=cand[i]), f"m={m}, four parts, refined {i}")
 
 
 # --------------------------------------------------------------------------------------------------------- ties
@@ -379,7 +497,7 @@ def test_ties_and_a_tie_across_the_candidate_cut(gpu, world):
 
 
 # -------------------------------------------------------------------------------------------------------- masks
-def test_masks_and_removed_rows_take_no_candidate_slot(world, gpu):
+def _masks_case(world, gpu):
     flat = _flat(world.corpus, gpu)
     index = IVFPQIndex.from_codebooks(flat, world.centroids, world.assignment, world.cb, codes=world.codes)
     rng = np.random.default_rng(41)
@@ -406,6 +524,15 @@ def test_masks_and_removed_rows_take_no_candidate_slot(world, gpu):
     assert (index.search(q, k, nprobe=nprobe, allow=cases["none"])[1] == -1).all()
     _same(index.search(q, k, nprobe=nprobe, allow=flat.row_filter(cases["half"])),
           index.search(q, k, nprobe=nprobe, allow=cases["half"]), "RowFilter")
+
+
+def test_masks_and_removed_rows_take_no_candidate_slot(world, gpu):
+    _masks_case(world, gpu)
+
+
+@pytest.mark.parametrize("m", [24, 96])
+def test_masks_and_removed_rows_at_the_edge_variants(mworlds, gpu, m):
+    _masks_case(mworlds(m), gpu)
 
 
 # -------------------------------------------------------------------------------------------- split independence
@@ -472,8 +599,7 @@ def test_training_is_deterministic_seeded_and_lowers_the_error(world, trained):
     assert np.array_equal(trained.codes_csr.cpu().numpy(), trained.codes_numpy()[rows])
 
 
-def test_one_training_iteration_is_the_restatement(world):
-    m = 8
+def _one_training_iteration(world, m):
     index = IVFPQIndex(flat=world.flat, m=m)
     index.train(nlist=NLIST, iterations=2, seed=99, pq_iterations=1)
     offsets, rows = index.lists_numpy()
@@ -484,6 +610,16 @@ def test_one_training_iteration_is_the_restatement(world):
     cb = pc.update_codebooks(cb, *pc.code_sums(resid, codes, m))
     assert np.array_equal(pc.bits32(index.codebooks_numpy()), pc.bits32(cb))
     assert np.array_equal(index.codes_numpy(), pc.encode(resid, cb))
+
+
+def test_one_training_iteration_is_the_restatement(world):
+    _one_training_iteration(world, 8)
+
+
+@pytest.mark.parametrize("m", [24, 96])
+def test_one_training_iteration_at_the_edge_variants(world, m):
+    """train() end to end - encode, code sums, the codebook update - at dsub = 16 (m = 24) and dsub = 4 (m = 96)"""
+    _one_training_iteration(world, m)
 
 
 # ---------------------------------------------------------------------------------------------------- lifecycle

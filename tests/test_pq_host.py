@@ -21,15 +21,18 @@ def _fr(a):
 
 
 # --------------------------------------------------------------------- the restatement against exact rationals
-@pytest.fixture(scope="module")
-def small():
+def _small(m):
     rng = np.random.default_rng(3)
-    m = 8
     cb = pc.seeded_codebooks(m, 5, scale=0.1)
     rows = rng.standard_normal((6, pc.DIM)).astype(np.float32) * 0.1
     centroids = rng.standard_normal((3, pc.DIM)).astype(np.float32) * 0.05
     assign = np.array([0, 2, 1, 1, 0, 2])
     return m, cb, rows, centroids, assign
+
+
+@pytest.fixture(scope="module")
+def small():
+    return _small(8)
 
 
 def test_residual_is_one_fp32_subtraction(small):
@@ -135,6 +138,40 @@ def test_probed_rows_skip_bad_probes_and_hidden_rows():
     allowed = np.array([True, False, True, True, True])
     rows, base = pc.probed([2, -1, 7, 1, 0], np.float32([0.5, 9, 9, 9, 0.25]), offsets, list_rows, 3, allowed)
     assert rows.tolist() == [0, 2, 3, 4] and base.tolist() == [0.5, 0.5, 0.25, 0.25]
+
+
+@pytest.mark.parametrize("check", [test_residual_is_one_fp32_subtraction, test_encode_distance_and_argmin_against_rationals,
+                                   test_encode_ties_go_to_the_lower_code, test_code_sums_against_rationals,
+                                   test_lut_against_rationals, test_adc_chain_and_rank_order], ids=lambda f: f.__name__)
+def test_the_restatement_at_m_24(check):
+    """the checks above at m = 24: dsub = 16, and an m that is not a power of two"""
+    check(_small(24))
+
+
+def test_the_world_of_m_96_has_no_tied_encoding_distance():
+    """The GPU tests compare the codes of every m with ``pc.encode``.  At m = 96 an entry has four components only, so
+    two entries at the same fp64 distance from a residual slice are conceivable; the lower-code rule would then carry the
+    comparison instead of the arithmetic.  Checked for the codebook seed the GPU world of m = 96 uses
+    (``test_pq_gpu.world_seed(96)`` = 196) and the seed of ``test_encode`` (106) on the 3 001-row world: the two smallest
+    distances of every (row, subspace) differ.  Should a change of the world produce a tie, change the seed."""
+    import test_pq_gpu as gpu_side
+    from oracle import search as oracle
+
+    m = 96
+    assert gpu_side.world_seed(m) == 196
+    corpus = oracle.seeded_unit_rows(gpu_side.N, pc.DIM, 1)
+    centroids = (oracle.seeded_unit_rows(gpu_side.NLIST, pc.DIM, 4) * np.float32(0.25)).astype(np.float32)
+    assignment = np.random.default_rng(3).integers(0, gpu_side.NLIST, size=gpu_side.N)
+    resid = pc.residuals(corpus, centroids, assignment)
+    for seed in (gpu_side.world_seed(m), 10 + m):
+        cb = gpu_side._sample_codebooks(resid, m, seed)
+        codes = pc.encode(resid, cb)
+        for j in range(m):
+            two = np.partition(pc.encode_distances(resid, cb, j), 1, axis=1)[:, :2]
+            assert (two[:, 0] < two[:, 1]).all(), f"seed {seed}, subspace {j}: tied distances"
+        # the sampled rows encode to their own entries at distance +0.0, a strict minimum
+        pick = np.sort(np.random.default_rng(seed).permutation(gpu_side.N)[:pc.CODES])
+        assert (codes[pick] == np.arange(pc.CODES, dtype=np.uint8)[:, None]).all()
 
 
 # ------------------------------------------------------------------------------------------------ python side
