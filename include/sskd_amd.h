@@ -685,6 +685,49 @@ int sskd_graph_search(const float* d_tiled, int64_t n_rows, const int32_t* d_gra
                       int width, int max_iterations, int64_t id_offset, const uint32_t* d_row_mask, float* d_out_scores,
                       int64_t* d_out_ids, int32_t* d_out_iterations, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Late interaction: token-level MaxSim re-ranking of a first stage's candidates
+ *   reference: features.enable_late_interaction of configs/service.yaml (.env.example: ENABLE_LATE_INTERACTION), a flag
+ *   the reference reads and has no code behind.  The rules below are this library's definition.
+ * Token store.  d_tokens DEVICE bf16 [n_tokens, 384], one L2-normalised row per real token, in CSR order: the tokens of
+ * row r are rows tok_lims[r] .. tok_lims[r + 1] - 1 (d_tok_lims DEVICE int64 [n_rows + 1], ascending from 0).
+ *   sskd_late_pack_tokens writes the rows of B texts: d_hidden DEVICE bf16 [B, S, 384] (sskd_encoder_hidden's output),
+ * d_lengths DEVICE int32 [B] (real tokens of every text, the attention-masked prefix), d_offsets DEVICE int64 [B] (the
+ * store row of every text's first token).  Positions >= the length are neither read nor written, nor is a row outside
+ * [0, n_tokens).  Per token, in fp32: columns 8 l .. 8 l + 7 are summed as an fma chain from +0.0 into p_l (l = 0 .. 47,
+ * p_48 .. p_63 = +0.0), then for o = 32, 16, 8, 4, 2, 1: p_l = p_l + p_(l xor o); ss = p_0; t = x / max(sqrt(ss), 1e-12)
+ * with correctly rounded sqrt and division, rounded to bf16 to nearest even.  One wave per token.
+ *
+ * sskd_late_rerank.  score(q, c) = sum over the query's tokens i (ascending, sequential fp32 from +0.0) of the max over
+ * the document's tokens j of <q_i, d_j>; a dot product is the fp32 accumulation of 384 exact bf16 x bf16 products by 24
+ * v_mfma_f32_32x32x16_bf16 from a zero accumulator (columns ascending across instructions; the order inside one
+ * instruction is the hardware's).  The bits of score(q, c) depend on the two token lists alone - not on nq, R, k, the
+ * candidate's position, its neighbours or the launch geometry.
+ *   d_q_tokens DEVICE bf16 [q_lims[nq], 384] with q_lims int64 [nq + 1] given TWICE: q_lims on the HOST (validated: every
+ * Tq = q_lims[q + 1] - q_lims[q] in [1, 128], q_lims[0] >= 0) and d_q_lims, the same values on the device (read by the
+ * kernel; nothing is copied by the call).  d_candidates DEVICE int64 [nq, R]: global ids as the searches write them
+ * (id_offset is subtracted); -1, an id outside the store and a row without tokens are no candidate.  Candidates of one
+ * query are expected to be distinct (a repeated id is returned once).
+ *   Out: d_out_scores fp32 [nq, k] / d_out_ids int64 [nq, k], score descending, ties by lower id, padded with
+ * (-inf, -1); d_out_raw NULL or fp32 [nq, R], every candidate's score in candidate order (-inf = no candidate).  With
+ * d_out_raw = NULL the raw scores live in the workspace (sskd_late_rerank_workspace_bytes; otherwise none is needed).
+ *   Two launches (sskd_late_rerank_plan reports the first: workgroups, threads, LDS bytes of one, candidates per
+ * workgroup): the scores, then one wave per query taking the top-k by the rank-order pick.  Limits: 1 <= Tq <= 128,
+ * 1 <= k <= R <= 1024, token matrices 16-byte aligned.  Stream-ordered, no host sync (graph-capturable), allocates
+ * nothing; every argument is checked before anything is enqueued (SSKD_ERR_INVALID); nq = 0 is a successful no-op.
+ * Non-finite tokens do not fault; what they score is unspecified (a NaN score is never returned in the top-k).
+ * ------------------------------------------------------------------------- */
+#define SSKD_LATE_TQ_MAX 128
+#define SSKD_LATE_R_MAX 1024
+int sskd_late_pack_tokens(const void* d_hidden, const int32_t* d_lengths, const int64_t* d_offsets, int B, int S,
+                          int64_t n_tokens, void* d_tokens, void* stream);
+int sskd_late_rerank_plan(int nq, int max_tq, int R, int k, int* workgroups, int* threads, int* lds_bytes, int* chunk);
+size_t sskd_late_rerank_workspace_bytes(int nq, int R);
+int sskd_late_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq, const void* d_tokens,
+                     const int64_t* d_tok_lims, int64_t n_rows, int64_t n_tokens, const int64_t* d_candidates, int R, int k,
+                     int64_t id_offset, float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -18,6 +18,7 @@ from .hybrid import HybridIndex  # noqa: F401
 from .graph import GraphIndex  # noqa: F401
 from .ivf import IVFIndex  # noqa: F401
 from .pq import IVFPQIndex  # noqa: F401
+from .late import LateInteractionIndex, is_late_dir  # noqa: F401
 from .evaluation import (  # noqa: F401
     KDEvaluator,
     compute_retrieval_metrics,
@@ -45,6 +46,8 @@ __all__ = [
     "GraphIndex",
     "IVFIndex",
     "IVFPQIndex",
+    "LateInteractionIndex",
+    "is_late_dir",
     "KDEvaluator",
     "compute_retrieval_metrics",
     "evaluate_lists",

@@ -207,6 +207,12 @@ SIGNATURES = {
     "sskd_graph_search": (
         _i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]
     ),
+    "sskd_late_pack_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "sskd_late_rerank_plan": (_i, [_i, _i, _i, _i, _ip, _ip, _ip, _ip]),
+    "sskd_late_rerank_workspace_bytes": (_sz, [_i, _i]),
+    "sskd_late_rerank": (
+        _i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

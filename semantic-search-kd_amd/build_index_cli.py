@@ -12,6 +12,9 @@ codes over the same lists (``pq.IVFPQIndex``: ``--pq-m``, ``--pq-refine``) behin
 ``--index-type graph`` builds a k-NN graph over the rows (``graph.GraphIndex``: ``--hnsw-m`` is its degree, ``--ef-search``
 its beam), again behind the recall gate and for single-index builds only.
 
+``--late-interaction`` adds the token store of ``late.LateInteractionIndex`` (``--late-max-doc-tokens``) beside any
+single index: the service re-ranks by token-level MaxSim when ``SEMANTIC_KD_FEATURES__ENABLE_LATE_INTERACTION`` is set.
+
 Row-sharded build (BASELINE cfg 3): launch the same command under
 ``python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m semantic_search_kd_amd.build_index_cli ...``
 and rank r encodes rows ``shard_bounds(N, G, r)`` straight into its own HBM shard and writes
@@ -73,6 +76,11 @@ def main(argv=None) -> int:
     ap.add_argument("--ef-search", type=_positive, default=64, help="graph: rows a search keeps in its beam (at most 256)")
     ap.add_argument("--recall-threshold", type=float, default=0.97,
                     help="ivf, ivf_pq, graph: fail if recall@10 against the exact search is below this")
+    ap.add_argument("--late-interaction", action="store_true",
+                    help="also build the late-interaction token store (late.LateInteractionIndex) and save it beside the "
+                         "index: 768 B per document token; single-index builds only")
+    ap.add_argument("--late-max-doc-tokens", type=_positive, default=180,
+                    help="late interaction: tokens kept per document ([CLS] and the closing [SEP] included)")
     args = ap.parse_args(argv)
     for flag, p in (("--model-path", args.model_path), ("--data-path", args.data_path)):
         if not Path(p).exists():
@@ -85,8 +93,12 @@ def main(argv=None) -> int:
         if args.index_type != "flat":
             what = "graph" if args.index_type == "graph" else "inverted lists"
             ap.error(f"--index-type {args.index_type}: the row-sharded index has no {what} yet")
+        if args.late_interaction:
+            ap.error("--late-interaction: the row-sharded index has no token store yet")
         return _build_sharded(args, world)
 
+    if args.late_interaction and args.late_max_doc_tokens < 2:
+        ap.error("--late-max-doc-tokens: at least 2 ([CLS] and [SEP])")
     if args.index_type == "graph":
         from .graph import GRAPH_EF_MAX, check_degree
 
@@ -154,6 +166,14 @@ def main(argv=None) -> int:
             return 1
     else:
         builder.save(Path(args.output_dir))
+    if args.late_interaction:
+        from .late import LateInteractionIndex
+
+        late = LateInteractionIndex(builder, max_doc_tokens=args.late_max_doc_tokens)
+        late.build_from_texts(model, [builder.doc_texts[i] for i in builder.doc_ids], batch_size=args.batch_size)
+        late.save(Path(args.output_dir))
+        print(f"Late-interaction token store: {late.n_tokens} tokens, {late.nbytes} bytes "
+              f"({late.n_tokens / max(late.ntotal, 1):.1f} tokens per row, at most {late.max_doc_tokens})")
     print(f"Index saved to: {args.output_dir}")
     print(f"Total vectors: {index.ntotal}")
     return 0

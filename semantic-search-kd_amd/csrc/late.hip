@@ -1,0 +1,344 @@
+// Late interaction (include/sskd_amd.h, "Late interaction"): the token store's pack kernel and the MaxSim re-rank.
+//
+// score(q, c) = sum over the query's tokens i of max over the document's tokens j of <q_i, d_j>, on L2-normalised bf16
+// token rows of 384 columns.  The dot products run on v_mfma_f32_32x32x16_bf16 with the DOCUMENT tokens as the A operand
+// and the QUERY tokens as B: both operands of that instruction are K-contiguous (lane l holds row l & 31, columns
+// 8 (l >> 5) .. + 7 of a k-step), so row-major token rows feed it with 16-byte reads and no transpose, and the result
+// tile has the query token on the lane and 32 document tokens in 16 registers x 2 lane halves - the max over document
+// tokens is a max over the lane's registers and one exchange with lane l ^ 32.
+//
+// Geometry.  A workgroup of 4 waves serves one (query, chunk of candidates): the query's tokens are staged once in LDS in
+// B-fragment order (24 KiB per block of 32 tokens, at most 4 blocks), wave w takes candidates w, w + 4, ... of the chunk
+// whole.  A document tile (32 consecutive token rows = 24 KiB contiguous in the store) is read by ONE burst of 24 16-byte
+// loads per lane - every byte of every 128-byte line of the tile is requested before the first MFMA waits - and then
+// multiplied against every block of the query.  One wave alone computes a candidate, in an order fixed by (Tq, Td), so a
+// score's bits depend on nothing but the two token lists.
+#include <cfloat>
+#include <cmath>
+
+#include "search_device.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int L_WAVES = 4;
+constexpr int L_THREADS = L_WAVES * 64;
+constexpr int L_KSTEPS = DIM / 16;          // 24 k-steps of v_mfma_f32_32x32x16_bf16
+constexpr int L_ROW_VEC = DIM / 8;          // 48 16-byte vectors per token row
+constexpr int L_TQ_MAX = SSKD_LATE_TQ_MAX;  // 128
+constexpr int L_R_MAX = SSKD_LATE_R_MAX;    // 1024
+constexpr int L_QB_MAX = L_TQ_MAX / 32;
+
+// ------------------------------------------------------------------------------------------------ pack
+// One wave per (text, position).  Lane l < 48 holds columns 8 l .. 8 l + 7 of the row (one 16-byte load: the wave reads
+// the whole 768-byte row at once).  Sum of squares, THE order (tests/late_cases.py pack_rows restates it):
+//   p_l = fma chain from +0.0f over the lane's 8 columns ascending (a bf16 square is exact in fp32, so the fma equals
+//         add(p, x * x));  p_l = +0.0f for lanes 48 .. 63;
+//   butterfly: for o = 32, 16, 8, 4, 2, 1: p_l = p_l + p_(l ^ o)   (fp32 addition commutes, so every lane holds the same bits).
+// t = x / max(sqrt(ss), 1e-12f) with correctly rounded sqrt and division, rounded to bf16 to nearest even.
+__global__ __launch_bounds__(L_THREADS) void late_pack_kernel(const uint16_t* __restrict__ hidden, const int32_t* __restrict__ lengths,
+                                                              const int64_t* __restrict__ offsets, int B, int S,
+                                                              int64_t n_tokens, uint16_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t tok = (int64_t)blockIdx.x * L_WAVES + (threadIdx.x >> 6);
+  if (tok >= (int64_t)B * S) return;
+  const int b = (int)(tok / S), s = (int)(tok % S);
+  if (s >= lengths[b]) return;                 // padding is never read and never written
+  const int64_t row = offsets[b] + s;
+  if (row < 0 || row >= n_tokens) return;      // (the host checked what it can see; this keeps a bad offset harmless)
+  float x[8];
+  float p = 0.f;
+  if (lane < L_ROW_VEC) {
+    const uint4 v = *reinterpret_cast<const uint4*>(hidden + tok * DIM + 8 * lane);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[2 * j] = __uint_as_float(w[j] << 16);
+      x[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p = fmaf(x[j], x[j], p);
+  }
+  const float ss = wave_sum(p);
+  const float denom = fmaxf(__builtin_sqrtf(ss), 1e-12f);   // IEEE: hipcc rounds fp32 sqrt and division correctly by default
+  if (lane < L_ROW_VEC) {
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t h[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const uint32_t u = __float_as_uint(x[2 * j + e] / denom);
+        h[e] = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;   // round to nearest even (finite input)
+      }
+      o[j] = h[0] | (h[1] << 16);
+    }
+    *reinterpret_cast<uint4*>(out + row * DIM + 8 * lane) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ scores
+struct LateParams {
+  const bf16x8* q_tokens;    // [sum Tq, 48]
+  const int64_t* q_lims;     // [nq + 1]
+  const bf16x8* tokens;      // [n_tokens, 48]
+  const int64_t* tok_lims;   // [n_rows + 1]
+  const int64_t* cand;       // [nq, R]
+  float* raw;                // [nq, R]
+  int64_t n_q_tokens, n_tokens, n_rows, id_offset;
+  int R, chunk;
+};
+
+// the token range of candidate id (global), or an empty range when there is no such candidate
+__device__ inline void cand_range(const LateParams& p, int64_t id, int64_t& beg, int64_t& td) {
+  beg = 0; td = 0;
+  const int64_t row = id - p.id_offset;
+  if (id < 0 || row < 0 || row >= p.n_rows) return;
+  const int64_t lo = p.tok_lims[row], hi = p.tok_lims[row + 1];
+  if (lo < 0 || hi > p.n_tokens || hi <= lo) return;
+  beg = lo; td = hi - lo;
+}
+
+// QB = blocks of 32 query tokens the workgroup holds in LDS (the batch's largest query decides; a shorter query uses
+// its own ceil(Tq / 32) blocks of them, so its scores do not depend on QB)
+template <int QB>
+__global__ __launch_bounds__(L_THREADS) void late_score_kernel(const LateParams p) {
+  __shared__ bf16x8 qs[QB][L_KSTEPS][64];   // B fragments: [block][k-step][lane]
+  const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r32 = lane & 31, h = lane >> 5;
+  int64_t q0 = p.q_lims[q], tq64 = p.q_lims[q + 1] - q0;
+  if (q0 < 0 || tq64 < 0 || q0 + tq64 > p.n_q_tokens) tq64 = 0;   // (the host validated its copy of the lims)
+  const int Tq = (int)(tq64 < QB * 32 ? tq64 : QB * 32);
+  const int nb = (Tq + 31) >> 5;            // blocks in use (workgroup-uniform)
+  // stage: token row i, 16-byte vector ch = 2 s + half -> qs[i >> 5][s][32 half + (i & 31)]; rows >= Tq are zeros
+  for (int idx = threadIdx.x; idx < nb * 32 * L_ROW_VEC; idx += L_THREADS) {
+    const int i = idx / L_ROW_VEC, ch = idx % L_ROW_VEC;
+    bf16x8 v = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
+    if (i < Tq) v = p.q_tokens[(q0 + i) * L_ROW_VEC + ch];
+    qs[i >> 5][ch >> 1][((ch & 1) << 5) | (i & 31)] = v;
+  }
+  __syncthreads();
+
+  const int c_begin = blockIdx.y * p.chunk;
+  const int c_end = min(c_begin + p.chunk, p.R);
+  for (int c = c_begin + wave; c < c_end; c += L_WAVES) {
+    const int64_t id = p.cand[(int64_t)q * p.R + c];
+    int64_t beg, td;
+    cand_range(p, id, beg, td);
+    float score = -INFINITY;                 // no candidate, or a row without tokens: absent
+    if (td > 0 && Tq > 0) {
+      float best[QB];
+#pragma unroll
+      for (int b = 0; b < QB; ++b) best[b] = -INFINITY;
+      for (int64_t t0 = 0; t0 < td; t0 += 32) {
+        // the lane's document row of this tile; rows past the end re-read the last real row and are masked below
+        const int64_t j = t0 + r32 < td ? t0 + r32 : td - 1;
+        const bf16x8* src = p.tokens + (beg + j) * L_ROW_VEC + h;
+        bf16x8 a[L_KSTEPS];
+#pragma unroll
+        for (int s = 0; s < L_KSTEPS; ++s) a[s] = src[2 * s];
+        const bool partial = td - t0 < 32;
+        const int left = (int)(td - t0);    // real rows of the tile when partial
+#pragma unroll
+        for (int b = 0; b < QB; ++b) {
+          if (b < nb) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < L_KSTEPS; ++s)
+              acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], qs[b][s][lane], acc, 0, 0, 0);
+            // register r of lane l: document row acc_row(r) + 4 (l >> 5) of the tile, query token 32 b + (l & 31)
+            float m = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const bool real = !partial || acc_row(r) + 4 * h < left;
+              m = fmaxf(m, real ? acc[r] : -INFINITY);
+            }
+            m = fmaxf(m, __shfl_xor(m, 32));
+            best[b] = fmaxf(best[b], m);
+          }
+        }
+      }
+      // sequential fp32 sum from +0.0f over the query tokens in ascending order (every lane computes the same chain)
+      score = 0.f;
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        if (b < nb) {
+          const int n = min(32, Tq - 32 * b);
+          for (int i = 0; i < n; ++i) score += __shfl(best[b], i);
+        }
+      }
+    }
+    if (lane == 0) p.raw[(int64_t)q * p.R + c] = score;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ top-k
+// One wave per query: the rank-order pick of search_device.h over the R raw scores (score descending, then lower id).
+// -inf and NaN scores are no candidates; the result is padded with (-inf, -1).
+__global__ __launch_bounds__(64) void late_pick_kernel(const float* __restrict__ raw, const int64_t* __restrict__ cand, int R,
+                                                       int k, float* __restrict__ out_scores, int64_t* __restrict__ out_ids) {
+  const int q = blockIdx.x, lane = threadIdx.x;
+  float cs[L_R_MAX / 64];
+  int64_t cid[L_R_MAX / 64];
+#pragma unroll
+  for (int c = 0; c < L_R_MAX / 64; ++c) {
+    const int idx = c * 64 + lane;
+    cs[c] = -INFINITY;
+    cid[c] = -1;
+    if (idx < R) {
+      const float s = raw[(int64_t)q * R + idx];
+      cs[c] = s;
+      cid[c] = s > -INFINITY ? cand[(int64_t)q * R + idx] : -1;   // false for -inf and for NaN
+    }
+  }
+  float bs = INFINITY;
+  int64_t bi = -1;
+  bool have = false;
+  for (int r = 0; r < k; ++r) {
+    float s = -INFINITY;
+    int64_t i = -1;
+#pragma unroll
+    for (int c = 0; c < L_R_MAX / 64; ++c)
+      if (cid[c] >= 0) pick_after(s, i, cs[c], cid[c], have, bs, bi);
+    wave_argbest(s, i);
+    if (i < 0) {
+      for (int rr = r + lane; rr < k; rr += 64) {
+        out_scores[(int64_t)q * k + rr] = -INFINITY;
+        out_ids[(int64_t)q * k + rr] = -1;
+      }
+      break;
+    }
+    if (lane == 0) {
+      out_scores[(int64_t)q * k + r] = s;
+      out_ids[(int64_t)q * k + r] = i;
+    }
+    bs = s; bi = i; have = true;
+  }
+}
+
+struct LatePlan {
+  int qb, chunk, chunks;
+};
+
+bool late_shape_ok(int nq, int max_tq, int R, int k) {
+  return nq >= 1 && max_tq >= 1 && max_tq <= L_TQ_MAX && R >= 1 && R <= L_R_MAX && k >= 1 && k <= R;
+}
+
+// chunk = candidates of one workgroup: a multiple of the 4 waves, small enough that a single query still spreads over the
+// chip (about 8 workgroups per compute unit in all), large enough that the staged query is amortised when there are many
+LatePlan late_plan(int nq, int max_tq, int R) {
+  LatePlan pl;
+  pl.qb = (max_tq + 31) / 32;
+  const int64_t target = 8 * (int64_t)sskd::cu_count();
+  int64_t per_query = sskd::ceil_div(target, nq);
+  const int64_t most = sskd::ceil_div(R, L_WAVES);
+  if (per_query > most) per_query = most;
+  if (per_query < 1) per_query = 1;
+  pl.chunk = (int)(sskd::ceil_div(sskd::ceil_div(R, per_query), L_WAVES) * L_WAVES);
+  pl.chunks = (int)sskd::ceil_div(R, pl.chunk);
+  return pl;
+}
+
+template <int QB>
+void launch_score(const LateParams& p, int nq, int chunks, hipStream_t st) {
+  hipLaunchKernelGGL(late_score_kernel<QB>, dim3((unsigned)nq, (unsigned)chunks), dim3(L_THREADS), 0, st, p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sskd_late_pack_tokens(const void* d_hidden, const int32_t* d_lengths, const int64_t* d_offsets, int B, int S,
+                          int64_t n_tokens, void* d_tokens, void* stream) {
+  SSKD_REQUIRE(B >= 0 && S >= 1, "late_pack_tokens: needs B >= 0 and S >= 1 (B=%d, S=%d)", B, S);
+  SSKD_REQUIRE(n_tokens >= 0, "late_pack_tokens: n_tokens < 0");
+  if (B == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_hidden && d_lengths && d_offsets && d_tokens, "late_pack_tokens: null pointer");
+  SSKD_REQUIRE(reinterpret_cast<uintptr_t>(d_hidden) % 16 == 0 && reinterpret_cast<uintptr_t>(d_tokens) % 16 == 0,
+               "late_pack_tokens: hidden states and token store must be 16-byte aligned");
+  const int64_t waves = (int64_t)B * S;
+  SSKD_REQUIRE(waves / L_WAVES < (int64_t)INT32_MAX, "late_pack_tokens: B * S too large");
+  hipLaunchKernelGGL(late_pack_kernel, dim3((unsigned)sskd::ceil_div(waves, L_WAVES)), dim3(L_THREADS), 0, sskd::as_stream(stream),
+                     static_cast<const uint16_t*>(d_hidden), d_lengths, d_offsets, B, S, n_tokens,
+                     static_cast<uint16_t*>(d_tokens));
+  return sskd::check_launch("late_pack_kernel");
+}
+
+int sskd_late_rerank_plan(int nq, int max_tq, int R, int k, int* workgroups, int* threads, int* lds_bytes, int* chunk) {
+  SSKD_REQUIRE(late_shape_ok(nq, max_tq, R, k), "late_rerank_plan: needs nq >= 1, 1 <= Tq <= %d, 1 <= k <= R <= %d", L_TQ_MAX,
+               L_R_MAX);
+  const LatePlan pl = late_plan(nq, max_tq, R);
+  if (workgroups) *workgroups = nq * pl.chunks;
+  if (threads) *threads = L_THREADS;
+  if (lds_bytes) *lds_bytes = pl.qb * L_KSTEPS * 64 * (int)sizeof(bf16x8);
+  if (chunk) *chunk = pl.chunk;
+  return SSKD_OK;
+}
+
+size_t sskd_late_rerank_workspace_bytes(int nq, int R) {
+  if (nq < 1 || R < 1 || R > L_R_MAX) return 0;
+  sskd::Carver ws(nullptr);
+  ws.take<float>((size_t)nq * R);   // the raw scores when the caller does not ask for them
+  return ws.bytes();
+}
+
+int sskd_late_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq, const void* d_tokens,
+                     const int64_t* d_tok_lims, int64_t n_rows, int64_t n_tokens, const int64_t* d_candidates, int R, int k,
+                     int64_t id_offset, float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
+                     size_t workspace_bytes, void* stream) {
+  // every check comes before the first HIP call
+  SSKD_REQUIRE(nq >= 0, "late_rerank: nq < 0");
+  SSKD_REQUIRE(R >= 1 && R <= L_R_MAX, "late_rerank: R=%d outside [1, %d]", R, L_R_MAX);
+  SSKD_REQUIRE(k >= 1 && k <= R, "late_rerank: k=%d outside [1, R=%d]", k, R);
+  SSKD_REQUIRE(n_rows >= 0 && n_tokens >= 0 && id_offset >= 0, "late_rerank: n_rows, n_tokens and id_offset must be >= 0");
+  if (nq == 0) return SSKD_OK;
+  SSKD_REQUIRE(q_lims, "late_rerank: the host copy of q_lims is required");
+  SSKD_REQUIRE(q_lims[0] >= 0, "late_rerank: q_lims[0] < 0");
+  int max_tq = 0;
+  for (int q = 0; q < nq; ++q) {
+    const int64_t tq = q_lims[q + 1] - q_lims[q];
+    SSKD_REQUIRE(tq >= 1 && tq <= L_TQ_MAX, "late_rerank: query %d has Tq=%lld outside [1, %d] (q_lims must ascend)", q,
+                 (long long)tq, L_TQ_MAX);
+    if (tq > max_tq) max_tq = (int)tq;
+  }
+  SSKD_REQUIRE(d_q_tokens && d_q_lims && d_candidates && d_out_scores && d_out_ids, "late_rerank: null pointer");
+  SSKD_REQUIRE(n_rows == 0 || (d_tokens && d_tok_lims) || n_tokens == 0, "late_rerank: null token store");
+  SSKD_REQUIRE(reinterpret_cast<uintptr_t>(d_q_tokens) % 16 == 0 && reinterpret_cast<uintptr_t>(d_tokens) % 16 == 0,
+               "late_rerank: token matrices must be 16-byte aligned");
+  float* raw = d_out_raw;
+  if (!raw) {
+    const size_t need = sskd_late_rerank_workspace_bytes(nq, R);
+    if (int rc = sskd::require_workspace("late_rerank", d_workspace, workspace_bytes, need)) return rc;
+    sskd::Carver ws(d_workspace);
+    raw = ws.take<float>((size_t)nq * R);
+  }
+  LateParams p{};
+  p.q_tokens = static_cast<const bf16x8*>(d_q_tokens);
+  p.q_lims = d_q_lims;
+  p.tokens = static_cast<const bf16x8*>(d_tokens);
+  p.tok_lims = d_tok_lims;
+  p.cand = d_candidates;
+  p.raw = raw;
+  p.n_q_tokens = q_lims[nq];
+  p.n_tokens = (d_tokens && d_tok_lims) ? n_tokens : 0;
+  p.n_rows = (d_tokens && d_tok_lims) ? n_rows : 0;
+  p.id_offset = id_offset;
+  p.R = R;
+  const LatePlan pl = late_plan(nq, max_tq, R);
+  p.chunk = pl.chunk;
+  hipStream_t st = sskd::as_stream(stream);
+  switch (pl.qb) {
+    case 1: launch_score<1>(p, nq, pl.chunks, st); break;
+    case 2: launch_score<2>(p, nq, pl.chunks, st); break;
+    case 3: launch_score<3>(p, nq, pl.chunks, st); break;
+    default: launch_score<4>(p, nq, pl.chunks, st); break;
+  }
+  if (int rc = sskd::check_launch("late_score_kernel")) return rc;
+  hipLaunchKernelGGL(late_pick_kernel, dim3((unsigned)nq), dim3(64), 0, st, raw, d_candidates, R, k, d_out_scores, d_out_ids);
+  return sskd::check_launch("late_pick_kernel");
+}
+
+}  // extern "C"

@@ -20,12 +20,14 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Any, Dict, List, Optional
 
+import numpy as np
 from fastapi import FastAPI, HTTPException, Request, status
 from fastapi.responses import JSONResponse
 
 logger = logging.getLogger("semantic_search_kd_amd.serve")
 
 from ..index import FAISSIndexBuilder  # noqa: E402,F401
+from ..late import LATE_R_MAX
 from ..sharded_index import open_index
 from ..student import StudentModel
 from .schemas import (
@@ -70,6 +72,11 @@ class ServeSettings:
     # the directory holds them, "graph" through the k-NN graph saved beside the index (graph.GraphIndex); anything else
     # ("hnsw" included) is the exact scan
     index_type: str = "flat"
+    # ``features.enable_late_interaction`` of the reference's configs/service.yaml (.env.example:
+    # ENABLE_LATE_INTERACTION; read there, no code behind it): /search re-ranks the first stage's candidates by
+    # token-level MaxSim over the token store saved beside the index (late.LateInteractionIndex)
+    late_interaction_enabled: bool = False
+    late_candidates: int = 100
 
     @staticmethod
     def from_env() -> "ServeSettings":
@@ -85,6 +92,9 @@ class ServeSettings:
             semantic_weight=float(e.get("SEMANTIC_KD_HYBRID__SEMANTIC_WEIGHT", ServeSettings.semantic_weight)),
             fusion_method=e.get("SEMANTIC_KD_HYBRID__FUSION_METHOD", ServeSettings.fusion_method),
             index_type=(e.get("SEMANTIC_KD_INDEX__INDEX_TYPE") or ServeSettings.index_type).strip().lower(),
+            late_interaction_enabled=_env_bool(e.get("SEMANTIC_KD_FEATURES__ENABLE_LATE_INTERACTION"),
+                                               ServeSettings.late_interaction_enabled),
+            late_candidates=int(e.get("SEMANTIC_KD_LATE__CANDIDATES") or ServeSettings.late_candidates),
         )
 
     def is_production(self) -> bool:
@@ -105,6 +115,7 @@ class AppState:
         self.hybrid = None   # hybrid.HybridIndex over index_builder when hybrid retrieval is on and its BM25 index fits
         self.ivf = None      # ivf.IVFIndex / pq.IVFPQIndex over index_builder when the index type asks for it and the directory holds its files
         self.graph = None    # graph.GraphIndex over index_builder, likewise (index type "graph", graph.json)
+        self.late = None     # late.LateInteractionIndex over index_builder when late interaction is on and the directory holds its store
 
     def is_ready(self) -> bool:
         return self.ready and self.student is not None
@@ -128,6 +139,7 @@ def _load_index_dir(index_dir: Path) -> Dict[str, Any]:
     app_state.hybrid = _load_hybrid(builder, app_state.settings)
     app_state.ivf = _load_ivf(builder, index_dir, app_state.settings)
     app_state.graph = _load_graph(builder, index_dir, app_state.settings)
+    app_state.late = _load_late(builder, index_dir, app_state.settings)
     return {"status": "loaded", "index_path": str(index_dir), "num_documents": len(app_state.doc_ids)}
 
 
@@ -171,6 +183,27 @@ def _load_graph(builder, index_dir: Path, settings: Optional["ServeSettings"]):
         return graph
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the graph (serving the exact scan): %s", exc)
+        return None
+
+
+def _load_late(builder, index_dir: Path, settings: Optional["ServeSettings"]):
+    """The ``LateInteractionIndex`` /search re-ranks with, or None (the first stage's ranking is the answer, as without
+    the feature): late interaction is off, the directory holds no ``late.json``, the index is row-sharded, or the store
+    does not load or covers another number of rows - then a warning is logged and the service answers as before."""
+    if settings is None or not settings.late_interaction_enabled:
+        return None
+    from ..late import LateInteractionIndex, is_late_dir
+
+    if not isinstance(builder, FAISSIndexBuilder) or not is_late_dir(index_dir):
+        logger.warning("Late interaction is enabled but %s holds no token store over a single-GPU index: serving "
+                       "without it", index_dir)
+        return None
+    try:
+        late = LateInteractionIndex(builder)
+        late.load(index_dir)
+        return late
+    except Exception as exc:  # noqa: BLE001
+        logger.warning("Failed to load the late-interaction token store (serving without it): %s", exc)
         return None
 
 
@@ -284,17 +317,32 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
             query_emb = app_state.student.encode_queries([request.query])
             k_retrieve = request.rerank_top_k if request.rerank else request.k
             hybrid = app_state.hybrid
-            if hybrid is not None and hybrid.dense is app_state.index_builder:
-                # both sides contribute at least k rows; the fused score is the result's score
-                depth = hybrid.clip_depth(max(hybrid.depth, k_retrieve))
-                distances, indices = hybrid.search([request.query], query_emb, k=min(k_retrieve, 2 * depth), depth=depth)
-            elif app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_retrieve <= 256:
-                distances, indices = app_state.ivf.search(query_emb, k=k_retrieve)
-            elif (app_state.graph is not None and app_state.graph.flat is app_state.index_builder
-                  and k_retrieve <= app_state.graph.ef):
-                distances, indices = app_state.graph.search(query_emb, k=k_retrieve)
+
+            def first_stage(k_first: int):
+                if hybrid is not None and hybrid.dense is app_state.index_builder:
+                    # both sides contribute at least k rows; the fused score is the result's score
+                    depth = hybrid.clip_depth(max(hybrid.depth, k_first))
+                    return hybrid.search([request.query], query_emb, k=min(k_first, 2 * depth), depth=depth)
+                if app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_first <= 256:
+                    return app_state.ivf.search(query_emb, k=k_first)
+                if (app_state.graph is not None and app_state.graph.flat is app_state.index_builder
+                        and k_first <= app_state.graph.ef):
+                    return app_state.graph.search(query_emb, k=k_first)
+                return app_state.index_builder.search(query_emb, k=k_first)
+
+            late = app_state.late
+            if late is not None and late.flat is app_state.index_builder and k_retrieve <= LATE_R_MAX:
+                # the first stage proposes, token-level MaxSim orders: score = MaxSim / Tq (1.0 = every query token
+                # has an identical document token)
+                wanted = max(1, int((app_state.settings or settings).late_candidates))
+                _, candidates = first_stage(min(max(wanted, k_retrieve), LATE_R_MAX))
+                q_tokens, q_lims = app_state.student.encode_tokens([request.query], is_query=True,
+                                                                   max_tokens=late.max_query_tokens)
+                k_late = min(k_retrieve, candidates.shape[1])
+                distances, indices = late.rerank(q_tokens, q_lims, np.ascontiguousarray(candidates, dtype=np.int64), k_late)
+                distances = distances / np.float32(q_lims[1] - q_lims[0])
             else:
-                distances, indices = app_state.index_builder.search(query_emb, k=k_retrieve)
+                distances, indices = first_stage(k_retrieve)
             results: List[SearchResult] = []
             for rank, (dist, idx) in enumerate(zip(distances[0], indices[0]), 1):
                 if idx < 0 or (app_state.doc_ids and idx >= len(app_state.doc_ids)):

@@ -111,6 +111,25 @@ class StudentModel:
         return self.model.encode(list(documents), batch_size=batch_size, convert_to_numpy=False, convert_to_tensor=True,
                                  normalize_embeddings=True)
 
+    def encode_tokens(self, texts: Union[str, List[str]], is_query: bool, max_tokens: Optional[int] = None,
+                      batch_size: int = 64):
+        """Token vectors for late interaction (``late.LateInteractionIndex``): ``(tokens, lims)`` with ``tokens`` a device
+        bf16 ``[T, 384]`` tensor of L2-normalised last-layer states, one row per real token (``[CLS]`` and ``[SEP]``
+        included), and ``lims`` int64 ``[n + 1]`` (NumPy): text ``i`` owns rows ``lims[i] .. lims[i + 1] - 1``.  The E5
+        prefix rule is that of ``encode_queries`` / ``encode_documents``; a text longer than ``max_tokens`` (default: 32
+        for queries, 180 for documents) is cut, keeping its closing ``[SEP]``.  The pooled embedding keeps coming from
+        ``encode_queries`` / ``encode_documents``.  Not part of the reference's surface."""
+        from .late import encode_tokens_device
+
+        if isinstance(texts, str):
+            texts = [texts]
+        if self.is_e5:
+            prefix = E5_QUERY_PREFIX if is_query else E5_PASSAGE_PREFIX
+            texts = [prefix + t for t in texts]
+        if max_tokens is None:
+            max_tokens = 32 if is_query else 180
+        return encode_tokens_device(self.model, list(texts), int(max_tokens), batch_size=batch_size)
+
     def encode_with_gradients(self, texts: List[str], normalize: bool = True):
         """Training entry point of the reference (src/kd/train.py:180-187): embeddings ``[n, 384]`` on
         ``self.device`` that carry gradients back to ``self.model.parameters()``.  Forward (saving
