@@ -11,9 +11,9 @@
 //   cand    the rows offered in this step (the seeds, then the neighbours of up to `width` parents: at most 512)
 //   seen    a hash table of row ids (full keys) that spares a row a second scoring
 // A step = pick the first `width` unexpanded entries of T, gather their neighbours, drop ids outside the index and ids
-// the table holds, score the rest in chunks of 32 rows exactly as ivf_scan_kernel does (all threads load the NEXT chunk
-// as whole rows into registers while wave 0 scores the CURRENT one out of LDS, one lane per row, row stride 97 float4),
-// and merge the scores into T (and R).  The merge is a rank computation, not an insertion loop: a candidate's place in
+// the table holds, score the rest in chunks of 32 rows, staged as in row_stage.h (all threads load the NEXT chunk into
+// registers while wave 0 scores the CURRENT one out of LDS, one lane per row, as ivf_scan_kernel does), and merge
+// the scores into T (and R).  The merge is a rank computation, not an insertion loop: a candidate's place in
 // the new list is (entries of the old list that rank before it, by binary search) + (candidates that rank before it);
 // an old entry's place is its index + (candidates that rank before it).  Places are distinct because the order is
 // total and the candidates that take part are distinct rows none of which the list holds; whatever lands past the
@@ -31,17 +31,15 @@
 // graph_prune_kernel: one workgroup per row u, thread j owns entry j of u's k-NN list and counts its detours in a
 // register - for every i < j, whether the list of L_u[i] (staged in LDS) names L_u[j] among its first j entries.
 // Integer compares only.  graph_merge_kernel: one wave per row joins forward and reverse edges without duplicates.
-#include "search_device.h"
+#include "row_stage.h"
 #include "search_host.h"
 
 #include <cfloat>
 
 namespace {
 
-constexpr int G_THREADS = 256;
-constexpr int G_ROWS = 32;                                 // rows per scoring chunk
-constexpr int G_STRIDE4 = CHUNKS + 1;                      // LDS row stride in float4 (97: conflict-free, see ivf.hip)
-constexpr int G_LOADS = G_ROWS * CHUNKS / G_THREADS;       // 12 float4 per thread and chunk
+constexpr int G_THREADS = STAGE_THREADS;                   // graph_search_kernel's workgroup is the staging workgroup
+constexpr int G_MERGE_THREADS = 256;                       // graph_merge_kernel: four rows per workgroup, one wave each
 constexpr int G_EF_MAX = 256;
 constexpr int G_WIDTH_MAX = 8;
 constexpr int G_M_MAX = 64;
@@ -52,7 +50,6 @@ constexpr int G_SEEN_RESET = 1024;                         // recorded rows afte
 constexpr int G_KNN_MAX = 128;
 constexpr int G_EXPANDED = (int)0x80000000;
 constexpr int G_ID = 0x7FFFFFFF;
-static_assert(G_ROWS * CHUNKS % G_THREADS == 0, "a chunk is a whole number of float4 per thread");
 static_assert(G_CAND >= G_EF_MAX, "the seeds of a query fit the candidate buffer");
 
 struct GraphParams {
@@ -84,7 +81,7 @@ struct GList {
 
 // the LDS of one workgroup of graph_search_kernel (sskd_graph_search_plan reports its size)
 struct GraphLds {
-  float4 rows[G_ROWS * G_STRIDE4];   // the current chunk
+  float4 rows[STAGE_FLOAT4];   // the current chunk
   float4 q[CHUNKS];
   float t_s[2 * G_EF_MAX];
   int t_i[2 * G_EF_MAX];
@@ -136,7 +133,7 @@ __device__ inline void g_merge(GList& l, const int* cand_i, const float* cand_s,
     int tb = -1;
     // a NaN score (a query or a row holding NaN) ranks nowhere - ranks_before is false both ways - and would break the
     // "places are distinct" argument below: such a candidate takes no part, so every score a list holds is ordered
-    if (id >= 0 && cand_s[j] == cand_s[j] && (!mask || ((mask[id >> 5] >> (id & 31)) & 1u))) {
+    if (id >= 0 && cand_s[j] == cand_s[j] && row_allowed(mask, id)) {
       tb = g_lower(l, cand_s[j], id);
       if (tb >= l.cap || (tb < l.count && (l.i(tb) & G_ID) == id)) tb = -1;   // past the end, or the list holds the row
     }
@@ -219,37 +216,25 @@ __global__ __launch_bounds__(G_THREADS) void graph_search_kernel(GraphParams p) 
         if (dup) cand_i[j] = -1;   // (the first copy is never overwritten, so a racing reader still finds it)
       }
       __syncthreads();
-      float4 regs[G_LOADS];
+      RowStage stage;
       auto load_chunk = [&](int ch) {
-#pragma unroll
-        for (int i = 0; i < G_LOADS; ++i) {
-          const int f = tid + G_THREADS * i, row = f / CHUNKS, c = f - row * CHUNKS;
-          const int j = ch * G_ROWS + row;
-          const int r = j < C ? cand_i[j] : -1;
-          regs[i] = r >= 0 ? rows4[(int64_t)r * CHUNKS + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        const int* ids = cand_i + ch * STAGE_ROWS;
+        const int left = C - ch * STAGE_ROWS;
+        stage.load(rows4, tid, [&](int row) { return row < left ? ids[row] : -1; });
       };
-      auto store_chunk = [&]() {
-#pragma unroll
-        for (int i = 0; i < G_LOADS; ++i) {
-          const int f = tid + G_THREADS * i, row = f / CHUNKS, c = f - row * CHUNKS;
-          rows_s[row * G_STRIDE4 + c] = regs[i];
-        }
-      };
-      const int n_chunks = (C + G_ROWS - 1) / G_ROWS;
+      const int n_chunks = (C + STAGE_ROWS - 1) / STAGE_ROWS;
       load_chunk(0);
-      store_chunk();
+      stage.store(rows_s, tid);
       __syncthreads();
       for (int ch = 0; ch < n_chunks; ++ch) {
         const bool more = ch + 1 < n_chunks;
         if (more) load_chunk(ch + 1);   // in flight while wave 0 scores
-        if (wave == 0 && lane < G_ROWS) {
-          const int j = ch * G_ROWS + lane;
-          if (j < C && cand_i[j] >= 0)
-            cand_s[j] = row_score_fma(&rows_s[lane * G_STRIDE4], reinterpret_cast<const float*>(q_s));
+        if (wave == 0 && lane < STAGE_ROWS) {
+          const int j = ch * STAGE_ROWS + lane;
+          if (j < C && cand_i[j] >= 0) cand_s[j] = stage_score(rows_s, lane, q_s);
         }
         __syncthreads();   // the chunk has been read
-        if (more) store_chunk();
+        if (more) stage.store(rows_s, tid);
         __syncthreads();
       }
       g_merge(T, cand_i, cand_s, C, nullptr, place_s, &n_valid, tid);
@@ -357,18 +342,17 @@ __global__ __launch_bounds__(G_KNN_MAX) void graph_prune_kernel(const int32_t* _
 }
 
 // one wave per row: first M/2 of fwd, then rev, then the rest of fwd, every row once, cut to M, -1 padded
-__global__ __launch_bounds__(G_THREADS) void graph_merge_kernel(const int32_t* __restrict__ fwd, const int32_t* __restrict__ rev,
+__global__ __launch_bounds__(G_MERGE_THREADS) void graph_merge_kernel(const int32_t* __restrict__ fwd, const int32_t* __restrict__ rev,
                                                                 int64_t n_rows, int M, int32_t* __restrict__ graph) {
-  __shared__ int seq_s[G_THREADS / 64][G_M_MAX + G_M_MAX / 2];
+  __shared__ int seq_s[G_MERGE_THREADS / 64][G_M_MAX + G_M_MAX / 2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t u = (int64_t)blockIdx.x * (G_THREADS / 64) + wave;
+  const int64_t u = (int64_t)blockIdx.x * (G_MERGE_THREADS / 64) + wave;
   if (u >= n_rows) return;   // (wave-uniform; no workgroup barrier below)
   const int h = M / 2, L = M + h;
   int* seq = seq_s[wave];
   for (int e = lane; e < L; e += 64)
     seq[e] = e < h ? fwd[u * M + e] : e < M ? rev[u * h + (e - h)] : fwd[u * M + (e - h)];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
   auto keep = [&](int e) {
     if (e >= L || !g_edge_ok(seq[e], (int)u, n_rows)) return false;
     for (int b = 0; b < e; ++b)
@@ -475,8 +459,8 @@ int sskd_graph_merge(const int32_t* d_fwd, const int32_t* d_rev, int64_t n_rows,
   SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS, "graph_merge: shard too large for int32 row ids");
   if (n_rows == 0) return SSKD_OK;
   SSKD_REQUIRE(d_fwd && d_rev && d_graph, "graph_merge: null pointer");
-  const int per_block = G_THREADS / 64;
-  hipLaunchKernelGGL(graph_merge_kernel, dim3((unsigned)sskd::ceil_div(n_rows, per_block)), dim3(G_THREADS), 0,
+  const int per_block = G_MERGE_THREADS / 64;
+  hipLaunchKernelGGL(graph_merge_kernel, dim3((unsigned)sskd::ceil_div(n_rows, per_block)), dim3(G_MERGE_THREADS), 0,
                      sskd::as_stream(stream), d_fwd, d_rev, n_rows, M, d_graph);
   return sskd::check_launch("graph_merge_kernel");
 }

@@ -7,6 +7,7 @@
 // proven when k groups were found or the ranking ran out of rows, and otherwise the `count` groups written are still
 // the exact top-count groups (the caller asks again with a larger k_rows).
 // ------------------------------------------------------------------------- //
+#include "search_device.h"
 #include "search_host.h"
 
 #include <algorithm>
@@ -86,9 +87,7 @@ __global__ __launch_bounds__(COLLAPSE_WAVES * 64) void group_collapse_kernel(Col
       kept[pos] = g;
     }
     count = min(p.k, count + __popcll(surv));
-    // the next step's lanes read what this step's lanes wrote to kept[]
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();   // the next step's lanes read what this step's lanes wrote to kept[]
   }
   for (int i = count + lane; i < p.k; i += 64) {
     os[i] = -FLT_MAX;

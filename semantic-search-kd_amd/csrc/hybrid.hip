@@ -133,7 +133,7 @@ __global__ __launch_bounds__(THREADS) void hybrid_fuse_kernel(FuseParams p) {
         } else {
           b = p.bm25_scores[(int64_t)q * len + at];
           if (b == 0.0) alive = false;   // +0.0 or -0.0: the row matched no query word
-          if (p.mask && !((p.mask[row >> 5] >> (row & 31)) & 1u)) alive = false;
+          if (!row_allowed(p.mask, row)) alive = false;
         }
       }
       const unsigned long long surv = __ballot(alive);

@@ -9,14 +9,12 @@
 // ivf_scan_kernel, one workgroup per (part p, query q).  The rows q probes form one virtual sequence of L_q = sum of the
 // probed lists' lengths; the workgroup owns positions [p L_q / P, (p + 1) L_q / P) of it and finds them from a prefix sum
 // over the list lengths in LDS (256 probes at a time), so the split is balanced however skewed the lists are, and an
-// empty list or a -1 probe is a list of length 0 and nothing more.  A part is walked in chunks of 32 rows:
+// empty list or a -1 probe is a list of length 0 and nothing more.  A part is walked in chunks of 32 rows, staged as in
+// row_stage.h:
 //   wave 1   turns positions into row numbers two chunks ahead (binary search in the prefix, list_rows, the mask bit)
-//   all      load the NEXT chunk's rows into registers - thread t takes float4 t, t + 256, ... of the 32 x 96, so every
-//            row is read as 1 536 contiguous bytes (whole 128-byte lines), never 16 bytes at a 1 536-byte stride -
+//   all      load the NEXT chunk's rows into registers
 //   wave 0   scores the CURRENT chunk out of LDS meanwhile, one lane per row, and offers the scores to the running top-k
 //   all      barrier, registers -> LDS, barrier.
-// The LDS row stride is 97 float4 (1 552 B): lane l starts at bank 4 l mod 64, and every 16-lane group of a
-// ds_read_b128 ({0-3, 12-15, 20-27}, ...) covers the 16 slots of the 256-byte bank row exactly once - conflict-free.
 // The running top-k is an unsorted list of k slots in LDS with its worst entry cached in registers; a row enters only if
 // it ranks before that entry (ranks_before: score descending, then lower id).  Each workgroup writes its list UNSORTED
 // to its [k] slots of the [P, nq, k] partials, padded with (-FLT_MAX, -1); sskd_topk_merge orders and cuts them, in two
@@ -26,6 +24,7 @@
 // order into one fp64 accumulator per column - one fixed order per output element and no atomics, so two runs agree bit
 // for bit.
 #include "ivf_device.h"
+#include "row_stage.h"
 #include "search_host.h"
 
 #include <algorithm>
@@ -33,13 +32,10 @@
 
 namespace {
 
-constexpr int IVF_ROWS = 32;                                   // rows per chunk
-constexpr int IVF_STRIDE4 = CHUNKS + 1;                        // LDS row stride in float4 (97: see above)
-constexpr int IVF_LOADS = IVF_ROWS * CHUNKS / IVF_THREADS;     // 12 float4 per thread and chunk
 constexpr int IVF_MAX_PARTS = 1024;
 constexpr int IVF_MERGE_CAND = 2048;                           // parts * k: the candidates of one query
 constexpr int IVF_MERGE_DIRECT = 512;                          // up to here one merge step joins them
-static_assert(IVF_ROWS * CHUNKS % IVF_THREADS == 0, "a chunk is a whole number of float4 per thread");
+static_assert(IVF_THREADS == STAGE_THREADS, "ivf_scan_kernel's workgroup is the staging workgroup");
 
 struct IvfParams {
   const float* rows;            // the index: row-major fp32 [n_rows][DIM]
@@ -65,15 +61,9 @@ struct IvfTop {
   int wi, wpos;
 };
 
-// what lane 0 wrote to the list is read by every lane of the wave
-__device__ inline void ivf_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // the list's worst entry: the one every other entry ranks before
 __device__ inline void ivf_find_worst(IvfTop& t, int lane) {
-  ivf_wave_sync();
+  wave_lds_sync();   // what lane 0 wrote to the list is read by every lane of the wave
   float s = 0.f;
   int i = -1, pos = 0;
   for (int e = lane; e < t.k; e += 64)
@@ -107,14 +97,14 @@ __device__ inline void ivf_offer(IvfTop& t, float s, int row, int lane) {
 }
 
 __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(IvfParams p) {
-  __shared__ float4 rows_s[IVF_ROWS * IVF_STRIDE4];   // the current chunk
+  __shared__ float4 rows_s[STAGE_FLOAT4];   // the current chunk
   __shared__ float4 q_s[CHUNKS];
   __shared__ float top_s[IVF_K_MAX];
   __shared__ int top_i[IVF_K_MAX];
   __shared__ int64_t pre_s[IVF_PROBES + 1];           // exclusive prefix of the block's list lengths
   __shared__ int64_t off_s[IVF_PROBES];               // first list_rows entry of every list of the block
   __shared__ int64_t wsum_s[IVF_THREADS / 64];
-  __shared__ int rid_s[2][IVF_ROWS];                  // row numbers of the current and the next chunk (-1 = skip)
+  __shared__ int rid_s[2][STAGE_ROWS];                  // row numbers of the current and the next chunk (-1 = skip)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int part = blockIdx.x, q = blockIdx.y;
@@ -138,22 +128,8 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(IvfParams p) {
   auto row_at = [&](int64_t v, int64_t end, int n_in_block) -> int {
     return ivf_row_at(pre, v, end, n_in_block, p.list_rows, p.row_mask, p.n_rows);
   };
-  float4 regs[IVF_LOADS];
-  auto load_chunk = [&](const int* rid) {
-#pragma unroll
-    for (int i = 0; i < IVF_LOADS; ++i) {
-      const int f = tid + IVF_THREADS * i, row = f / CHUNKS, c = f - row * CHUNKS;
-      const int r = rid[row];
-      regs[i] = r >= 0 ? rows4[(int64_t)r * CHUNKS + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int i = 0; i < IVF_LOADS; ++i) {
-      const int f = tid + IVF_THREADS * i, row = f / CHUNKS, c = f - row * CHUNKS;
-      rows_s[row * IVF_STRIDE4 + c] = regs[i];
-    }
-  };
+  RowStage stage;
+  auto load_chunk = [&](const int* rid) { stage.load(rows4, tid, [&](int row) { return rid[row]; }); };
 
   int64_t base = 0;
   for (int pb = 0; pb < n_blocks; ++pb) {   // every bound below is workgroup-uniform
@@ -163,37 +139,37 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(IvfParams p) {
     base += total;
     __syncthreads();   // the prefix is complete
     if (b <= a) continue;
-    const int64_t n_chunks = (b - a + IVF_ROWS - 1) / IVF_ROWS;
-    const bool finder = wave == 1 && lane < IVF_ROWS;
+    const int64_t n_chunks = (b - a + STAGE_ROWS - 1) / STAGE_ROWS;
+    const bool finder = wave == 1 && lane < STAGE_ROWS;
     if (finder) {
       rid_s[0][lane] = row_at(a + lane, b, n_in_block);
-      rid_s[1][lane] = row_at(a + IVF_ROWS + lane, b, n_in_block);
+      rid_s[1][lane] = row_at(a + STAGE_ROWS + lane, b, n_in_block);
     }
     __syncthreads();
     load_chunk(rid_s[0]);
-    store_chunk();
+    stage.store(rows_s, tid);
     __syncthreads();
     for (int64_t ch = 0; ch < n_chunks; ++ch) {
       const int cur = (int)(ch & 1);
       const bool more = ch + 1 < n_chunks;
       if (more) load_chunk(rid_s[cur ^ 1]);   // in flight while wave 0 scores
       int next_id = -1;
-      if (finder && ch + 2 < n_chunks) next_id = row_at(a + (ch + 2) * IVF_ROWS + lane, b, n_in_block);
+      if (finder && ch + 2 < n_chunks) next_id = row_at(a + (ch + 2) * STAGE_ROWS + lane, b, n_in_block);
       if (wave == 0) {
-        const int r = lane < IVF_ROWS ? rid_s[cur][lane] : -1;
+        const int r = lane < STAGE_ROWS ? rid_s[cur][lane] : -1;
         float s = 0.f;
-        if (r >= 0) s = row_score_fma(&rows_s[lane * IVF_STRIDE4], reinterpret_cast<const float*>(q_s));
+        if (r >= 0) s = stage_score(rows_s, lane, q_s);
         ivf_offer(top, s, r, lane);
       }
       __syncthreads();   // the chunk and its row numbers have been read
-      if (more) store_chunk();
+      if (more) stage.store(rows_s, tid);
       if (finder) rid_s[cur][lane] = next_id;
       __syncthreads();
     }
   }
 
   if (wave == 0) {
-    ivf_wave_sync();
+    wave_lds_sync();
     const int64_t o = ((int64_t)part * p.nq + q) * p.k;
     for (int e = lane; e < p.k; e += 64) {
       const bool have = e < top.count;
@@ -241,7 +217,7 @@ int ivf_parts(int nq, int nprobe, int k, int64_t n_rows, int64_t max_list_rows) 
   int64_t longest = (int64_t)nprobe * max_list_rows;
   if (longest > n_rows) longest = n_rows;
   int64_t parts = sskd::ceil_div(2 * IVF_CUS, nq);
-  parts = std::min<int64_t>(parts, std::max<int64_t>(1, sskd::ceil_div(longest, IVF_ROWS)));
+  parts = std::min<int64_t>(parts, std::max<int64_t>(1, sskd::ceil_div(longest, STAGE_ROWS)));
   parts = std::min<int64_t>(parts, std::max(1, IVF_MERGE_CAND / k));
   parts = std::min<int64_t>(parts, IVF_MAX_PARTS);
   return (int)std::max<int64_t>(parts, 1);
@@ -293,7 +269,7 @@ int sskd_ivf_search_plan(int nq, int nprobe, int k, int64_t n_rows, int64_t max_
                IVF_NLIST_MAX, IVF_K_MAX);
   const int P = ivf_split(ivf_parts(nq, nprobe, k, n_rows, max_list_rows), k).parts();
   if (parts) *parts = P;
-  if (chunk_rows) *chunk_rows = IVF_ROWS;
+  if (chunk_rows) *chunk_rows = STAGE_ROWS;
   if (workgroups) *workgroups = (int)std::min<int64_t>((int64_t)P * nq, INT32_MAX);
   return SSKD_OK;
 }

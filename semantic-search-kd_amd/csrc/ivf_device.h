@@ -76,7 +76,7 @@ __device__ inline int ivf_row_of_entry(int64_t at, const int32_t* __restrict__ l
   if (at < 0 || at >= n_rows) return -1;
   const int r = list_rows[at];
   if (r < 0 || r >= n_rows) return -1;
-  if (row_mask && ((row_mask[r >> 5] >> (r & 31)) & 1u) == 0u) return -1;
+  if (!row_allowed(row_mask, r)) return -1;
   return r;
 }
 

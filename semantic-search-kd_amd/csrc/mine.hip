@@ -49,9 +49,7 @@ __global__ __launch_bounds__(MINE_WAVES * 64) void mine_select_kernel(MineParams
     q4[lane] = src[lane];
     if (lane < CHUNKS - 64) q4[64 + lane] = src[64 + lane];
   }
-  // every lane reads what the other lanes of its wave wrote
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();   // every lane reads what the other lanes of its wave wrote
   const float* qv = reinterpret_cast<const float*>(q4);
 
   // ---- positives: one lane per row, 64 per round.  A row outside the index is no positive at all.

@@ -22,12 +22,13 @@
 //
 // pq_refine_kernel, one workgroup per query: a bitonic sort of the query's <= 4 096 partial records in LDS in rank
 // order (ADC score descending, then lower row; ids are distinct, so the order is total), the first R are the candidates;
-// their rows are gathered in whole lines through LDS 32 at a time (the ivf_scan_kernel staging, stride 97 float4) and
-// scored by row_score_fma, one lane per row; a second sort orders the exact scores and k are written.  With refine = 0
-// only the first sort runs and the ADC scores are the result.
+// their rows are gathered through LDS 32 at a time, staged as in row_stage.h, and scored by row_score_fma, one lane per
+// row; a second sort orders the exact scores and k are written.  With refine = 0 only the first sort runs and the ADC
+// scores are the result.
 //
 // pq_lut_kernel, pq_encode_kernel, pq_code_sums_kernel: off the hot path, fp64, one fixed order per output element.
 #include "ivf_device.h"
+#include "row_stage.h"
 #include "search_host.h"
 
 #include <algorithm>
@@ -41,9 +42,7 @@ constexpr int PQ_MAX_RECORDS = 4096;     // partial records of one query: what p
 // A part's code bytes (M per row) are at least four times the LUT bytes (1 024 M) its workgroup loads first.
 constexpr int PQ_MIN_PART_ROWS = 4096;
 constexpr int PQ_POOL = 1024;            // the scan's candidate pool in LDS: the kept records, then the pending ones
-constexpr int PQ_ROWS = 32;              // rows per gather chunk of the refine step
-constexpr int PQ_STRIDE4 = CHUNKS + 1;   // LDS row stride in float4 (97: conflict-free, see ivf.hip)
-constexpr int PQ_LOADS = PQ_ROWS * CHUNKS / IVF_THREADS;
+static_assert(IVF_THREADS == STAGE_THREADS, "pq_refine_kernel's workgroup is the staging workgroup");
 
 bool pq_m_ok(int m) { return m == 8 || m == 16 || m == 24 || m == 32 || m == 48 || m == 64 || m == 96; }
 
@@ -241,7 +240,7 @@ struct PqRefineParams {
   int64_t* out_cand;            // [nq][refine] or null
 };
 
-constexpr int PQ_STAGE_BYTES = PQ_ROWS * PQ_STRIDE4 * 16;   // 49 664: the gather chunk; the sort arrays (32 KiB) alias it
+constexpr int PQ_STAGE_BYTES = STAGE_FLOAT4 * 16;   // 49 664: the gather chunk; the sort arrays (32 KiB) alias it
 static_assert(PQ_STAGE_BYTES >= PQ_MAX_RECORDS * 8, "the staging area holds the sort arrays");
 
 __global__ __launch_bounds__(IVF_THREADS) void pq_refine_kernel(PqRefineParams p) {
@@ -287,18 +286,15 @@ __global__ __launch_bounds__(IVF_THREADS) void pq_refine_kernel(PqRefineParams p
 
   if (p.refine > 0) {
     const float4* rows4 = reinterpret_cast<const float4*>(p.rows);
-    for (int c0 = 0; c0 < n_cand; c0 += PQ_ROWS) {   // (uniform)
-#pragma unroll
-      for (int i = 0; i < PQ_LOADS; ++i) {
-        const int f = tid + IVF_THREADS * i, row = f / CHUNKS, c = f - row * CHUNKS;
-        const int r = c0 + row < n_cand ? keep_i[c0 + row] : -1;
-        rows_s[row * PQ_STRIDE4 + c] = r >= 0 ? rows4[(int64_t)r * CHUNKS + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
+    RowStage stage;
+    for (int c0 = 0; c0 < n_cand; c0 += STAGE_ROWS) {   // (uniform)
+      stage.load(rows4, tid, [&](int row) { return c0 + row < n_cand ? keep_i[c0 + row] : -1; });
+      stage.store(rows_s, tid);
       __syncthreads();
-      // 32 lanes of wave 0 score, the other 224 threads only stage: deliberate - the layout is ivf_scan_kernel's, and
-      // the whole kernel is 0.8 ms per 10 000 queries at R = 100, a tenth of the scan before it
-      if (wave == 0 && lane < PQ_ROWS && c0 + lane < n_cand)
-        keep_s[c0 + lane] = row_score_fma(&rows_s[lane * PQ_STRIDE4], reinterpret_cast<const float*>(q_s));
+      // 32 lanes of wave 0 score, the other 224 threads only stage, and nothing is pipelined: deliberate - the layout is
+      // row_stage.h's, and the whole kernel is 0.8 ms per 10 000 queries at R = 100, a tenth of
+      // the scan before it
+      if (wave == 0 && lane < STAGE_ROWS && c0 + lane < n_cand) keep_s[c0 + lane] = stage_score(rows_s, lane, q_s);
       __syncthreads();
     }
     int n2 = 2;

@@ -1,5 +1,5 @@
 // Index layout and the device helpers that more than one search translation unit uses (internal: not installed).
-// Included by search.hip, index_rows.hip, screen.hip, range.hip, mine.hip, hybrid.hip and eval.hip; what only one of them uses stays there.
+// What only one of them uses stays there.
 #pragma once
 #include "common.h"
 
@@ -69,6 +69,20 @@ __device__ inline T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// what lanes of a wave wrote to LDS is read by the other lanes of that wave (no workgroup barrier needed)
+__device__ inline void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// bit r of a row allow-mask given as words (the per-row test; the tile scans test a whole word, below); null = all allowed.
+// (Spelled as an early return: as `!mask || bit` the list scans' position -> row step compiles to other control flow.)
+template <typename I>
+__device__ inline bool row_allowed(const uint32_t* mask, I r) {
+  if (mask && ((mask[r >> 5] >> (r & 31)) & 1u) == 0u) return false;
+  return true;
 }
 
 // number of queries to serve: the host bound, or the device-side count when one is given (the

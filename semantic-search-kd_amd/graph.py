@@ -27,7 +27,7 @@ import torch
 
 from . import _native
 from .index import FAISSIndexBuilder, IndexHandle, _host_queries_to_device
-from .ivf import recall_at_k
+from .overlay import FlatOverlay, read_versioned_json
 
 GRAPH_EF_MAX = 256
 GRAPH_M_MAX = 64
@@ -99,9 +99,7 @@ def save_graph(out_dir: Union[str, Path], graph: np.ndarray, entry_rows: np.ndar
 def load_graph(index_dir: Union[str, Path]):
     """``(graph, entry_rows, meta)`` as ``save_graph`` wrote them; the adjacency and the entry rows are checked."""
     d = Path(index_dir)
-    meta = json.loads((d / "graph.json").read_text())
-    if int(meta.get("format_version", -1)) != FORMAT_VERSION:
-        raise ValueError(f"{d / 'graph.json'}: format version {meta.get('format_version')!r}, this build reads {FORMAT_VERSION}")
+    meta = read_versioned_json(d / "graph.json", FORMAT_VERSION)
     graph = np.load(d / "graph.npy")
     entry_rows = np.load(d / "graph_entry_rows.npy")
     check_graph(graph, graph.shape[0] if graph.ndim == 2 else -1)
@@ -120,16 +118,14 @@ def is_graph_dir(index_dir: Union[str, Path]) -> bool:
 
 
 # ------------------------------------------------------------------------------------------------ the index
-class GraphIndex:
+class GraphIndex(FlatOverlay):
     """k-NN graph over a ``FAISSIndexBuilder``: ``graph.flat`` holds the rows, ``graph.entry`` copies of the entry rows."""
 
     def __init__(self, flat: Optional[FAISSIndexBuilder] = None, embedding_dim: int = 384, metric: str = "cosine",
                  device: Optional[str] = None, M: int = 32, ef: int = 64, width: int = DEFAULT_WIDTH,
                  knn_k: Optional[int] = None, n_entry: Optional[int] = None) -> None:
-        self.flat = flat if flat is not None else FAISSIndexBuilder(embedding_dim=embedding_dim, index_type="HNSW",
-                                                                    metric=metric, device=device)
-        self.device = self.flat.device
-        self.embedding_dim = self.flat.embedding_dim
+        super().__init__(flat if flat is not None else FAISSIndexBuilder(embedding_dim=embedding_dim, index_type="HNSW",
+                                                                         metric=metric, device=device))
         self.entry = FAISSIndexBuilder(embedding_dim=self.embedding_dim, index_type="Flat", metric="ip",
                                        device=str(self.device))
         self.M = check_degree(M)
@@ -144,29 +140,8 @@ class GraphIndex:
 
     # ------------------------------------------------------------------ properties
     @property
-    def ntotal(self) -> int:
-        return self.flat.ntotal
-
-    @property
     def n_entry(self) -> int:
         return self.entry.ntotal
-
-    @property
-    def doc_ids(self):
-        return self.flat.doc_ids
-
-    @property
-    def doc_texts(self):
-        return self.flat.doc_texts
-
-    @property
-    def index(self) -> Optional[IndexHandle]:
-        return self.flat.index
-
-    def _rows_view(self) -> torch.Tensor:
-        """The flat index's rows as a ``[ntotal, dim]`` device view (the layout is plain row-major)."""
-        n = self.flat.ntotal
-        return self.flat._tiled[: n * self.embedding_dim].view(n, self.embedding_dim)
 
     def _require_graph(self) -> None:
         if self.graph is None or self._n_linked != self.flat.ntotal:
@@ -305,10 +280,6 @@ class GraphIndex:
         if self.flat.ntotal != first or self.graph is None:
             self.build_graph()
 
-    def remove_ids(self, ids) -> int:
-        """The flat index's tombstones: a removed row is still traversed, and never returned."""
-        return self.flat.remove_ids(ids)
-
     def compact(self) -> np.ndarray:
         """The flat ``compact()``, then the edges are remapped through the returned ``kept`` (``remap_graph``) and the
         entry rows rebuilt over the new ``ntotal``."""
@@ -384,17 +355,7 @@ class GraphIndex:
 
     def validate(self, num_queries: int = 1000, k: int = 10, seed: int = 0, ef: Optional[int] = None,
                  width: Optional[int] = None) -> float:
-        """recall@k of ``search`` against ``flat.search`` (the reference's ``validation:`` block: ``num_queries``
-        1000, ``brute_force_top_k`` 10), the queries being ``num_queries`` distinct rows of the index."""
-        n = self.flat.ntotal
-        if n < 1:
-            raise RuntimeError("validate(): the index is empty")
-        pick = np.sort(np.random.default_rng(seed).permutation(n)[: min(int(num_queries), n)])
-        with torch.cuda.device(self.device):
-            q = self._rows_view()[torch.from_numpy(pick).to(self.device)].cpu().numpy()
-        _, found = self.search(q, k, ef=ef, width=width)
-        _, truth = self.flat.search(q, k)
-        return recall_at_k(found, truth)
+        return super().validate(num_queries, k, seed, ef=ef, width=width)
 
     # ------------------------------------------------------------------ persistence
     def save(self, output_dir: Union[str, Path]) -> None:

@@ -26,6 +26,7 @@ import torch
 
 from . import _native
 from .index import FAISSIndexBuilder, IndexHandle, _host_queries_to_device
+from .overlay import FlatOverlay, read_versioned_json, recall_at_k  # noqa: F401  (recall_at_k: callers import it from here)
 
 IVF_K_MAX = 256
 IVF_NLIST_MAX = 65536
@@ -109,9 +110,7 @@ def save_lists(out_dir: Union[str, Path], centroids: np.ndarray, list_offsets: n
 def load_lists(index_dir: Union[str, Path]):
     """``(centroids, list_offsets, list_rows, meta)`` as ``save_lists`` wrote them; the CSR is checked."""
     d = Path(index_dir)
-    meta = json.loads((d / "ivf.json").read_text())
-    if int(meta.get("format_version", -1)) != FORMAT_VERSION:
-        raise ValueError(f"{d / 'ivf.json'}: format version {meta.get('format_version')!r}, this build reads {FORMAT_VERSION}")
+    meta = read_versioned_json(d / "ivf.json", FORMAT_VERSION)
     centroids = np.load(d / "ivf_centroids.npy").astype(np.float32)
     offsets = np.load(d / "ivf_list_offsets.npy").astype(np.int64)
     rows = np.load(d / "ivf_list_rows.npy").astype(np.int32)
@@ -125,26 +124,14 @@ def is_ivf_dir(index_dir: Union[str, Path]) -> bool:
     return (Path(index_dir) / "ivf.json").exists()
 
 
-def recall_at_k(found: np.ndarray, truth: np.ndarray) -> float:
-    """Mean over the queries of |found ids AND true ids| / |true ids| (-1 padding ignored; a query without true ids
-    counts as 1.0)."""
-    total = 0.0
-    for f, t in zip(np.asarray(found), np.asarray(truth)):
-        t = t[t >= 0]
-        total += 1.0 if t.size == 0 else np.intersect1d(f[f >= 0], t).size / t.size
-    return total / max(len(truth), 1)
-
-
 # ------------------------------------------------------------------------------------------------ the index
-class IVFIndex:
+class IVFIndex(FlatOverlay):
     """Inverted-file index over a ``FAISSIndexBuilder``: ``ivf.flat`` holds the rows, ``ivf.quantizer`` the centroids."""
 
     def __init__(self, flat: Optional[FAISSIndexBuilder] = None, embedding_dim: int = 384, metric: str = "cosine",
                  device: Optional[str] = None, nlist: Optional[int] = None, nprobe: int = 32) -> None:
-        self.flat = flat if flat is not None else FAISSIndexBuilder(embedding_dim=embedding_dim, index_type="IVF",
-                                                                    metric=metric, device=device)
-        self.device = self.flat.device
-        self.embedding_dim = self.flat.embedding_dim
+        super().__init__(flat if flat is not None else FAISSIndexBuilder(embedding_dim=embedding_dim, index_type="IVF",
+                                                                         metric=metric, device=device))
         self.quantizer = FAISSIndexBuilder(embedding_dim=self.embedding_dim, index_type="Flat", metric="ip",
                                            device=str(self.device))
         self.nlist_requested = None if nlist is None else int(nlist)
@@ -166,27 +153,6 @@ class IVFIndex:
     @property
     def nlist(self) -> int:
         return self.quantizer.ntotal
-
-    @property
-    def ntotal(self) -> int:
-        return self.flat.ntotal
-
-    @property
-    def doc_ids(self):
-        return self.flat.doc_ids
-
-    @property
-    def doc_texts(self):
-        return self.flat.doc_texts
-
-    @property
-    def index(self) -> Optional[IndexHandle]:
-        return self.flat.index
-
-    def _rows_view(self) -> torch.Tensor:
-        """The flat index's rows as a ``[ntotal, dim]`` device view (the layout is plain row-major)."""
-        n = self.flat.ntotal
-        return self.flat._tiled[: n * self.embedding_dim].view(n, self.embedding_dim)
 
     def _require_lists(self) -> None:
         if self.list_offsets is None or self._n_listed != self.flat.ntotal:
@@ -338,10 +304,6 @@ class IVFIndex:
             new = self._assign_device(self._rows_view()[first:])
             self._install(torch.cat([self._assign, new]))
 
-    def remove_ids(self, ids) -> int:
-        """The flat index's tombstones: they reach the IVF search through ``flat.search_mask``."""
-        return self.flat.remove_ids(ids)
-
     def compact(self) -> np.ndarray:
         """The flat ``compact()``, then the lists are remapped through the returned ``kept`` (``remap_lists``)."""
         self._require_lists()
@@ -457,17 +419,7 @@ class IVFIndex:
             return scores.cpu().numpy(), ids.cpu().numpy()
 
     def validate(self, num_queries: int = 1000, k: int = 10, seed: int = 0, nprobe: Optional[int] = None) -> float:
-        """recall@k of ``search`` against ``flat.search`` (the reference's ``validation:`` block: ``num_queries``
-        1000, ``brute_force_top_k`` 10), the queries being ``num_queries`` distinct rows of the index."""
-        n = self.flat.ntotal
-        if n < 1:
-            raise RuntimeError("validate(): the index is empty")
-        pick = np.sort(np.random.default_rng(seed).permutation(n)[: min(int(num_queries), n)])
-        with torch.cuda.device(self.device):
-            q = self._rows_view()[torch.from_numpy(pick).to(self.device)].cpu().numpy()
-        _, found = self.search(q, k, nprobe=nprobe)
-        _, truth = self.flat.search(q, k)
-        return recall_at_k(found, truth)
+        return super().validate(num_queries, k, seed, nprobe=nprobe)
 
     # ------------------------------------------------------------------ persistence
     def save(self, output_dir: Union[str, Path]) -> None:

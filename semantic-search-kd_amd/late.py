@@ -24,6 +24,7 @@ import torch
 
 from . import _native
 from .index import FAISSIndexBuilder, _host_queries_to_device
+from .overlay import read_versioned_json
 
 DIM = _native.SSKD_DIM
 LATE_TQ_MAX = 128
@@ -68,9 +69,7 @@ def save_store(out_dir: Union[str, Path], tokens_bf16_bits: np.ndarray, lims: np
 def load_store(index_dir: Union[str, Path]):
     """``(tokens uint16 [T, 384], lims int64 [n + 1], meta)`` as ``save_store`` wrote them, checked."""
     d = Path(index_dir)
-    meta = json.loads((d / "late.json").read_text())
-    if int(meta.get("format_version", -1)) != FORMAT_VERSION:
-        raise ValueError(f"{d / 'late.json'}: format version {meta.get('format_version')!r}, this build reads {FORMAT_VERSION}")
+    meta = read_versioned_json(d / "late.json", FORMAT_VERSION)
     if int(meta.get("dim", -1)) != DIM or meta.get("dtype") != "bfloat16":
         raise ValueError(f"{d / 'late.json'}: expected {DIM}-d bfloat16 tokens")
     lims = check_lims(np.load(d / "late_token_lims.npy"), n_rows=int(meta["ntotal"]), n_tokens=int(meta["n_tokens"]))

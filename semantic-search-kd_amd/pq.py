@@ -26,6 +26,7 @@ import torch
 from . import _native
 from .index import FAISSIndexBuilder, _host_queries_to_device
 from .ivf import IVF_K_MAX, IVF_NLIST_MAX, IVFIndex, csr_from_assignment, load_lists
+from .overlay import read_versioned_json
 
 PQ_DIM = 384
 PQ_NBITS = 8
@@ -95,9 +96,7 @@ def save_pq(out_dir: Union[str, Path], codebooks: np.ndarray, codes: np.ndarray,
 def load_pq(index_dir: Union[str, Path]):
     """``(codebooks, codes, meta)`` as ``save_pq`` wrote them; shapes and types are checked."""
     d = Path(index_dir)
-    meta = json.loads((d / "pq.json").read_text())
-    if int(meta.get("format_version", -1)) != PQ_FORMAT_VERSION:
-        raise ValueError(f"{d / 'pq.json'}: format version {meta.get('format_version')!r}, this build reads {PQ_FORMAT_VERSION}")
+    meta = read_versioned_json(d / "pq.json", PQ_FORMAT_VERSION)
     if int(meta.get("nbits", -1)) != PQ_NBITS:
         raise ValueError(f"{d / 'pq.json'}: nbits={meta.get('nbits')!r}, this build reads {PQ_NBITS}")
     m = check_m(meta["m"])

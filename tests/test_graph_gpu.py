@@ -187,6 +187,33 @@ def test_disconnected_graph_seeds_and_padding(gpu):
     _same(got[:2], oracle.topk_of_scores(scores, 200), "both components, exactly")
 
 
+@pytest.fixture(scope="module")
+def edgeless(world):
+    """degree 4, every entry -1: a search scores its seeds and nothing else"""
+    return GraphIndex.from_graph(world.flat, np.full((N, 4), -1, dtype=np.int32))
+
+
+@pytest.mark.parametrize("nq", [1, 3])
+@pytest.mark.parametrize("n", [1, 2, 31, 32, 33, 34, 64, 65, 66])
+def test_staging_seeds_only_is_the_exact_search_over_the_seeds(world, edgeless, n, nq):
+    """The seeds are the only rows staged, so their count sits on the 32-row chunk boundaries of the staging.  One seed
+    is -1 whenever n > 1 and takes no slot: n - 1 = 30, 31, 32 (exactly one chunk), 33 (one row into the second), 63,
+    64 (exactly two chunks) and 65 rows are scored; n = 2 leaves one real seed for k = 2, so the result ends in padding.
+    Every query has its own distinct rows."""
+    rng = np.random.default_rng(1000 + n)
+    seeds = np.stack([rng.permutation(N)[:n] for _ in range(nq)]).astype(np.int64)
+    if n > 1:
+        seeds[:, n // 2] = -1
+    k = min(n, 10)
+    q = torch.from_numpy(world.queries[:nq]).to(edgeless.device)
+    got = edgeless.search_device(q, k, ef=max(n, 16), seeds=torch.from_numpy(seeds).to(edgeless.device),
+                                 normalize_queries=False)
+    for i in range(nq):
+        ref = world.flat.search_device(q[i:i + 1], k, allow=seeds[i][seeds[i] >= 0], normalize_queries=False)
+        _same(tuple(t[i:i + 1].cpu().numpy() for t in got), tuple(t.cpu().numpy() for t in ref), f"n={n} query {i}")
+        assert (got[1][i] >= 0).sum().item() == min(k, max(n - 1, 1))
+
+
 def test_a_query_holding_nan_returns_padding(world):
     """A NaN score ranks nowhere, so it enters no list: the query gets padding and no iteration, its neighbours in the
     batch are untouched (the contract leaves such a query's result open; this is what the kernel does)."""

@@ -3,6 +3,7 @@
 The oracle of a search is ``oracle.topk_of_scores`` over ``oracle.scores_fma`` (the scan's fma order, in C) with every
 row outside the probed lists - and every filtered or removed row - set to -inf: the results are compared with
 ``np.array_equal``, scores by their bits.  With every list probed the oracle is the plain exact search."""
+import ctypes as C
 import math
 from types import SimpleNamespace
 
@@ -133,13 +134,20 @@ def _awkward(name):
             a[order[cuts[l]:cuts[l + 1]]] = l
         a[order[cuts[4]:]] = 4 + rng.integers(0, 2, size=N - cuts[4])
         return 6, a
+    if name == "tiny_64_65":   # exactly two chunks of 32 rows, and one row into a third
+        a = np.empty(N, dtype=np.int64)
+        order = rng.permutation(N)
+        a[order[:64]] = 0
+        a[order[64:129]] = 1
+        a[order[129:]] = 2 + rng.integers(0, 2, size=N - 129)
+        return 4, a
     if name == "nlist_1":
         return 1, np.zeros(N, dtype=np.int64)
     raise KeyError(name)
 
 
-@pytest.mark.parametrize("name", ["five_empty", "skewed_90", "tiny_1_31_32_33", "nlist_1"])
-def test_awkward_lists(world, name):
+@pytest.mark.parametrize("name", ["five_empty", "skewed_90", "tiny_1_31_32_33", "tiny_64_65", "nlist_1"])
+def test_awkward_lists(world, name, native_lib):
     nlist, assignment = _awkward(name)
     offsets, rows = ivf_mod.csr_from_assignment(assignment, nlist)
     sizes = np.diff(offsets)
@@ -164,6 +172,34 @@ def test_awkward_lists(world, name):
         D, I = index.search(empty_first, 5, nprobe=1)
         assert _probe_host(index, empty_first, 1)[0, 0] == 2
         assert (I == -1).all() and (D == oracle.NEG_PAD).all()
+    if name == "tiny_64_65":   # each small list probed alone with k = 256: few parts, and one part that walks every chunk
+        assert sizes[:2].tolist() == [64, 65]
+        lib, k = native_lib, 256
+        d_off, d_rows = torch.from_numpy(offsets).cuda(), torch.from_numpy(rows).cuda()
+        for l in (0, 1):
+            own = index.centroids_numpy()[[l]]   # a unit row: its own list scores 1.0 and is probed first
+            probe = _probe_host(index, own, 1)
+            assert probe[0, 0] == l
+            ref = _ivf_oracle(oracle.scores_fma(own, world.corpus), probe, offsets, rows, k)
+            assert (ref[1][0] >= 0).sum() == sizes[l]
+            _same(index.search(own, k, nprobe=1), ref, f"{name} list {l} alone")
+            _same(index.search(own, k, nprobe=1), world.flat.search(own, k, allow=rows[offsets[l]:offsets[l + 1]]),
+                  f"{name} list {l} alone vs flat.search")
+            # through the C-ABI with the workspace of ONE part: that part walks the list's two (three) chunks itself
+            parts = C.c_int(0)
+            _native.check(lib.sskd_ivf_search_plan(1, 1, k, N, 1, C.byref(parts), None, None))
+            assert parts.value == 1
+            one = int(lib.sskd_ivf_search_workspace_bytes(1, 1, k, N, 1))
+            q = torch.from_numpy(own.copy()).cuda()
+            out_s = torch.empty((1, k), dtype=torch.float32, device="cuda")
+            out_i = torch.empty((1, k), dtype=torch.int64, device="cuda")
+            ws = torch.empty(one, dtype=torch.uint8, device="cuda")
+            _native.check(lib.sskd_ivf_search(world.flat._tiled.data_ptr(), N, q.data_ptr(), 1,
+                                              torch.from_numpy(probe).cuda().data_ptr(), 1, d_off.data_ptr(),
+                                              d_rows.data_ptr(), nlist, k, 0, None, out_s.data_ptr(), out_i.data_ptr(),
+                                              ws.data_ptr(), one, stream()))
+            torch.cuda.synchronize()
+            _same((out_s.cpu().numpy(), out_i.cpu().numpy()), ref, f"{name} list {l} alone, one part")
 
 
 def test_capi_probe_with_minus_one_and_more_probes_than_a_prefix_block(world, native_lib):

@@ -230,7 +230,10 @@ def test_adc_search_without_refinement(world, ranked, nq, nprobe, k):
 
 
 # ------------------------------------------------------------------------------------------------ refined search
-@pytest.mark.parametrize("k, R", [(10, 100), (1, 1), (10, 256), (100, 100)])
+@pytest.mark.parametrize("k, R", [(10, 100), (1, 1), (10, 256), (100, 100),
+                                  # R on the 32-row chunk boundaries of the staging: a last chunk of 31, exactly one chunk,
+                                  # one row into the second, exactly two chunks, one row into the third
+                                  (1, 31), (32, 32), (33, 33), (10, 64), (10, 65)])
 def test_refined_search_is_the_exact_search_over_the_candidates(world, ranked, k, R):
     q = world.queries[:8]
     D, I, cand = world.index.search_with_candidates(q, k, nprobe=4, refine=R)
