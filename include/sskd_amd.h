@@ -728,6 +728,40 @@ int sskd_late_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_
                      int64_t id_offset, float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Compressed token store (residual compression as in ColBERTv2 / PLAID).  dim = 384, nbits in {2, 4}, L = 2^nbits.
+ * Codec: d_centroids DEVICE bf16 [C, 384] (1 <= C <= 65 536), d_cutoffs DEVICE fp32 [L - 1] ascending, d_weights DEVICE
+ * fp32 [L]; all finite.  Store: d_cid int32 [n_tokens], d_scale fp32 [n_tokens], d_codes uint8 [n_tokens, 48 nbits];
+ * tok_lims as above.  Per token t with centroid c = centroids[cid], per column d, in fp32:
+ *   r = fp32(t_d) - fp32(c_d);  code_d = the number of cutoffs strictly below r (a value on a cutoff falls in the lower
+ *   bucket, NaN gives 0);  dec_d = bf16(fp32(c_d) + weights[code_d]) rounded to nearest even - the only value a score sees;
+ *   scale = 1 / max(sqrt(ss), 1e-12f), ss the sum of squares of dec in sskd_late_pack_tokens' order, sqrt and division
+ *   correctly rounded.
+ * Byte order: column d = 16 s + 8 h + e (s < 24, h < 2, e < 8) is position p = 192 h + 8 s + e; position p occupies
+ * nbits bits from bit nbits (p mod (8 / nbits)) of byte p / (8 / nbits).
+ *   sskd_latec_compress writes store rows [row0, row0 + n) (which must lie inside [0, n_store)) from d_tokens DEVICE bf16
+ * [n, 384] and d_assign DEVICE int64 [n] (the centroid of every token; a value outside [0, C) is clamped into it).  One
+ * wave per token.
+ *   sskd_latec_rerank is sskd_late_rerank over such a store: v_ij = fl32(acc_ij * scale_j) with acc_ij the fp32
+ * accumulation of the 384 exact products q_i * dec_j by 24 v_mfma_f32_32x32x16_bf16 from a zero accumulator, score = sum
+ * over i ascending (sequential fp32 from +0.0) of max over j of v_ij.  The bits of a score depend on the query's tokens,
+ * the document's compressed tokens and the codec alone.  A cid outside [0, C) is read as clamped into it.  Arguments,
+ * outputs, limits and the two launches are those of sskd_late_rerank (_plan adds nbits; LDS holds 64 bytes of weights
+ * more); query tokens, centroids, cid, scale and codes 16-byte aligned.  Both calls: stream-ordered, no host sync
+ * (graph-capturable), nothing allocated, every argument checked before anything is enqueued; n = 0 / nq = 0 succeed. */
+#define SSKD_LATE_C_MAX 65536
+int sskd_latec_compress(const void* d_tokens, const int64_t* d_assign, int64_t n, const void* d_centroids, int C,
+                       const float* d_cutoffs, const float* d_weights, int nbits, int32_t* d_cid, float* d_scale,
+                       uint8_t* d_codes, int64_t row0, int64_t n_store, void* stream);
+int sskd_latec_rerank_plan(int nq, int max_tq, int R, int k, int nbits, int* workgroups, int* threads, int* lds_bytes,
+                                     int* chunk);
+size_t sskd_latec_rerank_workspace_bytes(int nq, int R);
+int sskd_latec_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq,
+                                const int32_t* d_cid, const float* d_scale, const uint8_t* d_codes, int nbits,
+                                const void* d_centroids, int C, const float* d_weights, const int64_t* d_tok_lims, int64_t n_rows,
+                                int64_t n_tokens, const int64_t* d_candidates, int R, int k, int64_t id_offset,
+                                float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -213,6 +213,12 @@ SIGNATURES = {
     "sskd_late_rerank": (
         _i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]
     ),
+    "sskd_latec_compress": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _vp]),
+    "sskd_latec_rerank_plan": (_i, [_i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),
+    "sskd_latec_rerank_workspace_bytes": (_sz, [_i, _i]),
+    "sskd_latec_rerank": (
+        _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

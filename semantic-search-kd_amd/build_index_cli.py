@@ -81,7 +81,12 @@ def main(argv=None) -> int:
                          "index: 768 B per document token; single-index builds only")
     ap.add_argument("--late-max-doc-tokens", type=_positive, default=180,
                     help="late interaction: tokens kept per document ([CLS] and the closing [SEP] included)")
+    ap.add_argument("--late-compress", type=int, choices=(2, 4), default=None,
+                    help="late interaction: hold the token store residual-compressed at this many bits per column (104 B "
+                         "or 200 B per token instead of 768 B); the codec is trained on a subset of the documents")
     args = ap.parse_args(argv)
+    if args.late_compress and not args.late_interaction:
+        ap.error("--late-compress needs --late-interaction")
     for flag, p in (("--model-path", args.model_path), ("--data-path", args.data_path)):
         if not Path(p).exists():
             ap.error(f"{flag}: {p} does not exist")
@@ -167,13 +172,19 @@ def main(argv=None) -> int:
     else:
         builder.save(Path(args.output_dir))
     if args.late_interaction:
-        from .late import LateInteractionIndex
+        from .late import LateInteractionIndex, store_bytes
 
         late = LateInteractionIndex(builder, max_doc_tokens=args.late_max_doc_tokens)
-        late.build_from_texts(model, [builder.doc_texts[i] for i in builder.doc_ids], batch_size=args.batch_size)
+        late.build_from_texts(model, [builder.doc_texts[i] for i in builder.doc_ids], batch_size=args.batch_size,
+                              compress=args.late_compress)
         late.save(Path(args.output_dir))
-        print(f"Late-interaction token store: {late.n_tokens} tokens, {late.nbytes} bytes "
-              f"({late.n_tokens / max(late.ntotal, 1):.1f} tokens per row, at most {late.max_doc_tokens})")
+        if args.late_compress:
+            print(f"Late-interaction token store: {late.n_tokens} tokens, {late.nbytes} bytes compressed to "
+                  f"{late.nbits} bits over {late.n_centroids} centroids ({store_bytes(late.n_tokens)} bytes as bf16; "
+                  f"{late.n_tokens / max(late.ntotal, 1):.1f} tokens per row, at most {late.max_doc_tokens})")
+        else:
+            print(f"Late-interaction token store: {late.n_tokens} tokens, {late.nbytes} bytes "
+                  f"({late.n_tokens / max(late.ntotal, 1):.1f} tokens per row, at most {late.max_doc_tokens})")
     print(f"Index saved to: {args.output_dir}")
     print(f"Total vectors: {index.ntotal}")
     return 0

@@ -91,7 +91,8 @@ struct LateParams {
 };
 
 // the token range of candidate id (global), or an empty range when there is no such candidate
-__device__ inline void cand_range(const LateParams& p, int64_t id, int64_t& beg, int64_t& td) {
+template <class P>
+__device__ inline void cand_range(const P& p, int64_t id, int64_t& beg, int64_t& td) {
   beg = 0; td = 0;
   const int64_t row = id - p.id_offset;
   if (id < 0 || row < 0 || row >= p.n_rows) return;
@@ -155,6 +156,192 @@ __global__ __launch_bounds__(L_THREADS) void late_score_kernel(const LateParams 
             for (int r = 0; r < 16; ++r) {
               const bool real = !partial || acc_row(r) + 4 * h < left;
               m = fmaxf(m, real ? acc[r] : -INFINITY);
+            }
+            m = fmaxf(m, __shfl_xor(m, 32));
+            best[b] = fmaxf(best[b], m);
+          }
+        }
+      }
+      // sequential fp32 sum from +0.0f over the query tokens in ascending order (every lane computes the same chain)
+      score = 0.f;
+#pragma unroll
+      for (int b = 0; b < QB; ++b) {
+        if (b < nb) {
+          const int n = min(32, Tq - 32 * b);
+          for (int i = 0; i < n; ++i) score += __shfl(best[b], i);
+        }
+      }
+    }
+    if (lane == 0) p.raw[(int64_t)q * p.R + c] = score;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ compressed store
+// A token is the id of a centroid (bf16 [C, 384]) plus an NBITS code per column: code = number of cutoffs strictly below
+// r = fp32(t) - fp32(c); what the score sees is dec = bf16_rn(fp32(c) + weights[code]) and scale = 1 / max(|dec|, 1e-12)
+// (include/sskd_amd.h, "compressed token store"; tests/late_codec_cases.py restates all of it).  Column d = 16 s + 8 h + e
+// sits at position 192 h + 8 s + e, NBITS bits each, low bits first: the A operand of lane half h is bytes
+// [24 NBITS h, 24 NBITS (h + 1)) of the row, and k-step s of it is the NBITS bytes from 24 NBITS h + NBITS s.
+constexpr int L_C_MAX = SSKD_LATE_C_MAX;    // 65 536
+
+__device__ inline uint32_t bf16_rn_bits(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;   // round to nearest even (finite input)
+}
+
+// One wave per token; lane l < 48 holds columns 8 l .. 8 l + 7 (k-step l >> 1, lane half l & 1) of the token and of its
+// centroid.  The sum of squares of dec runs in the pack kernel's order.
+template <int NBITS>
+__global__ __launch_bounds__(L_THREADS) void late_compress_kernel(const uint16_t* __restrict__ tokens, const int64_t* __restrict__ assign,
+                                                                  int64_t n, const uint16_t* __restrict__ centroids, int C,
+                                                                  const float* __restrict__ cutoffs, const float* __restrict__ weights,
+                                                                  int32_t* __restrict__ cid_out, float* __restrict__ scale_out,
+                                                                  uint8_t* __restrict__ codes_out, int64_t row0) {
+  constexpr int L = 1 << NBITS;
+  const int lane = threadIdx.x & 63;
+  const int64_t tok = (int64_t)blockIdx.x * L_WAVES + (threadIdx.x >> 6);
+  if (tok >= n) return;
+  const int64_t want = assign[tok];
+  const int c = want < 0 ? 0 : (want >= C ? C - 1 : (int)want);   // never an address from unchecked data
+  float p = 0.f;
+  uint32_t packed = 0u;
+  if (lane < L_ROW_VEC) {
+    const uint4 tv = *reinterpret_cast<const uint4*>(tokens + tok * DIM + 8 * lane);
+    const uint4 cv = *reinterpret_cast<const uint4*>(centroids + (int64_t)c * DIM + 8 * lane);
+    const uint32_t tw[4] = {tv.x, tv.y, tv.z, tv.w}, cw[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float t = __uint_as_float(e & 1 ? tw[e >> 1] & 0xFFFF0000u : tw[e >> 1] << 16);
+      const float cc = __uint_as_float(e & 1 ? cw[e >> 1] & 0xFFFF0000u : cw[e >> 1] << 16);
+      const float r = t - cc;
+      uint32_t code = 0u;
+#pragma unroll
+      for (int i = 0; i < L - 1; ++i) code += cutoffs[i] < r ? 1u : 0u;   // false for NaN: code 0
+      const float dec = __uint_as_float(bf16_rn_bits(cc + weights[code]) << 16);
+      p = fmaf(dec, dec, p);
+      packed |= code << (NBITS * e);
+    }
+  }
+  const float ss = wave_sum(p);
+  const float scale = 1.0f / fmaxf(__builtin_sqrtf(ss), 1e-12f);   // IEEE sqrt and division (see the pack kernel)
+  const int64_t row = row0 + tok;
+  if (lane < L_ROW_VEC) {
+    uint8_t* dst = codes_out + row * (6 * 8 * NBITS) + (24 * NBITS) * (lane & 1) + NBITS * (lane >> 1);
+    if (NBITS == 2) *reinterpret_cast<uint16_t*>(dst) = (uint16_t)packed;
+    else *reinterpret_cast<uint32_t*>(dst) = packed;
+  }
+  if (lane == 0) {
+    cid_out[row] = c;
+    scale_out[row] = scale;
+  }
+}
+
+struct LateCParams {
+  const bf16x8* q_tokens;    // [sum Tq, 48]
+  const int64_t* q_lims;     // [nq + 1]
+  const int32_t* cid;        // [n_tokens]
+  const float* scale;        // [n_tokens]
+  const uint8_t* codes;      // [n_tokens, 48 NBITS]
+  const bf16x8* centroids;   // [C, 48]
+  const float* weights;      // [2^NBITS]
+  const int64_t* tok_lims;   // [n_rows + 1]
+  const int64_t* cand;       // [nq, R]
+  float* raw;                // [nq, R]
+  int64_t n_q_tokens, n_tokens, n_rows, id_offset;
+  int R, chunk, C;
+};
+
+// late_score_kernel with the A operand decoded in registers: per tile a lane reads its row's centroid id, scale and its
+// half of the row's codes, gathers the 24 16-byte pieces of the centroid row (the request shape of the bf16 store's token
+// loads, the row address taken from the clamped id) and turns each piece into the k-step's fragment in place.  The weights
+// sit in a 16-float LDS table: the lanes of a wave read at most 16 consecutive words, which is conflict-free.
+template <int QB, int NBITS>
+__global__ __launch_bounds__(L_THREADS) void late_score_compressed_kernel(const LateCParams p) {
+  constexpr int CODE_VEC = 3 * NBITS / 2;   // 16-byte loads of one lane half's codes: 3 or 6
+  constexpr uint32_t MASK = (1u << NBITS) - 1u;
+  __shared__ bf16x8 qs[QB][L_KSTEPS][64];   // B fragments: [block][k-step][lane]
+  __shared__ float wt[16];
+  const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r32 = lane & 31, h = lane >> 5;
+  int64_t q0 = p.q_lims[q], tq64 = p.q_lims[q + 1] - q0;
+  if (q0 < 0 || tq64 < 0 || q0 + tq64 > p.n_q_tokens) tq64 = 0;   // (the host validated its copy of the lims)
+  const int Tq = (int)(tq64 < QB * 32 ? tq64 : QB * 32);
+  const int nb = (Tq + 31) >> 5;            // blocks in use (workgroup-uniform)
+  for (int idx = threadIdx.x; idx < nb * 32 * L_ROW_VEC; idx += L_THREADS) {
+    const int i = idx / L_ROW_VEC, ch = idx % L_ROW_VEC;
+    bf16x8 v = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
+    if (i < Tq) v = p.q_tokens[(q0 + i) * L_ROW_VEC + ch];
+    qs[i >> 5][ch >> 1][((ch & 1) << 5) | (i & 31)] = v;
+  }
+  if (threadIdx.x < 16) wt[threadIdx.x] = threadIdx.x <= MASK ? p.weights[threadIdx.x] : 0.f;
+  __syncthreads();
+
+  const int c_begin = blockIdx.y * p.chunk;
+  const int c_end = min(c_begin + p.chunk, p.R);
+  for (int c = c_begin + wave; c < c_end; c += L_WAVES) {
+    const int64_t id = p.cand[(int64_t)q * p.R + c];
+    int64_t beg, td;
+    cand_range(p, id, beg, td);
+    float score = -INFINITY;                 // no candidate, or a row without tokens: absent
+    if (td > 0 && Tq > 0) {
+      float best[QB];
+#pragma unroll
+      for (int b = 0; b < QB; ++b) best[b] = -INFINITY;
+      // the centroid id of the lane's row is loaded one tile ahead, so that the centroid gather of a tile does not wait
+      // for it behind the previous tile's MFMAs
+      int cid_next = p.cid[beg + (r32 < td ? r32 : td - 1)];
+      for (int64_t t0 = 0; t0 < td; t0 += 32) {
+        // the lane's document row of this tile; rows past the end re-read the last real row and are masked below
+        const int64_t row = beg + (t0 + r32 < td ? t0 + r32 : td - 1);
+        const int cen = min(max(cid_next, 0), p.C - 1);   // a corrupt store scores garbage and cannot fault
+        if (t0 + 32 < td) cid_next = p.cid[beg + (t0 + 32 + r32 < td ? t0 + 32 + r32 : td - 1)];
+        const float sc = p.scale[row];
+        const uint4* cp = reinterpret_cast<const uint4*>(p.codes + row * (6 * 8 * NBITS) + (24 * NBITS) * h);
+        uint32_t cw[4 * CODE_VEC];
+#pragma unroll
+        for (int v = 0; v < CODE_VEC; ++v) {
+          const uint4 u = cp[v];
+          cw[4 * v] = u.x; cw[4 * v + 1] = u.y; cw[4 * v + 2] = u.z; cw[4 * v + 3] = u.w;
+        }
+        const bf16x8* src = p.centroids + (int64_t)cen * L_ROW_VEC + h;
+        bf16x8 a[L_KSTEPS];
+#pragma unroll
+        for (int s = 0; s < L_KSTEPS; ++s) a[s] = src[2 * s];
+        // decode in place: widen, add weights[code], round to bf16 (nearest even), pack
+#pragma unroll
+        for (int s = 0; s < L_KSTEPS; ++s) {
+          const uint32_t bits = NBITS == 2 ? cw[s >> 1] >> (16 * (s & 1)) : cw[s];
+          const uint4 cv = __builtin_bit_cast(uint4, a[s]);
+          const uint32_t w[4] = {cv.x, cv.y, cv.z, cv.w};
+          uint32_t o[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float lo = __uint_as_float(w[j] << 16) + wt[(bits >> (NBITS * 2 * j)) & MASK];
+            const float hi = __uint_as_float(w[j] & 0xFFFF0000u) + wt[(bits >> (NBITS * (2 * j + 1))) & MASK];
+            o[j] = bf16_rn_bits(lo) | (bf16_rn_bits(hi) << 16);
+          }
+          a[s] = __builtin_bit_cast(bf16x8, make_uint4(o[0], o[1], o[2], o[3]));
+        }
+        // accumulator register r of lane l belongs to document row acc_row(r) + 4 (l >> 5) of the tile: its scale
+        float scr[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) scr[r] = __shfl(sc, acc_row(r) + 4 * h);
+        const bool partial = td - t0 < 32;
+        const int left = (int)(td - t0);    // real rows of the tile when partial
+#pragma unroll
+        for (int b = 0; b < QB; ++b) {
+          if (b < nb) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < L_KSTEPS; ++s)
+              acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], qs[b][s][lane], acc, 0, 0, 0);
+            float m = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const bool real = !partial || acc_row(r) + 4 * h < left;
+              m = fmaxf(m, real ? acc[r] * scr[r] : -INFINITY);
             }
             m = fmaxf(m, __shfl_xor(m, 32));
             best[b] = fmaxf(best[b], m);
@@ -247,6 +434,23 @@ void launch_score(const LateParams& p, int nq, int chunks, hipStream_t st) {
   hipLaunchKernelGGL(late_score_kernel<QB>, dim3((unsigned)nq, (unsigned)chunks), dim3(L_THREADS), 0, st, p);
 }
 
+template <int QB, int NBITS>
+void launch_score_compressed(const LateCParams& p, int nq, int chunks, hipStream_t st) {
+  hipLaunchKernelGGL((late_score_compressed_kernel<QB, NBITS>), dim3((unsigned)nq, (unsigned)chunks), dim3(L_THREADS), 0, st, p);
+}
+
+template <int NBITS>
+void launch_score_compressed_qb(const LateCParams& p, int qb, int nq, int chunks, hipStream_t st) {
+  switch (qb) {
+    case 1: launch_score_compressed<1, NBITS>(p, nq, chunks, st); break;
+    case 2: launch_score_compressed<2, NBITS>(p, nq, chunks, st); break;
+    case 3: launch_score_compressed<3, NBITS>(p, nq, chunks, st); break;
+    default: launch_score_compressed<4, NBITS>(p, nq, chunks, st); break;
+  }
+}
+
+bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
+
 }  // namespace
 
 extern "C" {
@@ -337,6 +541,112 @@ int sskd_late_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_
     default: launch_score<4>(p, nq, pl.chunks, st); break;
   }
   if (int rc = sskd::check_launch("late_score_kernel")) return rc;
+  hipLaunchKernelGGL(late_pick_kernel, dim3((unsigned)nq), dim3(64), 0, st, raw, d_candidates, R, k, d_out_scores, d_out_ids);
+  return sskd::check_launch("late_pick_kernel");
+}
+
+int sskd_latec_compress(const void* d_tokens, const int64_t* d_assign, int64_t n, const void* d_centroids, int C,
+                       const float* d_cutoffs, const float* d_weights, int nbits, int32_t* d_cid, float* d_scale,
+                       uint8_t* d_codes, int64_t row0, int64_t n_store, void* stream) {
+  SSKD_REQUIRE(nbits == 2 || nbits == 4, "latec_compress: nbits=%d, needs 2 or 4", nbits);
+  SSKD_REQUIRE(C >= 1 && C <= L_C_MAX, "latec_compress: C=%d outside [1, %d]", C, L_C_MAX);
+  SSKD_REQUIRE(n >= 0 && row0 >= 0 && n_store >= 0 && row0 <= n_store && n <= n_store - row0,
+               "latec_compress: rows [%lld, %lld + %lld) outside a store of %lld", (long long)row0, (long long)row0, (long long)n,
+               (long long)n_store);
+  if (n == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_tokens && d_assign && d_centroids && d_cutoffs && d_weights && d_cid && d_scale && d_codes,
+               "latec_compress: null pointer");
+  SSKD_REQUIRE(aligned16(d_tokens) && aligned16(d_centroids) && aligned16(d_codes) && aligned16(d_cid) && aligned16(d_scale),
+               "latec_compress: tokens, centroids and the store's arrays must be 16-byte aligned");
+  SSKD_REQUIRE(n / L_WAVES < (int64_t)INT32_MAX, "latec_compress: n too large");
+  const dim3 grid((unsigned)sskd::ceil_div(n, L_WAVES));
+  hipStream_t st = sskd::as_stream(stream);
+  const uint16_t* tokens = static_cast<const uint16_t*>(d_tokens);
+  const uint16_t* centroids = static_cast<const uint16_t*>(d_centroids);
+  if (nbits == 2)
+    hipLaunchKernelGGL(late_compress_kernel<2>, grid, dim3(L_THREADS), 0, st, tokens, d_assign, n, centroids, C, d_cutoffs,
+                       d_weights, d_cid, d_scale, d_codes, row0);
+  else
+    hipLaunchKernelGGL(late_compress_kernel<4>, grid, dim3(L_THREADS), 0, st, tokens, d_assign, n, centroids, C, d_cutoffs,
+                       d_weights, d_cid, d_scale, d_codes, row0);
+  return sskd::check_launch("late_compress_kernel");
+}
+
+int sskd_latec_rerank_plan(int nq, int max_tq, int R, int k, int nbits, int* workgroups, int* threads, int* lds_bytes,
+                                     int* chunk) {
+  SSKD_REQUIRE(nbits == 2 || nbits == 4, "latec_rerank_plan: nbits=%d, needs 2 or 4", nbits);
+  SSKD_REQUIRE(late_shape_ok(nq, max_tq, R, k), "latec_rerank_plan: needs nq >= 1, 1 <= Tq <= %d, 1 <= k <= R <= %d",
+               L_TQ_MAX, L_R_MAX);
+  const LatePlan pl = late_plan(nq, max_tq, R);
+  if (workgroups) *workgroups = nq * pl.chunks;
+  if (threads) *threads = L_THREADS;
+  if (lds_bytes) *lds_bytes = pl.qb * L_KSTEPS * 64 * (int)sizeof(bf16x8) + 16 * (int)sizeof(float);
+  if (chunk) *chunk = pl.chunk;
+  return SSKD_OK;
+}
+
+size_t sskd_latec_rerank_workspace_bytes(int nq, int R) { return sskd_late_rerank_workspace_bytes(nq, R); }
+
+int sskd_latec_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq,
+                                const int32_t* d_cid, const float* d_scale, const uint8_t* d_codes, int nbits,
+                                const void* d_centroids, int C, const float* d_weights, const int64_t* d_tok_lims, int64_t n_rows,
+                                int64_t n_tokens, const int64_t* d_candidates, int R, int k, int64_t id_offset,
+                                float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
+                                size_t workspace_bytes, void* stream) {
+  // every check comes before the first HIP call
+  SSKD_REQUIRE(nq >= 0, "latec_rerank: nq < 0");
+  SSKD_REQUIRE(nbits == 2 || nbits == 4, "latec_rerank: nbits=%d, needs 2 or 4", nbits);
+  SSKD_REQUIRE(C >= 1 && C <= L_C_MAX, "latec_rerank: C=%d outside [1, %d]", C, L_C_MAX);
+  SSKD_REQUIRE(R >= 1 && R <= L_R_MAX, "latec_rerank: R=%d outside [1, %d]", R, L_R_MAX);
+  SSKD_REQUIRE(k >= 1 && k <= R, "latec_rerank: k=%d outside [1, R=%d]", k, R);
+  SSKD_REQUIRE(n_rows >= 0 && n_tokens >= 0 && id_offset >= 0,
+               "latec_rerank: n_rows, n_tokens and id_offset must be >= 0");
+  if (nq == 0) return SSKD_OK;
+  SSKD_REQUIRE(q_lims, "latec_rerank: the host copy of q_lims is required");
+  SSKD_REQUIRE(q_lims[0] >= 0, "latec_rerank: q_lims[0] < 0");
+  int max_tq = 0;
+  for (int q = 0; q < nq; ++q) {
+    const int64_t tq = q_lims[q + 1] - q_lims[q];
+    SSKD_REQUIRE(tq >= 1 && tq <= L_TQ_MAX, "latec_rerank: query %d has Tq=%lld outside [1, %d] (q_lims must ascend)", q,
+                 (long long)tq, L_TQ_MAX);
+    if (tq > max_tq) max_tq = (int)tq;
+  }
+  SSKD_REQUIRE(d_q_tokens && d_q_lims && d_candidates && d_out_scores && d_out_ids && d_centroids && d_weights,
+               "latec_rerank: null pointer");
+  const bool store = d_cid && d_scale && d_codes && d_tok_lims;
+  SSKD_REQUIRE(n_rows == 0 || store || n_tokens == 0, "latec_rerank: null token store");
+  SSKD_REQUIRE(aligned16(d_q_tokens) && aligned16(d_centroids) && aligned16(d_codes) && aligned16(d_cid) && aligned16(d_scale),
+               "latec_rerank: query tokens, centroids and the store's arrays must be 16-byte aligned");
+  float* raw = d_out_raw;
+  if (!raw) {
+    const size_t need = sskd_latec_rerank_workspace_bytes(nq, R);
+    if (int rc = sskd::require_workspace("latec_rerank", d_workspace, workspace_bytes, need)) return rc;
+    sskd::Carver ws(d_workspace);
+    raw = ws.take<float>((size_t)nq * R);
+  }
+  LateCParams p{};
+  p.q_tokens = static_cast<const bf16x8*>(d_q_tokens);
+  p.q_lims = d_q_lims;
+  p.cid = d_cid;
+  p.scale = d_scale;
+  p.codes = d_codes;
+  p.centroids = static_cast<const bf16x8*>(d_centroids);
+  p.weights = d_weights;
+  p.tok_lims = d_tok_lims;
+  p.cand = d_candidates;
+  p.raw = raw;
+  p.n_q_tokens = q_lims[nq];
+  p.n_tokens = store ? n_tokens : 0;
+  p.n_rows = store ? n_rows : 0;
+  p.id_offset = id_offset;
+  p.R = R;
+  p.C = C;
+  const LatePlan pl = late_plan(nq, max_tq, R);
+  p.chunk = pl.chunk;
+  hipStream_t st = sskd::as_stream(stream);
+  if (nbits == 2) launch_score_compressed_qb<2>(p, pl.qb, nq, pl.chunks, st);
+  else launch_score_compressed_qb<4>(p, pl.qb, nq, pl.chunks, st);
+  if (int rc = sskd::check_launch("late_score_compressed_kernel")) return rc;
   hipLaunchKernelGGL(late_pick_kernel, dim3((unsigned)nq), dim3(64), 0, st, raw, d_candidates, R, k, d_out_scores, d_out_ids);
   return sskd::check_launch("late_pick_kernel");
 }

@@ -12,6 +12,10 @@ The reference's ``configs/service.yaml`` carries ``features.enable_late_interact
   their pooled vectors, ``rerank_device`` orders them by MaxSim: score descending, ties by lower id, ``(-inf, -1)``
   padding.  A row without tokens is no candidate.
 * Row filters and removed rows are the first stage's business: what it does not return is not re-ranked.
+* With a codec (``train_codec`` / ``set_codec``) the store can be held compressed, as ColBERTv2 / PLAID hold theirs: per
+  token the id of its nearest centroid, ``nbits`` in {2, 4} bits per column for the residual and one fp32 scale - 104 B
+  or 200 B instead of 768 B.  ``sskd_latec_rerank`` decodes inside the MaxSim kernel; the rules are in
+  ``include/sskd_amd.h``, "Compressed token store".  Without a codec nothing changes.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ DIM = _native.SSKD_DIM
 LATE_TQ_MAX = 128
 LATE_R_MAX = 1024
 TOKEN_BYTES = DIM * 2
+LATE_C_MAX = 65536
 FORMAT_VERSION = 1
 
 
@@ -47,9 +52,129 @@ def check_lims(lims, n_rows: Optional[int] = None, n_tokens: Optional[int] = Non
     return a
 
 
-def store_bytes(n_tokens: int) -> int:
-    """HBM (and file) bytes of a store of ``n_tokens`` token rows: 768 B each."""
-    return int(n_tokens) * TOKEN_BYTES
+def store_bytes(n_tokens: int, nbits: int = 0) -> int:
+    """HBM (and file) bytes of a store of ``n_tokens`` token rows: 768 B each as bf16 (``nbits = 0``); compressed, a
+    4-byte centroid id, a 4-byte scale and ``48 * nbits`` code bytes - 104 B at 2 bits, 200 B at 4 (the codec itself:
+    ``codec_bytes``)."""
+    if nbits == 0:
+        return int(n_tokens) * TOKEN_BYTES
+    _check_nbits(nbits)
+    return int(n_tokens) * (8 + code_bytes(nbits))
+
+
+def _check_nbits(nbits) -> int:
+    if nbits not in (2, 4):
+        raise ValueError(f"nbits={nbits}: the compressed store takes 2 or 4 bits per column")
+    return int(nbits)
+
+
+def code_bytes(nbits: int) -> int:
+    """Code bytes of one compressed token: 96 or 192."""
+    return DIM * int(nbits) // 8
+
+
+def codec_bytes(n_centroids: int, nbits: int) -> int:
+    """Bytes of a codec: bf16 centroids, ``2^nbits - 1`` fp32 cutoffs, ``2^nbits`` fp32 weights."""
+    return int(n_centroids) * TOKEN_BYTES + 4 * ((1 << nbits) - 1) + 4 * (1 << nbits)
+
+
+def default_n_centroids(n_tokens: int, sample_tokens: Optional[int] = None) -> int:
+    """The largest power of two ``<= 16 sqrt(n_tokens)``, at most 65 536 and at most the sample size."""
+    c = 1
+    while 2 * c <= 16.0 * float(np.sqrt(max(int(n_tokens), 1))) and 2 * c <= LATE_C_MAX:
+        c *= 2
+    return int(max(1, min(c, int(n_tokens) if sample_tokens is None else int(sample_tokens))))
+
+
+def check_codec(centroids, cutoffs, weights):
+    """A caller's codec, validated on the host: ``(centroid bf16 bits uint16 [C, 384], cutoffs fp32 [L - 1], weights
+    fp32 [L], nbits)``.  ``centroids``: NumPy uint16 (bf16 bits), NumPy / torch floating point (rounded to bf16, nearest
+    even).  Raises ``ValueError`` for a wrong shape, ``C`` outside [1, 65 536], ``L`` not 4 or 16, cutoffs that do not
+    ascend, and anything not finite."""
+    if isinstance(centroids, torch.Tensor):
+        bits = centroids.detach().to(torch.float32).to(torch.bfloat16).contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
+    else:
+        a = np.asarray(centroids)
+        if a.dtype == np.uint16:
+            bits = np.ascontiguousarray(a)
+        else:
+            bits = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    if bits.ndim != 2 or bits.shape[1] != DIM:
+        raise ValueError(f"centroids: expected [C, {DIM}], got {tuple(bits.shape)}")
+    if not 1 <= bits.shape[0] <= LATE_C_MAX:
+        raise ValueError(f"centroids: C={bits.shape[0]} outside [1, {LATE_C_MAX}]")
+    if ((bits & 0x7F80) == 0x7F80).any():
+        raise ValueError("centroids must be finite")
+    cut = np.ascontiguousarray(np.asarray(cutoffs, dtype=np.float32))
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32))
+    if w.ndim != 1 or w.size not in (4, 16):
+        raise ValueError(f"weights: expected [4] (2 bits) or [16] (4 bits), got {tuple(w.shape)}")
+    if cut.ndim != 1 or cut.size != w.size - 1:
+        raise ValueError(f"cutoffs: expected [{w.size - 1}] for {w.size} weights, got {tuple(cut.shape)}")
+    if not np.isfinite(w).all():
+        raise ValueError("weights must be finite")
+    if not np.isfinite(cut).all() or (np.diff(cut) < 0).any():
+        raise ValueError("cutoffs must be finite and ascend")
+    return bits, cut, w, 2 if w.size == 4 else 4
+
+
+COMPRESSED_FILES = ("late_cid.npy", "late_scale.npy", "late_codes.u8", "late_codec_centroids.bf16", "late_codec_cutoffs.npy",
+                    "late_codec_weights.npy")
+
+
+def save_compressed_store(out_dir: Union[str, Path], cid, scale, codes, centroid_bits, cutoffs, weights, lims, meta: dict) -> None:
+    """Writes ``late.json`` (with ``"nbits"`` and ``"n_centroids"``), ``late_token_lims.npy``, ``late_cid.npy``,
+    ``late_scale.npy``, ``late_codes.u8`` (raw bytes) and ``late_codec_{centroids.bf16, cutoffs.npy, weights.npy}``."""
+    cen, cut, w, nbits = check_codec(centroid_bits, cutoffs, weights)
+    cid = np.ascontiguousarray(cid, dtype=np.int32).reshape(-1)
+    scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(-1, code_bytes(nbits))
+    lims = check_lims(lims, n_tokens=cid.size)
+    if scale.size != cid.size or codes.shape[0] != cid.size:
+        raise ValueError("cid, scale and codes must cover the same tokens")
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "late_token_lims.npy", lims)
+    np.save(out / "late_cid.npy", cid)
+    np.save(out / "late_scale.npy", scale)
+    codes.tofile(out / "late_codes.u8")
+    cen.tofile(out / "late_codec_centroids.bf16")
+    np.save(out / "late_codec_cutoffs.npy", cut)
+    np.save(out / "late_codec_weights.npy", w)
+    with open(out / "late.json", "w") as f:
+        json.dump({**meta, "ntotal": int(lims.size - 1), "n_tokens": int(cid.size), "dim": DIM, "dtype": "bfloat16",
+                   "nbits": nbits, "n_centroids": int(cen.shape[0]), "format_version": FORMAT_VERSION}, f)
+
+
+def load_compressed_store(index_dir: Union[str, Path]):
+    """``(cid, scale, codes, centroid bits, cutoffs, weights, lims, meta)`` as ``save_compressed_store`` wrote them, checked."""
+    d = Path(index_dir)
+    meta = read_versioned_json(d / "late.json", FORMAT_VERSION)
+    nbits = _check_nbits(int(meta.get("nbits", 0)))
+    if int(meta.get("dim", -1)) != DIM:
+        raise ValueError(f"{d / 'late.json'}: expected {DIM}-d tokens")
+    n, C = int(meta["n_tokens"]), int(meta["n_centroids"])
+    lims = check_lims(np.load(d / "late_token_lims.npy"), n_rows=int(meta["ntotal"]), n_tokens=n)
+    cid = np.load(d / "late_cid.npy", allow_pickle=False)
+    scale = np.load(d / "late_scale.npy", allow_pickle=False)
+    codes = np.fromfile(d / "late_codes.u8", dtype=np.uint8)
+    cen = np.fromfile(d / "late_codec_centroids.bf16", dtype=np.uint16)
+    if cid.shape != (n,) or cid.dtype != np.int32 or scale.shape != (n,) or scale.dtype != np.float32:
+        raise ValueError(f"{d}: late_cid.npy / late_scale.npy do not hold {n} int32 / fp32 entries")
+    if codes.size != n * code_bytes(nbits):
+        raise ValueError(f"{d / 'late_codes.u8'}: {codes.size} bytes, late.json says {n * code_bytes(nbits)}")
+    if cen.size != C * DIM:
+        raise ValueError(f"{d / 'late_codec_centroids.bf16'}: {cen.size * 2} bytes, late.json says {C * TOKEN_BYTES}")
+    cen, cut, w, nb = check_codec(cen.reshape(-1, DIM), np.load(d / "late_codec_cutoffs.npy", allow_pickle=False),
+                                  np.load(d / "late_codec_weights.npy", allow_pickle=False))
+    if nb != nbits:
+        raise ValueError(f"{d}: the codec's tables are for {nb} bits, late.json says {nbits}")
+    return cid, scale, codes.reshape(-1, code_bytes(nbits)), cen, cut, w, lims, meta
+
+
+def stored_nbits(index_dir: Union[str, Path]) -> int:
+    """``nbits`` of the store in ``index_dir``: 0 for the bf16 store (and for a directory written before compression)."""
+    return int(read_versioned_json(Path(index_dir) / "late.json", FORMAT_VERSION).get("nbits", 0))
 
 
 def save_store(out_dir: Union[str, Path], tokens_bf16_bits: np.ndarray, lims: np.ndarray, meta: dict) -> None:
@@ -126,6 +251,15 @@ class LateInteractionIndex:
         self.lims = np.zeros(1, dtype=np.int64)           # host int64 [rows + 1]
         self._lims_dev: Optional[torch.Tensor] = None
         self._workspace: Optional[torch.Tensor] = None
+        # the codec (None: there is none) and the compressed store (None: the store, if any, is the bf16 one)
+        self.nbits = 0
+        self.centroids: Optional[torch.Tensor] = None    # device bf16 [C, 384]
+        self.cutoffs: Optional[torch.Tensor] = None      # device fp32 [2^nbits - 1]
+        self.weights: Optional[torch.Tensor] = None      # device fp32 [2^nbits]
+        self.cid: Optional[torch.Tensor] = None          # device int32 [n_tokens]
+        self.scale: Optional[torch.Tensor] = None        # device fp32 [n_tokens]
+        self.codes: Optional[torch.Tensor] = None        # device uint8 [n_tokens, 48 nbits]
+        self._quantizer: Optional[FAISSIndexBuilder] = None   # the centroids as fp32 rows, for the exact top-1 assignment
 
     # ------------------------------------------------------------------ properties
     @property
@@ -139,10 +273,22 @@ class LateInteractionIndex:
 
     @property
     def nbytes(self) -> int:
+        """Bytes of the store held: the bf16 rows, or the compressed arrays plus the codec."""
+        if self.compressed:
+            return store_bytes(self.n_tokens, self.nbits) + codec_bytes(self.n_centroids, self.nbits)
         return store_bytes(self.n_tokens)
 
+    @property
+    def compressed(self) -> bool:
+        """True when the compressed store is the one held (``compress()``, a compressing build, or such a directory)."""
+        return self.cid is not None
+
+    @property
+    def n_centroids(self) -> int:
+        return 0 if self.centroids is None else int(self.centroids.shape[0])
+
     def _require_store(self) -> None:
-        if self.tokens is None or self.ntotal != self.flat.ntotal:
+        if (self.tokens is None and self.cid is None) or self.ntotal != self.flat.ntotal:
             raise RuntimeError(f"the token store covers {self.ntotal} rows, the index holds {self.flat.ntotal}: call "
                                "set_tokens / add_tokens / build_from_texts (or load)")
 
@@ -156,6 +302,14 @@ class LateInteractionIndex:
     def _install(self, tokens: torch.Tensor, lims: np.ndarray) -> None:
         with torch.cuda.device(self.device):
             self.tokens = tokens
+            self.cid = self.scale = self.codes = None
+            self.lims = lims
+            self._lims_dev = torch.from_numpy(lims).to(self.device)
+
+    def _install_compressed(self, cid: torch.Tensor, scale: torch.Tensor, codes: torch.Tensor, lims: np.ndarray) -> None:
+        with torch.cuda.device(self.device):
+            self.tokens = None
+            self.cid, self.scale, self.codes = cid.contiguous(), scale.contiguous(), codes.contiguous()
             self.lims = lims
             self._lims_dev = torch.from_numpy(lims).to(self.device)
 
@@ -167,23 +321,162 @@ class LateInteractionIndex:
         self._install(t, check_lims(lims, n_rows=self.flat.ntotal, n_tokens=t.shape[0]))
 
     def add_tokens(self, tokens, lims) -> None:
-        """Appends the token vectors of the rows added with ``flat.add`` since: ``lims`` ``[new rows + 1]`` from 0."""
+        """Appends the token vectors of the rows added with ``flat.add`` since: ``lims`` ``[new rows + 1]`` from 0.  With
+        a codec installed and no bf16 store held (a compressed store, or none yet) they are compressed on arrival."""
         t = _tokens_to_device(tokens, self.device)
         new = check_lims(lims, n_tokens=t.shape[0])
         if self.ntotal + new.size - 1 > self.flat.ntotal:
             raise ValueError(f"{self.ntotal} + {new.size - 1} rows of tokens for an index of {self.flat.ntotal} rows")
+        lims = np.concatenate([self.lims, self.lims[-1] + new[1:]])
+        if self.centroids is not None and self.tokens is None:
+            # a codec and no bf16 store: the new tokens are compressed on arrival
+            with torch.cuda.device(self.device):
+                cid, scale, codes = self._compress_tokens(t)
+                if self.cid is not None:
+                    cid, scale, codes = (torch.cat([a, b]) for a, b in ((self.cid, cid), (self.scale, scale), (self.codes, codes)))
+            self._install_compressed(cid, scale, codes, lims)
+            return
         with torch.cuda.device(self.device):
             both = t if self.tokens is None else torch.cat([self.tokens, t])
-        self._install(both, np.concatenate([self.lims, self.lims[-1] + new[1:]]))
+        self._install(both, lims)
 
-    def build_from_texts(self, student, texts: Sequence[str], batch_size: int = 64) -> None:
+    def build_from_texts(self, student, texts: Sequence[str], batch_size: int = 64, compress: Optional[int] = None,
+                         train_texts: Optional[int] = None, encode_texts: int = 4096, **codec_args) -> None:
         """Encodes the documents of rows ``0 .. flat.ntotal - 1`` (``student``: a ``StudentModel``; the E5 passage prefix
-        is applied as ``encode_documents`` applies it) and installs their tokens."""
+        is applied as ``encode_documents`` applies it) and installs their tokens.
+
+        ``compress`` = 2 or 4 builds the compressed store without the whole bf16 store ever existing: unless a codec of
+        that width is installed, one is trained (``train_codec``'s rule, ``codec_args`` pass through) on the tokens of
+        ``train_texts`` texts spread evenly over ``texts`` (default: ``max(1024, len(texts) // 16)``); then the texts are
+        encoded and compressed ``encode_texts`` at a time."""
         if len(texts) != self.flat.ntotal:
             raise ValueError(f"{len(texts)} texts for an index of {self.flat.ntotal} rows")
-        tokens, lims = student.encode_tokens(list(texts), is_query=False, max_tokens=self.max_doc_tokens,
-                                             batch_size=batch_size)
-        self._install(tokens, lims)
+        texts = list(texts)
+        encode = lambda part: student.encode_tokens(part, is_query=False, max_tokens=self.max_doc_tokens,  # noqa: E731
+                                                    batch_size=batch_size)
+        if compress is None:
+            tokens, lims = encode(texts)
+            self._install(tokens, lims)
+            return
+        nbits = _check_nbits(compress)
+        if self.centroids is None or self.nbits != nbits:
+            m = min(len(texts), max(1024, len(texts) // 16) if train_texts is None else int(train_texts))
+            if m < 1:
+                raise ValueError("build_from_texts(compress=...): no texts to train the codec on")
+            sample, _ = encode([texts[(i * len(texts)) // m] for i in range(m)])
+            self._set_codec_device(*train_codec_tokens(sample, nbits=nbits, **codec_args))
+            del sample
+        parts, lims = [], [np.zeros(1, np.int64)]
+        for lo in range(0, len(texts), max(1, int(encode_texts))):
+            tokens, part_lims = encode(texts[lo: lo + max(1, int(encode_texts))])
+            with torch.cuda.device(self.device):
+                parts.append(self._compress_tokens(tokens))
+            lims.append(lims[-1][-1] + part_lims[1:])
+            del tokens
+        with torch.cuda.device(self.device):
+            cid, scale, codes = (torch.cat([p[i] for p in parts]) for i in range(3))
+        self._install_compressed(cid, scale, codes, np.concatenate(lims).astype(np.int64))
+
+    # ------------------------------------------------------------------ the codec and the compressed store
+    def _set_codec_device(self, centroids: torch.Tensor, cutoffs: np.ndarray, weights: np.ndarray) -> None:
+        """Installs a codec already validated: ``centroids`` device bf16 ``[C, 384]``."""
+        if self.cid is not None:
+            raise RuntimeError("the compressed store was written with the codec installed: it cannot be replaced")
+        with torch.cuda.device(self.device):
+            self.centroids = centroids.contiguous()
+            self.cutoffs = torch.from_numpy(np.ascontiguousarray(cutoffs, dtype=np.float32)).to(self.device)
+            self.weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32)).to(self.device)
+            self.nbits = 2 if self.weights.numel() == 4 else 4
+            self._quantizer = FAISSIndexBuilder(embedding_dim=DIM, index_type="Flat", metric="ip", device=str(self.device))
+            self._quantizer.build_from_embeddings(self.centroids.to(torch.float32))     # metric "ip": stored as given
+
+    def set_codec(self, centroids, cutoffs, weights) -> None:
+        """A caller's codec (``check_codec`` validates it on the host): ``centroids`` ``[C, 384]``, ``cutoffs``
+        ``[L - 1]`` ascending, ``weights`` ``[L]``, ``L`` = 4 (2 bits) or 16 (4 bits)."""
+        bits, cut, w, _ = check_codec(centroids, cutoffs, weights)
+        self._set_codec_device(_tokens_to_device(bits, self.device), cut, w)
+
+    def train_codec(self, nbits: int = 2, n_centroids: Optional[int] = None, sample_tokens: Optional[int] = None,
+                    iterations: int = 10, seed: int = 1234) -> None:
+        """Trains a codec on the bf16 store held and installs it (``train_codec_tokens`` has the rule); the same
+        inputs give the same codec bits."""
+        if self.tokens is None or self.n_tokens < 1:
+            raise RuntimeError("train_codec(): needs the bf16 token store (set_tokens / add_tokens / build_from_texts)")
+        self._set_codec_device(*train_codec_tokens(self.tokens, nbits=nbits, n_centroids=n_centroids,
+                                                   sample_tokens=sample_tokens, iterations=iterations, seed=seed))
+
+    def codec_numpy(self):
+        """Host copy of the codec: ``(centroid bf16 bits uint16 [C, 384], cutoffs fp32, weights fp32)``."""
+        if self.centroids is None:
+            raise RuntimeError("no codec is installed: call train_codec / set_codec (or load a compressed store)")
+        return (self.centroids.view(torch.int16).cpu().numpy().view(np.uint16), self.cutoffs.cpu().numpy(),
+                self.weights.cpu().numpy())
+
+    def _compress_tokens(self, tokens: torch.Tensor, batch: int = 1 << 16):
+        """``(cid, scale, codes)`` of device bf16 ``tokens`` under the codec installed: the exact top-1 search over the
+        centroids in batches (ties to the lower id), then ``sskd_latec_compress``."""
+        lib = _native.load()
+        if self.centroids is None:
+            raise RuntimeError("no codec is installed: call train_codec / set_codec")
+        n = int(tokens.shape[0])
+        cid = torch.empty(n, dtype=torch.int32, device=self.device)
+        scale = torch.empty(n, dtype=torch.float32, device=self.device)
+        codes = torch.empty((n, code_bytes(self.nbits)), dtype=torch.uint8, device=self.device)
+        for lo in range(0, n, batch):
+            part = tokens[lo: lo + batch]
+            _, ids = self._quantizer.search_device(part.to(torch.float32), 1, normalize_queries=False)
+            assign = ids[:, 0].contiguous()
+            _native.check(lib.sskd_latec_compress(
+                part.data_ptr(), assign.data_ptr(), part.shape[0], self.centroids.data_ptr(), self.n_centroids,
+                self.cutoffs.data_ptr(), self.weights.data_ptr(), self.nbits, cid.data_ptr(), scale.data_ptr(),
+                codes.data_ptr(), lo, n, _native.current_stream_ptr(self.device)))
+        return cid, scale, codes
+
+    def compress(self) -> None:
+        """Compresses the bf16 store under the codec installed and frees it."""
+        if self.tokens is None:
+            raise RuntimeError("compress(): there is no bf16 token store" + (" (it is compressed already)" if self.compressed else ""))
+        with torch.cuda.device(self.device):
+            cid, scale, codes = self._compress_tokens(self.tokens)
+        self._install_compressed(cid, scale, codes, self.lims)
+
+    def set_compressed(self, cid, scale, codes, lims) -> None:
+        """A compressed store computed elsewhere under the codec installed, for rows ``0 .. flat.ntotal - 1``: ``cid``
+        int32 ``[T]``, ``scale`` fp32 ``[T]``, ``codes`` uint8 ``[T, 48 nbits]`` (NumPy), ``lims`` ``[ntotal + 1]``.  Stored
+        as given: the kernel clamps a centroid id outside ``[0, C)``."""
+        if self.centroids is None:
+            raise RuntimeError("no codec is installed: call train_codec / set_codec")
+        cid = np.ascontiguousarray(cid, dtype=np.int32).reshape(-1)
+        scale = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        if scale.shape != cid.shape or codes.shape != (cid.size, code_bytes(self.nbits)):
+            raise ValueError(f"expected cid [T], scale [T] and codes [T, {code_bytes(self.nbits)}]")
+        lims = check_lims(lims, n_rows=self.flat.ntotal, n_tokens=cid.size)
+        with torch.cuda.device(self.device):
+            self._install_compressed(*(torch.from_numpy(a).to(self.device) for a in (cid, scale, codes)), lims)
+
+    def compressed_numpy(self):
+        """Host copies ``(cid int32 [n], scale fp32 [n], codes uint8 [n, 48 nbits])`` of the compressed store."""
+        if not self.compressed:
+            raise RuntimeError("the store is not compressed")
+        return self.cid.cpu().numpy(), self.scale.cpu().numpy(), self.codes.cpu().numpy()
+
+    def decoded_numpy(self):
+        """For checking: ``(dec bf16 bits uint16 [n_tokens, 384], scale fp32 [n_tokens])``, the values the compressed
+        re-rank multiplies (``dec = bf16(centroid + weights[code])``, a centroid id clamped into ``[0, C)``)."""
+        if not self.compressed:
+            raise RuntimeError("the store is not compressed")
+        nbits, per = self.nbits, 8 // self.nbits
+        with torch.cuda.device(self.device):
+            packed = self.codes.to(torch.int32)
+            by_pos = torch.empty((packed.shape[0], DIM), dtype=torch.int64, device=self.device)
+            for i in range(per):
+                by_pos[:, i::per] = (packed >> (nbits * i)) & ((1 << nbits) - 1)
+            d = torch.arange(DIM, device=self.device)
+            code = by_pos[:, 192 * ((d // 8) % 2) + 8 * (d // 16) + d % 8]
+            cen = self.centroids[self.cid.to(torch.int64).clamp(0, self.n_centroids - 1)].to(torch.float32)
+            dec = (cen + self.weights[code]).to(torch.bfloat16)
+            return dec.view(torch.int16).cpu().numpy().view(np.uint16), self.scale.cpu().numpy()
 
     # ------------------------------------------------------------------ re-rank
     def prepare_queries(self, q_tokens, q_lims) -> LateQueries:
@@ -214,6 +507,18 @@ class LateInteractionIndex:
         I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         raw = torch.empty((nq, R), dtype=torch.float32, device=self.device) if return_raw else None
         ws = None
+        if self.compressed:
+            if raw is None:
+                need = int(lib.sskd_latec_rerank_workspace_bytes(nq, R))
+                self._workspace = ws = _native.grown(self._workspace, need, self.device)
+            _native.check(lib.sskd_latec_rerank(
+                queries.tokens.data_ptr(), queries.lims_host.ctypes.data, queries.lims_dev.data_ptr(), nq,
+                self.cid.data_ptr(), self.scale.data_ptr(), self.codes.data_ptr(), self.nbits, self.centroids.data_ptr(),
+                self.n_centroids, self.weights.data_ptr(), self._lims_dev.data_ptr(), self.ntotal, self.n_tokens,
+                cand.data_ptr(), R, k, self.flat.id_offset, D.data_ptr(), I.data_ptr(),
+                None if raw is None else raw.data_ptr(), None if ws is None else ws.data_ptr(),
+                0 if ws is None else ws.numel(), _native.current_stream_ptr(self.device)))
+            return (D, I, raw) if return_raw else (D, I)
         if raw is None:
             self._workspace = ws = _native.grown(self._workspace, int(lib.sskd_late_rerank_workspace_bytes(nq, R)), self.device)
         _native.check(lib.sskd_late_rerank(
@@ -267,20 +572,40 @@ class LateInteractionIndex:
         lims = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         take = np.repeat(self.lims[old] - lims[:-1], counts) + np.arange(int(lims[-1]), dtype=np.int64)
         with torch.cuda.device(self.device):
-            tokens = self.tokens[torch.from_numpy(take).to(self.device)].contiguous()
+            pick = torch.from_numpy(take).to(self.device)
+            if self.compressed:
+                self._install_compressed(self.cid[pick], self.scale[pick], self.codes[pick], lims)
+                return
+            tokens = self.tokens[pick].contiguous()
         self._install(tokens, lims)
 
     def save(self, output_dir: Union[str, Path]) -> None:
         """``late.json``, ``late_token_lims.npy`` and ``late_tokens.bf16`` beside the index's own files (which the
         index's ``save`` writes)."""
+        meta = {"max_doc_tokens": self.max_doc_tokens, "max_query_tokens": self.max_query_tokens}
+        if self.compressed:
+            # the compressed store: late_cid.npy, late_scale.npy, late_codes.u8 and the codec's three files instead
+            save_compressed_store(output_dir, *self.compressed_numpy(), *self.codec_numpy(), self.lims, meta)
+            return
         if self.tokens is None:
             raise RuntimeError("save(): the token store is empty")
-        save_store(output_dir, self.tokens_numpy(), self.lims,
-                   {"max_doc_tokens": self.max_doc_tokens, "max_query_tokens": self.max_query_tokens})
+        save_store(output_dir, self.tokens_numpy(), self.lims, meta)
 
     def load(self, index_dir: Union[str, Path]) -> None:
         """The store of ``index_dir`` over the rows ``self.flat`` already holds; a store over another number of rows
-        raises ``ValueError``."""
+        raises ``ValueError``.  Whichever store the directory holds is loaded: bf16 rows, or the compressed arrays
+        with their codec (``"nbits"`` in ``late.json``)."""
+        if stored_nbits(index_dir):
+            cid, scale, codes, cen, cut, w, lims, meta = load_compressed_store(index_dir)
+            if lims.size - 1 != self.flat.ntotal:
+                raise ValueError(f"{index_dir}: a token store over {lims.size - 1} rows, the index holds {self.flat.ntotal}")
+            self.max_doc_tokens = int(meta.get("max_doc_tokens", self.max_doc_tokens))
+            self.max_query_tokens = int(meta.get("max_query_tokens", self.max_query_tokens))
+            self.cid = None
+            self._set_codec_device(_tokens_to_device(cen, self.device), cut, w)
+            with torch.cuda.device(self.device):
+                self._install_compressed(*(torch.from_numpy(a).to(self.device) for a in (cid, scale, codes)), lims)
+            return
         bits, lims, meta = load_store(index_dir)
         if lims.size - 1 != self.flat.ntotal:
             raise ValueError(f"{index_dir}: a token store over {lims.size - 1} rows, the index holds {self.flat.ntotal}")
@@ -290,7 +615,69 @@ class LateInteractionIndex:
 
     def cleanup(self) -> None:
         self.tokens = self._lims_dev = self._workspace = None
+        self.cid = self.scale = self.codes = self.centroids = self.cutoffs = self.weights = None
+        if self._quantizer is not None:
+            self._quantizer.cleanup()
+        self._quantizer = None
+        self.nbits = 0
         self.lims = np.zeros(1, dtype=np.int64)
+
+
+def _sorted_quantiles(sorted_values: torch.Tensor, fractions) -> np.ndarray:
+    """Quantiles of an ascending device fp32 vector by linear interpolation between neighbours, in fp64, as fp32."""
+    n = int(sorted_values.numel())
+    pos = np.asarray(fractions, dtype=np.float64) * (n - 1)
+    lo = np.floor(pos).astype(np.int64)
+    hi = np.minimum(lo + 1, n - 1)
+    both = sorted_values[torch.from_numpy(np.concatenate([lo, hi])).to(sorted_values.device)].cpu().numpy().astype(np.float64)
+    a, b = both[: lo.size], both[lo.size:]
+    return (a + (b - a) * (pos - lo)).astype(np.float32)
+
+
+def train_codec_tokens(tokens: torch.Tensor, nbits: int = 2, n_centroids: Optional[int] = None,
+                       sample_tokens: Optional[int] = None, iterations: int = 10, seed: int = 1234,
+                       residual_rows: int = 1 << 15):
+    """A codec from device bf16 ``tokens`` ``[n, 384]``: ``(centroids device bf16 [C, 384], cutoffs fp32 [L - 1],
+    weights fp32 [L])``, deterministic.
+
+    The sample is ``sample_tokens`` rows spread evenly over ``tokens`` (default ``min(n, 256 C)``).  It is widened into a
+    temporary flat index and ``IVFIndex.train`` runs its spherical k-means on it (its seeding, its update, ``iterations``
+    of it); the centroids are rounded to bf16 and the sample is assigned again, against the rounded centroids.  ``cutoffs``
+    and ``weights`` are the ``i / L`` and ``(i + 1/2) / L`` quantiles (ColBERTv2's rule) of the residuals
+    ``fp32(t) - fp32(c)`` of at most ``residual_rows`` sample rows, again spread evenly.  ``C`` defaults to
+    ``default_n_centroids``: the largest power of two ``<= 16 sqrt(n)``, at most 65 536 and at most the sample size."""
+    from .ivf import IVFIndex
+
+    nbits = _check_nbits(nbits)
+    n = int(tokens.shape[0])
+    if n < 1:
+        raise ValueError("train_codec: no tokens")
+    if sample_tokens is not None and not 1 <= int(sample_tokens) <= n:
+        raise ValueError(f"sample_tokens={sample_tokens} outside [1, {n}]")
+    C = default_n_centroids(n, sample_tokens) if n_centroids is None else int(n_centroids)
+    m = min(n, 256 * C) if sample_tokens is None else int(sample_tokens)
+    if not 1 <= C <= min(LATE_C_MAX, m):
+        raise ValueError(f"n_centroids={C} outside [1, min({LATE_C_MAX}, sample of {m})]")
+    device = tokens.device
+    L = 1 << nbits
+    with torch.cuda.device(device):
+        pick = torch.from_numpy((np.arange(m, dtype=np.int64) * n) // m).to(device)
+        sample = tokens[pick].to(torch.float32)
+        flat = FAISSIndexBuilder(embedding_dim=DIM, index_type="Flat", metric="ip", device=str(device))
+        flat.build_from_embeddings(sample)
+        ivf = IVFIndex(flat=flat)
+        ivf.train(nlist=C, iterations=iterations, seed=seed, max_train_rows=m)
+        centroids = torch.from_numpy(ivf.centroids_numpy()).to(device).to(torch.bfloat16).contiguous()
+        keep = torch.from_numpy((np.arange(min(m, residual_rows), dtype=np.int64) * m) // min(m, residual_rows)).to(device)
+        rows = sample[keep]
+        ivf._set_centroids(centroids.to(torch.float32))
+        assign = ivf._assign_device(rows)
+        residual = (rows - centroids.to(torch.float32)[assign]).reshape(-1)
+        ordered = torch.sort(residual).values
+        cutoffs = _sorted_quantiles(ordered, np.arange(1, L) / L)
+        weights = _sorted_quantiles(ordered, (np.arange(L) + 0.5) / L)
+        ivf.cleanup()
+    return centroids, cutoffs, weights
 
 
 def pack_tokens(hidden: torch.Tensor, lengths, offsets, out: torch.Tensor) -> None:

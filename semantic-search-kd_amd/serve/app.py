@@ -200,7 +200,9 @@ def _load_late(builder, index_dir: Path, settings: Optional["ServeSettings"]):
         return None
     try:
         late = LateInteractionIndex(builder)
-        late.load(index_dir)
+        late.load(index_dir)     # whichever store the directory holds: bf16 rows or the compressed arrays and their codec
+        logger.info("Late-interaction token store: %d tokens, %d bytes%s", late.n_tokens, late.nbytes,
+                    f" ({late.nbits}-bit residuals over {late.n_centroids} centroids)" if late.compressed else "")
         return late
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the late-interaction token store (serving without it): %s", exc)
