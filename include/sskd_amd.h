@@ -143,8 +143,8 @@ int sskd_index_search_profiled(const float* d_tiled, int64_t n_rows,
  * share of the sample phase lies inside its own slice (slice 0) empties its pool between the two phases, because
  * the same rows are offered again there (round 3 did not, and a row counted twice could lift the bound above
  * the true k-th best score: fixed in round 4, tests/test_screened_gpu.py "count_once" / "topic_sorted").  A query is answered by the exact scan inside the same call only when its band holds
- * more than 256 rows (hundreds of near-duplicates of its neighbours) or one run overflowed (> 64 band rows
- * in one lane's share of a slice) - the in-call fallback is sized for every query, so no output row is
+ * more than 256 rows (hundreds of near-duplicates of its neighbours) or one run overflowed (> 32 band rows
+ * in one 16-lane group's share of a slice: 4 rows of every 32-row tile a wave takes) - the in-call fallback is sized for every query, so no output row is
  * ever unproven and callers have nothing to check.  d_status (device int[2]): [0] = always 0 (kept for ABI
  * stability), [1] = the number of queries that took the exact fallback (a cost diagnostic).  ev_scan_begin /
  * ev_scan_end bracket the screening launch (a bound-only sample phase over the shard's first rows, then the slices).  d_bf16: the screening sidecar,
@@ -184,6 +184,17 @@ int sskd_index_search_screened(const float* d_tiled, const void* d_bf16, int64_t
 size_t sskd_index_screen_band_scratch_bytes(int nq);
 int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_eps2_out,
                            void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* Test hooks of the screening kernel's matrix core and pruning bounds (tests/test_screen_mfma16_gpu.py).
+ * sskd_index_screen_scores: the raw screen scores - the fp32 accumulators of v_mfma_f32_16x16x32_bf16 over the centred
+ * bf16 rows of the sidecar and the bf16-rounded queries - of nq <= 64 queries against every row, through the staging,
+ * tile ring and MFMA loop of the screening kernel itself: d_out is fp32 [32 ceil(n_rows / 32)][64], row-major (columns
+ * past nq and rows past n_rows are zero).
+ * sskd_screen_threshold_roundtrip: the kernel keeps its pruning bounds as fp16, rounded toward -inf when packed (a lower
+ * bound only lets more rows through to the exact fp32 test); d_out[i] = that fp16 of d_in[i], widened to fp32: never
+ * above d_in[i], -inf below the fp16 range and 65504 above it. */
+int sskd_index_screen_scores(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_out, void* stream);
+int sskd_screen_threshold_roundtrip(const float* d_in, int n, float* d_out, void* stream);
 
 /* Test hooks of the screening kernel's tile claiming (tests/test_screen_tile_claim_gpu.py).
  * sskd_index_search_screened_plan_claims: *claims = 1 when the plan has the waves of the slice phase CLAIM their tiles

@@ -40,10 +40,11 @@ using sskd::require_shard_rows;
 namespace {
 
 typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
-constexpr int BSTEPS = DIM / 16;                 // 24 k-steps of the 32x32x16 bf16 MFMA
-constexpr int BTILE_VEC = BSTEPS * 64;           // 16-byte vectors per 32-row bf16 tile (24 KiB)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int BSTEPS = DIM / 32;                 // 12 k-steps of the 16x16x32 bf16 MFMA
+constexpr int BTILE_VEC = 2 * BSTEPS * 64;       // 16-byte vectors per 32-row bf16 tile (24 KiB): 2 row blocks of 16 per k-step
 #ifndef SSKD_SCREEN_BGROUP
-#define SSKD_SCREEN_BGROUP 6
+#define SSKD_SCREEN_BGROUP 3
 #endif
 #ifndef SSKD_SCREEN_WAVES
 #define SSKD_SCREEN_WAVES 12
@@ -51,16 +52,27 @@ constexpr int BTILE_VEC = BSTEPS * 64;           // 16-byte vectors per 32-row b
 #ifndef SSKD_SCREEN_RING
 #define SSKD_SCREEN_RING 2
 #endif
-// Tile prefetch ring of a wave: RING register buffers of BGROUP k-steps each, RING - 1 groups in flight.  128 queries
-// per workgroup (64 accumulator registers): 6 k-steps x 2 buffers; 160 queries (80 accumulators): 3 x 2 - what is left
-// of the 168 registers three waves per SIMD allow (tools/ab_search.py sweeps: gpurun_out/r03_sweep*.log, r03_q5*.log)
+// Tile prefetch ring of a wave: RING register buffers of BGROUP k-steps (of 32 columns: two 16-row operands each), RING - 1
+// groups in flight.  128 queries per workgroup (64 accumulator registers): 3 k-steps x 2 buffers, 48 registers; 160
+// queries (80 accumulators): 1 x 3, 24 registers with two k-steps (4 KiB) in flight - what is left of the 168 registers
+// three waves per SIMD allow (2 x 2, the same bytes in flight in 32 registers, spills 27; 1 x 2 leaves 8 unused)
 constexpr int BGROUP = SSKD_SCREEN_BGROUP;
 constexpr int SCREEN_RING = SSKD_SCREEN_RING;
-constexpr int BGROUP_Q5 = 3, SCREEN_RING_Q5 = 2;
+#ifndef SSKD_SCREEN_BGROUP_Q5
+#define SSKD_SCREEN_BGROUP_Q5 1
+#endif
+#ifndef SSKD_SCREEN_RING_Q5
+#define SSKD_SCREEN_RING_Q5 3
+#endif
+constexpr int BGROUP_Q5 = SSKD_SCREEN_BGROUP_Q5, SCREEN_RING_Q5 = SSKD_SCREEN_RING_Q5;
 #ifndef SSKD_SCREEN_TAU_REFRESH_TILES
 #define SSKD_SCREEN_TAU_REFRESH_TILES 64
 #endif
 constexpr int SCREEN_TAU_REFRESH_TILES = SSKD_SCREEN_TAU_REFRESH_TILES;
+#ifndef SSKD_SCREEN_BOUND_REFRESH_TILES
+#define SSKD_SCREEN_BOUND_REFRESH_TILES 8
+#endif
+constexpr int SCREEN_BOUND_REFRESH_TILES = SSKD_SCREEN_BOUND_REFRESH_TILES;
 constexpr int SCREEN_WAVES = SSKD_SCREEN_WAVES;  // waves per screening workgroup
 template <int BG, int RG>
 struct ScreenRingOk {
@@ -69,7 +81,7 @@ struct ScreenRingOk {
 };
 static_assert(ScreenRingOk<BGROUP, SCREEN_RING>::value && ScreenRingOk<BGROUP_Q5, SCREEN_RING_Q5>::value, "");
 // fp32 accumulation slack of the two dot products, relative to |q| max|c|: the exact score is a 384-step fma
-// chain (<= 384 x 2^-24), the screen score 24 MFMAs of 16 exact products each accumulated in fp32 (<= 2 x 384
+// chain (<= 384 x 2^-24), the screen score 12 MFMAs of 32 exact products each accumulated in fp32 (<= 2 x 384
 // x 2^-24 even if every internal add truncated); 3 x 384 x 2^-24 (1 + 2^-8)^2 = 6.9e-5, rounded up generously
 constexpr float SCREEN_ACC_SLACK = 1.0e-4f;
 constexpr int SCREEN_MAX_CAND = 256;             // candidates re-scored per query (one per thread)
@@ -81,8 +93,11 @@ constexpr int SCREEN_FALLBACK_TIER1 = 1024;
 constexpr int SCREEN_LIGHT_MAX_TILES_PER_WAVE = 330;   // slices up to this length (500 k rows at 10 000 queries) keep their pools with one offer per lane and tile
 constexpr int SCREEN_CUS = 256;                  // MI355X: the launch geometry is planned in whole rounds of the chip
 
-// fp32 index -> bf16 tiles of the CENTRED rows in A-operand order of v_mfma_f32_32x32x16_bf16:
-// tile t, step s, lane l holds row 32t + (l & 31), columns 16s + 8(l >> 5) + 0..7   (make_bf16_tiles_kernel below)
+// fp32 index -> bf16 tiles of the CENTRED rows (make_bf16_tiles_kernel below).  Bytes of a tile, the layout the header
+// documents: 16-byte vector u * 32 + r holds row 32t + r, columns 8u + 0..7 (u = 0..47).  The A operand of
+// v_mfma_f32_16x16x32_bf16 for k-step S (32 columns) and row block mb (16 rows) is lane l <- row 16 mb + (l & 15),
+// columns 32 S + 8 (l >> 4) + 0..7, i.e. vector (4 S + (l >> 4)) * 32 + 16 mb + (l & 15): a wave-uniform offset
+// (S, mb) plus a per-lane offset - four 256-byte pieces per wave-instruction (load_bgroup)
 // column sums of the fp32 index -> colsum[384] (pre-zeroed): block b walks tiles b, b + grid, ...
 __global__ __launch_bounds__(256) void tile_colsum_kernel(const float4* __restrict__ tiled, int64_t n_tiles,
                                                           float* __restrict__ colsum) {
@@ -238,54 +253,60 @@ __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restri
   }
 }
 
-// k-steps [0, BG) at the wave-uniform address `base`: lane l reads the 16 bytes at lane_off = 16 l of every step.  Uniform
-// base + 32-bit lane offset is the scalar-base form of global_load: tile addresses cost scalar adds, no 64-bit vector
-// pointers held (and spilled) across the tile loop.
+// k-steps [0, BG) at the wave-uniform address `base` (the tile's vector 128 S of its first k-step S): both row blocks of
+// every step; lane l reads the 16 bytes at lane_off = 16 (32 (l >> 4) + (l & 15)).  Uniform base + 32-bit lane offset is
+// the scalar-base form of global_load: tile addresses cost scalar adds, no 64-bit vector pointers held (and spilled)
+// across the tile loop.
 template <int BG>
-__device__ __forceinline__ void load_bgroup(sbf16x8 (&buf)[BG], const sbf16x8* __restrict__ base, unsigned lane_off) {
+__device__ __forceinline__ void load_bgroup(sbf16x8 (&buf)[BG][2], const sbf16x8* __restrict__ base, unsigned lane_off) {
   asm volatile("" : "+v"(lane_off));   // widened next to its loads, not once per kernel into a 64-bit pair that spills
 #pragma unroll
   for (int s = 0; s < BG; ++s)
-    buf[s] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 64) + lane_off);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#ifdef SSKD_SCREEN_ABL_CONTIG   // timing ablation (wrong operands): every load one contiguous KiB, as a re-ordered sidecar would give
+      buf[s][mb] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 128 + mb * 64) + lane_off);
+#else
+      buf[s][mb] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 128 + mb * 16) + lane_off);
+#endif
 }
 
-// The query fragments of a workgroup sit in LDS as [QB][24 k-steps][64 lanes] x 16 bytes: 1 KiB per (sub-block, k-step),
-// up to 120 KiB in all, and a ds_read takes a 16-bit byte offset.  One base address per 64 fragments, set up once per
-// phase and hidden from the optimiser, makes every fragment address "base + immediate"; left alone, the compiler forms
-// the far addresses with a v_add_u32 and a register of their own per read.
+// The query fragments of a workgroup sit in LDS as [2 QB blocks of 16 queries][12 k-steps][64 lanes] x 16 bytes - lane l of
+// (block nb, step S) holds query 16 nb + (l & 15), columns 32 S + 8 (l >> 4) + 0..7, the B operand of
+// v_mfma_f32_16x16x32_bf16: 1 KiB per (block, k-step), up to 120 KiB in all, and a ds_read takes a 16-bit byte offset.
+// One base address per 64 fragments, set up once per phase and hidden from the optimiser, makes every fragment address
+// "base + immediate"; left alone, the compiler forms the far addresses with a v_add_u32 and a register of their own per read.
 typedef __attribute__((address_space(3))) const sbf16x8 screen_lds_frag;
 constexpr int SCREEN_FRAGS_PER_BASE = 64;
 template <int QB>
-constexpr int screen_frag_bases() { return (QB * BSTEPS + SCREEN_FRAGS_PER_BASE - 1) / SCREEN_FRAGS_PER_BASE; }
-// Fragment ring of a wave: the LDS read of MFMA i + SCREEN_FRAG_DEPTH - 1 is issued in front of MFMA i.  The register
-// budget of three waves per SIMD (168) decides the depth: 3 compiles with 8 spilled registers in the 160-query kernel
-// and a scratch reload inside its tile loop, 2 with the 2 it had before the ring (per instantiation: DESIGN.md 3.1b)
+constexpr int screen_frag_bases() { return (2 * QB * BSTEPS + SCREEN_FRAGS_PER_BASE - 1) / SCREEN_FRAGS_PER_BASE; }
+// Fragment ring of a wave: the LDS read of fragment i + SCREEN_FRAG_DEPTH - 1 is issued in front of the two MFMAs of
+// fragment i.  The register budget of three waves per SIMD (168) decides the depth (per instantiation: DESIGN.md 3.1b)
 #ifndef SSKD_SCREEN_FRAG_DEPTH
 #define SSKD_SCREEN_FRAG_DEPTH 2
 #endif
 constexpr int SCREEN_FRAG_DEPTH = SSKD_SCREEN_FRAG_DEPTH;
-static_assert(SCREEN_FRAG_DEPTH >= 2, "the fragment ring holds the MFMA's own operand and at least one read ahead");
+static_assert(SCREEN_FRAG_DEPTH >= 2, "the fragment ring holds the MFMAs' own operand and at least one read ahead");
 
-// fragment of the tile's I-th MFMA: MFMAs run k-step major, sub-block minor (I = kstep * QB + qq)
+// the tile's I-th fragment: fragments run k-step major, query block minor (I = kstep * 2 QB + nb)
 template <int QB, int NB>
 __device__ __forceinline__ sbf16x8 read_qfrag(screen_lds_frag* const (&qbase)[NB], int I) {
-  const int f = (I % QB) * BSTEPS + I / QB;
+  const int f = (I % (2 * QB)) * BSTEPS + I / (2 * QB);
   return qbase[f / SCREEN_FRAGS_PER_BASE][(f % SCREEN_FRAGS_PER_BASE) * 64];
 }
 
-// One group of k-steps: BG x QB MFMAs, each accumulator's k ascending.  The query fragments go through a register ring
-// D deep that runs D - 1 LDS reads ahead of the MFMA that consumes them, across the groups of a tile (the fragments do
-// not depend on the tile): every MFMA waits with a counted lgkmcnt(D - 2) for its own fragment while the next reads are
-// in flight, so ONE ready wave keeps the matrix pipe of its SIMD fed when its partners are parked on their tile ring or
-// in their epilogue.  A scheduling barrier on both sides of each MFMA pins that order - left to itself the machine
-// scheduler sinks every read to "read, lgkmcnt(0), MFMA", a full LDS round trip in front of each 32-cycle MFMA.  The
-// tile ring's global loads are issued by the caller ahead of the group and stay there.  (Rounds 2-3 measured a two-deep
-// pipeline pinned with sched_group_barrier on the list form of the kernel - two waves per SIMD, 255 registers - at
-// 9.6 ms against 8.5 ms: that order delayed the tile prefetch loads.  Numbers for this form: DESIGN.md section 3.1b.)
+// One group of k-steps: BG x 2 QB fragments, each feeding the MFMAs of the tile's two row blocks (query block outer, row
+// block inner: the LDS bytes per flop of the 32x32x16 form); each accumulator's k ascending.  The query fragments go
+// through a register ring D deep that runs D - 1 LDS reads ahead of the MFMAs that consume them, across the groups of a
+// tile (the fragments do not depend on the tile): the first MFMA of a fragment waits with a counted lgkmcnt(D - 2) for
+// it while the next reads are in flight, so ONE ready wave keeps the matrix pipe of its SIMD fed when its partners are
+// parked on their tile ring or in their epilogue.  A scheduling barrier on both sides of each MFMA pins that order -
+// left to itself the machine scheduler sinks every read to "read, lgkmcnt(0), MFMA", a full LDS round trip in front of
+// the MFMAs.  The tile ring's global loads are issued by the caller ahead of the group and stay there.
 template <int QB, int G, int BG, int D, int NB>
-__device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG], screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D],
-                                               f32x16 (&acc)[QB]) {
-  constexpr int N = BG * QB, I0 = G * N, TOTAL = BSTEPS * QB;
+__device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG][2], screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D],
+                                               f32x4 (&acc)[2][2 * QB]) {
+  constexpr int NQ = 2 * QB, N = BG * NQ, I0 = G * N, TOTAL = BSTEPS * NQ;
   asm volatile("" ::: "memory");  // keep the (tile-invariant) LDS query reads inside the tile (see compute_group)
 #ifndef SSKD_SCREEN_ABL_NOLDS
   if constexpr (G == 0) {
@@ -295,15 +316,17 @@ __device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG], screen_ld
 #endif
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    const int I = I0 + i, s = i / QB, qq = i % QB;
+    const int I = I0 + i, s = i / NQ, nb = i % NQ;
 #ifdef SSKD_SCREEN_ABL_NOLDS   // timing ablation (tools/ab_search.py, AB_NOCHECK): no LDS query-fragment reads
-    const sbf16x8 bi = a[(s + qq) % BG];
+    const sbf16x8 bi = a[(s + nb) % BG][nb & 1];
 #else
     if (I + D - 1 < TOTAL) b[(I + D - 1) % D] = read_qfrag<QB>(qbase, I + D - 1);
     const sbf16x8 bi = b[I % D];
 #endif
     __builtin_amdgcn_sched_barrier(0);
-    acc[qq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bi, acc[qq], 0, 0, 0);
+    acc[0][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][0], bi, acc[0][nb], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    acc[1][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[s][1], bi, acc[1][nb], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -311,19 +334,59 @@ __device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG], screen_ld
 // one tile's groups, compile-time unrolled over a ring of RG register buffers: group G is multiplied
 // from buffer G % RG while group G + RG - 1 (of this tile, or of the wave's next tile) loads
 template <int QB, int G, int BG, int RG, int D, int NB>
-__device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const sbf16x8* __restrict__ tile,
-                                                   screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D], f32x16 (&acc)[QB],
-                                                   bool more, int64_t next_tile, unsigned lane_off) {
+__device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG][2], const sbf16x8* __restrict__ tile,
+                                                   screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D],
+                                                   f32x4 (&acc)[2][2 * QB], bool more, int64_t next_tile, unsigned lane_off) {
   constexpr int NG = BSTEPS / BG;
   if constexpr (G < NG) {
     constexpr int PG = G + RG - 1;  // group to prefetch now
 #ifndef SSKD_SCREEN_ABL_NOGLOBAL  // timing ablation: no corpus tile loads (the ring keeps its first contents)
-    if constexpr (PG < NG) load_bgroup<BG>(buf[PG % RG], tile + PG * BG * 64, lane_off);
-    else if (more) load_bgroup<BG>(buf[PG % RG], tile + next_tile + (PG - NG) * BG * 64, lane_off);
+    if constexpr (PG < NG) load_bgroup<BG>(buf[PG % RG], tile + PG * BG * 128, lane_off);
+    else if (more) load_bgroup<BG>(buf[PG % RG], tile + next_tile + (PG - NG) * BG * 128, lane_off);
 #endif
     compute_bgroup<QB, G, BG, D, NB>(buf[G % RG], qbase, b, acc);
     screen_tile_groups<QB, G + 1, BG, RG, D, NB>(buf, tile, qbase, b, acc, more, next_tile, lane_off);
   }
+}
+
+// Pruning thresholds of a lane in the tile loop: two queries share a register as an fp16 pair, each rounded TOWARD -INF when
+// it is packed.  A smaller threshold only lets more rows through the first test (the row maximum of a query block
+// against the unpacked fp16), and the rows that pass it are tested again in fp32 against the exact threshold before
+// anything is appended (screen_tiles): the appended set still contains the whole band, and no entry is appended that
+// the fp32 test would not have taken.  Values below the fp16 range pack to -inf ("no bound": everything passes the first
+// test), values above it to 65504; NaN never gets here (the callers go through fmaxf).
+// cvt_pkrtz rounds toward zero: down for x >= 0, and for x < 0 at most one fp16 step above x - one step away from zero
+// (bits + 1 in sign-magnitude: -0 -> the smallest negative denormal, -65504 -> -inf) is then at or below x.
+typedef _Float16 sf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned screen_thr_pack2(float lo, float hi) {
+  const auto h = __builtin_amdgcn_cvt_pkrtz(lo, hi);
+  unsigned u = __builtin_bit_cast(unsigned, h);
+  u += (float)h[0] > lo ? 1u : 0u;
+  u += (float)h[1] > hi ? 0x10000u : 0u;
+  return u;
+}
+__device__ __forceinline__ float screen_thr_unpack(unsigned packed, int half) {
+  return (float)__builtin_bit_cast(sf16x2, packed)[half];
+}
+// In the D layout of the 16x16 MFMA the lanes n, n + 16, n + 32 and n + 48 of a wave own the same query (for different
+// rows of the tile), so "one pool offer per lane" is four compare-and-swap loops per query, wave and tile on the same
+// ten LDS slots where the 32x32 form made two - on a cold slice, where every lane offers, the whole difference between
+// the two forms on short slices.  The best of x over SCREEN_OFFER_SPAN of those lanes: the lane that holds it offers.
+#ifndef SSKD_SCREEN_OFFER_SPAN
+#define SSKD_SCREEN_OFFER_SPAN 4
+#endif
+__device__ __forceinline__ float screen_group_max(float x) {
+  if (SSKD_SCREEN_OFFER_SPAN >= 2) x = fmaxf(x, __shfl_xor(x, 16));
+  if (SSKD_SCREEN_OFFER_SPAN >= 4) x = fmaxf(x, __shfl_xor(x, 32));
+  return x;
+}
+// packed = max(packed, pack(lo, hi)) per half
+__device__ __forceinline__ void screen_thr_raise2(unsigned& packed, float lo, float hi) {
+  const sf16x2 a = __builtin_bit_cast(sf16x2, packed), b = __builtin_bit_cast(sf16x2, screen_thr_pack2(lo, hi));
+  packed = __builtin_bit_cast(unsigned, __builtin_elementwise_max(a, b));
+}
+__device__ __forceinline__ void screen_thr_raise(unsigned& packed, int half, float x) {
+  screen_thr_raise2(packed, half == 0 ? x : -INFINITY, half == 0 ? -INFINITY : x);
 }
 
 // ------------------------------------------------------------------------- //
@@ -331,7 +394,7 @@ __device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const
 // its own corpus tiles through a register ring, shared pruning pools) on bf16 operands, with one difference: no
 // per-lane sorted lists.  A lane APPENDS every row that reaches the pruning bound - score >= (best known lower bound
 // of the query's k-th best screen score) - 2e - to a private run of SCREEN_CAP entries in global memory (8-byte
-// fire-and-forget stores, no atomics; the count lives in a register).  Every bound is a valid lower bound of the
+// fire-and-forget stores, no atomics; the count lives in an LDS slot of the run's own).  Every bound is a valid lower bound of the
 // final k-th best screen score, so the appended set always contains the whole candidate band {score >= kth - 2e}:
 // nothing to prove afterwards except that no run overflowed.  (Rounds 2-3 kept 6- or 8-deep sorted lists in
 // registers: 12 registers per 32-query sub-block, an insertion network per accepted row, and a "list full inside the
@@ -344,12 +407,12 @@ __device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG], const
 // (every slice starts cold: its first tiles pass whole) to a few hundred.
 // ------------------------------------------------------------------------- //
 #ifndef SSKD_SCREEN_CAP
-#define SSKD_SCREEN_CAP 64
+#define SSKD_SCREEN_CAP 32
 #endif
 #ifndef SSKD_SCREEN_FIN_ENTRIES
 #define SSKD_SCREEN_FIN_ENTRIES 640
 #endif
-constexpr int SCREEN_CAP = SSKD_SCREEN_CAP;   // entries per (query, wave, half-wave) run
+constexpr int SCREEN_CAP = SSKD_SCREEN_CAP;   // entries per (query, wave, lane group of 16) run
 #ifndef SSKD_SCREEN_PRE_TILES
 #define SSKD_SCREEN_PRE_TILES 64
 #endif
@@ -414,6 +477,92 @@ __device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* 
   return w;
 }
 
+// the queries [q0, q0 + 32 QB) of the call, rounded to bf16, into the LDS fragment layout above (zero past nq)
+template <int QB>
+__device__ __forceinline__ void stage_query_frags(sbf16x8* __restrict__ qs, const float* __restrict__ queries, int q0, int nq,
+                                                  int tid, int n_threads) {
+  for (int idx = tid; idx < 2 * QB * BSTEPS * 64; idx += n_threads) {
+    const int l = idx & 63, sidx = (idx >> 6) % BSTEPS, nb = idx / (64 * BSTEPS);
+    const int q = q0 + nb * 16 + (l & 15);
+    sbf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.f;
+    if (q < nq) {
+      const float4* src = reinterpret_cast<const float4*>(queries + (int64_t)q * DIM + 32 * sidx + 8 * (l >> 4));
+      const float4 a = src[0], b = src[1];
+      v[0] = (__bf16)a.x; v[1] = (__bf16)a.y; v[2] = (__bf16)a.z; v[3] = (__bf16)a.w;
+      v[4] = (__bf16)b.x; v[5] = (__bf16)b.y; v[6] = (__bf16)b.z; v[7] = (__bf16)b.w;
+    }
+    qs[idx] = v;
+  }
+}
+
+// Test hook (sskd_index_screen_scores): the screen scores themselves, out[32 n_tiles][64], of up to 64 queries against
+// every row of the sidecar - one wave, the staging, tile ring and MFMA core of the screening kernel with nothing after
+// them.  A wrong lane -> (row, column) map in either operand still yields plausible search results; not here.
+__global__ __launch_bounds__(64) void screen_scores_probe_kernel(const sbf16x8* __restrict__ tiled, const float* __restrict__ queries,
+                                                                 int nq, int n_tiles, float* __restrict__ out) {
+  constexpr int QB = 2, BG = BGROUP, RG = SCREEN_RING, NB = screen_frag_bases<QB>();
+  extern __shared__ float4 qs_raw[];
+  sbf16x8* const qs = reinterpret_cast<sbf16x8*>(qs_raw);
+  const int lane = threadIdx.x, n = lane & 15, g = lane >> 4;
+  stage_query_frags<QB>(qs, queries, 0, nq, lane, 64);
+  __syncthreads();
+  screen_lds_frag* qbase[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) qbase[nb] = (screen_lds_frag*)(qs + lane) + nb * SCREEN_FRAGS_PER_BASE * 64;
+  sbf16x8 buf[RG][BG][2], qfrag[SCREEN_FRAG_DEPTH];
+  const unsigned lane_off = (unsigned)(n + 32 * g) * 16u;
+#pragma unroll
+  for (int gr = 0; gr + 1 < RG; ++gr) load_bgroup<BG>(buf[gr], tiled + gr * BG * 128, lane_off);
+  for (int t = 0; t < n_tiles; ++t) {
+    f32x4 acc[2][2 * QB];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < 2 * QB; ++nb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[mb][nb][i] = 0.f;
+    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tiled + (int64_t)t * BTILE_VEC, qbase, qfrag, acc,
+                                                             t + 1 < n_tiles, (int64_t)BTILE_VEC, lane_off);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < 2 * QB; ++nb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          out[(int64_t)(t * TILE_ROWS + 16 * mb + 4 * g + i) * (32 * QB) + 16 * nb + n] = acc[mb][nb][i];
+  }
+}
+
+// Test hook (sskd_screen_threshold_roundtrip): out[i] = unpack(pack(in[i])) of the fp16 pruning bounds, through both
+// halves of a pair (the other half holds in[i ^ 1], or -inf past n)
+__global__ __launch_bounds__(256) void screen_thr_probe_kernel(const float* __restrict__ in, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float x = in[i], y = (i ^ 1) < n ? in[i ^ 1] : -INFINITY;
+  const unsigned packed = (i & 1) ? screen_thr_pack2(y, x) : screen_thr_pack2(x, y);
+  out[i] = screen_thr_unpack(packed, i & 1);
+}
+
+// D layout of v_mfma_f32_16x16x32_bf16: accumulator register i of lane l holds query (column) l & 15 of the block and row
+// 4 (l >> 4) + i of the row block - tile row 16 mb + 4 g + i for acc[mb][nb][i], g = l >> 4.  A row the allow-mask
+// clears scores -inf (tile_mask_word, search_device.h): lane l tests bits 16 mb + i of word >> 4 g.
+template <int QB>
+__device__ __forceinline__ void apply_tile_mask16(f32x4 (&acc)[2][2 * QB], uint32_t word, int g) {
+  if (word == 0xFFFFFFFFu) return;   // (wave-uniform) every row of the tile is allowed
+  const uint32_t lw = word >> (4 * g);
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool off = ((lw >> (16 * mb + i)) & 1u) == 0u;
+#pragma unroll
+      for (int nb = 0; nb < 2 * QB; ++nb)
+        if (off) acc[mb][nb][i] = -INFINITY;
+    }
+}
+
 // One phase of the screening kernel: the tiles [t_begin, t_end) of this workgroup, one tile per wave at a time.
 // BOUND_ONLY: nothing is appended and nothing exchanged - one pool offer per lane and tile (the sample phase); wave w
 // takes tiles t_begin + w + WAVES i, as it does in a slice phase whose slices are short (p.claim == 0: screen_plan).
@@ -429,22 +578,35 @@ __device__ __attribute__((noinline)) int screen_compact_run(unsigned long long* 
 // readfirstlane) at the head of its last tile - a whole tile, ~10 us, later - so the prefetch ring always knows the
 // next tile's address; only a chunk that the slice's end cut down to one tile, and the hop to a sibling, draw and read
 // on the spot.  Every tile is still processed exactly once per query block, by a workgroup that appends to its OWN runs
-// (my_list); the pool invariant (distinct rows) is kept by the caller.
+// (list0 + g); the pool invariant (distinct rows) is kept by the caller.
 // MASKED: the row allow-mask (tile_mask_word).  Why the proof survives it: a masked row scores -inf right after the MFMAs,
-// and gthr starts at -FLT_MAX, so it never passes "x >= gthr" (no append), and every pool offer is either a row that passed
-// that test or the lane's best row m of a tile only when m >= gthr (the sample phase, LIGHT) or when some row was taken
-// (first tile): never -inf.  So a slot of a pool or bucket that is not INT_MIN is always the finite score of an allowed
+// and both tests of the epilogue compare against a bound of at least -FLT_MAX, so it never passes (no append), and every
+// pool offer is either a row that passed the fp32 test or the lane's best row m of a tile only when m passed the first
+// test (the sample phase) or when some row was taken (LIGHT, first tile): never -inf.  So a slot of a pool or bucket that is not INT_MIN is always the finite score of an allowed
 // row, the pool is "full" (its minimum above INT_MIN) only with K scores of DISTINCT allowed rows, and every bound is a
 // lower bound of the k-th best screen score among the ALLOWED rows - the band the finalize kernel needs.  With fewer than
 // k allowed rows no pool ever fills, nothing is pruned, and the finalize kernel takes every appended row (tau = -inf).
 // The in-call exact fallback scans with the same mask.
+// State of a lane across the tile loop.  Lane l owns query n = l & 15 of each of the 2 QB query blocks, for the rows of
+// its lane group g = l >> 4: ten queries at 160 per workgroup.  Held in registers, bound, band and count of ten
+// queries are 30 registers the 168 of three waves per SIMD do not have, so
+//  - the band 2e of the block's queries sits in LDS beside wthr (bandl[32 QB]); the head of a tile reads both;
+//  - the count of a run sits in a 16-bit LDS slot of its own per (query, wave, lane group) - cnts[32 QB][WAVES][4],
+//    touched only where rows are appended, by the one lane that owns the run: no atomics;
+//  - the pruning bound stays in registers as fp16 pairs, QB registers (screen_thr_pack2).
 template <int K, int QB, int WAVES, bool BOUND_ONLY, bool LIGHT, int BG, int RG, bool MASKED = false>
 __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_begin, int t_end, int slice, int* cursors,
-                                             int wave, int j, int h, int q0,
-                                             const sbf16x8* __restrict__ qlane,
-                                             int* __restrict__ pool, int* __restrict__ wthr, uint2* run0, int64_t run_stride,
-                                             bool ragged, float (&gthr)[QB], const float (&band)[QB], int (&cnt)[QB]) {
-  sbf16x8 buf[RG][BG];
+                                             int wave, int n, int g, int q0,
+                                             const sbf16x8* __restrict__ qlane, int* pool, int list0,
+                                             bool ragged, unsigned (&gthr)[QB]) {
+  constexpr int NQ = 2 * QB;
+  // (wave-uniform LDS addresses; every per-lane address below is formed where it is used, from a copy of n the
+  // optimiser cannot follow: hoisted out of the tile loop, the forty addresses of ten queries' pool, bound, band and
+  // count were held - and spilled - across the MFMAs)
+  int* const wthr = pool + QB * 32 * K;
+  float* const bandl = reinterpret_cast<float*>(wthr + QB * 32);
+  short* const cnts = reinterpret_cast<short*>(bandl + QB * 32);
+  sbf16x8 buf[RG][BG][2];
   constexpr int NB = screen_frag_bases<QB>();
   screen_lds_frag* qbase[NB];
 #pragma unroll
@@ -453,11 +615,13 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     asm volatile("" : "+v"(qbase[nb]));   // one register each, not re-derived per read
   }
   sbf16x8 qfrag[SCREEN_FRAG_DEPTH];
-  const unsigned lane_off = (unsigned)(j + 32 * h) * 16u;
-  // sub-block qq of this lane holds a real query (not padding of the last block) while 32 qq < n_real: one register and
-  // a compare per use instead of QB flags held across the MFMA burst
-  int n_real = p.nq - q0 - j;
-  asm volatile("" : "+v"(n_real));
+#ifdef SSKD_SCREEN_ABL_CONTIG
+  const unsigned lane_off = (unsigned)(n + 16 * g) * 16u;
+#else
+  const unsigned lane_off = (unsigned)(n + 32 * g) * 16u;
+#endif
+  // (a padding query of the last block - zero fragments, every score 0 - carries the bound +inf from the kernel's head:
+  // it passes no first test, and the tile loop holds no "real query" flags)
   constexpr int CH = SCREEN_CLAIM_TILES;
   // all wave-uniform (scalar registers) but `drawn`: the tile in hand (-1: none), the end of its chunk, the slice drawn
   // from [s_begin, s_end) and the siblings not yet tried, the draw in flight (lane 0) and whether there is one
@@ -472,7 +636,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     // the ring into vmcnt(0).)
     int at = sl;
     asm volatile("" : "+v"(at));
-    if (j + 32 * h == 0) drawn = __hip_atomic_fetch_add(cursors + at, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (n + 16 * g == 0) drawn = __hip_atomic_fetch_add(cursors + at, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     in_flight = true;
   };
   // first tile of the chunk drawn (its end: next_end), or -1 when the query block has no tile left for this wave
@@ -507,7 +671,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
   }
   if (t >= 0) {
 #pragma unroll
-    for (int g = 0; g + 1 < RG; ++g) load_bgroup<BG>(buf[g], p.tiled + (int64_t)t * BTILE_VEC + g * BG * 64, lane_off);
+    for (int gr = 0; gr + 1 < RG; ++gr) load_bgroup<BG>(buf[gr], p.tiled + (int64_t)t * BTILE_VEC + gr * BG * 128, lane_off);
   }
 
   for (int tiles_done = 0; t >= 0; t = next_t, ++tiles_done) {
@@ -526,119 +690,213 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     uint32_t mword = 0xFFFFFFFFu;
     if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
     // bounds are exchanged with global memory at tile 0 (the sample phases' bounds), tile 16 and every 64th: an exchange is
-    // ten dependent agent-scope loads + an atomic per sub-block (~3 us of stall); at tiles 0, 1, 2, 4, 8, 16, ... and
+    // ten dependent agent-scope loads + an atomic per query block (~3 us of stall); at tiles 0, 1, 2, 4, 8, 16, ... and
     // every 8th it cost 5 % of the kernel at 1 M rows and 10 % on a 125 k-row shard.  The sample phase never reads them.
     const bool exchange = !BOUND_ONLY && (tiles_done == 0 || tiles_done == 16 || tiles_done % SCREEN_TAU_REFRESH_TILES == 0);
+    // The registers' bounds follow the pools' at every SCREEN_BOUND_REFRESH_TILES-th tile of the wave (and wherever the
+    // lane appends, below): twenty LDS words and five packs at EVERY tile cost 0.24 ms of 5.9 at the bench shape
+    // (periods 1 / 2 / 4 / 8: 5.91 / 5.78 / 5.71 / 5.67 ms), and a bound a few tiles stale only lets a few more rows
+    // through to the fp32 test, which reads the pool's bound of that moment: 417 / 416 / 416 appended entries per query.
+    if (exchange || tiles_done % SCREEN_BOUND_REFRESH_TILES == 0) {
+    int nh = n;
+    asm volatile("" : "+v"(nh));
+    // The exchange is made by ONE lane group of the wave and lands in wthr (an LDS atomicMax: any lower bound of the
+    // final k-th best score may stand there, and it only rises), where the reads below - the same wave's, in order -
+    // and the fp32 test of the append path find it.  Made by all four groups it was four returning atomics per query
+    // and wave on the same word of tau: with 32 slices (1 000 queries x 1 M rows) they queued for 0.2 ms of a 0.85 ms launch.
+    if (exchange && g == 0) {
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-      const int w = wthr[qq * 32 + j];
-      gthr[qq] = fmaxf(gthr[qq], ordered_to_float(w) - band[qq]);
-      if (exchange && (qq * 32 < n_real))
-        gthr[qq] = fmaxf(gthr[qq],
-                         ordered_to_float(exchange_bound<K>(p.gpool, p.tau + q0 + qq * 32 + j, q0 + qq * 32 + j, w)) - band[qq]);
+      for (int nb = 0; nb < NQ; ++nb) {
+        const int ql = 16 * nb + nh;
+        if (q0 + ql < p.nq) atomicMax(wthr + ql, exchange_bound<K>(p.gpool, p.tau + q0 + ql, q0 + ql, wthr[ql]));
+      }
     }
-    f32x16 acc[QB];
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq)
+    for (int pr = 0; pr < QB; ++pr) {
+      float thr[2];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[qq][r] = 0.f;
+      for (int e = 0; e < 2; ++e) {
+        const int nb = 2 * pr + e, ql = 16 * nb + nh;
+        const int w = wthr[ql];
+        const float bd = bandl[ql];
+        thr[e] = ordered_to_float(w) - bd;   // (an empty pool: NaN)
+        thr[e] = fmaxf(thr[e], -INFINITY);   // no NaN into the pack
+      }
+      screen_thr_raise2(gthr[pr], thr[0], thr[1]);
+      // (packed HERE: left alone, the optimiser sinks the arithmetic to the epilogue, where the bound is first used, and
+      // carries the twenty words read from LDS across the MFMAs instead of these QB)
+      asm volatile("" : "+v"(gthr[pr]));
+    }
+    }
+    f32x4 acc[2][NQ];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < NQ; ++nb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[mb][nb][i] = 0.f;
 
     screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tile, qbase, qfrag, acc, next_t >= 0,
                                                              BOUND_ONLY ? (int64_t)WAVES * BTILE_VEC
                                                                         : (int64_t)(next_t - t) * BTILE_VEC, lane_off);
 
-    const int rowbase = t * TILE_ROWS + 4 * h;
+    // acc[mb][nb][i]: row rowbase + 16 mb + i, query 16 nb + n of the block
+    const int rowbase = t * TILE_ROWS + 4 * g;
     if (ragged && (int64_t)(t + 1) * TILE_ROWS > p.n_rows) {
 #pragma unroll
-      for (int qq = 0; qq < QB; ++qq)
+      for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (rowbase + acc_row(r) >= p.n_rows) acc[qq][r] = -INFINITY;
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int nb = 0; nb < NQ; ++nb)
+            if (rowbase + 16 * mb + i >= p.n_rows) acc[mb][nb][i] = -INFINITY;
     }
-    if constexpr (MASKED) apply_tile_mask<QB>(acc, mword, h);
+    if constexpr (MASKED) apply_tile_mask16<QB>(acc, mword, g);
 #ifdef SSKD_SCREEN_ABL_NOLIST  // timing ablation: no candidate / pool maintenance (accumulators kept alive)
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq)
+    for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc[qq][r]));
+      for (int nb = 0; nb < NQ; ++nb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(acc[mb][nb][i]));
     if (false)
 #endif
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-      float m = acc[qq][0];
+    for (int pr = 0; pr < QB; ++pr) {   // the two query blocks whose bounds share a register
+      float m[2], fthr[2];
+      bool pass[2];
 #pragma unroll
-      for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[qq][r]);
+      for (int e = 0; e < 2; ++e) {
+        const int nb = 2 * pr + e;
+        m[e] = acc[0][nb][0];
+#pragma unroll
+        for (int r = 1; r < 8; ++r) m[e] = fmaxf(m[e], acc[r >> 2][nb][r & 3]);
+        // first test, against the fp16 bound (at or below the exact one: a superset passes); never below -FLT_MAX - the
+        // -inf of a lane whose rows are all masked or past n_rows passes no bound, and no pool slot ever holds it
+        fthr[e] = fmaxf(screen_thr_unpack(gthr[pr], e), -FLT_MAX);
+        pass[e] = m[e] >= fthr[e];
+      }
       if constexpr (BOUND_ONLY) {
         // the sample phase only needs a bound: ONE offer per lane and tile (its best row) instead of one per row - every
         // row of a cold sample passes, and 80 compare-and-swap loops per lane and tile cost 0.05 ms per call
-        if ((qq * 32 < n_real) && m >= gthr[qq]) {
-          int xid = rowbase;
 #pragma unroll
-          for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
-          const int xi = float_to_ordered(m);
-          if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi)) {
-            // (the bucket address is formed here, on the rare path: hoisted out of the tile loop, the QB 64-bit
-            // addresses were spilled in the 160-query kernels)
-            int qa = q0 + qq * 32 + j;
-            asm volatile("" : "+v"(qa));
-            bucket_forward<K>(p.gpool, qa, xid, xi);
+        for (int e = 0; e < 2; ++e) {
+          const int nb = 2 * pr + e;
+          const float mg = screen_group_max(pass[e] ? m[e] : -INFINITY);   // (every lane of the wave is here)
+          if (pass[e]) {
+            int nc = n;
+            asm volatile("" : "+v"(nc));
+            const int ql = 16 * nb + nc;
+            if (m[e] == mg) {   // the query's best row of the tile: its lane offers, the others read the bound after it
+              int xid = rowbase;
+#pragma unroll
+              for (int r = 7; r >= 0; --r) xid = acc[r >> 2][nb][r & 3] == m[e] ? rowbase + 16 * (r >> 2) + (r & 3) : xid;
+              const int xi = float_to_ordered(m[e]);
+              if (pool_offer<K>(pool + ql * K, wthr + ql, xi)) {
+                bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+              }
+            }
+            screen_thr_raise(gthr[pr], e, fmaxf(ordered_to_float(wthr[ql]) - bandl[ql], -INFINITY));
           }
-          gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
         }
       } else
-      if (__any((qq * 32 < n_real) && m >= gthr[qq])) {
-#ifndef SSKD_SCREEN_NO_COMPACT
-        {
-          // A run that could fill up inside this tile (16 rows) first drops what the bound has overtaken since it was
-          // appended: rows arriving in ascending order of their score - a corpus sorted by topic - pass the bound one
-          // after the other and the bound follows them, so the entries worth keeping are the band of the CURRENT
-          // bound.  Own stores, read back from L2 after they were acknowledged; forward in-place compaction (w <= i).
-          const bool tight = cnt[qq] > SCREEN_CAP - 16 && cnt[qq] <= SCREEN_CAP;
-          if (__any(tight)) {
-            __builtin_amdgcn_s_waitcnt(0x0F70);
-            if (tight) cnt[qq] = screen_compact_run(reinterpret_cast<unsigned long long*>(run0 + qq * run_stride), cnt[qq], gthr[qq]);
-          }
-        }
-#endif
-        bool grew = false;
+      if (__any(pass[0] || pass[1])) {
+        // ONE entry for the pair - as often as the 32-query sub-blocks of the 32x32 form entered, half as often as one per
+        // query block while a slice's bounds are cold and every block has a row that passes - and one LDS round trip
+        // for the bounds, bands and counts of both blocks.
+        int nc = n;
+        asm volatile("" : "+v"(nc));
+        float pb[2];   // what the pools hold now, minus the band (-inf: no bound yet)
+        int c[2];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float x = acc[qq][r];
-          const int xid = rowbase + acc_row(r);
-          const bool take = (qq * 32 < n_real) && x >= gthr[qq];   // (padding queries own no run)
-          {   // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
-            if (take) {
-              {
-                unsigned long long* const run = reinterpret_cast<unsigned long long*>(run0 + qq * run_stride);
-                if (cnt[qq] < SCREEN_CAP)
-                  run[cnt[qq]] = (unsigned long long)__float_as_uint(x) | ((unsigned long long)(unsigned)xid << 32);
-                ++cnt[qq];   // (> SCREEN_CAP: the run overflowed - the band itself holds more than a run: exact fallback)
+        for (int e = 0; e < 2; ++e) {
+          const int ql = 32 * pr + 16 * e + nc;
+          pb[e] = fmaxf(ordered_to_float(wthr[ql]) - bandl[ql], -INFINITY);
+          c[e] = cnts[(ql * WAVES + wave) * 4 + g];
+        }
+        // the registers follow the pools here too: a lane that came in on a stale bound does not come in again
+        screen_thr_raise2(gthr[pr], pb[0], pb[1]);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int nb = 2 * pr + e, ql = 16 * nb + nc;
+          // The exact bound, in fp32: the pool's, or the register's fp16 as it was at the first test (the exchanges' bounds
+          // live only there: a valid bound, at most one fp16 step below the one it was packed from), never below
+          // -FLT_MAX - the -inf of a masked row or of a row past n_rows passes no finite bound.  A lane appends a row
+          // exactly when its best row reaches it.
+          const float thr = fmaxf(pb[e], fthr[e]);
+          if (!__any(m[e] >= thr)) continue;
+          short* const cslot = cnts + (ql * WAVES + wave) * 4 + g;
+          // run of (query, this wave, this lane group): list0 + g of the query's lists (padding queries own none)
+          unsigned long long* const run = reinterpret_cast<unsigned long long*>(
+              p.cand + ((int64_t)min(q0 + ql, p.nq - 1) * p.lists_per_query + list0 + g) * SCREEN_CAP);
+          int cc = c[e];
+          bool dirty = false;
+#ifndef SSKD_SCREEN_NO_COMPACT
+          {
+            // A run that could fill up inside this tile (8 rows) first drops what the bound has overtaken since it was
+            // appended: rows arriving in ascending order of their score - a corpus sorted by topic - pass the bound one
+            // after the other and the bound follows them, so the entries worth keeping are the band of the CURRENT
+            // bound.  Own stores, read back from L2 after they were acknowledged; forward in-place compaction (w <= i).
+            const bool tight = cc > SCREEN_CAP - 8 && cc <= SCREEN_CAP;
+            if (__any(tight)) {
+              __builtin_amdgcn_s_waitcnt(0x0F70);
+              if (tight) {
+                cc = screen_compact_run(run, cc, thr);
+                dirty = true;
               }
-              if (!LIGHT && tiles_done > 0) {
-                const int xi = float_to_ordered(x);
-                if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && (qq * 32 < n_real))
-                  bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
-              }
-              grew = true;
             }
           }
-        }
-        if (grew) {
-          if constexpr (LIGHT) {
-            // ONE pool offer per lane, sub-block and tile - its best row - instead of one per appended row.  The bound
-            // is a little weaker (two of a query's best rows in one lane's share of a tile count once) and its upkeep
-            // much cheaper: worth it while a slice is short (125 k-row shard -6 %, 60 k -12 %; 1 M rows +1 %, 8.8 M +3 %)
-            int xid = rowbase;
+#endif
+          bool grew = false;
 #pragma unroll
-            for (int r = 15; r >= 0; --r) xid = acc[qq][r] == m ? rowbase + acc_row(r) : xid;
-            const int xi = float_to_ordered(m);
-            if (pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, xi) && tiles_done > 0)
-              bucket_forward<K>(p.gpool, q0 + qq * 32 + j, xid, xi);
-          } else {
-            // first tile: every workgroup starts at the same instant - offer only the lane's best row
-            if (tiles_done == 0) pool_offer<K>(pool + (qq * 32 + j) * K, wthr + qq * 32 + j, float_to_ordered(m));
+          for (int r = 0; r < 8; ++r) {
+            const float x = acc[r >> 2][nb][r & 3];
+            const int xid = rowbase + 16 * (r >> 2) + (r & 3);
+            const bool take = x >= thr;   // (a padding query: thr = +inf)
+            {   // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
+              if (take) {
+                {
+                  if (cc < SCREEN_CAP)
+                    run[cc] = (unsigned long long)__float_as_uint(x) | ((unsigned long long)(unsigned)xid << 32);
+                  // (SCREEN_CAP + 1: the run overflowed - the band itself holds more than a run: exact fallback; the
+                  // count stops there, it lives in 16 bits)
+                  if (cc <= SCREEN_CAP) ++cc;
+                }
+                if (!LIGHT && tiles_done > 0) {
+                  const int xi = float_to_ordered(x);
+                  if (pool_offer<K>(pool + ql * K, wthr + ql, xi))
+                    bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+                }
+                grew = true;
+              }
+            }
           }
-          gthr[qq] = fmaxf(gthr[qq], ordered_to_float(wthr[qq * 32 + j]) - band[qq]);
+          if (grew || dirty) *cslot = (short)cc;
+          // (wave-uniform control flow up to here; beyond its first tile the long-slice form offers every appended row)
+          const float mg = (LIGHT || tiles_done == 0) ? screen_group_max(m[e]) : m[e];
+          if (grew) {
+            if (m[e] != mg) {
+              // another lane group holds the query's best row of this tile: it offers (if it appended)
+            } else
+            if constexpr (LIGHT) {
+              // ONE pool offer per query, wave and tile - its best row - instead of one per appended row.  The bound
+              // is a little weaker (two of a query's best rows in one tile count once) and its upkeep
+              // much cheaper: worth it while a slice is short (125 k-row shard -6 %, 60 k -12 %; 1 M rows +1 %, 8.8 M +3 %)
+              int xid = rowbase;
+#pragma unroll
+              for (int r = 7; r >= 0; --r) xid = acc[r >> 2][nb][r & 3] == m[e] ? rowbase + 16 * (r >> 2) + (r & 3) : xid;
+              const int xi = float_to_ordered(m[e]);
+              if (pool_offer<K>(pool + ql * K, wthr + ql, xi) && tiles_done > 0)
+                bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+            } else {
+              // first tile: every workgroup starts at the same instant - offer only the lane's best row
+              if (tiles_done == 0) pool_offer<K>(pool + ql * K, wthr + ql, float_to_ordered(m[e]));
+            }
+            // (the register's bound is NOT raised to what the offer made of the pool's: it follows at the lane's next entry
+            // and at the wave's next refresh, and the LDS round trip here - bound and band, after every append - was the
+            // whole of what short slices lost to the 32x32 form: 125 k rows x 10 000 queries 0.955 -> 0.925 ms, the same
+            // 226 appended entries per query)
+          }
         }
       }
     }
@@ -646,14 +904,22 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 
 }
 
+// dynamic LDS of screen_append_kernel<10, QB, WAVES, ..>: fragments, pools + wthr, bands, run counts (143 KiB of the 160 at
+// 160 queries and 12 waves)
+constexpr size_t screen_lds_bytes(int QB, int WAVES) {
+  return (size_t)2 * QB * BSTEPS * 64 * 16 + (size_t)QB * 32 * (10 + 2) * sizeof(int) + (size_t)QB * 32 * WAVES * 4 * sizeof(short);
+}
+static_assert(screen_lds_bytes(5, SCREEN_WAVES) <= 160 * 1024, "the 160-query workgroup must fit the CU's LDS");
+
 template <int K, int QB, int WAVES, bool LIGHT, int BG, int RG, bool MASKED = false>
 __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendParams p) {
+  static_assert(K == 10, "screen_lds_bytes counts ten pool slots per query");
   extern __shared__ float4 qs_raw[];
-  sbf16x8* const qs = reinterpret_cast<sbf16x8*>(qs_raw);  // [QB][24 steps][64 lanes]
+  sbf16x8* const qs = reinterpret_cast<sbf16x8*>(qs_raw);  // [2 QB blocks][12 steps][64 lanes]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 31, h = lane >> 5;
+  const int n = lane & 15, g = lane >> 4;
   // Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8) and each XCD has its own L2: give XCD x
   // a CONTIGUOUS range of (slice, query block) pairs, slice-major, so that a slice's tiles are pulled
   // through one or two L2s instead of all eight.
@@ -668,42 +934,24 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   if (lane == 0) stamp[0] = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  for (int idx = tid; idx < QB * BSTEPS * 64; idx += WAVES * 64) {
-    const int l = idx & 63, sidx = (idx >> 6) % BSTEPS, qq = idx / (64 * BSTEPS);
-    const int q = q0 + qq * 32 + (l & 31);
-    sbf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.f;
-    if (q < p.nq) {
-      const float4* src = reinterpret_cast<const float4*>(p.queries + (int64_t)q * DIM + 16 * sidx + 8 * (l >> 5));
-      const float4 a = src[0], b = src[1];
-      v[0] = (__bf16)a.x; v[1] = (__bf16)a.y; v[2] = (__bf16)a.z; v[3] = (__bf16)a.w;
-      v[4] = (__bf16)b.x; v[5] = (__bf16)b.y; v[6] = (__bf16)b.z; v[7] = (__bf16)b.w;
-    }
-    qs[idx] = v;
-  }
-  int* const pool = reinterpret_cast<int*>(qs + QB * BSTEPS * 64);
+  stage_query_frags<QB>(qs, p.queries, q0, p.nq, tid, WAVES * 64);
+  int* const pool = reinterpret_cast<int*>(qs + 2 * QB * BSTEPS * 64);
   int* const wthr = pool + QB * 32 * K;
+  float* const bandl = reinterpret_cast<float*>(wthr + QB * 32);             // 2e of the block's queries
+  short* const cnts = reinterpret_cast<short*>(bandl + QB * 32);             // [32 QB queries][WAVES][4 lane groups]
   for (int i = tid; i < QB * 32 * (K + 1); i += WAVES * 64) pool[i] = (int)0x80000000;
+  for (int i = tid; i < QB * 32; i += WAVES * 64) bandl[i] = p.eps2[min(q0 + i, p.nq - 1)];
+  for (int i = tid; i < QB * 32 * WAVES * 2; i += WAVES * 64) reinterpret_cast<int*>(cnts)[i] = 0;
   __syncthreads();
   const sbf16x8* qlane = qs + lane;
 
-  float gthr[QB];   // best known lower bound on the query's final K-th SCREEN score, minus 2e
-  float band[QB];
-  int cnt[QB];
-  bool real[QB];
+  // best known lower bound on the final K-th SCREEN score, minus 2e, of the lane's 2 QB queries: fp16 pairs, "none" = -inf
+  unsigned gthr[QB];
 #pragma unroll
-  for (int qq = 0; qq < QB; ++qq) {
-    gthr[qq] = -FLT_MAX;   // finite: the -inf scores of rows past n_rows never pass
-    const int qg = q0 + qq * 32 + j;
-    real[qq] = qg < p.nq;
-    band[qq] = p.eps2[real[qq] ? qg : p.nq - 1];
-    cnt[qq] = 0;
-  }
-  // run of (query q0 + j, this wave, this half-wave); sub-block qq is 32 queries further
-  const int my_list = (slice * WAVES + wave) * 2 + h;
-  uint2* const run0 = p.cand + ((int64_t)min(q0 + j, p.nq - 1) * p.lists_per_query + my_list) * SCREEN_CAP;
-  const int64_t run_stride = (int64_t)32 * p.lists_per_query * SCREEN_CAP;
+  for (int pr = 0; pr < QB; ++pr)   // (+inf for the padding queries of the last block: nothing ever passes)
+    gthr[pr] = (q0 + 32 * pr + n < p.nq ? 0xFC00u : 0x7C00u) | (q0 + 32 * pr + 16 + n < p.nq ? 0xFC000000u : 0x7C000000u);
+  // runs of this wave: lists list0 + g of a query, g the lane group
+  const int list0 = (slice * WAVES + wave) * 4;
 
   const bool ragged = (p.n_rows & 31) != 0;
 
@@ -718,12 +966,12 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   if (p.pre_tps > 0) {
     const int s_begin = slice * p.pre_tps;
     const int s_end = min(s_begin + p.pre_tps, p.pre_tiles);
-    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, slice, nullptr, wave, j, h, q0, qlane,
-                                             pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
+    screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, slice, nullptr, wave, n, g, q0, qlane,
+                                             pool, list0, ragged, gthr);
     // what this workgroup learned from its share of the sample; everybody's offers are in before phase 1
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq)
-      if (real[qq] && h == 0) atomicMax(p.tau + q0 + qq * 32 + j, wthr[qq * 32 + j]);
+    for (int nb = 0; nb < 2 * QB; ++nb)
+      if (g == 0 && q0 + nb * 16 + n < p.nq) atomicMax(p.tau + q0 + nb * 16 + n, wthr[nb * 16 + n]);
     __syncthreads();
     // INVARIANT OF THE POOL: every slot is the score of a DISTINCT row (pool_offer stores scores only and cannot tell
     // a row it already holds).  Where this workgroup's share of the sample lies inside its own slice - slice 0, whose
@@ -731,7 +979,9 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
     // minimum above the k-th best DISTINCT score, the "lower bound" above the true k-th best, and rows of the top k
     // would be pruned silently (round 3 shipped that hole: VERDICT r3 weak 1).  So such a workgroup empties its slots
     // here.  wthr stays: it is the minimum of a full pool of distinct SAMPLE rows, a valid bound on its own, and only
-    // ever rises to minima of full pools, which from here on hold phase-1 rows only.  Rows of other slices' sample
+    // ever rises - to minima of full pools, which from here on hold phase-1 rows only, and to exchanged bounds (tau and
+    // the minimum of the query's global buckets: screen_tiles puts them here with an LDS atomicMax), each of them a
+    // lower bound of the final k-th best screen score among the allowed rows, which is all the proof asks of wthr.  Rows of other slices' sample
     // shares never return in this workgroup's slice - but a wave that has run out of tiles there goes on to draw from
     // the sibling slices (screen_tiles), the sample's among them, so EVERY workgroup of a launch that claims its
     // tiles empties its slots; where tiles are dealt (short slices, or a build without stealing) the workgroups whose
@@ -745,19 +995,19 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
   if (lane == 0) stamp[1] = __builtin_amdgcn_s_memrealtime();
 #endif
   screen_tiles<K, QB, WAVES, false, LIGHT, BG, RG, MASKED>(p, t_begin, t_end, slice, p.cursors + (int64_t)qblk * p.n_slices,
-                                            wave, j, h, q0, qlane, pool, wthr, run0, run_stride, ragged, gthr, band, cnt);
+                                            wave, n, g, q0, qlane, pool, list0, ragged, gthr);
 #ifdef SSKD_SCREEN_STAMPS
   if (lane == 0) stamp[2] = __builtin_amdgcn_s_memrealtime();
 #endif
 
   // (the query numbers and "real" tests are formed again here from a lane number the optimiser cannot follow: kept
-  // from the kernel's head they were five registers and five exec masks alive - and spilled - across both tile loops)
-  int jt = j;
-  asm volatile("" : "+v"(jt));
+  // from the kernel's head they were registers and exec masks alive - and spilled - across both tile loops)
+  int nt = n;
+  asm volatile("" : "+v"(nt));
 #pragma unroll
-  for (int qq = 0; qq < QB; ++qq) {
-    const int q = q0 + qq * 32 + jt;
-    if (q < p.nq) p.cand_cnt[(int64_t)q * p.lists_per_query + my_list] = cnt[qq];
+  for (int nb = 0; nb < 2 * QB; ++nb) {
+    const int q = q0 + nb * 16 + nt;
+    if (q < p.nq) p.cand_cnt[(int64_t)q * p.lists_per_query + list0 + g] = cnts[((nb * 16 + nt) * WAVES + wave) * 4 + g];
   }
 }
 
@@ -1064,14 +1314,14 @@ bool screen_plan(int64_t n_rows, int nq, int k, ScreenPlan* sp) {
   if (pl.QB == 0) return false;
   pl.n_qblocks = (int)sskd::ceil_div(nq, 32 * pl.QB);
   pl.LK = SCREEN_CAP;   // entries per run
-  const int max_by_lists = 1024 / (2 * SCREEN_WAVES);   // <= 1 024 runs per query
+  const int max_by_lists = 2048 / (4 * SCREEN_WAVES);   // <= 2 048 runs per query (of SCREEN_CAP = 32 entries)
   if (slices > max_by_lists) slices = max_by_lists;
 #ifdef SSKD_SCREEN_FORCE_SLICES
   slices = SSKD_SCREEN_FORCE_SLICES;
 #endif
   pl.tiles_per_slice = (int)sskd::ceil_div(pl.n_tiles, slices);
   pl.n_slices = (int)sskd::ceil_div(pl.n_tiles, pl.tiles_per_slice);
-  pl.lists_per_query = pl.n_slices * SCREEN_WAVES * 2;
+  pl.lists_per_query = pl.n_slices * SCREEN_WAVES * 4;   // a run per (slice, wave, lane group of 16)
   pl.part_elems = (size_t)nq * pl.lists_per_query * pl.LK;
   // sample phase: the first SCREEN_PRE_TILES tiles (at most an eighth of the shard), cut over the slices
   // by slice length, not shard size: 1 000 queries cut 1 M rows into 32 slices of 81 tiles per wave (-7 % in the light
@@ -1205,6 +1455,29 @@ int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_qu
   return sskd::check_launch("screen_setup_kernel");
 }
 
+// test hook: the raw screen scores of nq <= 64 queries against every row of a sidecar, d_out[32 ceil(n_rows / 32)][64]
+int sskd_index_screen_scores(const void* d_bf16, int64_t n_rows, const float* d_queries, int nq, float* d_out, void* stream) {
+  SSKD_REQUIRE(n_rows > 0 && nq > 0 && nq <= 64, "index_screen_scores: needs rows and 1..64 queries (got rows=%lld nq=%d)",
+               (long long)n_rows, nq);
+  int rc = require_shard_rows("index_screen_scores", n_rows);
+  if (rc != SSKD_OK) return rc;
+  SSKD_REQUIRE(d_bf16 && d_queries && d_out, "index_screen_scores: null pointer");
+  const size_t lds = (size_t)2 * 2 * BSTEPS * 64 * 16;
+  hipLaunchKernelGGL(screen_scores_probe_kernel, dim3(1), dim3(64), lds, sskd::as_stream(stream),
+                     static_cast<const sbf16x8*>(d_bf16), d_queries, nq, (int)sskd::ceil_div(n_rows, TILE_ROWS), d_out);
+  return sskd::check_launch("screen_scores_probe_kernel");
+}
+
+// test hook: d_out[i] = the fp16 pruning bound the screening kernel keeps for an fp32 bound d_in[i], widened again
+int sskd_screen_threshold_roundtrip(const float* d_in, int n, float* d_out, void* stream) {
+  SSKD_REQUIRE(n >= 0, "screen_threshold_roundtrip: n < 0");
+  if (n == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_in && d_out, "screen_threshold_roundtrip: null pointer");
+  hipLaunchKernelGGL(screen_thr_probe_kernel, dim3((unsigned)sskd::ceil_div(n, 256)), dim3(256), 0, sskd::as_stream(stream),
+                     d_in, n, d_out);
+  return sskd::check_launch("screen_thr_probe_kernel");
+}
+
 int sskd_index_search_screened_plan(int64_t n_rows, int nq, int k, int* queries_per_block, int* corpus_passes,
                                     int* n_slices) {
   ScreenPlan pl{};
@@ -1269,7 +1542,8 @@ int sskd_index_search_screened_claim(const float* d_tiled, const void* d_bf16, i
 
   launch_screen_setup(max_norm2, d_queries, nq, w.eps2, w.tau, w.fb_count, d_status, w.cursors, pl.n_qblocks * pl.n_slices, st);
 
-  static_assert((SCREEN_CAP * sizeof(float)) % 256 == 0, "the runs span part_scores and part_ids back to back");
+  // (part_elems is a multiple of the runs of one slice and query: 4 WAVES x SCREEN_CAP entries)
+  static_assert((4 * SCREEN_WAVES * SCREEN_CAP * sizeof(float)) % 256 == 0, "the runs span part_scores and part_ids back to back");
   ScreenAppendParams sp{};
   sp.tiled = static_cast<const sbf16x8*>(d_bf16);
   sp.queries = d_queries;
@@ -1287,7 +1561,7 @@ int sskd_index_search_screened_claim(const float* d_tiled, const void* d_bf16, i
 #ifdef SSKD_SCREEN_STAMPS
   sp.stamps = w.stamps;
 #endif
-  const size_t lds = (size_t)pl.QB * BSTEPS * 64 * 16 + (size_t)pl.QB * 32 * 11 * sizeof(int);
+  const size_t lds = screen_lds_bytes(pl.QB, SCREEN_WAVES);
   const void* kern = nullptr;
   switch (pl.QB) {
 #define SSKD_SCREEN_KERN(qb, light, bg, rg)                                                                           \

@@ -136,7 +136,8 @@ __device__ inline float ordered_to_float(int k) { return __int_as_float(k >= 0 ?
 // shared by the workgroup's 16 lists: lock-free, "replace the current minimum by compare-and-swap".
 // Slot values only grow and each is the score of a distinct row seen by this workgroup, so the
 // minimum over any (even stale) snapshot of a full pool is a valid lower bound on the query's
-// final K-th score; it is cached in `wthr` (one LDS word per query, atomicMax).  What a workgroup
+// final K-th score; it is cached in `wthr` (one LDS word per query, atomicMax - the screening kernel also raises that
+// word to the bounds it exchanges through global memory: any lower bound of the final K-th score may stand there).  What a workgroup
 // pool accepts after its first tile is forwarded to K **buckets** per query in global memory:
 // bucket (row id mod K) keeps the best score of its rows by a no-return atomicMax - fire and
 // forget, because a compare-and-swap pool there cost three dependent round trips to the memory

@@ -120,15 +120,15 @@ def stamp_report(name, lib, ws, waves=12):
           f"query block to the launch's last {(t1 - qb_end).mean() / L:.4f}", flush=True)
 
 
-def appended_entries(lib, ws, waves=12, cap=64):
+def appended_entries(lib, ws, waves=12, cap=32, runs=4):
     """mean number of rows a query's runs took in the last call (the counts follow the runs at the head of the carve)"""
     qpb, passes, nsl = C.c_int(), C.c_int(), C.c_int()
     assert lib.sskd_index_search_screened_plan(N, NQ, K, C.byref(qpb), C.byref(passes), C.byref(nsl)) == 0
-    lists = nsl.value * waves * 2
+    lists = nsl.value * waves * runs
     part = (NQ * lists * cap * 4 + 255) & ~255
     cnt = ws[2 * part:2 * part + NQ * lists * 4].view(torch.int32)
-    # This mirrors the head of screen_carve (csrc/screen.hip: scores, ids, counts; SCREEN_CAP = 64 entries per run, 12
-    # waves x 2 runs per slice).  A carve that moved would put other data here: a count is a number of rows of ONE
+    # This mirrors the head of screen_carve (csrc/screen.hip: scores, ids, counts; SCREEN_CAP = 32 entries per run, 12
+    # waves x 4 runs - one per 16-lane group - per slice).  A carve that moved would put other data here: a count is a number of rows of ONE
     # wave's tiles, so every word must lie in [0, rows] and their sum within the pairs screened - else refuse to print.
     assert 2 * part + NQ * lists * 4 <= ws.numel(), "workspace smaller than the carve this reader assumes"
     assert int(cnt.min()) >= 0 and int(cnt.max()) <= N and int(cnt.sum()) <= NQ * N, \
