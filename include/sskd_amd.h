@@ -773,6 +773,46 @@ int sskd_latec_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64
                                 float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* Candidate generation from the compressed token store (PLAID's first stages).  The store of
+ * sskd_latec_rerank plus CENTROID LISTS - d_list_lims DEVICE int64 [C + 1] ascending from 0, d_list_rows DEVICE int32
+ * [n_list]: LOCAL row r is in list c exactly when some token of r has centroid c (its cid clamped into [0, C)), every
+ * (c, r) pair once, rows ascending inside a list - retrieves by itself:
+ *   1. sskd_plaid_centroid_scores: S[c, t] = <centroid_c, q_t> for every query token of the batch, fp32, element (c, t) at
+ *      d_S[c * ld + t] (ld >= n_q_tokens): the fp32 accumulation of 384 exact bf16 x bf16 products by 24
+ *      v_mfma_f32_32x32x16_bf16 from a zero accumulator.  The bits of S[c, t] depend on the two rows alone.
+ *      |S - s64| <= 1.01 * 2 * 384 * 2^-24 |q_t| |centroid_c| against fp64 on the stored bf16 values.
+ *   sskd_plaid_candidates, everything below being a function of the bits of S:
+ *   2. probes: per query token t, P_t = the first nprobe centroids by (S[c, t] descending, c ascending); NaN and -inf are
+ *      never picked (a token may have fewer than nprobe probes);
+ *   3. Cand(q) = the rows of the lists of all probes of all tokens of q that d_row_mask allows (the format of "Filtered
+ *      search", NULL = all rows) and that lie in [0, n_rows);
+ *   4. approx(q, r) = sum over the query's tokens i (ascending, sequential fp32 from +0.0) of the max over ALL tokens j of r
+ *      of S[cid_j, t_i] (cid clamped into [0, C); the max is exact, ignores NaN and starts from -inf); a candidate whose
+ *      approx is NaN or -inf is dropped;
+ *   5. the best R by (approx descending, row ascending): d_cand_ids int64 [nq, R] global ids (row + id_offset) padded with
+ *      -1, d_cand_scores fp32 [nq, R] padded with -inf, d_n_cand int32 [nq] = |Cand(q)| before the drop and the cut.
+ * d_cand_ids is what sskd_latec_rerank takes as d_candidates.  q_lims / d_q_lims as in sskd_late_rerank; query token i of
+ * query q is column q_lims[q] + i of S.  n_list = the length of d_list_rows (at most n_tokens); list bounds are read
+ * clamped into [0, n_list] and a listed row outside [0, n_rows) is skipped.
+ *   Limits: 1 <= Tq <= 128, 1 <= C <= 65 536, 1 <= nprobe <= min(C, 32), 1 <= R <= 1024; query tokens and centroids
+ * 16-byte aligned, the workspace 256-byte aligned.  Workspace: sskd_plaid_candidates_workspace_bytes covers the whole
+ * batch up to a budget of 256 MiB (and always one query, sized for every row being a candidate); any workspace that holds
+ * one query's worth runs the call in chunks of queries.  sskd_plaid_candidates_plan reports one query's bytes, the
+ * queries per chunk under workspace_bytes (0 = what the size query returns), the parts the probe search cuts the centroids
+ * into and the interaction's workgroups per query.  Stream-ordered, no host sync (graph-capturable), allocates nothing;
+ * every argument is checked before anything is enqueued (SSKD_ERR_INVALID); nq = 0 / n_q_tokens = 0 succeed. */
+#define SSKD_PLAID_NPROBE_MAX 32
+int sskd_plaid_centroid_scores(const void* d_q_tokens, int64_t n_q_tokens, const void* d_centroids, int C, float* d_S,
+                               int64_t ld, void* stream);
+size_t sskd_plaid_candidates_workspace_bytes(int nq, int64_t n_rows, int nprobe);
+int sskd_plaid_candidates_plan(int nq, int max_tq, int C, int64_t n_rows, int nprobe, int R, size_t workspace_bytes,
+                               size_t* per_query_bytes, int* queries_per_chunk, int* probe_parts, int* interact_workgroups);
+int sskd_plaid_candidates(const float* d_S, int64_t ld, const int64_t* q_lims, const int64_t* d_q_lims, int nq, int C,
+                          const int32_t* d_cid, const int64_t* d_tok_lims, int64_t n_rows, int64_t n_tokens,
+                          const int64_t* d_list_lims, const int32_t* d_list_rows, int64_t n_list, const uint32_t* d_row_mask,
+                          int nprobe, int R, int64_t id_offset, int64_t* d_cand_ids, float* d_cand_scores, int32_t* d_n_cand,
+                          void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Knowledge-distillation losses of the reference and their gradient (loss
  * half).  Replaces MarginMSELoss / ListwiseKDLoss / ContrastiveLoss / CombinedKDLoss.forward
  * (src/kd/losses.py:35-60, 81-106, 127-149, 219-252) on device-resident [batch, n_docs] fp32 score

@@ -221,6 +221,12 @@ SIGNATURES = {
     "sskd_latec_rerank": (
         _i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]
     ),
+    "sskd_plaid_centroid_scores": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _vp]),
+    "sskd_plaid_candidates_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "sskd_plaid_candidates_plan": (_i, [_i, _i, _i, _i64, _i, _i, _sz, C.POINTER(_sz), _ip, _ip, _ip]),
+    "sskd_plaid_candidates": (
+        _i, [_vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]
+    ),
     "sskd_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sskd_kd_loss": (_i, [_vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sskd_similarity": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

@@ -14,6 +14,8 @@ its beam), again behind the recall gate and for single-index builds only.
 
 ``--late-interaction`` adds the token store of ``late.LateInteractionIndex`` (``--late-max-doc-tokens``) beside any
 single index: the service re-ranks by token-level MaxSim when ``SEMANTIC_KD_FEATURES__ENABLE_LATE_INTERACTION`` is set.
+``--late-compress {2,4} --late-centroid-lists`` also writes the compressed store's centroid lists, from which the service
+takes its candidates when ``SEMANTIC_KD_LATE__FIRST_STAGE=centroids``.
 
 Row-sharded build (BASELINE cfg 3): launch the same command under
 ``python -m torch.distributed.run --nproc-per-node G --master-addr 127.0.0.1 -m semantic_search_kd_amd.build_index_cli ...``
@@ -84,9 +86,14 @@ def main(argv=None) -> int:
     ap.add_argument("--late-compress", type=int, choices=(2, 4), default=None,
                     help="late interaction: hold the token store residual-compressed at this many bits per column (104 B "
                          "or 200 B per token instead of 768 B); the codec is trained on a subset of the documents")
+    ap.add_argument("--late-centroid-lists", action="store_true",
+                    help="late interaction: also write the centroid lists of the compressed store (late_list_lims.npy, "
+                         "late_list_rows.npy), so that the store retrieves by itself (LateInteractionIndex.search_tokens)")
     args = ap.parse_args(argv)
     if args.late_compress and not args.late_interaction:
         ap.error("--late-compress needs --late-interaction")
+    if args.late_centroid_lists and not args.late_compress:
+        ap.error("--late-centroid-lists needs --late-interaction --late-compress {2,4}: the lists index a compressed store")
     for flag, p in (("--model-path", args.model_path), ("--data-path", args.data_path)):
         if not Path(p).exists():
             ap.error(f"{flag}: {p} does not exist")
@@ -177,7 +184,12 @@ def main(argv=None) -> int:
         late = LateInteractionIndex(builder, max_doc_tokens=args.late_max_doc_tokens)
         late.build_from_texts(model, [builder.doc_texts[i] for i in builder.doc_ids], batch_size=args.batch_size,
                               compress=args.late_compress)
+        if args.late_centroid_lists:
+            late.build_centroid_lists()
         late.save(Path(args.output_dir))
+        if args.late_centroid_lists:
+            print(f"Late-interaction centroid lists: {int(late.list_rows.numel())} (centroid, row) pairs over "
+                  f"{late.n_centroids} lists, {late.centroid_list_bytes} bytes")
         if args.late_compress:
             print(f"Late-interaction token store: {late.n_tokens} tokens, {late.nbytes} bytes compressed to "
                   f"{late.nbits} bits over {late.n_centroids} centroids ({store_bytes(late.n_tokens)} bytes as bf16; "

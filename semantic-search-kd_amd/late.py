@@ -16,6 +16,11 @@ The reference's ``configs/service.yaml`` carries ``features.enable_late_interact
   token the id of its nearest centroid, ``nbits`` in {2, 4} bits per column for the residual and one fp32 scale - 104 B
   or 200 B instead of 768 B.  ``sskd_latec_rerank`` decodes inside the MaxSim kernel; the rules are in
   ``include/sskd_amd.h``, "Compressed token store".  Without a codec nothing changes.
+* With centroid lists over a compressed store (``build_centroid_lists``: list ``c`` = the rows that own a token of centroid
+  ``c``) the store is a retriever of its own, as PLAID's first stages are: ``search_tokens`` scores every centroid against
+  every query token, probes the ``nprobe`` best lists per token, orders the rows found by the centroid interaction
+  ``sum_i max_j S[cid_j, t_i]`` and hands the best ``ndocs`` to the compressed MaxSim (``include/sskd_amd.h``, "Candidate
+  generation").  Without lists nothing changes.
 """
 from __future__ import annotations
 
@@ -35,6 +40,8 @@ LATE_TQ_MAX = 128
 LATE_R_MAX = 1024
 TOKEN_BYTES = DIM * 2
 LATE_C_MAX = 65536
+PLAID_NPROBE_MAX = 32
+PLAID_S_BUDGET = 256 << 20     # bytes of centroid scores one chunk of queries may take
 FORMAT_VERSION = 1
 
 
@@ -172,6 +179,57 @@ def load_compressed_store(index_dir: Union[str, Path]):
     return cid, scale, codes.reshape(-1, code_bytes(nbits)), cen, cut, w, lims, meta
 
 
+LIST_FILES = ("late_list_lims.npy", "late_list_rows.npy")
+
+
+def check_centroid_lists(list_lims, list_rows, n_centroids: int, n_rows: int, n_tokens: int):
+    """Centroid lists as ``(int64 [C + 1], int32 [n_list])``; raises ``ValueError`` unless the bounds start at 0, ascend
+    and end at the number of listed rows, there are at most ``n_tokens`` of those, every row lies in ``[0, n_rows)`` and
+    the rows of a list ascend strictly."""
+    lims = np.ascontiguousarray(np.asarray(list_lims)).reshape(-1)
+    rows = np.ascontiguousarray(np.asarray(list_rows)).reshape(-1)
+    if lims.dtype != np.int64 or rows.dtype != np.int32:
+        raise ValueError("centroid lists: expected int64 bounds and int32 rows")
+    if lims.size != n_centroids + 1 or lims[0] != 0 or (np.diff(lims) < 0).any() or lims[-1] != rows.size:
+        raise ValueError(f"centroid lists: the bounds must ascend from 0 to {rows.size} over {n_centroids} lists")
+    if rows.size > n_tokens:
+        raise ValueError(f"centroid lists: {rows.size} listed rows for a store of {n_tokens} tokens")
+    if rows.size and (rows.min() < 0 or rows.max() >= n_rows):
+        raise ValueError(f"centroid lists: rows outside [0, {n_rows})")
+    if rows.size > 1:
+        inner = np.ones(rows.size, dtype=bool)
+        inner[lims[1:-1][lims[1:-1] < rows.size]] = False      # the first row of a list has no predecessor in it
+        if (np.diff(rows) <= 0)[inner[1:]].any():
+            raise ValueError("centroid lists: the rows of a list must ascend")
+    return lims, rows
+
+
+def save_centroid_lists(out_dir: Union[str, Path], list_lims, list_rows) -> None:
+    """``late_list_lims.npy`` and ``late_list_rows.npy`` beside a compressed store, and ``"centroid_lists": true`` in its
+    ``late.json``."""
+    out = Path(out_dir)
+    meta = read_versioned_json(out / "late.json", FORMAT_VERSION)
+    np.save(out / "late_list_lims.npy", np.ascontiguousarray(list_lims, dtype=np.int64))
+    np.save(out / "late_list_rows.npy", np.ascontiguousarray(list_rows, dtype=np.int32))
+    with open(out / "late.json", "w") as f:
+        json.dump({**meta, "centroid_lists": True}, f)
+
+
+def has_centroid_lists(index_dir: Union[str, Path]) -> bool:
+    """True when ``late.json`` of ``index_dir`` announces centroid lists."""
+    d = Path(index_dir)
+    return is_late_dir(d) and bool(read_versioned_json(d / "late.json", FORMAT_VERSION).get("centroid_lists", False))
+
+
+def load_centroid_lists(index_dir: Union[str, Path]):
+    """``(list_lims, list_rows)`` as ``save_centroid_lists`` wrote them, checked against the store's ``late.json``."""
+    d = Path(index_dir)
+    meta = read_versioned_json(d / "late.json", FORMAT_VERSION)
+    return check_centroid_lists(np.load(d / "late_list_lims.npy", allow_pickle=False),
+                                np.load(d / "late_list_rows.npy", allow_pickle=False), int(meta["n_centroids"]),
+                                int(meta["ntotal"]), int(meta["n_tokens"]))
+
+
 def stored_nbits(index_dir: Union[str, Path]) -> int:
     """``nbits`` of the store in ``index_dir``: 0 for the bf16 store (and for a directory written before compression)."""
     return int(read_versioned_json(Path(index_dir) / "late.json", FORMAT_VERSION).get("nbits", 0))
@@ -233,6 +291,7 @@ class LateQueries:
     def __init__(self, tokens: torch.Tensor, lims_host: np.ndarray, lims_dev: torch.Tensor):
         self.tokens, self.lims_host, self.lims_dev = tokens, lims_host, lims_dev
         self.nq = int(lims_host.size - 1)
+        self._chunks = {}      # search_tokens_device: token budget -> the batch cut into LateQueries that fit it
 
 
 class LateInteractionIndex:
@@ -260,6 +319,11 @@ class LateInteractionIndex:
         self.scale: Optional[torch.Tensor] = None        # device fp32 [n_tokens]
         self.codes: Optional[torch.Tensor] = None        # device uint8 [n_tokens, 48 nbits]
         self._quantizer: Optional[FAISSIndexBuilder] = None   # the centroids as fp32 rows, for the exact top-1 assignment
+        # centroid lists over the compressed store (None: there are none): list c = the rows owning a token of centroid c
+        self.list_lims: Optional[torch.Tensor] = None    # device int64 [C + 1]
+        self.list_rows: Optional[torch.Tensor] = None    # device int32 [n_list]
+        self._plaid_S: Optional[torch.Tensor] = None
+        self._plaid_ws: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ properties
     @property
@@ -303,15 +367,23 @@ class LateInteractionIndex:
         with torch.cuda.device(self.device):
             self.tokens = tokens
             self.cid = self.scale = self.codes = None
+            self.list_lims = self.list_rows = None
             self.lims = lims
             self._lims_dev = torch.from_numpy(lims).to(self.device)
 
-    def _install_compressed(self, cid: torch.Tensor, scale: torch.Tensor, codes: torch.Tensor, lims: np.ndarray) -> None:
+    def _install_compressed(self, cid: torch.Tensor, scale: torch.Tensor, codes: torch.Tensor, lims: np.ndarray,
+                            rebuild_lists: bool = False) -> None:
+        """``rebuild_lists``: the centroid lists, when there were any, are built again over the new store (``add_tokens``,
+        ``compact``); otherwise they are dropped with the store they described."""
+        had = self.list_lims is not None
         with torch.cuda.device(self.device):
             self.tokens = None
             self.cid, self.scale, self.codes = cid.contiguous(), scale.contiguous(), codes.contiguous()
             self.lims = lims
             self._lims_dev = torch.from_numpy(lims).to(self.device)
+            self.list_lims = self.list_rows = None
+        if had and rebuild_lists:
+            self.build_centroid_lists()
 
     def set_tokens(self, tokens, lims) -> None:
         """Pre-computed token vectors for rows ``0 .. flat.ntotal - 1``: ``tokens`` ``[T, 384]`` (NumPy fp32, NumPy uint16
@@ -334,7 +406,7 @@ class LateInteractionIndex:
                 cid, scale, codes = self._compress_tokens(t)
                 if self.cid is not None:
                     cid, scale, codes = (torch.cat([a, b]) for a, b in ((self.cid, cid), (self.scale, scale), (self.codes, codes)))
-            self._install_compressed(cid, scale, codes, lims)
+            self._install_compressed(cid, scale, codes, lims, rebuild_lists=True)
             return
         with torch.cuda.device(self.device):
             both = t if self.tokens is None else torch.cat([self.tokens, t])
@@ -382,6 +454,7 @@ class LateInteractionIndex:
         """Installs a codec already validated: ``centroids`` device bf16 ``[C, 384]``."""
         if self.cid is not None:
             raise RuntimeError("the compressed store was written with the codec installed: it cannot be replaced")
+        self.list_lims = self.list_rows = None
         with torch.cuda.device(self.device):
             self.centroids = centroids.contiguous()
             self.cutoffs = torch.from_numpy(np.ascontiguousarray(cutoffs, dtype=np.float32)).to(self.device)
@@ -540,7 +613,14 @@ class LateInteractionIndex:
         """First stage, then MaxSim: ``first_stage`` (default: the flat index; an ``IVFIndex``, ``IVFPQIndex``,
         ``GraphIndex`` or ``HybridIndex`` over the same rows) is asked for ``candidates`` rows per query through its
         ``search_device`` (``first_stage_kw`` pass through: ``allow``, ``nprobe``, ``ef`` ...; a ``HybridIndex`` also
-        needs ``query_texts``), and they are re-ranked to ``k``.  Device tensors ``(D, I)``."""
+        needs ``query_texts``), and they are re-ranked to ``k``.  Device tensors ``(D, I)``.
+
+        ``first_stage="centroids"`` takes the candidates from the store's own centroid lists instead
+        (``search_tokens_device`` with ``ndocs=candidates``; ``nprobe`` and ``allow`` pass through, ``q_emb`` is unused)."""
+        if isinstance(first_stage, str):
+            if first_stage != "centroids":
+                raise ValueError(f"first_stage={first_stage!r}: the only first stage with a name is 'centroids'")
+            return self.search_tokens_device(q_tokens, q_lims, k, ndocs=candidates, **first_stage_kw)
         first = self.flat if first_stage is None else first_stage
         candidates = int(candidates)
         if candidates < k or candidates > LATE_R_MAX:
@@ -556,10 +636,166 @@ class LateInteractionIndex:
                ) -> Tuple[np.ndarray, np.ndarray]:
         """``search_device`` for host (or device) pooled query embeddings ``[nq, 384]``, returning NumPy ``(D, I)``."""
         with torch.cuda.device(self.device):
-            qd = q_emb if isinstance(q_emb, torch.Tensor) else _host_queries_to_device(q_emb, self.device)
+            by_lists = isinstance(first_stage, str)      # "centroids": the pooled embeddings are not used
+            qd = q_emb if by_lists or isinstance(q_emb, torch.Tensor) else _host_queries_to_device(q_emb, self.device)
             D, I = self.search_device(qd, q_tokens, q_lims, k, candidates=candidates, first_stage=first_stage,
                                       **first_stage_kw)
             return D.cpu().numpy(), I.cpu().numpy()
+
+    # ------------------------------------------------------------------ candidate generation from the store itself
+    @property
+    def has_centroid_lists(self) -> bool:
+        return self.list_lims is not None
+
+    def build_centroid_lists(self) -> None:
+        """Builds the centroid lists of the compressed store on the device: list ``c`` holds, ascending and once each,
+        the rows that own a token whose centroid id (clamped into ``[0, C)``) is ``c``.  Deterministic: the same store
+        gives the same bits.  ``add_tokens`` and ``compact`` rebuild them, ``set_compressed`` and ``set_codec`` drop them."""
+        if not self.compressed:
+            raise RuntimeError("build_centroid_lists(): centroid lists index a compressed store - call compress() first "
+                               "(or build / load a compressed store)")
+        C, n = self.n_centroids, self.ntotal
+        with torch.cuda.device(self.device):
+            counts = torch.from_numpy(np.diff(self.lims)).to(self.device)
+            row_of = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=self.device), counts)
+            pairs = torch.unique(self.cid.to(torch.int64).clamp(0, C - 1) * max(n, 1) + row_of)      # sorted, distinct
+            per_list = torch.bincount(pairs // max(n, 1), minlength=C)
+            self.list_lims = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(per_list, 0)]).contiguous()
+            self.list_rows = (pairs % max(n, 1)).to(torch.int32).contiguous()
+
+    def centroid_lists_numpy(self):
+        """Host copies ``(list_lims int64 [C + 1], list_rows int32)`` of the centroid lists."""
+        if not self.has_centroid_lists:
+            raise RuntimeError("there are no centroid lists: call build_centroid_lists()")
+        return self.list_lims.cpu().numpy(), self.list_rows.cpu().numpy()
+
+    @property
+    def centroid_list_bytes(self) -> int:
+        return 0 if not self.has_centroid_lists else 8 * int(self.list_lims.numel()) + 4 * int(self.list_rows.numel())
+
+    def _token_chunks(self, queries: LateQueries):
+        """``queries`` cut into runs of whole queries whose centroid scores fit ``PLAID_S_BUDGET`` (at least one query
+        each).  The cut is made once per ``LateQueries`` and kept on it: the bounds of every run are uploaded here, so a
+        later call with the same object enqueues no copy and can be captured into a graph."""
+        budget = max(LATE_TQ_MAX, PLAID_S_BUDGET // (4 * max(self.n_centroids, 1)))
+        if budget not in queries._chunks:
+            lims = queries.lims_host
+            if int(lims[-1] - lims[0]) <= budget and lims[0] == 0:
+                queries._chunks[budget] = [(0, queries)]
+            else:
+                parts, a = [], 0
+                while a < queries.nq:
+                    b = max(a + 1, int(np.searchsorted(lims, lims[a] + budget, side="right")) - 1)
+                    sub = np.ascontiguousarray(lims[a: b + 1] - lims[a])
+                    parts.append((a, LateQueries(queries.tokens[int(lims[a]): int(lims[b])], sub,
+                                                 torch.from_numpy(sub).to(self.device))))
+                    a = b
+                queries._chunks[budget] = parts
+        return queries._chunks[budget]
+
+    def prepare_token_queries(self, q_tokens, q_lims) -> LateQueries:
+        """``prepare_queries`` plus the cut ``search_tokens_device`` makes of the batch: what that call takes inside a
+        graph capture."""
+        queries = self.prepare_queries(q_tokens, q_lims)
+        self._token_chunks(queries)
+        return queries
+
+    def candidates_device(self, q_tokens, q_lims, nprobe: int = 2, ndocs: int = 256, allow=None, return_scores: bool = False):
+        """The first stages alone, for a batch whose centroid scores fit one chunk: ``(cand_I int64 [nq, ndocs], cand_A
+        fp32 [nq, ndocs], n_cand int32 [nq])`` on the device (and ``S`` fp32 ``[C, ld]``, a view of a buffer the next call
+        overwrites, with ``return_scores``)."""
+        lib = _native.load()
+        self._require_store()
+        if not self.has_centroid_lists:
+            raise RuntimeError("there are no centroid lists: call build_centroid_lists() (a compressed store only)")
+        queries = self.prepare_queries(q_tokens, q_lims)
+        nq, R, nprobe = queries.nq, int(ndocs), int(nprobe)
+        C = self.n_centroids
+        if not 1 <= nprobe <= min(C, PLAID_NPROBE_MAX):
+            raise ValueError(f"nprobe={nprobe} outside [1, min(C={C}, {PLAID_NPROBE_MAX})]")
+        if not 1 <= R <= LATE_R_MAX:
+            raise ValueError(f"ndocs={R} outside [1, {LATE_R_MAX}]")
+        T = int(queries.lims_host[-1])
+        ld = max(32, -(-T // 32) * 32)
+        mask = self.flat.search_mask(allow)
+        stream = _native.current_stream_ptr(self.device)
+        self._plaid_S = _native.grown(self._plaid_S, 4 * C * ld, self.device)
+        need = int(lib.sskd_plaid_candidates_workspace_bytes(nq, self.ntotal, nprobe))
+        self._plaid_ws = _native.grown(self._plaid_ws, need, self.device)
+        S, ws = self._plaid_S, self._plaid_ws
+        cand_I = torch.empty((nq, R), dtype=torch.int64, device=self.device)
+        cand_A = torch.empty((nq, R), dtype=torch.float32, device=self.device)
+        n_cand = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        _native.check(lib.sskd_plaid_centroid_scores(queries.tokens.data_ptr(), T, self.centroids.data_ptr(), C, S.data_ptr(),
+                                                     ld, stream))
+        _native.check(lib.sskd_plaid_candidates(
+            S.data_ptr(), ld, queries.lims_host.ctypes.data, queries.lims_dev.data_ptr(), nq, C, self.cid.data_ptr(),
+            self._lims_dev.data_ptr(), self.ntotal, self.n_tokens, self.list_lims.data_ptr(), self.list_rows.data_ptr(),
+            int(self.list_rows.numel()), None if mask is None else mask.data_ptr(), nprobe, R, self.flat.id_offset,
+            cand_I.data_ptr(), cand_A.data_ptr(), n_cand.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        if return_scores:
+            return cand_I, cand_A, n_cand, S[: 4 * C * ld].view(torch.float32).view(C, ld)
+        return cand_I, cand_A, n_cand
+
+    def search_tokens_device(self, q_tokens, q_lims, k: int, nprobe: int = 2, ndocs: int = 256, allow=None,
+                             return_candidates: bool = False):
+        """Retrieval from the token store alone: the centroid scores of every query token, ``nprobe`` lists per token,
+        the ``ndocs`` best rows by centroid interaction (``candidates_device``), then ``rerank_device`` to ``k``.  Device
+        tensors ``(D, I)``; ``return_candidates`` adds ``(cand_I, cand_A, n_cand)``.  ``allow`` takes what ``flat.search``
+        takes; removed rows are hidden through the flat index's mask.  Queries run in chunks whose centroid scores stay
+        under ``PLAID_S_BUDGET``.  No host synchronisation once the queries are prepared (``prepare_token_queries``)."""
+        queries = self.prepare_queries(q_tokens, q_lims)
+        k, ndocs = int(k), int(ndocs)
+        if not 1 <= k <= ndocs:
+            raise ValueError(f"k={k} outside [1, ndocs={ndocs}]")
+        if allow is not None:
+            allow = self.flat.row_filter(allow)         # prepared once, not per chunk
+        outs = []
+        for _, part in self._token_chunks(queries):
+            cand = self.candidates_device(part, None, nprobe=nprobe, ndocs=ndocs, allow=allow)
+            outs.append(self.rerank_device(part, None, cand[0], k) + (cand if return_candidates else ()))
+        return outs[0] if len(outs) == 1 else tuple(torch.cat([o[i] for o in outs]) for i in range(len(outs[0])))
+
+    def search_tokens(self, q_tokens, q_lims, k: int = 10, nprobe: int = 2, ndocs: int = 256, allow=None,
+                      return_candidates: bool = False):
+        """``search_tokens_device`` returning NumPy."""
+        with torch.cuda.device(self.device):
+            out = self.search_tokens_device(q_tokens, q_lims, k, nprobe=nprobe, ndocs=ndocs, allow=allow,
+                                            return_candidates=return_candidates)
+            return tuple(o.cpu().numpy() for o in out)
+
+    def exhaustive_tokens(self, q_tokens, q_lims, k: int, rows_per_call: int = LATE_R_MAX) -> Tuple[np.ndarray, np.ndarray]:
+        """The exact MaxSim top-``k`` over ALL rows, for checking: every row goes through ``rerank_device(return_raw=True)``
+        in runs of at most 1 024 candidates, and the raw scores are ordered on the host (score descending, lower id)."""
+        queries = self.prepare_queries(q_tokens, q_lims)
+        n, nq = self.ntotal, queries.nq
+        step = max(1, min(int(rows_per_call), LATE_R_MAX))
+        raw = np.full((nq, n), -np.inf, dtype=np.float32)
+        with torch.cuda.device(self.device):
+            for lo in range(0, n, step):
+                hi = min(n, lo + step)
+                ids = torch.arange(lo, hi, dtype=torch.int64, device=self.device) + self.flat.id_offset
+                raw[:, lo:hi] = self.rerank_device(queries, None, ids.repeat(nq, 1), 1, return_raw=True)[2].cpu().numpy()
+        order = np.argsort(-raw, axis=1, kind="stable")[:, :k]
+        D = np.take_along_axis(raw, order, axis=1)
+        I = np.where(D > -np.inf, order + self.flat.id_offset, -1)
+        if D.shape[1] < k:
+            D = np.concatenate([D, np.full((nq, k - D.shape[1]), -np.inf, np.float32)], axis=1)
+            I = np.concatenate([I, np.full((nq, k - I.shape[1]), -1, np.int64)], axis=1)
+        return D, I.astype(np.int64)
+
+    def validate_tokens(self, q_tokens, q_lims, k: int = 10, nprobe: int = 2, ndocs: int = 256) -> float:
+        """Recall@``k`` of ``search_tokens`` against the exhaustive MaxSim over all rows (``exhaustive_tokens``): the
+        share of the exhaustive top-``k`` that the search returns, averaged over the queries."""
+        queries = self.prepare_queries(q_tokens, q_lims)
+        _, got = self.search_tokens(queries, None, k, nprobe=nprobe, ndocs=ndocs)
+        _, want = self.exhaustive_tokens(queries, None, k)
+        hits = total = 0
+        for g, w in zip(got, want):
+            w = w[w >= 0]
+            hits += int(np.isin(w, g).sum())
+            total += int(w.size)
+        return hits / max(total, 1)
 
     # ------------------------------------------------------------------ maintenance
     def compact(self, kept) -> None:
@@ -574,7 +810,7 @@ class LateInteractionIndex:
         with torch.cuda.device(self.device):
             pick = torch.from_numpy(take).to(self.device)
             if self.compressed:
-                self._install_compressed(self.cid[pick], self.scale[pick], self.codes[pick], lims)
+                self._install_compressed(self.cid[pick], self.scale[pick], self.codes[pick], lims, rebuild_lists=True)
                 return
             tokens = self.tokens[pick].contiguous()
         self._install(tokens, lims)
@@ -586,6 +822,8 @@ class LateInteractionIndex:
         if self.compressed:
             # the compressed store: late_cid.npy, late_scale.npy, late_codes.u8 and the codec's three files instead
             save_compressed_store(output_dir, *self.compressed_numpy(), *self.codec_numpy(), self.lims, meta)
+            if self.has_centroid_lists:
+                save_centroid_lists(output_dir, *self.centroid_lists_numpy())
             return
         if self.tokens is None:
             raise RuntimeError("save(): the token store is empty")
@@ -605,6 +843,10 @@ class LateInteractionIndex:
             self._set_codec_device(_tokens_to_device(cen, self.device), cut, w)
             with torch.cuda.device(self.device):
                 self._install_compressed(*(torch.from_numpy(a).to(self.device) for a in (cid, scale, codes)), lims)
+                if meta.get("centroid_lists", False):
+                    list_lims, list_rows = load_centroid_lists(index_dir)
+                    self.list_lims = torch.from_numpy(list_lims).to(self.device)
+                    self.list_rows = torch.from_numpy(list_rows).to(self.device)
             return
         bits, lims, meta = load_store(index_dir)
         if lims.size - 1 != self.flat.ntotal:
@@ -615,6 +857,7 @@ class LateInteractionIndex:
 
     def cleanup(self) -> None:
         self.tokens = self._lims_dev = self._workspace = None
+        self.list_lims = self.list_rows = self._plaid_S = self._plaid_ws = None
         self.cid = self.scale = self.codes = self.centroids = self.cutoffs = self.weights = None
         if self._quantizer is not None:
             self._quantizer.cleanup()

@@ -27,7 +27,7 @@ from fastapi.responses import JSONResponse
 logger = logging.getLogger("semantic_search_kd_amd.serve")
 
 from ..index import FAISSIndexBuilder  # noqa: E402,F401
-from ..late import LATE_R_MAX
+from ..late import LATE_R_MAX, PLAID_NPROBE_MAX
 from ..sharded_index import open_index
 from ..student import StudentModel
 from .schemas import (
@@ -77,6 +77,11 @@ class ServeSettings:
     # token-level MaxSim over the token store saved beside the index (late.LateInteractionIndex)
     late_interaction_enabled: bool = False
     late_candidates: int = 100
+    # where the candidates of the re-rank come from: "dense" (the first stage above) or "centroids" - the compressed token
+    # store's own centroid lists (late.LateInteractionIndex.search_tokens, late_nprobe lists per query token), when the
+    # directory holds them
+    late_first_stage: str = "dense"
+    late_nprobe: int = 2
 
     @staticmethod
     def from_env() -> "ServeSettings":
@@ -95,6 +100,8 @@ class ServeSettings:
             late_interaction_enabled=_env_bool(e.get("SEMANTIC_KD_FEATURES__ENABLE_LATE_INTERACTION"),
                                                ServeSettings.late_interaction_enabled),
             late_candidates=int(e.get("SEMANTIC_KD_LATE__CANDIDATES") or ServeSettings.late_candidates),
+            late_first_stage=(e.get("SEMANTIC_KD_LATE__FIRST_STAGE") or ServeSettings.late_first_stage).strip().lower(),
+            late_nprobe=int(e.get("SEMANTIC_KD_LATE__NPROBE") or ServeSettings.late_nprobe),
         )
 
     def is_production(self) -> bool:
@@ -203,6 +210,16 @@ def _load_late(builder, index_dir: Path, settings: Optional["ServeSettings"]):
         late.load(index_dir)     # whichever store the directory holds: bf16 rows or the compressed arrays and their codec
         logger.info("Late-interaction token store: %d tokens, %d bytes%s", late.n_tokens, late.nbytes,
                     f" ({late.nbits}-bit residuals over {late.n_centroids} centroids)" if late.compressed else "")
+        if settings.late_first_stage == "centroids":
+            if late.has_centroid_lists:
+                logger.info("Late interaction takes its candidates from the centroid lists (%d bytes, nprobe %d)",
+                            late.centroid_list_bytes, settings.late_nprobe)
+            else:
+                logger.warning("SEMANTIC_KD_LATE__FIRST_STAGE is centroids but %s holds no centroid lists: the candidates "
+                               "come from the dense first stage as before", index_dir)
+        elif settings.late_first_stage != "dense":
+            logger.warning("SEMANTIC_KD_LATE__FIRST_STAGE=%s is neither dense nor centroids: serving with dense",
+                           settings.late_first_stage)
         return late
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the late-interaction token store (serving without it): %s", exc)
@@ -336,12 +353,18 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
             if late is not None and late.flat is app_state.index_builder and k_retrieve <= LATE_R_MAX:
                 # the first stage proposes, token-level MaxSim orders: score = MaxSim / Tq (1.0 = every query token
                 # has an identical document token)
-                wanted = max(1, int((app_state.settings or settings).late_candidates))
-                _, candidates = first_stage(min(max(wanted, k_retrieve), LATE_R_MAX))
+                live = app_state.settings or settings
+                wanted = min(max(1, int(live.late_candidates), k_retrieve), LATE_R_MAX)
                 q_tokens, q_lims = app_state.student.encode_tokens([request.query], is_query=True,
                                                                    max_tokens=late.max_query_tokens)
-                k_late = min(k_retrieve, candidates.shape[1])
-                distances, indices = late.rerank(q_tokens, q_lims, np.ascontiguousarray(candidates, dtype=np.int64), k_late)
+                if live.late_first_stage == "centroids" and late.has_centroid_lists:
+                    # the token store retrieves by itself: centroid lists, centroid interaction, then MaxSim
+                    nprobe = min(max(1, int(live.late_nprobe)), late.n_centroids, PLAID_NPROBE_MAX)
+                    distances, indices = late.search_tokens(q_tokens, q_lims, k=k_retrieve, nprobe=nprobe, ndocs=wanted)
+                else:
+                    _, candidates = first_stage(wanted)
+                    k_late = min(k_retrieve, candidates.shape[1])
+                    distances, indices = late.rerank(q_tokens, q_lims, np.ascontiguousarray(candidates, dtype=np.int64), k_late)
                 distances = distances / np.float32(q_lims[1] - q_lims[0])
             else:
                 distances, indices = first_stage(k_retrieve)
