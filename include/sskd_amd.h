@@ -739,6 +739,47 @@ int sskd_late_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_
                      int64_t id_offset, float* d_out_scores, int64_t* d_out_ids, float* d_out_raw, void* d_workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Late interaction: training through MaxSim (the sskd_latet_ entries).  score(q, c) = sum_i max_t <q_i, d_cand[q,c],t> differentiated with respect
+ * to both token lists; cand[q, c] names a document of the BATCH (0 .. nd - 1; -1, an id outside the batch and a document
+ * without tokens are absent pairs).  Both sides are CSR bf16 [T, 384] with lims as sskd_late_pack_tokens writes them; the
+ * query side's lims are given on the host (validated: they run from 0 to n_q_tokens, every Tq in [1, 128]) and on the
+ * device.  tq_stride = the batch's largest Tq rounded up to 32 (anything else: SSKD_ERR_INVALID).  Limits per call:
+ * R <= 1024, Tq <= 128, dim 384.  Every entry validates the whole call and then enqueues (stream-ordered, no host sync,
+ * graph-capturable, allocates nothing); nq = 0 or R = 0 is SSKD_OK with nothing launched.
+ *
+ * sskd_latet_maxsim_fwd: sskd_late_rerank's score kernel - same geometry, same arithmetic; d_scores fp32 [nq, R] is BIT FOR
+ * BIT the d_out_raw of sskd_late_rerank over a store holding the same rows (-inf for an absent pair) - plus
+ * d_arg int32 [nq, R, tq_stride]: arg[q, c, i] = the document-relative index t of the token that holds the maximum for
+ * query token i, the SMALLEST such t when several dot products are equal; -1 for i >= Tq and for an absent pair.
+ *
+ * sskd_latet_maxsim_bwd_q: d_dq fp32 [n_q_tokens, 384], dQ[q, i, :] = sum_c g[q, c] * d[cand[q, c], arg[q, c, i], :].
+ * sskd_latet_maxsim_bwd_d: d_dd fp32 [n_d_tokens, 384], dD[j, t, :] = sum over the contributions e = (q R + c) tq_stride + i
+ *   with cand[q, c] = j and arg[q, c, i] = t of g[q, c] * q[q, i, :].  The caller groups them by destination: d_order
+ *   int64 [E = nq R tq_stride] = the contributions stably sorted by key (key = d_lims[j] + t, n_d_tokens for a
+ *   contribution with arg < 0), d_seg int64 [n_d_tokens + 1] = the first position of every key in the sorted keys.
+ * Arithmetic of both, per column: acc = +0.0f; for the contributions ascending (c for dQ, e for dD) acc = acc + g * x with
+ * x the bf16 value widened to fp32, multiply and add rounded SEPARATELY (never an fma).  No atomics: one wave per output
+ * row, so the bits do not depend on the launch; a row without contributions is exact zeros.  The g of an absent pair (and
+ * of arg < 0) is never read into the arithmetic.  Every output row is written.
+ *
+ * sskd_latet_pack_tokens_bwd: backward of sskd_late_pack_tokens.  d_hidden / d_lengths / d_offsets / B / S / n_tokens as
+ * the pack took them, H must be 384 (else SSKD_ERR_UNSUPPORTED), d_dtok fp32 [n_tokens, 384]; writes d_dhidden bf16
+ * [B, S, 384], zeros at positions >= the length.  Per token, fp32: ss and n = max(sqrt(ss), 1e-12) exactly the pack's;
+ * y_c = x_c / n (the bf16 rounding of the stored token is straight-through); dot = sum_c g_c y_c in the pack's order
+ * (lane chain over columns 8 l .. 8 l + 7 from +0.0 with multiply then add, p_48 .. p_63 = +0.0, xor butterfly 32 .. 1);
+ * dh_c = (g_c - y_c * dot) / n with separate multiply, subtract and IEEE division, rounded to bf16 to nearest even. */
+int sskd_latet_maxsim_fwd(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq, int64_t n_q_tokens,
+                         const void* d_d_tokens, const int64_t* d_d_lims, int64_t nd, int64_t n_d_tokens,
+                         const int64_t* d_candidates, int R, float* d_scores, int32_t* d_arg, int tq_stride, void* stream);
+int sskd_latet_maxsim_bwd_q(const void* d_d_tokens, const int64_t* d_d_lims, int64_t nd, int64_t n_d_tokens, const int64_t* q_lims,
+                           const int64_t* d_q_lims, int nq, int64_t n_q_tokens, const int64_t* d_candidates, int R,
+                           const int32_t* d_arg, int tq_stride, const float* d_g, float* d_dq, void* stream);
+int sskd_latet_maxsim_bwd_d(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq, int64_t n_q_tokens, int R,
+                           int tq_stride, const int64_t* d_order, const int64_t* d_seg, int64_t n_d_tokens, const float* d_g,
+                           float* d_dd, void* stream);
+int sskd_latet_pack_tokens_bwd(const void* d_hidden, const int32_t* d_lengths, const int64_t* d_offsets, int B, int S, int H,
+                              int64_t n_tokens, const float* d_dtok, void* d_dhidden, void* stream);
+
 /* Compressed token store (residual compression as in ColBERTv2 / PLAID).  dim = 384, nbits in {2, 4}, L = 2^nbits.
  * Codec: d_centroids DEVICE bf16 [C, 384] (1 <= C <= 65 536), d_cutoffs DEVICE fp32 [L - 1] ascending, d_weights DEVICE
  * fp32 [L]; all finite.  Store: d_cid int32 [n_tokens], d_scale fp32 [n_tokens], d_codes uint8 [n_tokens, 48 nbits];
@@ -1058,6 +1099,14 @@ int sskd_generic_forward(const sskd_generic_config* cfg, const sskd_generic_weig
 int sskd_generic_backward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
                           const int32_t* d_ids, const int32_t* d_mask, int B, int S, int normalize, const float* d_dout,
                           void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of the forward with pool == 0: d_dhidden DEVICE bf16 [B, S, H] (16-byte aligned) = d loss / d final hidden
+ * states, read in place and left unchanged.  Everything else - the saved activations, the parameter gradients that are
+ * ACCUMULATED into `grads`, the whole and two-halves runs, every H the generic encoder serves - is sskd_generic_backward's,
+ * which is this call behind the backward of the pool. */
+int sskd_generic_backward_hidden(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
+                                 const int32_t* d_ids, const int32_t* d_mask, int B, int S, const void* d_dhidden,
+                                 void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Teacher cross-encoder score (replaces CrossEncoder.predict behind TeacherModel.score; reference:
  * src/mining/miners.py:135-137, src/serve/app.py:325-326; model = XLM-R-large shaped

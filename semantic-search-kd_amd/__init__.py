@@ -19,6 +19,7 @@ from .graph import GraphIndex  # noqa: F401
 from .ivf import IVFIndex  # noqa: F401
 from .pq import IVFPQIndex  # noqa: F401
 from .late import LateInteractionIndex, is_late_dir  # noqa: F401
+from .late_training import TokenLayout, TokenStates, maxsim_scores  # noqa: F401
 from .evaluation import (  # noqa: F401
     KDEvaluator,
     compute_retrieval_metrics,
@@ -48,6 +49,9 @@ __all__ = [
     "IVFPQIndex",
     "LateInteractionIndex",
     "is_late_dir",
+    "TokenLayout",
+    "TokenStates",
+    "maxsim_scores",
     "KDEvaluator",
     "compute_retrieval_metrics",
     "evaluate_lists",

@@ -215,6 +215,10 @@ SIGNATURES = {
     "sskd_late_rerank": (
         _i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]
     ),
+    "sskd_latet_maxsim_fwd": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _i, _vp]),
+    "sskd_latet_maxsim_bwd_q": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "sskd_latet_maxsim_bwd_d": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "sskd_latet_pack_tokens_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "sskd_latec_compress": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _vp]),
     "sskd_latec_rerank_plan": (_i, [_i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),
     "sskd_latec_rerank_workspace_bytes": (_sz, [_i, _i]),
@@ -249,6 +253,10 @@ SIGNATURES = {
     "sskd_generic_backward": (
         _i, [C.POINTER(GenericConfig), C.POINTER(GenericWeights), C.POINTER(GenericGrads), _vp, _vp, _i, _i, _i, _vp,
              _vp, _sz, _vp]
+    ),
+    "sskd_generic_backward_hidden": (
+        _i, [C.POINTER(GenericConfig), C.POINTER(GenericWeights), C.POINTER(GenericGrads), _vp, _vp, _i, _i, _vp, _vp,
+             _sz, _vp]
     ),
     "sskd_teacher_workspace_bytes": (_sz, [C.POINTER(GenericConfig), _i, _i]),
     "sskd_teacher_score": (

@@ -86,8 +86,9 @@ struct LateParams {
   const int64_t* tok_lims;   // [n_rows + 1]
   const int64_t* cand;       // [nq, R]
   float* raw;                // [nq, R]
+  int32_t* arg;              // [nq, R, tq_stride], late_score_kernel<QB, true> only (the training forward)
   int64_t n_q_tokens, n_tokens, n_rows, id_offset;
-  int R, chunk;
+  int R, chunk, tq_stride;
 };
 
 // the token range of candidate id (global), or an empty range when there is no such candidate
@@ -102,8 +103,11 @@ __device__ inline void cand_range(const P& p, int64_t id, int64_t& beg, int64_t&
 }
 
 // QB = blocks of 32 query tokens the workgroup holds in LDS (the batch's largest query decides; a shorter query uses
-// its own ceil(Tq / 32) blocks of them, so its scores do not depend on QB)
-template <int QB>
+// its own ceil(Tq / 32) blocks of them, so its scores do not depend on QB).
+// ARG (sskd_latet_maxsim_fwd): also report, per query token, the document-relative index of the token that holds the max -
+// the smallest such index.  The values and every operation on them are those of ARG = false (the index is found by
+// comparing against the tile's max AFTER it has been formed), so the score's bits are the re-rank's.
+template <int QB, bool ARG>
 __global__ __launch_bounds__(L_THREADS) void late_score_kernel(const LateParams p) {
   __shared__ bf16x8 qs[QB][L_KSTEPS][64];   // B fragments: [block][k-step][lane]
   const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -130,8 +134,12 @@ __global__ __launch_bounds__(L_THREADS) void late_score_kernel(const LateParams 
     float score = -INFINITY;                 // no candidate, or a row without tokens: absent
     if (td > 0 && Tq > 0) {
       float best[QB];
+      int barg[QB];                            // ARG: document token of best[b], 0 until a tile beats -inf
 #pragma unroll
-      for (int b = 0; b < QB; ++b) best[b] = -INFINITY;
+      for (int b = 0; b < QB; ++b) {
+        best[b] = -INFINITY;
+        barg[b] = 0;
+      }
       for (int64_t t0 = 0; t0 < td; t0 += 32) {
         // the lane's document row of this tile; rows past the end re-read the last real row and are masked below
         const int64_t j = t0 + r32 < td ? t0 + r32 : td - 1;
@@ -152,12 +160,27 @@ __global__ __launch_bounds__(L_THREADS) void late_score_kernel(const LateParams 
               acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], qs[b][s][lane], acc, 0, 0, 0);
             // register r of lane l: document row acc_row(r) + 4 (l >> 5) of the tile, query token 32 b + (l & 31)
             float m = -INFINITY;
+            int rows_left = partial ? left : 32;
+            // ARG: the 16 row masks are formed again for every block (one compare each) instead of being kept in 32
+            // scalar registers across the block loop, which this variant does not have to spare
+            if (ARG) asm volatile("" : "+v"(rows_left));
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const bool real = !partial || acc_row(r) + 4 * h < left;
-              m = fmaxf(m, real ? acc[r] : -INFINITY);
+              const bool real = ARG ? acc_row(r) + 4 * h < rows_left : !partial || acc_row(r) + 4 * h < left;
+              const float v = real ? acc[r] : -INFINITY;
+              if (ARG) acc[r] = v;             // (the masked value is what the index search below compares)
+              m = fmaxf(m, v);
             }
             m = fmaxf(m, __shfl_xor(m, 32));
+            if (ARG) {
+              // first row of the tile that equals the tile's max: the lane's own rows ascend with r, the partner
+              // half's interleave with them; an earlier tile keeps a tie (strict >, which a tile of -inf never passes)
+              int first = 32;
+#pragma unroll
+              for (int r = 0; r < 16; ++r) first = min(first, acc[r] == m ? acc_row(r) + 4 * h : 32);
+              first = min(first, __shfl_xor(first, 32));
+              if (m > best[b] && first < 32) barg[b] = (int)t0 + first;
+            }
             best[b] = fmaxf(best[b], m);
           }
         }
@@ -171,6 +194,14 @@ __global__ __launch_bounds__(L_THREADS) void late_score_kernel(const LateParams 
           for (int i = 0; i < n; ++i) score += __shfl(best[b], i);
         }
       }
+      if (ARG) {   // tq_stride == 32 QB (the host checked): the QB blocks cover a pair's whole row of arg
+        int32_t* out = p.arg + ((int64_t)q * p.R + c) * (32 * QB) + r32;
+#pragma unroll
+        for (int b = 0; b < QB; ++b)
+          if (h == 0) out[32 * b] = 32 * b + r32 < Tq ? barg[b] : -1;
+      }
+    } else if (ARG) {
+      for (int i = lane; i < p.tq_stride; i += 64) p.arg[((int64_t)q * p.R + c) * p.tq_stride + i] = -1;
     }
     if (lane == 0) p.raw[(int64_t)q * p.R + c] = score;
   }
@@ -429,9 +460,19 @@ LatePlan late_plan(int nq, int max_tq, int R) {
   return pl;
 }
 
-template <int QB>
+template <int QB, bool ARG>
 void launch_score(const LateParams& p, int nq, int chunks, hipStream_t st) {
-  hipLaunchKernelGGL(late_score_kernel<QB>, dim3((unsigned)nq, (unsigned)chunks), dim3(L_THREADS), 0, st, p);
+  hipLaunchKernelGGL((late_score_kernel<QB, ARG>), dim3((unsigned)nq, (unsigned)chunks), dim3(L_THREADS), 0, st, p);
+}
+
+template <bool ARG>
+void launch_score_qb(const LateParams& p, int qb, int nq, int chunks, hipStream_t st) {
+  switch (qb) {
+    case 1: launch_score<1, ARG>(p, nq, chunks, st); break;
+    case 2: launch_score<2, ARG>(p, nq, chunks, st); break;
+    case 3: launch_score<3, ARG>(p, nq, chunks, st); break;
+    default: launch_score<4, ARG>(p, nq, chunks, st); break;
+  }
 }
 
 template <int QB, int NBITS>
@@ -534,15 +575,53 @@ int sskd_late_rerank(const void* d_q_tokens, const int64_t* q_lims, const int64_
   const LatePlan pl = late_plan(nq, max_tq, R);
   p.chunk = pl.chunk;
   hipStream_t st = sskd::as_stream(stream);
-  switch (pl.qb) {
-    case 1: launch_score<1>(p, nq, pl.chunks, st); break;
-    case 2: launch_score<2>(p, nq, pl.chunks, st); break;
-    case 3: launch_score<3>(p, nq, pl.chunks, st); break;
-    default: launch_score<4>(p, nq, pl.chunks, st); break;
-  }
+  launch_score_qb<false>(p, pl.qb, nq, pl.chunks, st);
   if (int rc = sskd::check_launch("late_score_kernel")) return rc;
   hipLaunchKernelGGL(late_pick_kernel, dim3((unsigned)nq), dim3(64), 0, st, raw, d_candidates, R, k, d_out_scores, d_out_ids);
   return sskd::check_launch("late_pick_kernel");
+}
+
+int sskd_latet_maxsim_fwd(const void* d_q_tokens, const int64_t* q_lims, const int64_t* d_q_lims, int nq, int64_t n_q_tokens,
+                         const void* d_d_tokens, const int64_t* d_d_lims, int64_t nd, int64_t n_d_tokens,
+                         const int64_t* d_candidates, int R, float* d_scores, int32_t* d_arg, int tq_stride, void* stream) {
+  // every check comes before the first HIP call
+  SSKD_REQUIRE(nq >= 0 && R >= 0, "late_maxsim_fwd: nq=%d, R=%d must be >= 0", nq, R);
+  SSKD_REQUIRE(R <= L_R_MAX, "late_maxsim_fwd: R=%d above %d (score the candidates in chunks)", R, L_R_MAX);
+  SSKD_REQUIRE(nd >= 0 && n_d_tokens >= 0 && n_q_tokens >= 0, "late_maxsim_fwd: nd, n_d_tokens and n_q_tokens must be >= 0");
+  if (nq == 0 || R == 0) return SSKD_OK;
+  SSKD_REQUIRE(q_lims, "late_maxsim_fwd: the host copy of q_lims is required");
+  SSKD_REQUIRE(q_lims[0] == 0 && q_lims[nq] == n_q_tokens, "late_maxsim_fwd: q_lims runs from %lld to %lld, there are %lld query token rows",
+               (long long)q_lims[0], (long long)q_lims[nq], (long long)n_q_tokens);
+  int max_tq = 0;
+  for (int q = 0; q < nq; ++q) {
+    const int64_t tq = q_lims[q + 1] - q_lims[q];
+    SSKD_REQUIRE(tq >= 1 && tq <= L_TQ_MAX, "late_maxsim_fwd: query %d has Tq=%lld outside [1, %d] (q_lims must ascend)", q,
+                 (long long)tq, L_TQ_MAX);
+    if (tq > max_tq) max_tq = (int)tq;
+  }
+  const LatePlan pl = late_plan(nq, max_tq, R);
+  SSKD_REQUIRE(tq_stride == 32 * pl.qb, "late_maxsim_fwd: tq_stride=%d, the largest Tq=%d rounded up to 32 is %d", tq_stride, max_tq,
+               32 * pl.qb);
+  SSKD_REQUIRE(d_q_tokens && d_q_lims && d_candidates && d_scores && d_arg, "late_maxsim_fwd: null pointer");
+  SSKD_REQUIRE(nd == 0 || n_d_tokens == 0 || (d_d_tokens && d_d_lims), "late_maxsim_fwd: null document tokens");
+  SSKD_REQUIRE(aligned16(d_q_tokens) && aligned16(d_d_tokens), "late_maxsim_fwd: token matrices must be 16-byte aligned");
+  LateParams p{};
+  p.q_tokens = static_cast<const bf16x8*>(d_q_tokens);
+  p.q_lims = d_q_lims;
+  p.tokens = static_cast<const bf16x8*>(d_d_tokens);
+  p.tok_lims = d_d_lims;
+  p.cand = d_candidates;
+  p.raw = d_scores;
+  p.arg = d_arg;
+  p.n_q_tokens = n_q_tokens;
+  p.n_tokens = (d_d_tokens && d_d_lims) ? n_d_tokens : 0;
+  p.n_rows = (d_d_tokens && d_d_lims) ? nd : 0;
+  p.id_offset = 0;
+  p.R = R;
+  p.chunk = pl.chunk;
+  p.tq_stride = tq_stride;
+  launch_score_qb<true>(p, pl.qb, nq, pl.chunks, sskd::as_stream(stream));
+  return sskd::check_launch("late_score_kernel<arg>");
 }
 
 int sskd_latec_compress(const void* d_tokens, const int64_t* d_assign, int64_t n, const void* d_centroids, int C,

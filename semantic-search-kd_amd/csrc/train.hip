@@ -477,14 +477,19 @@ struct Rows {
   }
 };
 
+// d_dhidden: null = backward of the pooled forward (the pool backward turns d_dout into the hidden-state gradient in
+// tH2); else the caller's gradient of the final hidden states, bf16 [rows, S, H], read IN PLACE: it is the dx2 of the top
+// layer's first kernel (the embedding LayerNorm's when there are no layers), which is its only reader, and nothing of the
+// backward writes outside the workspace and the gradient buffers.
 int backward_rows(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads, Rows& r,
-                  const int32_t* d_ids, const int32_t* d_mask, int normalize, const float* d_dout, hipStream_t st) {
+                  const int32_t* d_ids, const int32_t* d_mask, int normalize, const float* d_dout, const bf16_t* d_dhidden,
+                  hipStream_t st) {
   const Dims& d = r.d;
   Saved& sv = r.sv;
   // gradient flowing into the current layer's output = dx + dxb (dxb: the residual share, null at the top)
-  const bf16_t* dx = sv.tH2;
+  const bf16_t* dx = d_dhidden ? d_dhidden : sv.tH2;
   const bf16_t* dxb = nullptr;
-  TRY(launch_pool_bwd(d_dout, sv.pooled, d_mask, d.B, d.S, d.H, normalize, sv.tH2, st));
+  if (!d_dhidden) TRY(launch_pool_bwd(d_dout, sv.pooled, d_mask, d.B, d.S, d.H, normalize, sv.tH2, st));
   for (int l = d.L - 1; l >= 0; --l) {
     const bf16_t* x_in = l == 0 ? sv.x0 : sv.layer[l - 1].x2;
     TRY(layer_backward(d, w->layers[l], grads->layers[l], x_in, d_mask, sv.layer[l], sv, dx, dxb, st));
@@ -529,13 +534,15 @@ int sskd_generic_forward(const sskd_generic_config* cfg, const sskd_generic_weig
   });
 }
 
-int sskd_generic_backward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
-                          const int32_t* d_ids, const int32_t* d_mask, int B, int S, int normalize, const float* d_dout,
-                          void* d_workspace, size_t workspace_bytes, void* stream) {
+// the two backward entries: exactly one of d_dout (pooled forward) and d_dhidden (hidden states) is given
+static int generic_backward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
+                            const int32_t* d_ids, const int32_t* d_mask, int B, int S, int normalize, bool hidden,
+                            const float* d_dout, const void* d_dhidden, void* d_workspace, size_t workspace_bytes, void* stream) {
   Dims d{};
   int rc = validate("generic encoder", cfg, w, B, S, 1, d_workspace, workspace_bytes, &d);
   if (rc != SSKD_OK || B == 0) return rc;
-  SSKD_REQUIRE(grads && d_ids && d_mask && d_dout, "generic_backward: null pointer");
+  SSKD_REQUIRE(grads && d_ids && d_mask && (hidden ? d_dhidden != nullptr : d_dout != nullptr), "generic_backward: null pointer");
+  SSKD_REQUIRE(reinterpret_cast<uintptr_t>(d_dhidden) % 16 == 0, "generic_backward_hidden: d_dhidden must be 16-byte aligned");
   SSKD_REQUIRE(grads->word_emb && grads->pos_emb && grads->type_emb && grads->emb_ln_g && grads->emb_ln_b &&
                    (cfg->layers == 0 || grads->layers),
                "generic_backward: null gradient pointer");
@@ -543,12 +550,26 @@ int sskd_generic_backward(const sskd_generic_config* cfg, const sskd_generic_wei
     const sskd_generic_layer_weights& lw = w->layers[l];
     SSKD_REQUIRE(lw.wqkv_t && lw.wo_t && lw.w1_t && lw.w2_t, "generic_backward: layer %d lacks transposed weights", l);
   }
+  const bf16_t* dhidden = static_cast<const bf16_t*>(d_dhidden);
   // two halves ADD into the same gradient buffers: every accumulation of the backward is atomic (generic_parts)
   return run_whole_or_halves(cfg, d, d_workspace, sskd::as_stream(stream), [&](int i, int rows, void* ws, hipStream_t st) {
     Rows r(d, rows, ws);
     const int64_t row0 = (int64_t)i * rows;
-    return backward_rows(cfg, w, grads, r, d_ids + row0 * S, d_mask + row0 * S, normalize, d_dout + row0 * d.H, st);
+    return backward_rows(cfg, w, grads, r, d_ids + row0 * S, d_mask + row0 * S, normalize, hidden ? nullptr : d_dout + row0 * d.H,
+                         hidden ? dhidden + row0 * S * d.H : nullptr, st);
   });
+}
+
+int sskd_generic_backward(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
+                          const int32_t* d_ids, const int32_t* d_mask, int B, int S, int normalize, const float* d_dout,
+                          void* d_workspace, size_t workspace_bytes, void* stream) {
+  return generic_backward(cfg, w, grads, d_ids, d_mask, B, S, normalize, false, d_dout, nullptr, d_workspace, workspace_bytes, stream);
+}
+
+int sskd_generic_backward_hidden(const sskd_generic_config* cfg, const sskd_generic_weights* w, const sskd_generic_grads* grads,
+                                 const int32_t* d_ids, const int32_t* d_mask, int B, int S, const void* d_dhidden,
+                                 void* d_workspace, size_t workspace_bytes, void* stream) {
+  return generic_backward(cfg, w, grads, d_ids, d_mask, B, S, 0, true, nullptr, d_dhidden, d_workspace, workspace_bytes, stream);
 }
 
 size_t sskd_teacher_workspace_bytes(const sskd_generic_config* cfg, int B, int S) {

@@ -140,6 +140,27 @@ class StudentModel:
         tok = self.model.tokenize(list(texts))
         return self.model.trainable()(tok["input_ids"], tok["attention_mask"], normalize=normalize)
 
+    def encode_tokens_with_gradients(self, texts: List[str], max_tokens: int):
+        """Training entry point of the late-interaction score: ``late_training.TokenStates`` (the final hidden states
+        bf16 ``[n, S, 384]`` carrying gradients back to ``self.model.parameters()``, and every text's token count) for
+        ``late_training.maxsim_scores``.  Texts are tokenised and cut as ``encode_tokens`` cuts them (to ``max_tokens``,
+        keeping the closing ``[SEP]``); E5 prefixes are the caller's business, as in ``encode_with_gradients``."""
+        from .late import _token_rows
+        from .late_training import TokenStates
+
+        if isinstance(texts, str):
+            texts = [texts]
+        rows = _token_rows(self.model, list(texts), int(max_tokens))
+        if not rows or min(len(r) for r in rows) < 1:
+            raise ValueError("encode_tokens_with_gradients needs texts, each of at least one token")
+        lengths = np.fromiter((len(r) for r in rows), np.int64, count=len(rows))
+        ids = np.zeros((len(rows), int(lengths.max())), np.int32)
+        mask = np.zeros_like(ids)
+        for j, r in enumerate(rows):
+            ids[j, : len(r)] = r
+            mask[j, : len(r)] = 1
+        return TokenStates(self.model.trainable().forward_tokens(ids, mask), lengths)
+
     # -------------------------------------------------------------- similarity
     def compute_similarity(self, query_embeddings: np.ndarray, doc_embeddings: np.ndarray) -> np.ndarray:
         """``q @ d.T`` in fp32 on the GPU (same fma order as the index scan)."""

@@ -7,6 +7,9 @@ Here the encoder forward that saves its activations and the whole backward pass 
 (``sskd_generic_forward`` / ``sskd_generic_backward``, csrc/train.hip) behind ONE
 ``torch.autograd.Function``; torch holds the fp32 master parameters (what the optimizer updates)
 and supplies device memory.  bf16 compute, fp32 accumulation and gradients.  No CPU path.
+
+``TrainableEncoder.forward_tokens`` is the same pair without the pool (``sskd_generic_backward_hidden`` starts from the
+gradient of the final hidden states): the encoder side of training through MaxSim (late_training.py).
 """
 from __future__ import annotations
 
@@ -71,6 +74,47 @@ class _EncoderFunction(torch.autograd.Function):
                 dout.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), _native.current_stream_ptr(ids.device)))
         ctx.ws = None
         return (None, None, None, None) + (None,) * len(module.names)
+
+
+class _EncoderTokensFunction(torch.autograd.Function):
+    """``_EncoderFunction`` without the pool: ids -> the final hidden states bf16 ``[B, S, H]``
+    (``sskd_generic_forward(training=1, pool=0)``), backward from their gradient (``sskd_generic_backward_hidden``).
+    The autograd contract, the refusals and the ``p.grad`` side effects are ``_EncoderFunction``'s."""
+
+    @staticmethod
+    def forward(ctx, module: "TrainableEncoder", ids: torch.Tensor, mask: torch.Tensor, *params):
+        lib = _native.load()
+        B, S = ids.shape
+        module._check_autograd_contract()
+        module._refresh_device_weights()
+        need = int(lib.sskd_generic_workspace_bytes(module.cfg_struct, B, S, 1))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=ids.device)
+        out = torch.empty((B, S, module.config.hidden_size), dtype=torch.bfloat16, device=ids.device)
+        with torch.cuda.device(ids.device):
+            _native.check(lib.sskd_generic_forward(
+                module.cfg_struct, module.w_struct, ids.data_ptr(), mask.data_ptr(), B, S, 1, 0, 0,
+                out.data_ptr(), ws.data_ptr(), ws.numel(), _native.current_stream_ptr(ids.device)))
+        ctx.module, ctx.ws = module, ws
+        ctx.save_for_backward(ids, mask)
+        ctx.weights_version = module._weights_version
+        return out
+
+    @staticmethod
+    def backward(ctx, dhidden):
+        lib = _native.load()
+        module: TrainableEncoder = ctx.module
+        ids, mask = ctx.saved_tensors
+        B, S = ids.shape
+        if ctx.weights_version != module._weights_version:
+            raise RuntimeError("parameters changed between forward and backward of forward_tokens")
+        module._attach_grads()
+        dhidden = dhidden.to(torch.bfloat16).contiguous()   # bf16 or fp32 in, bf16 to the kernels
+        with torch.cuda.device(ids.device):
+            _native.check(lib.sskd_generic_backward_hidden(
+                module.cfg_struct, module.w_struct, module.g_struct, ids.data_ptr(), mask.data_ptr(), B, S,
+                dhidden.data_ptr(), ctx.ws.data_ptr(), ctx.ws.numel(), _native.current_stream_ptr(ids.device)))
+        ctx.ws = None
+        return (None, None, None) + (None,) * len(module.names)
 
 
 class TrainableEncoder(nn.Module):
@@ -247,6 +291,14 @@ class TrainableEncoder(nn.Module):
         ids, mask = _native.padded_ids_mask(input_ids, attention_mask, self.device)
         params = [self.p(n) for n in self.names]
         return _EncoderFunction.apply(self, ids, mask, normalize, *params)
+
+    def forward_tokens(self, input_ids, attention_mask=None) -> torch.Tensor:
+        """ids / mask ``[B, S]`` -> the final hidden states bf16 ``[B, S', hidden]`` (S' = S padded to a multiple of 32;
+        on device, differentiable with respect to every parameter; the gradient may be bf16 or fp32).  What
+        ``late_training.maxsim_scores`` normalises into token vectors."""
+        ids, mask = _native.padded_ids_mask(input_ids, attention_mask, self.device)
+        params = [self.p(n) for n in self.names]
+        return _EncoderTokensFunction.apply(self, ids, mask, *params)
 
     def state_dict_numpy(self) -> Dict[str, np.ndarray]:
         return {n: self.p(n).detach().cpu().numpy() for n in self.names}
