@@ -475,6 +475,73 @@ int sskd_hybrid_fuse(const float* d_tiled, int64_t n_rows, const float* d_querie
                      float* d_out_dense, double* d_out_bm25, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Query expansion: pseudo-relevance feedback between a first search and a second one (Rocchio, RM3)
+ *   reference: features.enable_query_expansion of configs/service.yaml:108-113 (.env.example:
+ *   ENABLE_QUERY_EXPANSION), a flag the reference reads and has no code behind.  The two rules below are this
+ *   library's definition.
+ *
+ * sskd_prf_rocchio, the dense side.  Inputs per query q: the PREPARED query d_queries[q] (fp32 [384], the tensor the
+ * first search used) and its ranking d_rank_scores fp32 / d_rank_ids int64 [nq, kd] as any search above writes it with
+ * id_offset 0 (LOCAL rows, padded with id -1).
+ *   - feedback rows: the first fb_docs entries of the ranking up to the first id -1, ids outside [0, n_rows) skipped;
+ *     m = how many remain.  m == 0: the output row is the input row bit for bit.
+ *   - weights, fp32.  weighting 0 (uniform): b_i = beta / (float)m.  weighting 1 (score): s+_i = s_i when s_i > 0, else
+ *     +0.0f; S = the s+_i summed in rank order from +0.0f; S == 0: the uniform weights; else b_i = beta * (s+_i / S)
+ *     (the division rounded, then the product).
+ *   - per column c: acc = alpha * q[c], then in rank order acc = acc + b_i * row_i[c]; every product and every sum is
+ *     rounded once (no fma).  d_out_queries fp32 [nq, 384] = acc, NOT normalised: the second search prepares it as it
+ *     prepares any query (sskd_l2_normalize_rows under the cosine metric).  d_out_counts int32 [nq] = m.
+ * One wave per query; rows are read whole (1 536 bytes, 16-byte loads).  Limits: 1 <= fb_docs <= kd <= SSKD_K_MAX;
+ * alpha and beta finite and >= 0; weighting 0 or 1; n_rows < 2^31 - 64; d_tiled, d_queries and d_out_queries 16-byte
+ * aligned; d_out_queries may not overlap d_queries.  Scores, queries and rows are finite: the call does not check that.
+ *
+ * sskd_prf_rm3, the lexical side, over the BM25 index of "BM25 search" plus a FORWARD INDEX built on the host
+ * (semantic-search-kd_amd/bm25.py): CSR by row, d_fwd_lims int64 [n_rows + 1], entry i = (d_fwd_terms[i] int32,
+ * d_fwd_p[i] fp64) with p = tf / dl in fp64 (tf = occurrences of the term in the row, dl = the row's full token count);
+ * n_fwd = the number of entries.  A row keeps at most SSKD_RM3_ROW_TERMS distinct terms, the largest tf first, ties to
+ * the lower term id, stored ascending by term id; a term occurs at most once per row.
+ *   - feedback rows: walk the BM25 ranking d_rank_scores fp64 / d_rank_ids int64 [nq, kb] (as sskd_bm25_search writes it)
+ *     up to the first id -1, skipping ids outside [0, n_rows), scores equal to 0.0 of either sign and rows that d_mask
+ *     (DEVICE allow-mask words as in "Row filters", NULL = off) clears - the candidate rule of sskd_hybrid_fuse.  The
+ *     first fb_docs survivors are the feedback rows; d_out_fb int32 [nq] = how many there are.
+ *   - term weights, fp64, every operation rounded once: S = the feedback rows' scores summed in rank order from +0.0;
+ *     P_d = s_d / S;  w(t) = the sum over the feedback rows that hold t, in rank order, from +0.0, of p(t, d) * P_d.
+ *     (S == 0 or a non-finite score: the call is safe and what it selects is unspecified.)
+ *   - candidates: a term of a feedback row with an id in [0, n_terms) that is not among the query's own tokens
+ *     d_q_terms[d_q_lims[q] .. d_q_lims[q + 1]) and, when max_df > 0, whose document frequency d_term_offsets[t + 1] -
+ *     d_term_offsets[t] is <= max_df (max_df = 0: no limit).
+ *   - selection: the best fb_terms candidates under (w descending, term id ascending; -0.0 below +0.0).
+ *   - output: d_out_terms int32 laid out by d_out_lims int64 [nq + 1]; segment q has exactly orig_repeat * len_q +
+ *     fb_terms slots: the query's own token sequence orig_repeat times, the selected terms in selection order, -1 in
+ *     every remaining slot.  sskd_bm25_search and sskd_hybrid_fuse skip term ids outside [0, n_terms), so (d_out_lims,
+ *     d_out_terms) is a legal query CSR for both as it stands.  Also d_out_sel_terms int32 [nq, fb_terms] (padded with
+ *     -1), d_out_sel_w fp64 [nq, fb_terms] (padded with +0.0), d_out_counts int32 [nq] = the number selected.
+ *   q_lims and out_lims are given TWICE, as sskd_late_rerank takes its q_lims: on the HOST (validated before the launch:
+ *   both start at >= 0, q_lims does not decrease, every segment has the length above) and on the device (read by the
+ *   kernel; nothing is copied by the call).
+ * One workgroup of 256 threads per query; the term table (8 192 slots: 16 rows x 256 disjoint terms at load factor 1/2,
+ * keys and fp64 weights, 96 KiB) lives in LDS; one barrier between feedback rows fixes every sum's order without float
+ * atomics.  A malformed forward index cannot make the kernel spin or write outside the table: a row's list is read
+ * clamped into [0, n_fwd] and cut to 256 entries, every probe loop is bounded by the table size, and a term that finds
+ * no slot is dropped.  Limits: 1 <= fb_docs <= 16; fb_docs <= kb <= 256; 1 <= fb_terms <= 64; 1 <= orig_repeat
+ * <= 8; max_df >= 0; n_rows < 2^31 - 64.
+ *
+ * Both calls: stream-ordered, no host sync (graph-capturable), no workspace, allocate nothing; arguments are checked
+ * before the launch (SSKD_ERR_INVALID); nq = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+#define SSKD_RM3_ROW_TERMS 256
+int sskd_prf_rocchio(const float* d_tiled, int64_t n_rows, const float* d_queries, int nq, const float* d_rank_scores,
+                     const int64_t* d_rank_ids, int kd, int fb_docs, float alpha, float beta, int weighting,
+                     float* d_out_queries, int32_t* d_out_counts, void* stream);
+int sskd_prf_rm3(const int64_t* d_fwd_lims, const int32_t* d_fwd_terms, const double* d_fwd_p, int64_t n_fwd,
+                 const int64_t* d_term_offsets, int64_t n_rows, int64_t n_terms, const int64_t* q_lims,
+                 const int64_t* d_q_lims, const int32_t* d_q_terms, const double* d_rank_scores,
+                 const int64_t* d_rank_ids, int kb, const uint32_t* d_mask, int nq, int fb_docs, int fb_terms,
+                 int orig_repeat, int64_t max_df, const int64_t* out_lims, const int64_t* d_out_lims,
+                 int32_t* d_out_terms, int32_t* d_out_sel_terms, double* d_out_sel_w, int32_t* d_out_counts,
+                 int32_t* d_out_fb, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Retrieval evaluation: nDCG / MRR / recall / precision per cutoff, and the discordant pairs behind Kendall's tau
  *   reference: ndcg_at_k / mrr_at_k / recall_at_k / precision_at_k / kendall_tau, src/utils/metrics.py:11-157;
  *   KDEvaluator.evaluate_retrieval / _evaluate_model / evaluate_ranking_quality, src/kd/eval.py:42-265

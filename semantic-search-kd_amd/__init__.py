@@ -15,6 +15,7 @@ from .student import StudentModel  # noqa: F401
 from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELoss  # noqa: F401
 from .bm25 import BM25Index, build_bm25_index  # noqa: F401
 from .hybrid import HybridIndex  # noqa: F401
+from .expand import ExpandedIndex, QueryExpansion  # noqa: F401
 from .graph import GraphIndex  # noqa: F401
 from .ivf import IVFIndex  # noqa: F401
 from .pq import IVFPQIndex  # noqa: F401
@@ -44,6 +45,8 @@ __all__ = [
     "BM25Miner",
     "build_bm25_index",
     "HybridIndex",
+    "ExpandedIndex",
+    "QueryExpansion",
     "GraphIndex",
     "IVFIndex",
     "IVFPQIndex",

@@ -186,6 +186,11 @@ SIGNATURES = {
         _i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i, C.c_double,
              C.c_double, C.c_double, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
     ),
+    "sskd_prf_rocchio": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
+    "sskd_prf_rm3": (
+        _i, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i64, _vp, _vp,
+             _vp, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_eval_judge": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp]),
     "sskd_eval_lists": (
         _i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]

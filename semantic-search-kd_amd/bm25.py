@@ -26,6 +26,7 @@ import numpy as np
 from . import _native
 
 K_MAX = 256   # sskd_bm25_search: 1 <= k <= 256
+RM3_ROW_TERMS = 256   # SSKD_RM3_ROW_TERMS: distinct terms a row keeps in the forward index
 
 
 class BM25Postings:
@@ -34,7 +35,8 @@ class BM25Postings:
     ``vocab`` maps a word to its term id, ids in order of first appearance in the corpus (the insertion order of the
     library's dicts); ``idf`` is fp64 ``[n_terms]`` with negative values already replaced by ``epsilon *
     average_idf``; term ``t``'s postings are ``post_rows[term_offsets[t]:term_offsets[t + 1]]`` (int32, ascending) and
-    ``post_w`` (fp64) beside them."""
+    ``post_w`` (fp64) beside them, with ``post_tf`` (int32), the term's count in that row, kept for the forward index
+    (``forward_index``)."""
 
     def __init__(self, tokenized_corpus: Sequence[Sequence[str]], k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25):
         n = len(tokenized_corpus)
@@ -83,10 +85,43 @@ class BM25Postings:
         else:
             self.post_w = np.zeros(0, dtype=np.float64)
         self.post_rows = post_rows.astype(np.int32)
+        self.post_tf = freq.astype(np.int32)
+        self._words: Optional[List[str]] = None
 
     @property
     def n_terms(self) -> int:
         return len(self.vocab)
+
+    @property
+    def words(self) -> List[str]:
+        """The vocabulary by term id."""
+        if self._words is None:
+            self._words = list(self.vocab)
+        return self._words
+
+    def forward_index(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The index by row, what query expansion reads (``include/sskd_amd.h``, "Query expansion"): ``(fwd_lims int64
+        [rows + 1], fwd_terms int32, fwd_p float64)``, row ``r``'s entries at ``fwd_lims[r]:fwd_lims[r + 1]``, ascending
+        by term id, ``p = tf / dl`` in fp64 with ``dl`` the row's full token count.  A row keeps at most
+        ``RM3_ROW_TERMS`` = 256 distinct terms: the largest ``tf`` first, ties to the lower term id.  12 bytes per
+        distinct (row, term) - the size of the postings - plus 8 per row."""
+        n, n_terms = self.corpus_size, self.n_terms
+        term = np.repeat(np.arange(n_terms, dtype=np.int64), np.diff(self.term_offsets))
+        rows = self.post_rows.astype(np.int64)
+        tf = self.post_tf.astype(np.int64)
+        per_row = np.bincount(rows, minlength=n)
+        if per_row.size and int(per_row.max()) > RM3_ROW_TERMS:
+            order = np.lexsort((term, -tf, rows))                        # by row, then tf descending, then term id
+            starts = np.cumsum(per_row) - per_row
+            place = np.arange(order.size, dtype=np.int64) - starts[rows[order]]
+            keep = order[place < RM3_ROW_TERMS]
+            term, rows, tf = term[keep], rows[keep], tf[keep]
+        order = np.lexsort((term, rows))                                 # CSR by row, ascending term ids
+        term, rows, tf = term[order], rows[order], tf[order]
+        lims = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(rows, minlength=n), out=lims[1:])
+        p = np.asarray(tf / self.doc_len[rows], dtype=np.float64) if rows.size else np.zeros(0, dtype=np.float64)
+        return lims, term.astype(np.int32), p
 
     def term_ids(self, tokens: Sequence[str]) -> List[int]:
         """Term ids of a token list in order, repeats kept, out-of-vocabulary tokens dropped (they score nothing)."""
@@ -104,6 +139,7 @@ class BM25Index:
         self.tokenized_corpus: List[List[str]] = []
         self.device = device
         self._device_tables = None
+        self._forward_tables = None
         if auto_load and self.index_path and (self.index_path / "tokenized_corpus.json").exists():
             self.load()
 
@@ -114,6 +150,7 @@ class BM25Index:
     def _rebuild(self, k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25) -> None:
         self.bm25 = BM25Postings(self.tokenized_corpus, k1=k1, b=b, epsilon=epsilon)
         self._device_tables = None
+        self._forward_tables = None
 
     def build_from_texts(self, doc_ids: Sequence, texts: Sequence[str]) -> None:
         """Index ``texts`` under ``doc_ids`` (nothing is written; ``save()`` does that when ``index_path`` is set)."""
@@ -220,10 +257,31 @@ class BM25Index:
                                    up(post.post_w, np.float64), up(post.idf, np.float64))
         return self._device_tables
 
+    def forward_tables(self):
+        """The forward index in HBM (``BM25Postings.forward_index``; built and uploaded at the first query expansion,
+        not before, and never persisted: it follows from the tokenised corpus): ``(fwd_lims, fwd_terms, fwd_p,
+        entries)``."""
+        if self._forward_tables is None:
+            import torch
+
+            dev = self._tables()[0]
+            lims, terms, p = self._require_built().forward_index()
+            n_fwd = int(terms.size)
+            if n_fwd == 0:      # the C-ABI wants real pointers: one unused element
+                terms, p = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float64)
+            self._forward_tables = (torch.from_numpy(lims).to(dev), torch.from_numpy(terms).to(dev),
+                                    torch.from_numpy(p).to(dev), n_fwd)
+        return self._forward_tables
+
     def query_csr(self, queries: Sequence[str]):
         """The queries' term ids as the device CSR the kernels read: ``(lims int64 [nq + 1], terms int32)`` device
         tensors, tokens in query order, repeats kept, out-of-vocabulary tokens dropped.  Made once per batch and shared
         by every call that scores it (``search_device``, ``HybridIndex``)."""
+        return self.query_csr_host(queries)[:2]
+
+    def query_csr_host(self, queries: Sequence[str]):
+        """``query_csr`` and, third, the host copy of ``lims`` (NumPy int64 ``[nq + 1]``) for a call that validates
+        the segment lengths before its launch (``sskd_prf_rm3``)."""
         import torch
 
         post = self._require_built()
@@ -235,7 +293,7 @@ class BM25Index:
         flat = np.fromiter(chain.from_iterable(q_ids), dtype=np.int32, count=int(lims[-1]))
         if flat.size == 0:
             flat = np.zeros(1, dtype=np.int32)
-        return torch.from_numpy(lims).to(dev), torch.from_numpy(flat).to(dev)
+        return torch.from_numpy(lims).to(dev), torch.from_numpy(flat).to(dev), lims
 
     def search_device(self, queries: Sequence[str], top_k: int = 100, max_workspace_bytes: Optional[int] = None):
         """``(D float64 [nq, top_k], I int64 [nq, top_k])`` device tensors: rows of the corpus, best first (score

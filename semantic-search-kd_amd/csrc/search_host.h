@@ -1,5 +1,6 @@
 // Host-side pieces the search translation units share (internal: not installed).  search.hip defines what is only
-// declared here; index_rows.hip, screen.hip, range.hip, grouped.hip, mine.hip, bm25.hip, hybrid.hip and eval.hip use it.
+// declared here; index_rows.hip, screen.hip, range.hip, grouped.hip, mine.hip, bm25.hip, hybrid.hip, expand.hip and eval.hip
+// use it.
 #pragma once
 #include "common.h"
 

@@ -85,7 +85,7 @@ class HybridIndex:
 
     def search_device(self, queries: Sequence[str], query_emb, k: int = 10, *, allow=None, depth: Optional[int] = None,
                       fusion_method: Optional[str] = None, semantic_weight: Optional[float] = None,
-                      bm25_weight: Optional[float] = None, details: bool = False):
+                      bm25_weight: Optional[float] = None, details: bool = False, query_csr=None):
         """``(D float64 [nq, k], I int64 [nq, k])`` device tensors: the best ``k`` rows of the union of both sides'
         ``depth`` best, by fused score descending then lower row, ids as the dense index's ``search`` numbers them,
         padded with ``(-inf, -1)``.  ``queries`` are the texts (BM25 side), ``query_emb`` their ``[nq, 384]`` float32
@@ -100,7 +100,11 @@ class HybridIndex:
         ``allow`` and the dense index's removed rows are honoured by both sides: the dense search applies them as
         always, the BM25 ranking is filtered inside the fuse kernel by the same mask and ranked among the survivors.
         Because that filter comes after the BM25 retrieval, fewer than ``depth`` lexical candidates may survive it.
-        ``depth`` is clipped to ``min(depth, rows, 256)``; ``k`` above twice that raises ``ValueError``."""
+        ``depth`` is clipped to ``min(depth, rows, 256)``; ``k`` above twice that raises ``ValueError``.
+
+        ``query_csr``: the BM25 side's queries already as a device CSR ``(lims int64 [nq + 1], terms int32)`` in
+        ``BM25Index.query_csr``'s form (an expanded query, ``expand.ExpandedIndex``); the texts are then not
+        tokenised.  The dense side takes whatever embeddings it is given, so an expanded embedding needs no keyword."""
         import torch
 
         self.check_same_rows()
@@ -132,7 +136,7 @@ class HybridIndex:
                 mask = dense.search_mask(allow)
                 # both rankings in LOCAL rows; the prepared query is what the linear completion scores against
                 rank_s, rank_i = dense._search_device_masked(q, d, False, None, None, mask, id_offset=0)
-                csr = bm25.query_csr(queries)
+                csr = bm25.query_csr(queries) if query_csr is None else query_csr
                 rank_b, rank_j = bm25._search_csr(csr, nq, d)
                 n_rows = int(dense.ntotal)
                 _native.check(

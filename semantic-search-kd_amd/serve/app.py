@@ -82,6 +82,26 @@ class ServeSettings:
     # directory holds them
     late_first_stage: str = "dense"
     late_nprobe: int = 2
+    # ``features.enable_query_expansion`` of the reference's configs/service.yaml:108-113 (.env.example:
+    # ENABLE_QUERY_EXPANSION; read there, no code behind it): /search wraps whatever first stage it resolves to in
+    # pseudo-relevance feedback (expand.ExpandedIndex: Rocchio on the dense side, RM3 on the BM25 side)
+    query_expansion_enabled: bool = False
+    expansion_fb_docs: int = 5
+    expansion_fb_terms: int = 10
+    expansion_alpha: float = 1.0
+    expansion_beta: float = 0.75
+    expansion_orig_repeat: int = 2
+    expansion_max_df_fraction: float = 0.25
+
+    def query_expansion(self):
+        """The ``QueryExpansion`` /search applies, or None (the flag is off)."""
+        if not self.query_expansion_enabled:
+            return None
+        from ..expand import QueryExpansion
+
+        return QueryExpansion(fb_docs=self.expansion_fb_docs, fb_terms=self.expansion_fb_terms,
+                              alpha=self.expansion_alpha, beta=self.expansion_beta,
+                              orig_repeat=self.expansion_orig_repeat, max_df_fraction=self.expansion_max_df_fraction)
 
     @staticmethod
     def from_env() -> "ServeSettings":
@@ -102,6 +122,15 @@ class ServeSettings:
             late_candidates=int(e.get("SEMANTIC_KD_LATE__CANDIDATES") or ServeSettings.late_candidates),
             late_first_stage=(e.get("SEMANTIC_KD_LATE__FIRST_STAGE") or ServeSettings.late_first_stage).strip().lower(),
             late_nprobe=int(e.get("SEMANTIC_KD_LATE__NPROBE") or ServeSettings.late_nprobe),
+            query_expansion_enabled=_env_bool(e.get("SEMANTIC_KD_FEATURES__ENABLE_QUERY_EXPANSION"),
+                                              ServeSettings.query_expansion_enabled),
+            expansion_fb_docs=int(e.get("SEMANTIC_KD_EXPANSION__FB_DOCS") or ServeSettings.expansion_fb_docs),
+            expansion_fb_terms=int(e.get("SEMANTIC_KD_EXPANSION__FB_TERMS") or ServeSettings.expansion_fb_terms),
+            expansion_alpha=float(e.get("SEMANTIC_KD_EXPANSION__ALPHA") or ServeSettings.expansion_alpha),
+            expansion_beta=float(e.get("SEMANTIC_KD_EXPANSION__BETA") or ServeSettings.expansion_beta),
+            expansion_orig_repeat=int(e.get("SEMANTIC_KD_EXPANSION__ORIG_REPEAT") or ServeSettings.expansion_orig_repeat),
+            expansion_max_df_fraction=float(e.get("SEMANTIC_KD_EXPANSION__MAX_DF_FRACTION")
+                                            or ServeSettings.expansion_max_df_fraction),
         )
 
     def is_production(self) -> bool:
@@ -337,17 +366,29 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
             k_retrieve = request.rerank_top_k if request.rerank else request.k
             hybrid = app_state.hybrid
 
+            expansion = (app_state.settings or settings).query_expansion()
+            if expansion is not None and not isinstance(app_state.index_builder, FAISSIndexBuilder):
+                expansion = None   # (a row-sharded index: the feedback rows live on other ranks)
+
+            def expanded(stage):
+                # features.enable_query_expansion wraps whatever the first stage resolves to
+                if expansion is None:
+                    return stage
+                from ..expand import ExpandedIndex
+
+                return ExpandedIndex(stage, expansion)
+
             def first_stage(k_first: int):
                 if hybrid is not None and hybrid.dense is app_state.index_builder:
                     # both sides contribute at least k rows; the fused score is the result's score
                     depth = hybrid.clip_depth(max(hybrid.depth, k_first))
-                    return hybrid.search([request.query], query_emb, k=min(k_first, 2 * depth), depth=depth)
+                    return expanded(hybrid).search([request.query], query_emb, k=min(k_first, 2 * depth), depth=depth)
                 if app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_first <= 256:
-                    return app_state.ivf.search(query_emb, k=k_first)
+                    return expanded(app_state.ivf).search(query_emb, k=k_first)
                 if (app_state.graph is not None and app_state.graph.flat is app_state.index_builder
                         and k_first <= app_state.graph.ef):
-                    return app_state.graph.search(query_emb, k=k_first)
-                return app_state.index_builder.search(query_emb, k=k_first)
+                    return expanded(app_state.graph).search(query_emb, k=k_first)
+                return expanded(app_state.index_builder).search(query_emb, k=k_first)
 
             late = app_state.late
             if late is not None and late.flat is app_state.index_builder and k_retrieve <= LATE_R_MAX:
