@@ -380,6 +380,13 @@ __device__ __forceinline__ float screen_group_max(float x) {
   if (SSKD_SCREEN_OFFER_SPAN >= 4) x = fmaxf(x, __shfl_xor(x, 32));
   return x;
 }
+// The lane's number, read where it is wanted (two VALU) instead of carried: a value the optimiser can follow back to the
+// kernel's head is kept - with everything derived from it - in registers across the MFMAs of every tile.
+__device__ __forceinline__ int screen_lane_now() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
 // packed = max(packed, pack(lo, hi)) per half
 __device__ __forceinline__ void screen_thr_raise2(unsigned& packed, float lo, float hi) {
   const sf16x2 a = __builtin_bit_cast(sf16x2, packed), b = __builtin_bit_cast(sf16x2, screen_thr_pack2(lo, hi));
@@ -600,9 +607,10 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
                                              const sbf16x8* __restrict__ qlane, int* pool, int list0,
                                              bool ragged, unsigned (&gthr)[QB]) {
   constexpr int NQ = 2 * QB;
-  // (wave-uniform LDS addresses; every per-lane address below is formed where it is used, from a copy of n the
-  // optimiser cannot follow: hoisted out of the tile loop, the forty addresses of ten queries' pool, bound, band and
-  // count were held - and spilled - across the MFMAs)
+  // (wave-uniform LDS addresses; every per-lane address below is formed where it is used, from a lane number the
+  // optimiser cannot follow - a laundered copy of n in the sample phase, screen_lane_now() in the slice phase, where
+  // n and g themselves are then dead: hoisted out of the tile loop, the forty addresses of ten queries' pool, bound,
+  // band and count were held - and spilled - across the MFMAs)
   int* const wthr = pool + QB * 32 * K;
   float* const bandl = reinterpret_cast<float*>(wthr + QB * 32);
   short* const cnts = reinterpret_cast<short*>(bandl + QB * 32);
@@ -636,7 +644,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     // the ring into vmcnt(0).)
     int at = sl;
     asm volatile("" : "+v"(at));
-    if (n + 16 * g == 0) drawn = __hip_atomic_fetch_add(cursors + at, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (screen_lane_now() == 0) drawn = __hip_atomic_fetch_add(cursors + at, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     in_flight = true;
   };
   // first tile of the chunk drawn (its end: next_end), or -1 when the query block has no tile left for this wave
@@ -698,13 +706,12 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     // (periods 1 / 2 / 4 / 8: 5.91 / 5.78 / 5.71 / 5.67 ms), and a bound a few tiles stale only lets a few more rows
     // through to the fp32 test, which reads the pool's bound of that moment: 417 / 416 / 416 appended entries per query.
     if (exchange || tiles_done % SCREEN_BOUND_REFRESH_TILES == 0) {
-    int nh = n;
-    asm volatile("" : "+v"(nh));
+    const int lh = screen_lane_now(), nh = lh & 15;
     // The exchange is made by ONE lane group of the wave and lands in wthr (an LDS atomicMax: any lower bound of the
     // final k-th best score may stand there, and it only rises), where the reads below - the same wave's, in order -
     // and the fp32 test of the append path find it.  Made by all four groups it was four returning atomics per query
     // and wave on the same word of tau: with 32 slices (1 000 queries x 1 M rows) they queued for 0.2 ms of a 0.85 ms launch.
-    if (exchange && g == 0) {
+    if (exchange && lh < 16) {
 #pragma unroll
       for (int nb = 0; nb < NQ; ++nb) {
         const int ql = 16 * nb + nh;
@@ -741,7 +748,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
                                                                         : (int64_t)(next_t - t) * BTILE_VEC, lane_off);
 
     // acc[mb][nb][i]: row rowbase + 16 mb + i, query 16 nb + n of the block
-    const int rowbase = t * TILE_ROWS + 4 * g;
+    const int rowbase = t * TILE_ROWS + 4 * (BOUND_ONLY ? g : screen_lane_now() >> 4);
     if (ragged && (int64_t)(t + 1) * TILE_ROWS > p.n_rows) {
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb)
@@ -751,7 +758,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
           for (int nb = 0; nb < NQ; ++nb)
             if (rowbase + 16 * mb + i >= p.n_rows) acc[mb][nb][i] = -INFINITY;
     }
-    if constexpr (MASKED) apply_tile_mask16<QB>(acc, mword, g);
+    if constexpr (MASKED) apply_tile_mask16<QB>(acc, mword, BOUND_ONLY ? g : screen_lane_now() >> 4);
 #ifdef SSKD_SCREEN_ABL_NOLIST  // timing ablation: no candidate / pool maintenance (accumulators kept alive)
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
@@ -804,100 +811,153 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
         // ONE entry for the pair - as often as the 32-query sub-blocks of the 32x32 form entered, half as often as one per
         // query block while a slice's bounds are cold and every block has a row that passes - and one LDS round trip
         // for the bounds, bands and counts of both blocks.
-        int nc = n;
-        asm volatile("" : "+v"(nc));
+        const int lc = screen_lane_now(), nc = lc & 15, gc = lc >> 4;
         float pb[2];   // what the pools hold now, minus the band (-inf: no bound yet)
         int c[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int ql = 32 * pr + 16 * e + nc;
           pb[e] = fmaxf(ordered_to_float(wthr[ql]) - bandl[ql], -INFINITY);
-          c[e] = cnts[(ql * WAVES + wave) * 4 + g];
+          c[e] = cnts[(ql * WAVES + wave) * 4 + gc];
         }
         // the registers follow the pools here too: a lane that came in on a stale bound does not come in again
         screen_thr_raise2(gthr[pr], pb[0], pb[1]);
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int nb = 2 * pr + e, ql = 16 * nb + nc;
-          // The exact bound, in fp32: the pool's, or the register's fp16 as it was at the first test (the exchanges' bounds
-          // live only there: a valid bound, at most one fp16 step below the one it was packed from), never below
-          // -FLT_MAX - the -inf of a masked row or of a row past n_rows passes no finite bound.  A lane appends a row
-          // exactly when its best row reaches it.
-          const float thr = fmaxf(pb[e], fthr[e]);
-          if (!__any(m[e] >= thr)) continue;
-          short* const cslot = cnts + (ql * WAVES + wave) * 4 + g;
-          // run of (query, this wave, this lane group): list0 + g of the query's lists (padding queries own none)
-          unsigned long long* const run = reinterpret_cast<unsigned long long*>(
-              p.cand + ((int64_t)min(q0 + ql, p.nq - 1) * p.lists_per_query + list0 + g) * SCREEN_CAP);
-          int cc = c[e];
-          bool dirty = false;
+        // The exact bound, in fp32: the pool's, or the register's fp16 as it was at the first test (the exchanges' bounds
+        // live only there: a valid bound, at most one fp16 step below the one it was packed from), never below
+        // -FLT_MAX - the -inf of a masked row or of a row past n_rows passes no finite bound.  A lane appends a row
+        // exactly when the row reaches it.
+        const float thr[2] = {fmaxf(pb[0], fthr[0]), fmaxf(pb[1], fthr[1])};
+        // run of (query ql of the block, this wave, this lane group): list0 + g of the query's lists (padding queries own none)
+        const auto run_of = [&](int ql) {
+          return reinterpret_cast<unsigned long long*>(
+              p.cand + ((int64_t)min(q0 + ql, p.nq - 1) * p.lists_per_query + list0 + gc) * SCREEN_CAP);
+        };
+        // A run that could fill up inside this tile (8 rows) first drops what the bound has overtaken since it was
+        // appended: rows arriving in ascending order of their score - a corpus sorted by topic - pass the bound one
+        // after the other and the bound follows them, so the entries worth keeping are the band of the CURRENT
+        // bound.  Own stores, read back from L2 after they were acknowledged; forward in-place compaction (w <= i).
+        // (wave-uniform control flow at every call; true: the count changed)
+        const auto compact_if_tight = [&](int ql, int& cc, float bound) {
 #ifndef SSKD_SCREEN_NO_COMPACT
-          {
-            // A run that could fill up inside this tile (8 rows) first drops what the bound has overtaken since it was
-            // appended: rows arriving in ascending order of their score - a corpus sorted by topic - pass the bound one
-            // after the other and the bound follows them, so the entries worth keeping are the band of the CURRENT
-            // bound.  Own stores, read back from L2 after they were acknowledged; forward in-place compaction (w <= i).
-            const bool tight = cc > SCREEN_CAP - 8 && cc <= SCREEN_CAP;
-            if (__any(tight)) {
-              __builtin_amdgcn_s_waitcnt(0x0F70);
-              if (tight) {
-                cc = screen_compact_run(run, cc, thr);
-                dirty = true;
-              }
-            }
+          const bool tight = cc > SCREEN_CAP - 8 && cc <= SCREEN_CAP;
+          if (__any(tight)) {
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (tight) cc = screen_compact_run(run_of(ql), cc, bound);
           }
+          return tight;
+#else
+          return false;
 #endif
-          bool grew = false;
+        };
+        if constexpr (LIGHT) {
+          // Short slices: the sixteen rows of the pair are walked unrolled.  Nothing is offered per row, so a row's body
+          // is a store and a count (the whole kernel is 40-50 KiB and stays in the instruction cache), and most appends
+          // come from the cold head of the slice where every row passes: the loop below, one row per pass, cost the
+          // 125 k-row shard 2.5 % (profiles/rolled_append/README.md).
 #pragma unroll
-          for (int r = 0; r < 8; ++r) {
-            const float x = acc[r >> 2][nb][r & 3];
-            const int xid = rowbase + 16 * (r >> 2) + (r & 3);
-            const bool take = x >= thr;   // (a padding query: thr = +inf)
-            {   // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
-              if (take) {
-                {
-                  if (cc < SCREEN_CAP)
-                    run[cc] = (unsigned long long)__float_as_uint(x) | ((unsigned long long)(unsigned)xid << 32);
-                  // (SCREEN_CAP + 1: the run overflowed - the band itself holds more than a run: exact fallback; the
-                  // count stops there, it lives in 16 bits)
-                  if (cc <= SCREEN_CAP) ++cc;
-                }
-                if (!LIGHT && tiles_done > 0) {
-                  const int xi = float_to_ordered(x);
-                  if (pool_offer<K>(pool + ql * K, wthr + ql, xi))
-                    bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
-                }
+          for (int e = 0; e < 2; ++e) {
+            const int nb = 2 * pr + e, ql = 16 * nb + nc;
+            if (!__any(m[e] >= thr[e])) continue;
+            unsigned long long* const run = run_of(ql);
+            int cc = c[e];
+            const bool dirty = compact_if_tight(ql, cc, thr[e]);
+            bool grew = false;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+              const float x = acc[r >> 2][nb][r & 3];
+              const int xid = rowbase + 16 * (r >> 2) + (r & 3);
+              // (no wave-wide __any() around it: the exec mask skips an empty body, and the test cost more than it saved)
+              if (x >= thr[e]) {   // (a padding query: thr = +inf)
+                if (cc < SCREEN_CAP)
+                  run[cc] = (unsigned long long)__float_as_uint(x) | ((unsigned long long)(unsigned)xid << 32);
+                // (SCREEN_CAP + 1: the run overflowed - the band itself holds more than a run: exact fallback; the
+                // count stops there, it lives in 16 bits)
+                if (cc <= SCREEN_CAP) ++cc;
                 grew = true;
               }
             }
-          }
-          if (grew || dirty) *cslot = (short)cc;
-          // (wave-uniform control flow up to here; beyond its first tile the long-slice form offers every appended row)
-          const float mg = (LIGHT || tiles_done == 0) ? screen_group_max(m[e]) : m[e];
-          if (grew) {
-            if (m[e] != mg) {
-              // another lane group holds the query's best row of this tile: it offers (if it appended)
-            } else
-            if constexpr (LIGHT) {
-              // ONE pool offer per query, wave and tile - its best row - instead of one per appended row.  The bound
-              // is a little weaker (two of a query's best rows in one tile count once) and its upkeep
-              // much cheaper: worth it while a slice is short (125 k-row shard -6 %, 60 k -12 %; 1 M rows +1 %, 8.8 M +3 %)
+            if (grew || dirty) cnts[(ql * WAVES + wave) * 4 + gc] = (short)cc;
+            // (wave-uniform control flow up to here)
+            // ONE pool offer per query, wave and tile - its best row, from the lane group that holds it - instead of one
+            // per appended row.  The bound is a little weaker (two of a query's best rows in one tile count once) and
+            // its upkeep much cheaper: worth it while a slice is short (125 k-row shard -6 %, 60 k -12 %; 1 M rows +1 %,
+            // 8.8 M +3 %)
+            const float mg = screen_group_max(m[e]);
+            if (grew && m[e] == mg) {
               int xid = rowbase;
 #pragma unroll
               for (int r = 7; r >= 0; --r) xid = acc[r >> 2][nb][r & 3] == m[e] ? rowbase + 16 * (r >> 2) + (r & 3) : xid;
               const int xi = float_to_ordered(m[e]);
               if (pool_offer<K>(pool + ql * K, wthr + ql, xi) && tiles_done > 0)
                 bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
-            } else {
-              // first tile: every workgroup starts at the same instant - offer only the lane's best row
-              if (tiles_done == 0) pool_offer<K>(pool + ql * K, wthr + ql, float_to_ordered(m[e]));
             }
-            // (the register's bound is NOT raised to what the offer made of the pool's: it follows at the lane's next entry
-            // and at the wave's next refresh, and the LDS round trip here - bound and band, after every append - was the
-            // whole of what short slices lost to the 32x32 form: 125 k rows x 10 000 queries 0.955 -> 0.925 ms, the same
-            // 226 appended entries per query)
+          }
+        } else {
+          // Long slices: every appended row is offered to the pool, and sixteen unrolled copies of store + ten-slot pool
+          // read + compare-and-swap + global atomic per pair were 82 KiB of steady-state code that a wave entered at a
+          // random one of eighty places about twice per tile - 1.86 M instruction-cache misses per launch at the bench
+          // shape ("The rolled append body").  So: bit 8 e + r of `take` is row r of query block
+          // 2 pr + e, and ONE append + offer body per pair is walked once per set bit.  Ascending bits are the order e,
+          // then r: a run's entries are written in the order they always were.
+          unsigned take = 0;
+#pragma unroll
+          for (int b = 15; b >= 0; --b)   // (a padding query: thr = +inf; shifted in: no bit constants held in registers)
+            take = (take << 1) | (acc[(b >> 2) & 1][2 * pr + (b >> 3)][b & 3] >= thr[b >> 3] ? 1u : 0u);
+          if (!__any(take != 0)) continue;
+          int cc[2] = {c[0], c[1]};
+          bool dirty[2] = {false, false};
+#pragma unroll
+          for (int e = 0; e < 2; ++e)
+            if (__any((take >> (8 * e) & 0xFFu) != 0)) dirty[e] = compact_if_tight(32 * pr + 16 * e + nc, cc[e], thr[e]);
+#pragma clang loop unroll(disable)
+          for (unsigned rest = take; rest != 0; rest &= rest - 1) {
+            const int b = __builtin_ctz(rest);
+            const int e = b >> 3;
+            // the row's score out of the pair's sixteen: a tree of selects on the bits of b (a chain of sixteen equality
+            // tests is sixteen compare-then-select pairs with the wait states between them, two thirds of the body's
+            // issue time).  Scalars, not arrays: a select between two elements of a local array comes back as a
+            // run-time index into scratch.
+            const bool b0 = b & 1, b1 = b & 2, b2 = b & 4, b3 = b & 8;
+            const auto &a0 = acc[0][2 * pr], &a1 = acc[1][2 * pr], &a2 = acc[0][2 * pr + 1], &a3 = acc[1][2 * pr + 1];
+            const float x00 = b0 ? a0[1] : a0[0], x01 = b0 ? a0[3] : a0[2], x02 = b0 ? a1[1] : a1[0], x03 = b0 ? a1[3] : a1[2];
+            const float x04 = b0 ? a2[1] : a2[0], x05 = b0 ? a2[3] : a2[2], x06 = b0 ? a3[1] : a3[0], x07 = b0 ? a3[3] : a3[2];
+            const float x10 = b1 ? x01 : x00, x11 = b1 ? x03 : x02, x12 = b1 ? x05 : x04, x13 = b1 ? x07 : x06;
+            const float x20 = b2 ? x11 : x10, x21 = b2 ? x13 : x12;
+            const float x = b3 ? x21 : x20;
+            const int xid = rowbase + 4 * (b & 4) + (b & 3);
+            const int ql = 32 * pr + 16 * e + nc;
+            int cn = e ? cc[1] : cc[0];
+            if (cn < SCREEN_CAP) run_of(ql)[cn] = (unsigned long long)__float_as_uint(x) | ((unsigned long long)(unsigned)xid << 32);
+            // (SCREEN_CAP + 1: the run overflowed - the band itself holds more than a run: exact fallback; the
+            // count stops there, it lives in 16 bits)
+            if (cn <= SCREEN_CAP) ++cn;
+            cc[0] = e ? cc[0] : cn;
+            cc[1] = e ? cn : cc[1];
+            if (tiles_done > 0) {   // (the first tile: below)
+              const int xi = float_to_ordered(x);
+              if (pool_offer<K>(pool + ql * K, wthr + ql, xi))
+                bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+            }
+          }
+          // (wave-uniform control flow again: the cross-lane step of screen_group_max must not sit in the loop)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int ql = 32 * pr + 16 * e + nc;
+            if (!__any((take >> (8 * e) & 0xFFu) != 0)) continue;
+            const bool grew = (take >> (8 * e) & 0xFFu) != 0;
+            if (grew || dirty[e]) cnts[(ql * WAVES + wave) * 4 + gc] = (short)cc[e];
+            // first tile: every workgroup starts at the same instant - only the query's best row of the tile is offered,
+            // by the lane group that holds it
+            if (tiles_done == 0) {
+              const float mg = screen_group_max(m[e]);
+              if (grew && m[e] == mg) pool_offer<K>(pool + ql * K, wthr + ql, float_to_ordered(m[e]));
+            }
           }
         }
+        // (the register's bound is NOT raised to what the offers made of the pool's: it follows at the lane's next entry
+        // and at the wave's next refresh, and the LDS round trip here - bound and band, after every append - was the
+        // whole of what short slices lost to the 32x32 form: 125 k rows x 10 000 queries 0.955 -> 0.925 ms, the same
+        // 226 appended entries per query)
       }
     }
   }
@@ -1002,12 +1062,11 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
 
   // (the query numbers and "real" tests are formed again here from a lane number the optimiser cannot follow: kept
   // from the kernel's head they were registers and exec masks alive - and spilled - across both tile loops)
-  int nt = n;
-  asm volatile("" : "+v"(nt));
+  const int lt = screen_lane_now(), nt = lt & 15, gt = lt >> 4;
 #pragma unroll
   for (int nb = 0; nb < 2 * QB; ++nb) {
     const int q = q0 + nb * 16 + nt;
-    if (q < p.nq) p.cand_cnt[(int64_t)q * p.lists_per_query + list0 + g] = cnts[((nb * 16 + nt) * WAVES + wave) * 4 + g];
+    if (q < p.nq) p.cand_cnt[(int64_t)q * p.lists_per_query + list0 + gt] = cnts[((nb * 16 + nt) * WAVES + wave) * 4 + gt];
   }
 }
 
