@@ -208,6 +208,15 @@ int sskd_index_search_screened_claim(const float* d_tiled, const void* d_bf16, i
                                      float* d_out_scores, int64_t* d_out_ids, int* d_status, void* d_workspace,
                                      size_t workspace_bytes, void* stream, void* ev_scan_begin, void* ev_scan_end);
 
+/* Test hooks of the screening kernel's bound exchange (tests/test_screen_bound_exchange_gpu.py).
+ * A query's pruning bound travels between workgroups as sskd_screen_bucket_count() words per query, bucket (row id mod
+ * count) holding the best screen score of its rows as a monotone int32 image (INT32_MIN: empty); the exchanged bound
+ * is the k-th largest of a query's words, equal words counted separately - INT32_MIN while fewer than k are filled.
+ * sskd_screen_bucket_bound: d_out[q] = that selection over d_in[q][count], by the kernel's own code, for 1 <= k <= 10
+ * (the kernel uses k = 10).  A result above the true k-th largest would prune rows of the top k. */
+int sskd_screen_bucket_count(void);
+int sskd_screen_bucket_bound(const int32_t* d_in, int nq, int k, int32_t* d_out, void* stream);
+
 /* One-pass variant for the online shape (reference: src/serve/app.py:285-301, schemas.py:12-16 -
  * one query, k <= 100, rerank_top_k <= 200).  sskd_index_search serves k > SSKD_K_PASS by chained
  * corpus passes; this entry point scans the corpus ONCE with plain per-lane lists, collects the best

@@ -151,6 +151,8 @@ SIGNATURES = {
     "sskd_index_screen_band": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
     "sskd_index_screen_scores": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
     "sskd_screen_threshold_roundtrip": (_i, [_vp, _i, _vp, _vp]),
+    "sskd_screen_bucket_count": (_i, []),
+    "sskd_screen_bucket_bound": (_i, [_vp, _i, _i, _vp, _vp]),
     "sskd_index_search_onepass_workspace_bytes": (_sz, [_i64, _i, _i]),
     "sskd_index_search_onepass": (_i, [_vp, _i64, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sskd_row_mask_words": (_i64, [_i64]),

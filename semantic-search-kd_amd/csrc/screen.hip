@@ -66,9 +66,24 @@ constexpr int SCREEN_RING = SSKD_SCREEN_RING;
 #endif
 constexpr int BGROUP_Q5 = SSKD_SCREEN_BGROUP_Q5, SCREEN_RING_Q5 = SSKD_SCREEN_RING_Q5;
 #ifndef SSKD_SCREEN_TAU_REFRESH_TILES
-#define SSKD_SCREEN_TAU_REFRESH_TILES 64
+#define SSKD_SCREEN_TAU_REFRESH_TILES 16
 #endif
 constexpr int SCREEN_TAU_REFRESH_TILES = SSKD_SCREEN_TAU_REFRESH_TILES;
+// global buckets per query (bucket_forward_wide, search_device.h): the exchanged bound is the 10th largest of their maxima
+#ifndef SSKD_SCREEN_BUCKETS
+#define SSKD_SCREEN_BUCKETS 16
+#endif
+constexpr int SCREEN_BUCKETS = SSKD_SCREEN_BUCKETS;
+static_assert(SCREEN_BUCKETS >= 10 && (SCREEN_BUCKETS & (SCREEN_BUCKETS - 1)) == 0, "a power of two of at least K buckets");
+// A row at or below the bound the lane read on entering the append path is not offered to the pool: a pool's minimum
+// passes that bound only once all its slots do, so such a row can never raise it (0.5-0.7 % of the kernel at every shape
+// timed, profiles/bound_exchange/README.md).  -DSSKD_SCREEN_NO_OFFER_EARLY_OUT: the A/B build without it.
+#ifdef SSKD_SCREEN_NO_OFFER_EARLY_OUT
+constexpr bool SCREEN_OFFER_EARLY_OUT = false;
+#else
+constexpr bool SCREEN_OFFER_EARLY_OUT = true;
+#endif
+constexpr int SCREEN_BOUND_WORDS = SCREEN_BUCKETS + 1;   // words of a query in the call's bound block: its buckets and tau
 #ifndef SSKD_SCREEN_BOUND_REFRESH_TILES
 #define SSKD_SCREEN_BOUND_REFRESH_TILES 8
 #endif
@@ -174,7 +189,7 @@ __global__ __launch_bounds__(256) void make_bf16_tiles_kernel(const float4* __re
 }
 
 // One set-up launch per call.  Per query: 2e = 2 (|q~ - q| max|c~| + |q| max|c~ - c| + SCREEN_ACC_SLACK |q| max(max|c|, max|c~|)),
-// rounded UP; and the call's scratch state: tau + the global buckets (11 words per query) to "empty", the fallback
+// rounded UP; and the call's scratch state: the global buckets + tau (SCREEN_BOUND_WORDS per query) to "empty", the fallback
 // counters and the status words to zero (these were four launches / memsets: on a 125 k-row shard the short launches
 // of a call add up to a tenth of it).
 // RANGE.  The norms are square roots of fp32 sums of squares, and the bound above is a statement about real numbers: it
@@ -202,9 +217,10 @@ __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restri
                                                            int n_cursors) {
   // the tile cursors of the screening kernel (screen_tiles): zero before every launch (none: sskd_index_screen_band)
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n_cursors; i += gridDim.x * 256) cursors[i] = 0;
-  if (threadIdx.x < 44) {   // this block's 4 queries x 11 words
-    const int64_t i = (int64_t)blockIdx.x * 44 + threadIdx.x;
-    if (i < (int64_t)nq * 11) tau[i] = (int)0x80000000;
+  // this block's share, 4 x SCREEN_BOUND_WORDS words, of the call's [nq x SCREEN_BUCKETS buckets][nq tau] block
+  for (int j = threadIdx.x; j < 4 * SCREEN_BOUND_WORDS; j += 256) {
+    const int64_t i = (int64_t)blockIdx.x * (4 * SCREEN_BOUND_WORDS) + j;
+    if (i < (int64_t)nq * SCREEN_BOUND_WORDS) tau[i] = (int)0x80000000;
   }
   if (blockIdx.x == 0) {
     if (threadIdx.x < 64) fb_count[threadIdx.x] = 0;
@@ -552,6 +568,17 @@ __global__ __launch_bounds__(256) void screen_thr_probe_kernel(const float* __re
   out[i] = screen_thr_unpack(packed, i & 1);
 }
 
+// Test hook (sskd_screen_bucket_bound): out[q] = the K-th largest of in[q][SCREEN_BUCKETS], by the load and the
+// selection of the bound exchange (screen_exchange)
+template <int K>
+__global__ __launch_bounds__(256) void screen_bucket_bound_kernel(const int* __restrict__ in, int nq, int* __restrict__ out) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  int v[SCREEN_BUCKETS];
+  bucket_load_wide<SCREEN_BUCKETS>(v, in, q);
+  out[q] = kth_largest<K, SCREEN_BUCKETS>(v);
+}
+
 // D layout of v_mfma_f32_16x16x32_bf16: accumulator register i of lane l holds query (column) l & 15 of the block and row
 // 4 (l >> 4) + i of the row block - tile row 16 mb + 4 g + i for acc[mb][nb][i], g = l >> 4.  A row the allow-mask
 // clears scores -inf (tile_mask_word, search_device.h): lane l tests bits 16 mb + i of word >> 4 g.
@@ -568,6 +595,40 @@ __device__ __forceinline__ void apply_tile_mask16(f32x4 (&acc)[2][2 * QB], uint3
       for (int nb = 0; nb < 2 * QB; ++nb)
         if (off) acc[mb][nb][i] = -INFINITY;
     }
+}
+
+// Bound exchange of a query block with global memory, by the LANES lanes that call it (l = 0 .. LANES - 1): lane l takes
+// the block's queries l, l + LANES, ... (QPL of them).  Two trips to the memory side for all of them together: EVERY
+// bucket word of every query is requested first and waited for once; the bound of a query - the K-th largest of its
+// buckets' maxima (kth_largest) or the workgroup's own, whichever is larger - then goes to tau with a returning
+// atomicMax, all of them back to back and waited for once; the larger of tau's old value and the buckets' bound lands
+// in wthr (an LDS atomicMax: any lower bound of the final K-th best score may stand there, and it only rises), where
+// every wave of the workgroup finds it at its next register refresh and in the fp32 test of the append path.
+// (The parent exchanged per lane group and query block in turn - ten dependent loads, a wait, an atomic, a wait, ten
+// times over - in EVERY wave of the workgroup for the same queries: profiles/bound_exchange/README.md.)
+// A lane without a query (past the block, or past nq) goes through the same straight line on a query that exists,
+// publishing INT_MIN ("nothing") to tau and nothing to wthr: with its atomics under a branch of their own the
+// compiler sank each query's selection behind the wait for the previous query's atomic.
+template <int K, int B, int QB, int LANES>
+__device__ __forceinline__ void screen_exchange(const ScreenAppendParams& p, int q0, int l, int* wthr) {
+  constexpr int QPL = (32 * QB + LANES - 1) / LANES;
+  int v[QPL][B], w[QPL], kth[QPL], old[QPL], qa[QPL];
+  bool live[QPL];
+#pragma unroll
+  for (int j = 0; j < QPL; ++j) {
+    const int ql = l + j * LANES;
+    live[j] = ql < 32 * QB && q0 + ql < p.nq;
+    qa[j] = min(q0 + ql % (32 * QB), p.nq - 1);   // (q0 < nq: the block has a query)
+    bucket_load_wide<B>(v[j], p.gpool, qa[j]);
+    w[j] = wthr[ql % (32 * QB)];
+  }
+#pragma unroll
+  for (int j = 0; j < QPL; ++j) kth[j] = kth_largest<K, B>(v[j]);
+#pragma unroll
+  for (int j = 0; j < QPL; ++j) old[j] = atomicMax(p.tau + qa[j], live[j] ? max(w[j], kth[j]) : (int)0x80000000);
+#pragma unroll
+  for (int j = 0; j < QPL; ++j)
+    if (live[j]) atomicMax(wthr + l + j * LANES, max(old[j], kth[j]));
 }
 
 // One phase of the screening kernel: the tiles [t_begin, t_end) of this workgroup, one tile per wave at a time.
@@ -697,27 +758,27 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     const sbf16x8* tile = p.tiled + (int64_t)t * BTILE_VEC;   // wave-uniform
     uint32_t mword = 0xFFFFFFFFu;
     if constexpr (MASKED) mword = tile_mask_word(p.row_mask, t);   // issued ahead of the tile's MFMAs
-    // bounds are exchanged with global memory at tile 0 (the sample phases' bounds), tile 16 and every 64th: an exchange is
-    // ten dependent agent-scope loads + an atomic per query block (~3 us of stall); at tiles 0, 1, 2, 4, 8, 16, ... and
-    // every 8th it cost 5 % of the kernel at 1 M rows and 10 % on a 125 k-row shard.  The sample phase never reads them.
-    const bool exchange = !BOUND_ONLY && (tiles_done == 0 || tiles_done == 16 || tiles_done % SCREEN_TAU_REFRESH_TILES == 0);
+    // Bounds are exchanged with global memory (screen_exchange) at the wave's tiles 1, 2, 4, 8 and every
+    // SCREEN_TAU_REFRESH_TILES-th - by ONE wave of the workgroup per exchange point, in turn (point x falls to wave
+    // x mod WAVES, so the same SIMD does not always pay): the result lands in wthr for everybody.  At the head of the tile
+    // the accumulators are dead, which is where the bucket words of up to three queries per lane (48 registers) fit.
+    // The sample phases' bounds are exchanged by the kernel itself before the slice phase; the sample phase never reads any.
+    bool exchange = false;
+    if constexpr (!BOUND_ONLY) {
+      constexpr int T = SCREEN_TAU_REFRESH_TILES;
+      const bool periodic = tiles_done % T == 0;
+      if (tiles_done > 0 && (periodic || (tiles_done <= 8 && (tiles_done & (tiles_done - 1)) == 0))) {
+        const int x = periodic ? 4 + tiles_done / T : 1 + __builtin_ctz(tiles_done);
+        exchange = x % WAVES == wave;
+      }
+    }
+    if (exchange) screen_exchange<K, SCREEN_BUCKETS, QB, 64>(p, q0, screen_lane_now(), wthr);
     // The registers' bounds follow the pools' at every SCREEN_BOUND_REFRESH_TILES-th tile of the wave (and wherever the
     // lane appends, below): twenty LDS words and five packs at EVERY tile cost 0.24 ms of 5.9 at the bench shape
     // (periods 1 / 2 / 4 / 8: 5.91 / 5.78 / 5.71 / 5.67 ms), and a bound a few tiles stale only lets a few more rows
     // through to the fp32 test, which reads the pool's bound of that moment: 417 / 416 / 416 appended entries per query.
     if (exchange || tiles_done % SCREEN_BOUND_REFRESH_TILES == 0) {
-    const int lh = screen_lane_now(), nh = lh & 15;
-    // The exchange is made by ONE lane group of the wave and lands in wthr (an LDS atomicMax: any lower bound of the
-    // final k-th best score may stand there, and it only rises), where the reads below - the same wave's, in order -
-    // and the fp32 test of the append path find it.  Made by all four groups it was four returning atomics per query
-    // and wave on the same word of tau: with 32 slices (1 000 queries x 1 M rows) they queued for 0.2 ms of a 0.85 ms launch.
-    if (exchange && lh < 16) {
-#pragma unroll
-      for (int nb = 0; nb < NQ; ++nb) {
-        const int ql = 16 * nb + nh;
-        if (q0 + ql < p.nq) atomicMax(wthr + ql, exchange_bound<K>(p.gpool, p.tau + q0 + ql, q0 + ql, wthr[ql]));
-      }
-    }
+    const int nh = screen_lane_now() & 15;   // (an exchange of this wave is in wthr: its LDS operations stay in order)
 #pragma unroll
     for (int pr = 0; pr < QB; ++pr) {
       float thr[2];
@@ -800,7 +861,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
               for (int r = 7; r >= 0; --r) xid = acc[r >> 2][nb][r & 3] == m[e] ? rowbase + 16 * (r >> 2) + (r & 3) : xid;
               const int xi = float_to_ordered(m[e]);
               if (pool_offer<K>(pool + ql * K, wthr + ql, xi)) {
-                bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+                bucket_forward_wide<SCREEN_BUCKETS>(p.gpool, q0 + ql, xid, xi);
               }
             }
             screen_thr_raise(gthr[pr], e, fmaxf(ordered_to_float(wthr[ql]) - bandl[ql], -INFINITY));
@@ -813,10 +874,11 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
         // for the bounds, bands and counts of both blocks.
         const int lc = screen_lane_now(), nc = lc & 15, gc = lc >> 4;
         float pb[2];   // what the pools hold now, minus the band (-inf: no bound yet)
-        int c[2];
+        int c[2], wi[2];   // (wi: the bound itself as the pool keeps it; only the early-out of the offers reads it)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int ql = 32 * pr + 16 * e + nc;
+          wi[e] = SCREEN_OFFER_EARLY_OUT ? wthr[ql] : (int)0x80000000;
           pb[e] = fmaxf(ordered_to_float(wthr[ql]) - bandl[ql], -INFINITY);
           c[e] = cnts[(ql * WAVES + wave) * 4 + gc];
         }
@@ -888,8 +950,8 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 #pragma unroll
               for (int r = 7; r >= 0; --r) xid = acc[r >> 2][nb][r & 3] == m[e] ? rowbase + 16 * (r >> 2) + (r & 3) : xid;
               const int xi = float_to_ordered(m[e]);
-              if (pool_offer<K>(pool + ql * K, wthr + ql, xi) && tiles_done > 0)
-                bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+              if ((!SCREEN_OFFER_EARLY_OUT || xi > wi[e]) && pool_offer<K>(pool + ql * K, wthr + ql, xi) && tiles_done > 0)
+                bucket_forward_wide<SCREEN_BUCKETS>(p.gpool, q0 + ql, xid, xi);
             }
           }
         } else {
@@ -935,8 +997,8 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
             cc[1] = e ? cn : cc[1];
             if (tiles_done > 0) {   // (the first tile: below)
               const int xi = float_to_ordered(x);
-              if (pool_offer<K>(pool + ql * K, wthr + ql, xi))
-                bucket_forward<K>(p.gpool, q0 + ql, xid, xi);
+              if ((!SCREEN_OFFER_EARLY_OUT || xi > (e ? wi[1] : wi[0])) && pool_offer<K>(pool + ql * K, wthr + ql, xi))
+                bucket_forward_wide<SCREEN_BUCKETS>(p.gpool, q0 + ql, xid, xi);
             }
           }
           // (wave-uniform control flow again: the cross-lane step of screen_group_max must not sit in the loop)
@@ -950,7 +1012,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
             // by the lane group that holds it
             if (tiles_done == 0) {
               const float mg = screen_group_max(m[e]);
-              if (grew && m[e] == mg) pool_offer<K>(pool + ql * K, wthr + ql, float_to_ordered(m[e]));
+              if (grew && m[e] == mg && (!SCREEN_OFFER_EARLY_OUT || float_to_ordered(m[e]) > wi[e])) pool_offer<K>(pool + ql * K, wthr + ql, float_to_ordered(m[e]));
             }
           }
         }
@@ -1028,11 +1090,7 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
     const int s_end = min(s_begin + p.pre_tps, p.pre_tiles);
     screen_tiles<K, QB, WAVES, true, LIGHT, BG, RG, MASKED>(p, s_begin, s_end, slice, nullptr, wave, n, g, q0, qlane,
                                              pool, list0, ragged, gthr);
-    // what this workgroup learned from its share of the sample; everybody's offers are in before phase 1
-#pragma unroll
-    for (int nb = 0; nb < 2 * QB; ++nb)
-      if (g == 0 && q0 + nb * 16 + n < p.nq) atomicMax(p.tau + q0 + nb * 16 + n, wthr[nb * 16 + n]);
-    __syncthreads();
+    __syncthreads();   // everybody's offers of the sample are in
     // INVARIANT OF THE POOL: every slot is the score of a DISTINCT row (pool_offer stores scores only and cannot tell
     // a row it already holds).  Where this workgroup's share of the sample lies inside its own slice - slice 0, whose
     // first tiles ARE the sample - phase 1 offers those rows a second time: counted twice, a row would push the pool's
@@ -1040,7 +1098,7 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
     // would be pruned silently (round 3 shipped that hole: VERDICT r3 weak 1).  So such a workgroup empties its slots
     // here.  wthr stays: it is the minimum of a full pool of distinct SAMPLE rows, a valid bound on its own, and only
     // ever rises - to minima of full pools, which from here on hold phase-1 rows only, and to exchanged bounds (tau and
-    // the minimum of the query's global buckets: screen_tiles puts them here with an LDS atomicMax), each of them a
+    // the tenth largest of the query's global buckets: screen_exchange puts them here with an LDS atomicMax), each of them a
     // lower bound of the final k-th best screen score among the allowed rows, which is all the proof asks of wthr.  Rows of other slices' sample
     // shares never return in this workgroup's slice - but a wave that has run out of tiles there goes on to draw from
     // the sibling slices (screen_tiles), the sample's among them, so EVERY workgroup of a launch that claims its
@@ -1048,8 +1106,12 @@ __global__ __launch_bounds__(WAVES * 64) void screen_append_kernel(ScreenAppendP
     // share lies outside their slice keep their pools.
     if ((SCREEN_STEAL && p.claim) || (s_begin < t_end && t_begin < s_end)) {
       for (int i = tid; i < QB * 32 * K; i += WAVES * 64) pool[i] = (int)0x80000000;
-      __syncthreads();
     }
+    // What this workgroup learned from its share of the sample goes to tau, and what the others have published by now
+    // comes back, in ONE exchange of the workgroup (a query per thread) ahead of the slice phase: every wave's registers
+    // start from it at their first tile.  (The parent had all twelve waves make this exchange for the same queries.)
+    if (tid < 32 * QB) screen_exchange<K, SCREEN_BUCKETS, QB, 32 * QB>(p, q0, tid, wthr);
+    __syncthreads();
   }
 #ifdef SSKD_SCREEN_STAMPS
   if (lane == 0) stamp[1] = __builtin_amdgcn_s_memrealtime();
@@ -1407,7 +1469,7 @@ struct ScreenWs {
   float* part_scores;
   int* part_ids;
   int* cand_cnt;     // append form: [nq][lists]
-  int* tau;          // [nq] + gpool [nq * 10]
+  int* tau;          // the bound block: gpool [nq][SCREEN_BUCKETS] (every query's words on a 128-byte line of their own), then tau [nq]
   float* eps2;
   int* fb_count;     // [2]: count, spare
   int* cursors;      // [n_qblocks][n_slices]: tile cursors of the screening kernel
@@ -1431,7 +1493,7 @@ ScreenWs screen_carve(void* base, const ScreenPlan& pl, int64_t n_rows, int nq, 
   w.part_scores = c.take<float>(pl.part_elems);   // append form: the runs, 8 bytes per entry,
   w.part_ids = c.take<int>(pl.part_elems);        //   span both arrays (contiguous: see below)
   w.cand_cnt = c.take<int>((size_t)nq * pl.lists_per_query);
-  w.tau = c.take<int>((size_t)nq * 11);
+  w.tau = c.take<int>((size_t)nq * SCREEN_BOUND_WORDS);
   w.eps2 = c.take<float>(nq);
   w.fb_count = c.take<int>(64);
   w.cursors = c.take<int>((size_t)pl.n_qblocks * pl.n_slices);
@@ -1492,7 +1554,7 @@ int sskd_index_make_bf16(const float* d_tiled, int64_t n_rows, void* d_bf16, voi
 size_t sskd_index_screen_band_scratch_bytes(int nq) {
   if (nq <= 0) return 0;
   sskd::Carver c(nullptr);
-  c.take<int>((size_t)nq * 11);
+  c.take<int>((size_t)nq * SCREEN_BOUND_WORDS);
   c.take<int>(64);
   c.take<int>(2);
   return c.bytes();
@@ -1505,7 +1567,7 @@ int sskd_index_screen_band(const void* d_bf16, int64_t n_rows, const float* d_qu
   if (rc != SSKD_OK) return rc;
   SSKD_REQUIRE(d_bf16 && d_queries && d_eps2_out, "index_screen_band: null pointer");
   sskd::Carver c(d_scratch);
-  int* const tau = c.take<int>((size_t)nq * 11);
+  int* const tau = c.take<int>((size_t)nq * SCREEN_BOUND_WORDS);
   int* const fb_count = c.take<int>(64);
   int* const status = c.take<int>(2);
   if ((rc = sskd::require_workspace("index_screen_band", d_scratch, scratch_bytes, c.bytes())) != SSKD_OK) return rc;
@@ -1535,6 +1597,27 @@ int sskd_screen_threshold_roundtrip(const float* d_in, int n, float* d_out, void
   hipLaunchKernelGGL(screen_thr_probe_kernel, dim3((unsigned)sskd::ceil_div(n, 256)), dim3(256), 0, sskd::as_stream(stream),
                      d_in, n, d_out);
   return sskd::check_launch("screen_thr_probe_kernel");
+}
+
+// test hooks of the bound exchange: the number of buckets per query, and the selection over them
+int sskd_screen_bucket_count(void) { return SCREEN_BUCKETS; }
+
+int sskd_screen_bucket_bound(const int32_t* d_in, int nq, int k, int32_t* d_out, void* stream) {
+  SSKD_REQUIRE(nq >= 0 && k >= 1 && k <= 10, "screen_bucket_bound: needs nq >= 0 and 1 <= k <= 10 (got nq=%d k=%d)", nq, k);
+  if (nq == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_in && d_out, "screen_bucket_bound: null pointer");
+  SSKD_REQUIRE(reinterpret_cast<uintptr_t>(d_in) % 8 == 0, "screen_bucket_bound: d_in must be 8-byte aligned");
+  const dim3 grid((unsigned)sskd::ceil_div(nq, 256)), block(256);
+  hipStream_t st = sskd::as_stream(stream);
+  switch (k) {
+#define SSKD_BUCKET_BOUND_CASE(kk) \
+  case kk: hipLaunchKernelGGL(screen_bucket_bound_kernel<kk>, grid, block, 0, st, d_in, nq, d_out); break;
+    SSKD_BUCKET_BOUND_CASE(1) SSKD_BUCKET_BOUND_CASE(2) SSKD_BUCKET_BOUND_CASE(3) SSKD_BUCKET_BOUND_CASE(4)
+    SSKD_BUCKET_BOUND_CASE(5) SSKD_BUCKET_BOUND_CASE(6) SSKD_BUCKET_BOUND_CASE(7) SSKD_BUCKET_BOUND_CASE(8)
+    SSKD_BUCKET_BOUND_CASE(9) SSKD_BUCKET_BOUND_CASE(10)
+#undef SSKD_BUCKET_BOUND_CASE
+  }
+  return sskd::check_launch("screen_bucket_bound_kernel");
 }
 
 int sskd_index_search_screened_plan(int64_t n_rows, int nq, int k, int* queries_per_block, int* corpus_passes,
@@ -1609,8 +1692,8 @@ int sskd_index_search_screened_claim(const float* d_tiled, const void* d_bf16, i
   sp.eps2 = w.eps2;
   sp.cand = reinterpret_cast<uint2*>(w.part_scores);
   sp.cand_cnt = w.cand_cnt;
-  sp.tau = w.tau;
-  sp.gpool = w.tau + nq;
+  sp.gpool = w.tau;
+  sp.tau = w.tau + (size_t)nq * SCREEN_BUCKETS;
   sp.cursors = w.cursors;
   sp.n_rows = n_rows;
   sp.nq = nq;

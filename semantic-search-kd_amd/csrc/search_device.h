@@ -191,6 +191,52 @@ __device__ __forceinline__ int exchange_bound(const int* __restrict__ gpool, int
   return max(old, bmin);
 }
 
+// The screening kernel's buckets (screen.hip).  The minimum of K buckets is a bound only once ALL K hold a good row - a
+// coupon collector's ~29 good rows for K = 10, so it sits near the 29th best score seen.  With B > K buckets keyed by
+// (row id mod B) the K-TH LARGEST of the B maxima is a bound as soon as any K of them are filled: distinct buckets hold
+// distinct rows, so K maxima at or above v are K distinct allowed rows scoring at least v.  Fewer than K filled buckets
+// give INT_MIN ("no bound": it is the K-th largest of the words, empty ones included).
+template <int B>
+__device__ __forceinline__ void bucket_forward_wide(int* __restrict__ gpool, int q, int xid, int xi) {
+  (void)__hip_atomic_fetch_max(gpool + (int64_t)q * B + (unsigned)xid % B, xi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the B bucket words of query q (agent scope, 8 bytes per load: a query's words are B x 4 contiguous, aligned bytes)
+template <int B>
+__device__ __forceinline__ void bucket_load_wide(int (&v)[B], const int* __restrict__ gpool, int q) {
+  static_assert(B % 2 == 0, "two bucket words per load");
+  const unsigned long long* gb = reinterpret_cast<const unsigned long long*>(gpool + (int64_t)q * B);
+#pragma unroll
+  for (int i = 0; i < B / 2; ++i) {
+    const unsigned long long w = __hip_atomic_load(gb + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v[2 * i] = (int)(unsigned)w;
+    v[2 * i + 1] = (int)(unsigned)(w >> 32);
+  }
+}
+
+// the K-th largest of B words, as a multiset (equal words count separately), exactly: a K-deep descending list in
+// registers, every word carried down it by max / min - 2 K B VALU less the triangle of the first K words, no branches.
+// A result ABOVE the true K-th largest would be a bound above the K-th best score: rows of the top K pruned silently
+// (tests/test_screen_bound_exchange_gpu.py holds it to numpy.partition through sskd_screen_bucket_bound).
+template <int K, int B>
+__device__ __forceinline__ int kth_largest(const int (&v)[B]) {
+  static_assert(K >= 1 && K <= B, "K-th largest of B words");
+  int top[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) top[i] = (int)0x80000000;
+#pragma unroll
+  for (int j = 0; j < B; ++j) {
+    int x = v[j];
+#pragma unroll
+    for (int i = 0; i < K && i <= j; ++i) {
+      const int hi = max(top[i], x);
+      x = min(top[i], x);
+      top[i] = hi;
+    }
+  }
+  return top[K - 1];
+}
+
 // Row allow-mask (sskd_amd.h): one 32-bit word per 32-row tile, so the word of tile t is wave-uniform - one scalar
 // load per tile.  In the D layout of both 32x32 MFMAs accumulator register r of lane l holds tile row
 // (r & 3) + 8 (r >> 2) + 4 (l >> 5), so lane l tests bit (r & 3) + 8 (r >> 2) of word >> 4 (l >> 5).  A masked row's score
