@@ -17,6 +17,9 @@
  *   - every function returns 0 (SSKD_OK) or an SSKD_ERR_* code and never throws;
  *     `sskd_last_error()` gives a thread-local message for the last failure
  *   - scratch memory is caller-provided; `*_workspace_bytes()` sizes it
+ *   - the workspace may hold anything on entry (a call initialises every byte it later reads), no byte outside
+ *     [d_workspace, d_workspace + the size its `*_workspace_bytes()` reports) is touched, and its contents on return
+ *     are unspecified (DESIGN.md "Workspace contract"; tests/test_workspace_contract_gpu.py)
  */
 #ifndef SSKD_AMD_H
 #define SSKD_AMD_H

@@ -102,28 +102,36 @@ class Probe:
         torch.cuda.synchronize()
         return hid.cpu().double(), ctx.cpu().double()
 
-    def forward(self, inp, layers, normalize):
+    def _workspace(self, cfg, B, S, ws):
+        """``(pointer, bytes)`` of the call's workspace: the caller's ``ws`` pair, or a fresh buffer of the reported size"""
+        if ws is not None:
+            return ws
+        buf = torch.empty(int(self.lib.sskd_encoder_workspace_bytes(cfg, B, S)), dtype=torch.uint8, device="cuda")
+        self._ws_keep = buf
+        return buf.data_ptr(), buf.numel()
+
+    def forward(self, inp, layers, normalize, ws=None):
         ids, mask = torch.from_numpy(inp["ids"]).cuda(), torch.from_numpy(inp["mask"]).cuda()
         B, S = ids.shape
         cfg = self.ccfg(layers)
         out = torch.full((B, 384), float("nan"), device="cuda")
-        ws = torch.empty(int(self.lib.sskd_encoder_workspace_bytes(cfg, B, S)), dtype=torch.uint8, device="cuda")
+        ws_ptr, ws_bytes = self._workspace(cfg, B, S, ws)
         self.native.check(self.lib.sskd_encoder_forward(cfg, self.w.struct, ids.data_ptr(), mask.data_ptr(), B, S,
-                                                        int(normalize), out.data_ptr(), ws.data_ptr(), ws.numel(), _st()))
+                                                        int(normalize), out.data_ptr(), ws_ptr, ws_bytes, _st()))
         torch.cuda.synchronize()
         return out.cpu().double()
 
-    def forward_packed(self, inp, layers, normalize):
+    def forward_packed(self, inp, layers, normalize, ws=None):
         ids, seg = torch.from_numpy(inp["ids"]).cuda(), torch.from_numpy(inp["seg"]).cuda()
         table = torch.from_numpy(inp["table"]).cuda()
         B, S = ids.shape
         cfg = self.ccfg(layers)
         n_seq = inp["table"].shape[0]
         out = torch.full((n_seq, 384), float("nan"), device="cuda")
-        ws = torch.empty(int(self.lib.sskd_encoder_workspace_bytes(cfg, B, S)), dtype=torch.uint8, device="cuda")
+        ws_ptr, ws_bytes = self._workspace(cfg, B, S, ws)
         self.native.check(self.lib.sskd_encoder_forward_packed(
             cfg, self.w.struct, ids.data_ptr(), seg.data_ptr(), B, S, table.data_ptr(), n_seq, int(normalize), out.data_ptr(),
-            ws.data_ptr(), ws.numel(), _st()))
+            ws_ptr, ws_bytes, _st()))
         torch.cuda.synchronize()
         return out.cpu().double()
 

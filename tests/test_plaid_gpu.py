@@ -87,15 +87,32 @@ def centroid_scores(lib, cen_bits, q_bits, ld=None):
     return host[GUARD: GUARD + C_ * ld].reshape(C_, ld)
 
 
-def candidates(lib, world, S, q_lims, nprobe, R, mask_words=None, ws_bytes=None, expect=0, **override):
+class _Lent:
+    """a caller's ``(pointer, bytes)`` workspace behind the two tensor methods ``candidates`` uses"""
+
+    def __init__(self, ptr, nbytes):
+        self._ptr, self._n = int(ptr), int(nbytes)
+
+    def data_ptr(self):
+        return self._ptr
+
+    def numel(self):
+        return self._n
+
+
+def candidates(lib, world, S, q_lims, nprobe, R, mask_words=None, ws_bytes=None, expect=0, ws=None, **override):
     """``sskd_plaid_candidates`` on host ``S`` with guarded outputs: ``(rc, cand_I, cand_A, n_cand, intact)`` - ``intact``
-    says that nothing but the outputs proper was written (and with ``expect != 0``: nothing at all)."""
+    says that nothing but the outputs proper was written (and with ``expect != 0``: nothing at all).  ``ws``: the caller's
+    ``(pointer, bytes)`` workspace instead of a fresh buffer."""
     late = world.late
     q_lims = np.ascontiguousarray(q_lims, np.int64)
     nq = q_lims.size - 1
     S_dev, lims_dev = _dev(np.ascontiguousarray(S, np.float32)), _dev(q_lims)
     need = int(lib.sskd_plaid_candidates_workspace_bytes(max(nq, 1), world.n, min(max(nprobe, 1), 32)))
-    ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device="cuda")
+    if ws is not None:
+        ws = _Lent(*ws)
+    else:
+        ws = torch.empty(max(need if ws_bytes is None else ws_bytes, 256), dtype=torch.uint8, device="cuda")
     cells = max(nq, 1) * max(min(R, 1024), 1)
     I = torch.full((cells + 2 * GUARD,), -777, dtype=torch.int64, device="cuda")
     A = torch.full((cells + 2 * GUARD,), -555.0, dtype=torch.float32, device="cuda")

@@ -55,16 +55,19 @@ def _pack(lib, runs, nq, cap):
 SENTINEL_ID, SENTINEL_BITS = -7, 0x7FC00ABC
 
 
-def _merge(lib, buf, w, nq, cap, max_results, room=None, outputs=True):
-    """-> (lims, scores, ids) host arrays of ``room`` entries (default max_results + 5); untouched slots keep sentinels"""
+def _merge(lib, buf, w, nq, cap, max_results, room=None, outputs=True, ws=None):
+    """-> (lims, scores, ids) host arrays of ``room`` entries (default max_results + 5); untouched slots keep sentinels.
+    ``ws``: the caller's ``(pointer, bytes)`` workspace instead of a fresh buffer of the reported size."""
     room = max_results + 5 if room is None else room
     lims = torch.full((nq + 1,), -5, dtype=torch.int64, device="cuda")
     out_s = torch.full((room,), SENTINEL_BITS, dtype=torch.int32, device="cuda")
     out_i = torch.full((room,), SENTINEL_ID, dtype=torch.int64, device="cuda")
-    ws = torch.empty(max(int(lib.sskd_range_merge_workspace_bytes(w, nq, max_results)), 1), dtype=torch.uint8, device="cuda")
+    if ws is None:
+        own = torch.empty(max(int(lib.sskd_range_merge_workspace_bytes(w, nq, max_results)), 1), dtype=torch.uint8, device="cuda")
+        ws = (own.data_ptr(), own.numel())
     _native.check(lib.sskd_range_merge_packed(buf.data_ptr(), w, nq, cap, lims.data_ptr(),
                                               out_s.data_ptr() if outputs else None, out_i.data_ptr() if outputs else None,
-                                              max_results, ws.data_ptr(), ws.numel(), stream()))
+                                              max_results, ws[0], ws[1], stream()))
     torch.cuda.synchronize()
     return lims.cpu().numpy(), out_s.cpu().numpy().view(np.float32), out_i.cpu().numpy()
 
