@@ -11,28 +11,11 @@
 // is off in these kernels; tests/late_train_cases.py restates them bit for bit) - so there are no atomics and a gradient's
 // bits do not depend on the launch.  A row gather is latency-bound (768 bytes per dependent address), so the loads of
 // L_INFLIGHT contributions are issued before the first add waits.
-#include <cfloat>
-#include <cmath>
-
-#include "search_device.h"
+#include "late_device.h"
 
 namespace {
 
-constexpr int L_WAVES = 4;
-constexpr int L_THREADS = L_WAVES * 64;
-constexpr int L_ROW_VEC = DIM / 8;          // 48 16-byte vectors per bf16 token row
-constexpr int L_TQ_MAX = SSKD_LATE_TQ_MAX;  // 128
-constexpr int L_R_MAX = SSKD_LATE_R_MAX;    // 1024
 constexpr int L_INFLIGHT = 8;               // source rows whose loads are in flight together
-
-__device__ inline void widen8(const uint4& v, float (&x)[8]) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    x[2 * j] = __uint_as_float(w[j] << 16);
-    x[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-}
 
 __device__ inline void store8(float* dst, const float (&a)[8]) {
   reinterpret_cast<float4*>(dst)[0] = make_float4(a[0], a[1], a[2], a[3]);
@@ -61,8 +44,8 @@ __global__ __launch_bounds__(L_THREADS) void late_maxsim_bwd_q_kernel(const Grad
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x, i = blockIdx.y * L_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t q0 = p.q_lims[q], tq = p.q_lims[q + 1] - q0;
-  if (q0 < 0 || tq < 0 || q0 + tq > p.n_q_tokens) return;   // (the host validated its copy of the lims)
+  int64_t q0, tq;
+  query_range(p.q_lims, p.n_q_tokens, q, q0, tq);
   if (i >= tq || i >= p.tq_stride) return;
   float acc[8];
 #pragma unroll
@@ -191,17 +174,14 @@ __global__ __launch_bounds__(L_THREADS) void late_pack_bwd_kernel(const uint16_t
     return;
   }
   float x[8], g[8];
-  float p = 0.f;
   if (lane < L_ROW_VEC) {
     widen8(*reinterpret_cast<const uint4*>(hidden + tok * DIM + 8 * lane), x);
     const float4 g0 = reinterpret_cast<const float4*>(dtok + row * DIM + 8 * lane)[0];
     const float4 g1 = reinterpret_cast<const float4*>(dtok + row * DIM + 8 * lane)[1];
     g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w;
     g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) p = fmaf(x[j], x[j], p);   // exact products: the pack's chain
   }
-  const float ss = wave_sum(p);
+  const float ss = row_sum_squares(x, lane < L_ROW_VEC);   // exact products: the pack's chain
   const float n = fmaxf(__builtin_sqrtf(ss), 1e-12f);
   float y[8];
   float d = 0.f;
@@ -215,43 +195,15 @@ __global__ __launch_bounds__(L_THREADS) void late_pack_bwd_kernel(const uint16_t
   }
   const float dot = wave_sum(d);
   if (lane < L_ROW_VEC) {
-    uint32_t o[4];
+    float dh[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t h[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const float t = y[2 * j + e] * dot;
-        const float num = g[2 * j + e] - t;
-        const uint32_t u = __float_as_uint(num / n);
-        h[e] = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;   // round to nearest even (finite input)
-      }
-      o[j] = h[0] | (h[1] << 16);
+    for (int j = 0; j < 8; ++j) {
+      const float t = y[j] * dot;
+      const float num = g[j] - t;
+      dh[j] = num / n;
     }
-    *reinterpret_cast<uint4*>(dhidden + tok * DIM + 8 * lane) = make_uint4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<uint4*>(dhidden + tok * DIM + 8 * lane) = pack8(dh);
   }
-}
-
-bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
-
-// what both gradient entries check of the query side: returns the largest Tq, or -1 after recording the error
-int check_query_lims(const char* what, const int64_t* q_lims, int nq, int64_t n_q_tokens, int tq_stride) {
-  if (!q_lims) return sskd::fail(SSKD_ERR_INVALID, "%s: the host copy of q_lims is required", what), -1;
-  if (q_lims[0] != 0 || q_lims[nq] != n_q_tokens)
-    return sskd::fail(SSKD_ERR_INVALID, "%s: q_lims runs from %lld to %lld, there are %lld query token rows", what,
-                      (long long)q_lims[0], (long long)q_lims[nq], (long long)n_q_tokens), -1;
-  int max_tq = 0;
-  for (int q = 0; q < nq; ++q) {
-    const int64_t tq = q_lims[q + 1] - q_lims[q];
-    if (tq < 1 || tq > L_TQ_MAX)
-      return sskd::fail(SSKD_ERR_INVALID, "%s: query %d has Tq=%lld outside [1, %d] (q_lims must ascend)", what, q, (long long)tq,
-                        L_TQ_MAX), -1;
-    if (tq > max_tq) max_tq = (int)tq;
-  }
-  if (tq_stride != (max_tq + 31) / 32 * 32)
-    return sskd::fail(SSKD_ERR_INVALID, "%s: tq_stride=%d, the largest Tq=%d rounded up to 32 is %d", what, tq_stride, max_tq,
-                      (max_tq + 31) / 32 * 32), -1;
-  return max_tq;
 }
 
 }  // namespace

@@ -10,61 +10,36 @@
 //   plaid_interact_kernel  approx(q, r) = sum_i max_j S[cid_j, t_i] over ALL tokens of r, one wave per (query, candidate);
 //   plaid_select_kernel    the best R by (approx descending, row ascending): radix select on a 64-bit key, rank-order sort.
 // Everything after S is a function of S's bits: no step rounds but the sequential fp32 sum of the interaction.
-#include <cfloat>
-#include <cmath>
-
-#include "search_device.h"
+#include "late_device.h"
 #include "search_host.h"   // sskd::MAX_SHARD_ROWS: rows are int32 per index
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int P_THREADS = 256;
-constexpr int P_WAVES = P_THREADS / 64;
-constexpr int P_KSTEPS = DIM / 16;              // 24 k-steps of v_mfma_f32_32x32x16_bf16
-constexpr int P_ROW_VEC = DIM / 8;              // 48 16-byte vectors per bf16 row
-constexpr int P_TQ_MAX = SSKD_LATE_TQ_MAX;      // 128
-constexpr int P_R_MAX = SSKD_LATE_R_MAX;        // 1024
-constexpr int P_C_MAX = SSKD_LATE_C_MAX;        // 65 536
 constexpr int P_NPROBE_MAX = SSKD_PLAID_NPROBE_MAX;   // 32
 constexpr int P_PARTS_MAX = 64;                 // parts of the centroid range one token's probe search is cut into
 constexpr int P_RANK_THREADS = 1024;
 constexpr size_t WORKSPACE_BUDGET = (size_t)256 << 20;   // what the size query asks for at most (if one query fits)
 
 // ------------------------------------------------------------------------------------------------ centroid scores
-// A workgroup of 4 waves serves one block of 32 query tokens, staged once in LDS in B-fragment order as late_score_kernel
-// stages a query (24 KiB); wave w walks centroid tiles of 32 rows, each read by one burst of 24 16-byte loads per lane, as
-// that kernel reads a document tile.  Element (c, t) is the chain of 24 MFMAs over row c and row t alone, so its bits do
-// not depend on what else the batch holds.  Tokens past T are zero rows, centroids past C re-read the last real row;
-// neither is stored.
-__global__ __launch_bounds__(P_THREADS) void plaid_scores_kernel(const bf16x8* __restrict__ q_tokens, int64_t T,
+// The tile engine of late_device.h with one block: a workgroup of 4 waves serves one block of 32 query tokens, staged once
+// in LDS; wave w walks centroid tiles of 32 rows.  Element (c, t) is the chain of 24 MFMAs over row c and row t alone, so
+// its bits do not depend on what else the batch holds.  Tokens past T are zero rows, centroids past C re-read the last
+// real row; neither is stored.
+__global__ __launch_bounds__(L_THREADS) void plaid_scores_kernel(const bf16x8* __restrict__ q_tokens, int64_t T,
                                                                  const bf16x8* __restrict__ centroids, int C,
                                                                  float* __restrict__ S, int64_t ld) {
-  __shared__ bf16x8 qs[P_KSTEPS][64];   // B fragments: [k-step][lane]
+  __shared__ QueryFragments<1> qs;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r32 = lane & 31, h = lane >> 5;
   const int64_t t0 = (int64_t)blockIdx.y * 32;
-  // stage: token row i, 16-byte vector ch = 2 s + half -> qs[s][32 half + i]
-  for (int idx = threadIdx.x; idx < 32 * P_ROW_VEC; idx += P_THREADS) {
-    const int i = idx / P_ROW_VEC, ch = idx % P_ROW_VEC;
-    bf16x8 v = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
-    if (t0 + i < T) v = q_tokens[(t0 + i) * P_ROW_VEC + ch];
-    qs[ch >> 1][((ch & 1) << 5) | i] = v;
-  }
+  stage_query<1>(qs, q_tokens, t0, (int)(T - t0 < 32 ? T - t0 : 32));
   __syncthreads();
   const int tiles = (C + 31) >> 5;
-  for (int ct = blockIdx.x * P_WAVES + wave; ct < tiles; ct += gridDim.x * P_WAVES) {
+  for (int ct = blockIdx.x * L_WAVES + wave; ct < tiles; ct += gridDim.x * L_WAVES) {
     const int c = min(ct * 32 + r32, C - 1);
-    const bf16x8* src = centroids + (int64_t)c * P_ROW_VEC + h;
-    bf16x8 a[P_KSTEPS];
-#pragma unroll
-    for (int s = 0; s < P_KSTEPS; ++s) a[s] = src[2 * s];
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < P_KSTEPS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], qs[s][lane], acc, 0, 0, 0);
+    bf16x8 a[L_KSTEPS];
+    load_row_fragments(a, centroids + (int64_t)c * L_ROW_VEC + h);
+    const f32x16 acc = tile_product(a, qs[0], lane);
     // register r of lane l: centroid 32 ct + acc_row(r) + 4 (l >> 5), query token t0 + (l & 31): 128 contiguous bytes
     // per lane half and register
     if (t0 + r32 < T) {
@@ -93,9 +68,9 @@ struct PlaidParams {
   int parts, span;           // probe search: parts of `span` centroids each
   int words;                 // ceil(n_rows / 32)
   // workspace of the chunk, indexed by the query's position ql in it
-  float* part_s;             // [chunk][P_TQ_MAX][parts][nprobe]
+  float* part_s;             // [chunk][L_TQ_MAX][parts][nprobe]
   int32_t* part_c;           //   "
-  int32_t* probes;           // [chunk][P_TQ_MAX][nprobe]
+  int32_t* probes;           // [chunk][L_TQ_MAX][nprobe]
   uint32_t* bitmap;          // [chunk][words_pad]
   int32_t* rows;             // [chunk][rows_pad]   the candidates, ascending
   float* approx;             // [chunk][rows_pad]
@@ -106,12 +81,11 @@ struct PlaidParams {
   int32_t* n_cand;           // [nq]
 };
 
-// the query's token range, clamped as late_score_kernel clamps it (the host validated its copy of the lims)
+// the query's token range (late_device.h), at most L_TQ_MAX tokens of it
 __device__ inline void query_range(const PlaidParams& p, int q, int64_t& q_begin, int& Tq) {
-  q_begin = p.q_lims[q];
-  int64_t tq = p.q_lims[q + 1] - q_begin;
-  if (q_begin < 0 || tq < 0 || q_begin + tq > p.n_q_tokens) { q_begin = 0; tq = 0; }
-  Tq = (int)(tq < P_TQ_MAX ? tq : P_TQ_MAX);
+  int64_t tq;
+  query_range(p.q_lims, p.n_q_tokens, q, q_begin, tq);
+  Tq = (int)(tq < L_TQ_MAX ? tq : L_TQ_MAX);
 }
 
 // ------------------------------------------------------------------------------------------------ probes
@@ -143,12 +117,12 @@ struct ProbeList {
 // grid (ceil(Tq_pad * parts / 256), chunk): thread -> (part, token) with the token fastest, so that the lanes of a wave
 // read consecutive floats of one row of S.  Part `part` covers centroids [part * span, (part + 1) * span).
 template <int NP>
-__global__ __launch_bounds__(P_THREADS) void plaid_probe_kernel(const PlaidParams p, int tq_pad) {
+__global__ __launch_bounds__(L_THREADS) void plaid_probe_kernel(const PlaidParams p, int tq_pad) {
   const int ql = blockIdx.y, q = p.q0 + ql;
   int64_t q_begin;
   int Tq;
   query_range(p, q, q_begin, Tq);
-  const int slot = blockIdx.x * P_THREADS + threadIdx.x;
+  const int slot = blockIdx.x * L_THREADS + threadIdx.x;
   const int i = slot % tq_pad, part = slot / tq_pad;
   if (i >= Tq || part >= p.parts) return;
   ProbeList<NP> best;
@@ -157,7 +131,7 @@ __global__ __launch_bounds__(P_THREADS) void plaid_probe_kernel(const PlaidParam
   const float* col = p.S + q_begin + i;
 #pragma unroll 8
   for (int c = c_begin; c < c_end; ++c) best.offer(col[(int64_t)c * p.ld], c);
-  const int64_t out = (((int64_t)ql * P_TQ_MAX + i) * p.parts + part) * p.nprobe;
+  const int64_t out = (((int64_t)ql * L_TQ_MAX + i) * p.parts + part) * p.nprobe;
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     if (j < p.nprobe) {
@@ -176,14 +150,14 @@ __global__ __launch_bounds__(64) void plaid_probe_merge_kernel(const PlaidParams
   int Tq;
   query_range(p, q, q_begin, Tq);
   const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= P_TQ_MAX) return;
-  int32_t* out = p.probes + ((int64_t)ql * P_TQ_MAX + i) * p.nprobe;
+  if (i >= L_TQ_MAX) return;
+  int32_t* out = p.probes + ((int64_t)ql * L_TQ_MAX + i) * p.nprobe;
   if (i >= Tq) {
     for (int j = 0; j < p.nprobe; ++j) out[j] = -1;
     return;
   }
   for (int l = 0; l < p.parts; ++l) cursor[l][threadIdx.x] = 0;
-  const int64_t base = ((int64_t)ql * P_TQ_MAX + i) * p.parts * p.nprobe;
+  const int64_t base = ((int64_t)ql * L_TQ_MAX + i) * p.parts * p.nprobe;
   for (int j = 0; j < p.nprobe; ++j) {
     float bs = -INFINITY;
     int bc = -1, bl = -1;
@@ -203,12 +177,12 @@ __global__ __launch_bounds__(64) void plaid_probe_merge_kernel(const PlaidParams
 // One wave per (query, token, probe): the rows of the probed list are OR-ed into the query's bitmap.  A centroid probed
 // by several tokens is walked once per token: the OR does not care.  list_lims is read clamped into [0, n_list] and a
 // row outside [0, n_rows) is skipped, so a damaged list cannot write outside the bitmap.
-__global__ __launch_bounds__(P_THREADS) void plaid_union_kernel(const PlaidParams p) {
+__global__ __launch_bounds__(L_THREADS) void plaid_union_kernel(const PlaidParams p) {
   const int ql = blockIdx.y;
   const int lane = threadIdx.x & 63;
-  const int slot = blockIdx.x * P_WAVES + (threadIdx.x >> 6);
-  if (slot >= P_TQ_MAX * p.nprobe) return;
-  const int c = p.probes[(int64_t)ql * P_TQ_MAX * p.nprobe + slot];
+  const int slot = blockIdx.x * L_WAVES + (threadIdx.x >> 6);
+  if (slot >= L_TQ_MAX * p.nprobe) return;
+  const int c = p.probes[(int64_t)ql * L_TQ_MAX * p.nprobe + slot];
   if (c < 0 || c >= p.C) return;
   int64_t lo = p.list_lims[c], hi = p.list_lims[c + 1];
   lo = lo < 0 ? 0 : lo;
@@ -283,7 +257,7 @@ __global__ __launch_bounds__(P_RANK_THREADS) void plaid_compact_kernel(const Pla
 // per_query workgroups of a query follow each other on ONE XCD, and that XCD's L2 holds the few slabs of S (C * Tq
 // floats each) its resident workgroups gather from.  Placement is not a contract: another dealing is slower, not wrong.
 // Fewer than 8 queries would leave XCDs idle that way: their workgroups are dealt query by query over the whole chip.
-__global__ __launch_bounds__(P_THREADS) void plaid_interact_kernel(const PlaidParams p, int n_queries, int per_query) {
+__global__ __launch_bounds__(L_THREADS) void plaid_interact_kernel(const PlaidParams p, int n_queries, int per_query) {
   int ql, worker;
   if (n_queries >= 8) {
     const int seq = blockIdx.x >> 3;
@@ -303,7 +277,7 @@ __global__ __launch_bounds__(P_THREADS) void plaid_interact_kernel(const PlaidPa
   const int32_t* rows = p.rows + (int64_t)ql * p.rows_pad;
   float* approx = p.approx + (int64_t)ql * p.rows_pad;
   const int nb = (Tq + 31) >> 5;
-  for (int ci = worker * P_WAVES + (threadIdx.x >> 6); ci < n; ci += per_query * P_WAVES) {
+  for (int ci = worker * L_WAVES + (threadIdx.x >> 6); ci < n; ci += per_query * L_WAVES) {
     const int64_t row = rows[ci];
     int64_t lo = 0, hi = 0;
     if (row >= 0 && row < p.n_rows) { lo = p.tok_lims[row]; hi = p.tok_lims[row + 1]; }
@@ -358,12 +332,12 @@ struct SelectShared {
   int hist[256];
   int sel_digit, sel_above, sel_count;
   int out_count, valid;
-  uint64_t win[P_R_MAX];
+  uint64_t win[L_R_MAX];
 };
 
 // One workgroup per query.  Radix select, 8 bits per pass from the top (the scheme of bm25.hip's select, on one 64-bit
 // word and up to 1 024 winners), then the winners are ordered by counting, for each, the winners ahead of it.
-__global__ __launch_bounds__(P_THREADS) void plaid_select_kernel(const PlaidParams p) {
+__global__ __launch_bounds__(L_THREADS) void plaid_select_kernel(const PlaidParams p) {
   __shared__ SelectShared sh;
   const int ql = blockIdx.x, q = p.q0 + ql;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -375,19 +349,19 @@ __global__ __launch_bounds__(P_THREADS) void plaid_select_kernel(const PlaidPara
   if (tid == 0) { sh.valid = 0; sh.out_count = 0; }
   __syncthreads();
   int local = 0;
-  for (int i = tid; i < n; i += P_THREADS) local += approx[i] > -INFINITY ? 1 : 0;
+  for (int i = tid; i < n; i += L_THREADS) local += approx[i] > -INFINITY ? 1 : 0;
   local = wave_sum(local);
   if (lane == 0 && local) atomicAdd(&sh.valid, local);
   __syncthreads();
   const int kk = min(p.R, sh.valid);          // (uniform)
-  for (int i = kk + tid; i < p.R; i += P_THREADS) { oi[i] = -1; os[i] = -INFINITY; }
+  for (int i = kk + tid; i < p.R; i += L_THREADS) { oi[i] = -1; os[i] = -INFINITY; }
   if (kk <= 0) return;
   uint64_t thr = 0;
   int need = kk;
   for (int pass = 0; pass < 8; ++pass) {
     sh.hist[tid] = 0;
     __syncthreads();
-    for (int i = tid; i < n; i += P_THREADS) {
+    for (int i = tid; i < n; i += L_THREADS) {
       uint64_t key;
       if (!select_key(approx[i], rows[i], key)) continue;
       if (pass > 0 && (key >> (64 - 8 * pass)) != (thr >> (64 - 8 * pass))) continue;
@@ -422,16 +396,16 @@ __global__ __launch_bounds__(P_THREADS) void plaid_select_kernel(const PlaidPara
     if (count == need) break;  // (uniform) everything under this prefix is wanted
   }
   // the winners: every key >= threshold, exactly kk of them
-  for (int i = tid; i < n; i += P_THREADS) {
+  for (int i = tid; i < n; i += L_THREADS) {
     uint64_t key;
     if (select_key(approx[i], rows[i], key) && key >= thr) {
       const int at = atomicAdd(&sh.out_count, 1);
-      if (at < P_R_MAX) sh.win[at] = key;
+      if (at < L_R_MAX) sh.win[at] = key;
     }
   }
   __syncthreads();
   const int won = min(sh.out_count, kk);
-  for (int e = tid; e < won; e += P_THREADS) {
+  for (int e = tid; e < won; e += L_THREADS) {
     const uint64_t key = sh.win[e];
     int rank = 0;
     for (int j = 0; j < won; ++j) rank += sh.win[j] > key ? 1 : 0;   // (every lane reads the same slot: broadcast)
@@ -464,9 +438,9 @@ inline Carve carve(void* base, const Plan& pl, int chunk, int nprobe) {
   sskd::Carver ws(base);
   Carve c;
   const size_t n = (size_t)chunk;
-  c.part_s = ws.take<float>(n * P_TQ_MAX * P_PARTS_MAX * nprobe);
-  c.part_c = ws.take<int32_t>(n * P_TQ_MAX * P_PARTS_MAX * nprobe);
-  c.probes = ws.take<int32_t>(n * P_TQ_MAX * nprobe);
+  c.part_s = ws.take<float>(n * L_TQ_MAX * P_PARTS_MAX * nprobe);
+  c.part_c = ws.take<int32_t>(n * L_TQ_MAX * P_PARTS_MAX * nprobe);
+  c.probes = ws.take<int32_t>(n * L_TQ_MAX * nprobe);
   c.bitmap = ws.take<uint32_t>(n * (size_t)pl.words_pad);
   c.rows = ws.take<int32_t>(n * (size_t)pl.rows_pad);
   c.approx = ws.take<float>(n * (size_t)pl.rows_pad);
@@ -476,8 +450,8 @@ inline Carve carve(void* base, const Plan& pl, int chunk, int nprobe) {
 }
 
 inline bool shape_ok(int nq, int max_tq, int C, int64_t n_rows, int nprobe, int R) {
-  return nq >= 1 && max_tq >= 1 && max_tq <= P_TQ_MAX && C >= 1 && C <= P_C_MAX && n_rows >= 0 &&
-         n_rows < sskd::MAX_SHARD_ROWS && nprobe >= 1 && nprobe <= P_NPROBE_MAX && nprobe <= C && R >= 1 && R <= P_R_MAX;
+  return nq >= 1 && max_tq >= 1 && max_tq <= L_TQ_MAX && C >= 1 && C <= L_C_MAX && n_rows >= 0 &&
+         n_rows < sskd::MAX_SHARD_ROWS && nprobe >= 1 && nprobe <= P_NPROBE_MAX && nprobe <= C && R >= 1 && R <= L_R_MAX;
 }
 
 inline Plan make_plan(int chunk, int max_tq, int C, int64_t n_rows, int nprobe) {
@@ -523,16 +497,14 @@ inline int chunk_that_fits(size_t bytes, int64_t n_rows, int nprobe, int nq) {
 inline int64_t interact_per_query(int chunk, int64_t n_rows) {
   int64_t g = sskd::ceil_div(8 * (int64_t)sskd::cu_count(), chunk);
   if (g < 64) g = 64;
-  const int64_t most = sskd::ceil_div(n_rows > 0 ? n_rows : 1, P_WAVES);
+  const int64_t most = sskd::ceil_div(n_rows > 0 ? n_rows : 1, L_WAVES);
   return g > most ? most : g;
 }
 
-bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
-
 template <int NP>
 void launch_probe(const PlaidParams& p, const Plan& pl, int n, hipStream_t st) {
-  const unsigned gx = (unsigned)sskd::ceil_div((int64_t)pl.tq_pad * pl.parts, P_THREADS);
-  hipLaunchKernelGGL(plaid_probe_kernel<NP>, dim3(gx, (unsigned)n), dim3(P_THREADS), 0, st, p, pl.tq_pad);
+  const unsigned gx = (unsigned)sskd::ceil_div((int64_t)pl.tq_pad * pl.parts, L_THREADS);
+  hipLaunchKernelGGL(plaid_probe_kernel<NP>, dim3(gx, (unsigned)n), dim3(L_THREADS), 0, st, p, pl.tq_pad);
 }
 
 }  // namespace
@@ -544,18 +516,18 @@ int sskd_plaid_centroid_scores(const void* d_q_tokens, int64_t n_q_tokens, const
   // every check comes before the first HIP call
   SSKD_REQUIRE(n_q_tokens >= 0 && n_q_tokens <= (int64_t)65535 * 32, "plaid_centroid_scores: n_q_tokens=%lld outside [0, %lld]",
                (long long)n_q_tokens, (long long)65535 * 32);
-  SSKD_REQUIRE(C >= 1 && C <= P_C_MAX, "plaid_centroid_scores: C=%d outside [1, %d]", C, P_C_MAX);
+  SSKD_REQUIRE(C >= 1 && C <= L_C_MAX, "plaid_centroid_scores: C=%d outside [1, %d]", C, L_C_MAX);
   SSKD_REQUIRE(ld >= n_q_tokens, "plaid_centroid_scores: ld=%lld < n_q_tokens=%lld", (long long)ld, (long long)n_q_tokens);
   if (n_q_tokens == 0) return SSKD_OK;
   SSKD_REQUIRE(d_q_tokens && d_centroids && d_S, "plaid_centroid_scores: null pointer");
   SSKD_REQUIRE(aligned16(d_q_tokens) && aligned16(d_centroids) && reinterpret_cast<uintptr_t>(d_S) % 4 == 0,
                "plaid_centroid_scores: query tokens and centroids must be 16-byte aligned");
   const int64_t gy = sskd::ceil_div(n_q_tokens, 32);
-  const int64_t groups = sskd::ceil_div(sskd::ceil_div(C, 32), P_WAVES);
+  const int64_t groups = sskd::ceil_div(sskd::ceil_div(C, 32), L_WAVES);
   int64_t gx = sskd::ceil_div(8 * (int64_t)sskd::cu_count(), gy);   // about 8 workgroups per compute unit in all
   if (gx > groups) gx = groups;
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(plaid_scores_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(P_THREADS), 0, sskd::as_stream(stream),
+  hipLaunchKernelGGL(plaid_scores_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(L_THREADS), 0, sskd::as_stream(stream),
                      static_cast<const bf16x8*>(d_q_tokens), n_q_tokens, static_cast<const bf16x8*>(d_centroids), C, d_S, ld);
   return sskd::check_launch("plaid_scores_kernel");
 }
@@ -573,8 +545,8 @@ int sskd_plaid_candidates_plan(int nq, int max_tq, int C, int64_t n_rows, int np
                                size_t* per_query_bytes_out, int* queries_per_chunk, int* probe_parts,
                                int* interact_workgroups) {
   SSKD_REQUIRE(shape_ok(nq, max_tq, C, n_rows, nprobe, R),
-               "plaid_candidates_plan: needs nq >= 1, 1 <= Tq <= %d, 1 <= C <= %d, 1 <= nprobe <= min(C, %d), 1 <= R <= %d", P_TQ_MAX,
-               P_C_MAX, P_NPROBE_MAX, P_R_MAX);
+               "plaid_candidates_plan: needs nq >= 1, 1 <= Tq <= %d, 1 <= C <= %d, 1 <= nprobe <= min(C, %d), 1 <= R <= %d", L_TQ_MAX,
+               L_C_MAX, P_NPROBE_MAX, L_R_MAX);
   const size_t have = workspace_bytes ? workspace_bytes : sskd_plaid_candidates_workspace_bytes(nq, n_rows, nprobe);
   const int chunk = chunk_that_fits(have, n_rows, nprobe, nq);
   SSKD_REQUIRE(chunk >= 1, "plaid_candidates_plan: a workspace of %zu B does not hold one query (%zu B)", have,
@@ -594,25 +566,18 @@ int sskd_plaid_candidates(const float* d_S, int64_t ld, const int64_t* q_lims, c
                           void* d_workspace, size_t workspace_bytes, void* stream) {
   // every check comes before the first HIP call
   SSKD_REQUIRE(nq >= 0, "plaid_candidates: nq < 0");
-  SSKD_REQUIRE(C >= 1 && C <= P_C_MAX, "plaid_candidates: C=%d outside [1, %d]", C, P_C_MAX);
+  SSKD_REQUIRE(C >= 1 && C <= L_C_MAX, "plaid_candidates: C=%d outside [1, %d]", C, L_C_MAX);
   SSKD_REQUIRE(nprobe >= 1 && nprobe <= P_NPROBE_MAX && nprobe <= C, "plaid_candidates: nprobe=%d outside [1, min(C=%d, %d)]",
                nprobe, C, P_NPROBE_MAX);
-  SSKD_REQUIRE(R >= 1 && R <= P_R_MAX, "plaid_candidates: R=%d outside [1, %d]", R, P_R_MAX);
+  SSKD_REQUIRE(R >= 1 && R <= L_R_MAX, "plaid_candidates: R=%d outside [1, %d]", R, L_R_MAX);
   SSKD_REQUIRE(n_rows >= 0 && n_tokens >= 0 && id_offset >= 0, "plaid_candidates: n_rows, n_tokens and id_offset must be >= 0");
   if (int rc = sskd::require_shard_rows("plaid_candidates", n_rows)) return rc;
   SSKD_REQUIRE(n_list >= 0 && n_list <= n_tokens,
                "plaid_candidates: the centroid lists hold %lld rows, a store of %lld tokens has at most that many (centroid, row) pairs",
                (long long)n_list, (long long)n_tokens);
   if (nq == 0) return SSKD_OK;
-  SSKD_REQUIRE(q_lims, "plaid_candidates: the host copy of q_lims is required");
-  SSKD_REQUIRE(q_lims[0] >= 0, "plaid_candidates: q_lims[0] < 0");
-  int max_tq = 0;
-  for (int q = 0; q < nq; ++q) {
-    const int64_t tq = q_lims[q + 1] - q_lims[q];
-    SSKD_REQUIRE(tq >= 1 && tq <= P_TQ_MAX, "plaid_candidates: query %d has Tq=%lld outside [1, %d] (q_lims must ascend)", q,
-                 (long long)tq, P_TQ_MAX);
-    if (tq > max_tq) max_tq = (int)tq;
-  }
+  const int max_tq = check_query_lims("plaid_candidates", q_lims, nq);
+  if (max_tq < 0) return SSKD_ERR_INVALID;
   SSKD_REQUIRE(ld >= q_lims[nq], "plaid_candidates: ld=%lld < the batch's %lld query tokens", (long long)ld, (long long)q_lims[nq]);
   SSKD_REQUIRE(d_S && d_q_lims && d_list_lims && d_cand_ids && d_cand_scores && d_n_cand, "plaid_candidates: null pointer");
   SSKD_REQUIRE(n_list == 0 || d_list_rows, "plaid_candidates: null list rows");
@@ -672,16 +637,16 @@ int sskd_plaid_candidates(const float* d_S, int64_t ld, const int64_t* q_lims, c
     else if (nprobe <= 16) launch_probe<16>(p, pl, n, st);
     else launch_probe<32>(p, pl, n, st);
     if (int rc = sskd::check_launch("plaid_probe_kernel")) return rc;
-    hipLaunchKernelGGL(plaid_probe_merge_kernel, dim3(P_TQ_MAX / 64, (unsigned)n), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(plaid_probe_merge_kernel, dim3(L_TQ_MAX / 64, (unsigned)n), dim3(64), 0, st, p);
     if (int rc = sskd::check_launch("plaid_probe_merge_kernel")) return rc;
-    hipLaunchKernelGGL(plaid_union_kernel, dim3((unsigned)sskd::ceil_div(P_TQ_MAX * nprobe, P_WAVES), (unsigned)n), dim3(P_THREADS), 0,
+    hipLaunchKernelGGL(plaid_union_kernel, dim3((unsigned)sskd::ceil_div(L_TQ_MAX * nprobe, L_WAVES), (unsigned)n), dim3(L_THREADS), 0,
                        st, p);
     if (int rc = sskd::check_launch("plaid_union_kernel")) return rc;
     hipLaunchKernelGGL(plaid_compact_kernel, dim3((unsigned)n), dim3(P_RANK_THREADS), 0, st, p);
     if (int rc = sskd::check_launch("plaid_compact_kernel")) return rc;
-    hipLaunchKernelGGL(plaid_interact_kernel, dim3((unsigned)((n >= 8 ? 8 * sskd::ceil_div(n, 8) : n) * ig)), dim3(P_THREADS), 0, st, p, n, (int)ig);
+    hipLaunchKernelGGL(plaid_interact_kernel, dim3((unsigned)((n >= 8 ? 8 * sskd::ceil_div(n, 8) : n) * ig)), dim3(L_THREADS), 0, st, p, n, (int)ig);
     if (int rc = sskd::check_launch("plaid_interact_kernel")) return rc;
-    hipLaunchKernelGGL(plaid_select_kernel, dim3((unsigned)n), dim3(P_THREADS), 0, st, p);
+    hipLaunchKernelGGL(plaid_select_kernel, dim3((unsigned)n), dim3(L_THREADS), 0, st, p);
     if (int rc = sskd::check_launch("plaid_select_kernel")) return rc;
   }
   return SSKD_OK;

@@ -580,25 +580,19 @@ class LateInteractionIndex:
         I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         raw = torch.empty((nq, R), dtype=torch.float32, device=self.device) if return_raw else None
         ws = None
-        if self.compressed:
-            if raw is None:
-                need = int(lib.sskd_latec_rerank_workspace_bytes(nq, R))
-                self._workspace = ws = _native.grown(self._workspace, need, self.device)
-            _native.check(lib.sskd_latec_rerank(
-                queries.tokens.data_ptr(), queries.lims_host.ctypes.data, queries.lims_dev.data_ptr(), nq,
-                self.cid.data_ptr(), self.scale.data_ptr(), self.codes.data_ptr(), self.nbits, self.centroids.data_ptr(),
-                self.n_centroids, self.weights.data_ptr(), self._lims_dev.data_ptr(), self.ntotal, self.n_tokens,
-                cand.data_ptr(), R, k, self.flat.id_offset, D.data_ptr(), I.data_ptr(),
-                None if raw is None else raw.data_ptr(), None if ws is None else ws.data_ptr(),
-                0 if ws is None else ws.numel(), _native.current_stream_ptr(self.device)))
-            return (D, I, raw) if return_raw else (D, I)
-        if raw is None:
+        if raw is None:   # (the two stores ask for the same workspace: the raw scores)
             self._workspace = ws = _native.grown(self._workspace, int(lib.sskd_late_rerank_workspace_bytes(nq, R)), self.device)
-        _native.check(lib.sskd_late_rerank(
-            queries.tokens.data_ptr(), queries.lims_host.ctypes.data, queries.lims_dev.data_ptr(), nq,
-            self.tokens.data_ptr(), self._lims_dev.data_ptr(), self.ntotal, self.n_tokens, cand.data_ptr(), R, k,
-            self.flat.id_offset, D.data_ptr(), I.data_ptr(), None if raw is None else raw.data_ptr(),
-            None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _native.current_stream_ptr(self.device)))
+        if self.compressed:
+            call = lib.sskd_latec_rerank
+            store = (self.cid.data_ptr(), self.scale.data_ptr(), self.codes.data_ptr(), self.nbits, self.centroids.data_ptr(),
+                     self.n_centroids, self.weights.data_ptr())
+        else:
+            call, store = lib.sskd_late_rerank, (self.tokens.data_ptr(),)
+        _native.check(call(
+            queries.tokens.data_ptr(), queries.lims_host.ctypes.data, queries.lims_dev.data_ptr(), nq, *store,
+            self._lims_dev.data_ptr(), self.ntotal, self.n_tokens, cand.data_ptr(), R, k, self.flat.id_offset, D.data_ptr(),
+            I.data_ptr(), None if raw is None else raw.data_ptr(), None if ws is None else ws.data_ptr(),
+            0 if ws is None else ws.numel(), _native.current_stream_ptr(self.device)))
         return (D, I, raw) if return_raw else (D, I)
 
     def rerank(self, q_tokens, q_lims, cand_I, k: int) -> Tuple[np.ndarray, np.ndarray]:

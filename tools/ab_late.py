@@ -3,6 +3,7 @@ store, same candidates.
 
     python tools/ab_late.py [--rows 100000] [--mean-td 80] [--tq 32] [--candidates 100] [--batches 1 1024]
                             [--reps 5] [--iters 20] [--out FILE] [--only-cell NQ] [--no-torch] [--no-serve]
+                            [--dump-outputs DIR]
 
 The store holds `--rows` documents whose lengths are drawn around `--mean-td` tokens (normal, sigma a quarter of the
 mean, clipped to [8, 180]); every token is a random unit row.  For every batch size the candidates are `--candidates`
@@ -14,7 +15,7 @@ the computation on the same tokens - padded gather, einsum, amax, sum - in chunk
 with events, and its scores are compared with the kernel's.  The last section times the library path of one `/search`
 (encode the pooled query, first stage, and with the store: encode the query's tokens, pack, re-rank) on a synthetic
 12-layer encoder, with and without the store.  `--only-cell NQ` replays that one cell a few times and nothing else (for
-a kernel trace).  Prints one JSON object.
+a kernel trace).  `--dump-outputs DIR` saves every cell's raw scores as `DIR/late_raw_nq<NQ>.npy`.  Prints one JSON object.
 """
 import argparse
 import json
@@ -66,6 +67,12 @@ def _unit_rows(n, gen, chunk=1 << 20):
     return out
 
 
+def _dump(out_dir, name, tensor):
+    """`--dump-outputs`: one output as `.npy` (the inputs are seeded: the files of two builds are compared with `cmp`)."""
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    np.save(Path(out_dir) / f"{name}.npy", tensor.cpu().numpy())
+
+
 def torch_maxsim(q_tok, tq, store, lims_dev, cand, chunk):
     """The restatement: q_tok bf16 [nq * tq, 384] (every query tq tokens), cand int64 [nq, R] -> fp32 [nq, R]."""
     nq, R = cand.shape
@@ -98,6 +105,7 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--no-serve", action="store_true")
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--dump-outputs", type=str, default=None)
     args = ap.parse_args()
 
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -122,6 +130,8 @@ def main():
             torch.cuda.synchronize()
             continue
         eager, graph = _measure(call, args.iters, args.reps)
+        if args.dump_outputs:
+            _dump(args.dump_outputs, f"late_raw_nq{nq}", call()[2])
         pair_td = td[cand.cpu().numpy()]
         gathered = float(pair_td.sum()) * DIM * 2
         flops = float((np.ceil(pair_td / 32) * 32).sum()) * 2 * DIM * (-(-args.tq // 32) * 32)

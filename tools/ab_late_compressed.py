@@ -3,6 +3,7 @@ unchanged) in the same process: same documents, same queries, same candidates (D
 
     python tools/ab_late_compressed.py [--rows 100000] [--mean-td 80] [--tq 32] [--candidates 100] [--batches 1 1024]
                                        [--bits 2 4] [--centroids 4096 65536] [--reps 5] [--iters 20] [--out FILE]
+                                       [--dump-outputs DIR]
 
 The store is the one of `tools/ab_late.py`: `--rows` documents of about `--mean-td` random unit tokens.  For every
 (`--bits`, `--centroids`) a codec is made by `train_codec` (k-means seeding only: `iterations=0`, the timing does not
@@ -13,7 +14,8 @@ replay is first checked to reproduce the eager call's scores bit for bit; eager 
 median per store is reported with its ratio to the bf16 store's.  From the time: the bytes a pair needs - compressed
 `sum Td * (8 + 48 nbits)` from the store plus `sum Td * 768` of centroid rows (cache-resident when C is small) - over
 the time, and the bf16 FLOP/s the MFMAs execute against the peak.  The top-10 overlap with the bf16 ranking is reported
-for what it is: on random tokens it says nothing about real text.  Prints one JSON object.
+for what it is: on random tokens it says nothing about real text.  `--dump-outputs DIR` saves every store's raw scores
+as `DIR/latec_raw_<store>_nq<NQ>.npy`.  Prints one JSON object.
 """
 import argparse
 import json
@@ -50,6 +52,12 @@ def _unit_rows(n, gen, chunk=1 << 20):
     return out
 
 
+def _dump(out_dir, name, tensor):
+    """`--dump-outputs`: one output as `.npy` (the inputs are seeded: the files of two builds are compared with `cmp`)."""
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    np.save(Path(out_dir) / f"{name}.npy", tensor.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000)
@@ -62,6 +70,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--dump-outputs", type=str, default=None)
     args = ap.parse_args()
 
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -101,6 +110,8 @@ def main():
             call = lambda late=late, queries=queries: late.rerank_device(queries, None, cand, 10, return_raw=True)   # noqa: E731
             eager_out = call()
             tops[name] = eager_out[1].cpu().numpy()
+            if args.dump_outputs:
+                _dump(args.dump_outputs, f"latec_raw_{name}_nq{nq}", eager_out[2])
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):

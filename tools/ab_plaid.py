@@ -4,6 +4,7 @@ exact first stage over pooled vectors, then the same compressed MaxSim; unchange
 
     python tools/ab_plaid.py [--rows 100000] [--mean-td 80] [--tq 32] [--batches 1 1024] [--centroids 4096 65536]
                              [--nprobe 2] [--ndocs 256] [--reps 5] [--iters 20] [--out FILE] [--trace-only]
+                             [--dump-outputs DIR]
 
 The store is the one of `tools/ab_late.py` and `tools/ab_late_compressed.py`: `--rows` documents of about `--mean-td`
 random unit tokens, compressed to 2 bits under a codec of `train_codec(iterations=0)` per `--centroids`.  Per batch size
@@ -14,7 +15,8 @@ rows of `Tq` floats per query, an estimate that takes every candidate for a docu
 nothing to cluster: the figures say what the kernels cost at these list lengths, nothing about ranking quality.
 
 `--trace-only` runs three eager calls of `search_tokens_device` per cell and nothing else: the run to put under
-`rocprofv3 --kernel-trace --stats` for the per-stage kernel times.  Prints one JSON object.
+`rocprofv3 --kernel-trace --stats` for the per-stage kernel times.  `--dump-outputs DIR` saves every cell's candidate
+ids and approximate scores as `DIR/plaid_{ids,approx}_C<C>_nq<NQ>.npy`.  Prints one JSON object.
 """
 import argparse
 import json
@@ -49,6 +51,12 @@ def _unit_rows(n, gen, chunk=1 << 20):
     return out
 
 
+def _dump(out_dir, name, tensor):
+    """`--dump-outputs`: one output as `.npy` (the inputs are seeded: the files of two builds are compared with `cmp`)."""
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    np.save(Path(out_dir) / f"{name}.npy", tensor.cpu().numpy())
+
+
 def _captured(call, what):
     """`call` run once eagerly, captured, and the replay checked against the eager outputs bit for bit."""
     eager = call()
@@ -79,6 +87,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--dump-outputs", type=str, default=None)
     args = ap.parse_args()
 
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -123,7 +132,11 @@ def main():
                 torch.cuda.synchronize()
                 result["cells"].append({"nq": nq, "centroids": C, "traced_calls": 3})
                 continue
-            n_cand = by_lists()[4].cpu().numpy()
+            first = by_lists()
+            n_cand = first[4].cpu().numpy()
+            if args.dump_outputs:
+                _dump(args.dump_outputs, f"plaid_ids_C{C}_nq{nq}", first[2])
+                _dump(args.dump_outputs, f"plaid_approx_C{C}_nq{nq}", first[3])
             graphs = {"centroids": _captured(by_lists, f"centroids, C={C}, nq={nq}")[0],
                       "flat": _captured(by_flat, f"flat, C={C}, nq={nq}")[0]}
             times = {name: [] for name in graphs}
