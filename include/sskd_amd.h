@@ -742,6 +742,29 @@ int sskd_pq_search(const float* d_tiled, int64_t n_rows, const float* d_queries,
  *     entries of fwd[u]; an entry that is not valid or equals an earlier one is skipped; cut to M, -1 padded.
  *   Both are integer-only and write every element of their output exactly once: two calls give the same bits.
  *
+ * Incremental insertion.  n_old rows are linked (d_graph_old [n_old, M]); rows [n_old, n_total) are new, n_new of them.
+ * d_knn_new DEVICE int32 [n_new, knn_k]: the lists of the new rows, searched against ALL n_total rows, ids global.
+ *   sskd_graph_insert_prune.  sskd_graph_prune's rule for the new rows, where the list N(w) of a neighbour w is
+ *     graph_old[w] (width M) for w < n_old and knn_new[w - n_old] (width knn_k) otherwise: the detour count of L[j] is
+ *     the number of i < j, L[i] valid, for which some p < min(j, width(N(L[i]))) has N(L[i])[p] == L[j].  d_fwd_new
+ *     DEVICE int32 [n_new, M].  With n_old = 0 it is sskd_graph_prune.
+ *   Reverse edges (the caller's, one stable sort): incoming[t] = the new rows that name t among the first M / 2 entries
+ *     of their fwd_new list, by (position, source), the first M / 2, -1 padded; for new targets and for old ones.
+ *   sskd_graph_merge_rows.  sskd_graph_merge for the n_rows rows [row_base, row_base + n_rows) of an index of n_total:
+ *     d_fwd / d_incoming / d_graph_rows hold those rows only, ids are global, an entry is valid in [0, n_total) when
+ *     it is not row_base + (the row's place).  sskd_graph_merge is this call with row_base = 0, n_total = n_rows.
+ *   sskd_graph_link.  d_touched DEVICE int32 [n_touched]: linked rows named by new ones, STRICTLY ascending;
+ *     d_incoming DEVICE int32 [n_touched, M / 2]: the row of entry t belongs to d_touched[t].  For u = d_touched[t]:
+ *     adj = the valid entries of graph[u] (in [0, n_total), not u, first occurrence only) in order; head = adj[:M / 2]
+ *     stays; pool = adj[M / 2:], then the entries of incoming[t] that are valid and neither in adj nor earlier in
+ *     incoming[t]; every pool row is scored against row u with the exact scan's fma chain; graph[u] = head, then the
+ *     best M - |head| pool rows in rank order, -1 padded.  Rank order here is total: score descending, then lower id, a
+ *     NaN score after every number.  d_graph (DEVICE int32 [n_total, M]) is updated IN PLACE, a workgroup reading and
+ *     writing its own row only: an entry of d_touched outside [0, n_old), or not greater than the entry before it,
+ *     leaves its row as it is, and rows not named are not written.  No float atomics: two calls on equal inputs give
+ *     the same bits.  One workgroup of 256 threads per touched row; d_tiled 16-byte aligned.
+ *   The three calls take every buffer from the caller: no workspace.  n_new = 0 / n_rows = 0 / n_touched = 0 succeed.
+ *
  * sskd_graph_search, per query.  T = the ef best rows scored so far in rank order, whatever the mask says, each with
  * an "expanded" flag; R = the k best scored rows whose bit of d_row_mask is set (NULL: all rows; the format of
  * "Filtered search").  To OFFER a set of rows: drop -1 and ids outside [0, n_rows), score the rest, and for T, and
@@ -767,6 +790,12 @@ int sskd_pq_search(const float* d_tiled, int64_t n_rows, const float* d_queries,
  * ------------------------------------------------------------------------- */
 int sskd_graph_prune(const int32_t* d_knn, int64_t n_rows, int knn_k, int M, int32_t* d_fwd, void* stream);
 int sskd_graph_merge(const int32_t* d_fwd, const int32_t* d_rev, int64_t n_rows, int M, int32_t* d_graph, void* stream);
+int sskd_graph_insert_prune(const int32_t* d_graph_old, int64_t n_old, const int32_t* d_knn_new, int64_t n_new, int knn_k,
+                            int M, int32_t* d_fwd_new, void* stream);
+int sskd_graph_merge_rows(const int32_t* d_fwd, const int32_t* d_incoming, int64_t n_rows, int64_t row_base, int64_t n_total,
+                          int M, int32_t* d_graph_rows, void* stream);
+int sskd_graph_link(const float* d_tiled, int32_t* d_graph, int64_t n_old, int64_t n_total, int M, const int32_t* d_touched,
+                    const int32_t* d_incoming, int64_t n_touched, void* stream);
 int sskd_graph_search_plan(int nq, int k, int ef, int width, int M, int n_seeds, int* workgroups, int* threads,
                            int* lds_bytes, int* step_rows);
 size_t sskd_graph_search_workspace_bytes(int nq, int k, int ef, int width, int M, int n_seeds);

@@ -211,6 +211,9 @@ SIGNATURES = {
     ),
     "sskd_graph_prune": (_i, [_vp, _i64, _i, _i, _vp, _vp]),
     "sskd_graph_merge": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "sskd_graph_insert_prune": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp, _vp]),
+    "sskd_graph_merge_rows": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _vp, _vp]),
+    "sskd_graph_link": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _i64, _vp]),
     "sskd_graph_search_plan": (_i, [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip]),
     "sskd_graph_search_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sskd_graph_search": (

@@ -30,7 +30,18 @@
 //
 // graph_prune_kernel: one workgroup per row u, thread j owns entry j of u's k-NN list and counts its detours in a
 // register - for every i < j, whether the list of L_u[i] (staged in LDS) names L_u[j] among its first j entries.
-// Integer compares only.  graph_merge_kernel: one wave per row joins forward and reverse edges without duplicates.
+// Integer compares only.  The list of a neighbour comes from a look-up (KnnLists: the one k-NN table of a build;
+// InsertLists: the adjacency of the rows already linked or the k-NN lists of the rows being inserted), so the build and
+// the insertion run the same body.  graph_merge_kernel: one wave per row joins forward and reverse edges without
+// duplicates; rows are numbered from row_base, so it serves a whole build and the slice of an insertion alike.
+//
+// graph_link_kernel (incremental insertion: sskd_graph_link), one workgroup of 256 threads per touched row u: the valid
+// entries of graph[u] and of incoming[u] are packed without repeats (wave 0, two ballots), the first M / 2 of graph[u]
+// stay, everything after them is the pool; row u is the query in LDS, the pool (at most M <= 64 rows) is staged as in
+// row_stage.h in two chunks of 32, the second loading while wave 0 scores the first; the best M - |head| rows of the
+// pool follow the head in rank order - each pool row counts the pool rows that rank before it (l_before: NaN after every
+// number, then lower id, so the order is total and the places distinct).  A workgroup reads and writes its own row only,
+// reads it whole before the barrier that precedes the first write, and writes every element of it once.
 #include "row_stage.h"
 #include "search_host.h"
 
@@ -302,23 +313,54 @@ __global__ __launch_bounds__(G_THREADS) void graph_search_kernel(GraphParams p) 
 // ---------------------------------------------------------------------------------------------- building the graph
 __device__ inline bool g_edge_ok(int v, int u, int64_t n_rows) { return v >= 0 && v < n_rows && v != u; }
 
-// one workgroup of G_KNN_MAX threads per row u; thread j owns L_u[j]
-__global__ __launch_bounds__(G_KNN_MAX) void graph_prune_kernel(const int32_t* __restrict__ knn, int64_t n_rows, int K0, int M,
-                                                                int32_t* __restrict__ fwd) {
+// entry e of a sequence of L candidate edges of row u is kept: a valid edge that no earlier entry names
+__device__ inline bool g_first_edge(const int* seq, int e, int L, int u, int64_t n_rows) {
+  if (e >= L || !g_edge_ok(seq[e], u, n_rows)) return false;
+  for (int b = 0; b < e; ++b)
+    if (seq[b] == seq[e]) return false;
+  return true;
+}
+
+// Where graph_prune_kernel finds the list N(w) of a neighbour w (w is valid: in [0, n_total)) and how wide it is.
+struct KnnLists {             // a build: every row's list is a row of the k-NN table
+  const int32_t* knn;
+  int K0;
+  __device__ const int32_t* list(int w, int& width) const { width = K0; return knn + (int64_t)w * K0; }
+};
+struct InsertLists {          // an insertion: rows below n_old have their adjacency, the rows being inserted their k-NN lists
+  const int32_t* graph_old;   // [n_old][M]
+  const int32_t* knn_new;     // [n_total - n_old][K0]
+  int64_t n_old;
+  int M, K0;
+  __device__ const int32_t* list(int w, int& width) const {
+    if (w < n_old) { width = M; return graph_old + (int64_t)w * M; }
+    width = K0;
+    return knn_new + ((int64_t)w - n_old) * K0;
+  }
+};
+
+// one workgroup of G_KNN_MAX threads per row; thread j owns L[j].  knn / fwd hold the rows [row_base, row_base + grid),
+// ids are global: an entry is valid in [0, n_total) when it is not the row itself.
+template <typename Lists>
+__global__ __launch_bounds__(G_KNN_MAX) void graph_prune_kernel(Lists lists, const int32_t* __restrict__ knn, int64_t row_base,
+                                                                int64_t n_total, int K0, int M, int32_t* __restrict__ fwd) {
   __shared__ int lu_s[G_KNN_MAX];
   __shared__ int lv_s[G_KNN_MAX];
   __shared__ int det_s[G_KNN_MAX];
   const int j = threadIdx.x;
-  const int u = blockIdx.x;
-  const int mine = j < K0 ? knn[(int64_t)u * K0 + j] : -1;
-  const bool valid = g_edge_ok(mine, u, n_rows);
+  const int64_t r = blockIdx.x;                  // the row's place in knn / fwd
+  const int u = (int)(row_base + r);             // its id
+  const int mine = j < K0 ? knn[r * K0 + j] : -1;
+  const bool valid = g_edge_ok(mine, u, n_total);
   lu_s[j] = mine;
   __syncthreads();
   int det = 0;
   for (int i = 0; i + 1 < K0; ++i) {
     const int v = lu_s[i];                       // (uniform)
-    if (!g_edge_ok(v, u, n_rows)) continue;
-    if (j < K0) lv_s[j] = knn[(int64_t)v * K0 + j];
+    if (!g_edge_ok(v, u, n_total)) continue;
+    int width;
+    const int32_t* lv = lists.list(v, width);    // (uniform)
+    lv_s[j] = j < width ? lv[j] : -1;            // past the list's width: -1, which no valid entry equals
     __syncthreads();
     if (valid && j > i) {
       bool found = false;
@@ -337,29 +379,26 @@ __global__ __launch_bounds__(G_KNN_MAX) void graph_prune_kernel(const int32_t* _
     ++n_valid;
     if (valid && (d < det || (d == det && e < j))) ++rank;
   }
-  if (valid && rank < M) fwd[(int64_t)u * M + rank] = mine;
-  if (j >= n_valid && j < M) fwd[(int64_t)u * M + j] = -1;
+  if (valid && rank < M) fwd[r * M + rank] = mine;
+  if (j >= n_valid && j < M) fwd[r * M + j] = -1;
 }
 
-// one wave per row: first M/2 of fwd, then rev, then the rest of fwd, every row once, cut to M, -1 padded
+// one wave per row: first M/2 of fwd, then rev, then the rest of fwd, every row once, cut to M, -1 padded.  fwd / rev /
+// graph hold the rows [row_base, row_base + n_rows); ids are global and valid in [0, n_total).
 __global__ __launch_bounds__(G_MERGE_THREADS) void graph_merge_kernel(const int32_t* __restrict__ fwd, const int32_t* __restrict__ rev,
-                                                                int64_t n_rows, int M, int32_t* __restrict__ graph) {
+                                                                int64_t n_rows, int64_t row_base, int64_t n_total, int M,
+                                                                int32_t* __restrict__ graph) {
   __shared__ int seq_s[G_MERGE_THREADS / 64][G_M_MAX + G_M_MAX / 2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t u = (int64_t)blockIdx.x * (G_MERGE_THREADS / 64) + wave;
   if (u >= n_rows) return;   // (wave-uniform; no workgroup barrier below)
+  const int id = (int)(row_base + u);
   const int h = M / 2, L = M + h;
   int* seq = seq_s[wave];
   for (int e = lane; e < L; e += 64)
     seq[e] = e < h ? fwd[u * M + e] : e < M ? rev[u * h + (e - h)] : fwd[u * M + (e - h)];
   wave_lds_sync();
-  auto keep = [&](int e) {
-    if (e >= L || !g_edge_ok(seq[e], (int)u, n_rows)) return false;
-    for (int b = 0; b < e; ++b)
-      if (seq[b] == seq[e]) return false;
-    return true;
-  };
-  const bool k0 = keep(lane), k1 = keep(lane + 64);
+  const bool k0 = g_first_edge(seq, lane, L, id, n_total), k1 = g_first_edge(seq, lane + 64, L, id, n_total);
   const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1);
   const unsigned long long lt = (1ull << lane) - 1ull;
   const int n0 = __popcll(m0), pos0 = __popcll(m0 & lt), pos1 = n0 + __popcll(m1 & lt);
@@ -369,11 +408,116 @@ __global__ __launch_bounds__(G_MERGE_THREADS) void graph_merge_kernel(const int3
   if (lane >= total && lane < M) graph[u * M + lane] = -1;
 }
 
+// ------------------------------------------------------------------------------------- linking into linked rows
+constexpr int G_LINK_SEQ = G_M_MAX + G_M_MAX / 2;          // graph[u] followed by incoming[u]
+static_assert(G_M_MAX <= 2 * STAGE_ROWS && G_LINK_SEQ <= 128, "the pool is two chunks; one wave packs the sequence in two ballots");
+
+// rank order made total: a NaN score ranks after every number, and among NaNs the lower id comes first
+__device__ inline bool l_before(float sa, int ia, float sb, int ib) {
+  const bool na = sa != sa, nb = sb != sb;
+  if (na || nb) return na == nb ? ia < ib : nb;
+  return ranks_before(sa, ia, sb, ib);
+}
+
+struct LinkLds {
+  float4 rows[STAGE_FLOAT4];   // the current chunk of the pool
+  float4 q[CHUNKS];            // row u
+  int seq[G_LINK_SEQ];         // graph[u], then incoming[u]
+  int kept[G_LINK_SEQ];        // the valid entries of seq without repeats, in order: head, then the pool
+  float score[G_M_MAX];        // of the pool
+  int n_kept, n_head;
+};
+
+__global__ __launch_bounds__(G_THREADS) void graph_link_kernel(const float* __restrict__ rows, int32_t* graph, int64_t n_old,
+                                                              int64_t n_total, int M, const int32_t* __restrict__ touched,
+                                                              const int32_t* __restrict__ incoming) {
+  __shared__ LinkLds lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t t = blockIdx.x;
+  const int u = touched[t];
+  // (uniform) in place: two workgroups must never own one row, which strictly ascending entries rule out
+  if (u < 0 || u >= n_old || (t > 0 && touched[t - 1] >= u)) return;
+  const float4* rows4 = reinterpret_cast<const float4*>(rows);
+  const int h = M / 2, L = M + h;
+  int32_t* mine = graph + (int64_t)u * M;
+  if (tid < CHUNKS) lds.q[tid] = rows4[(int64_t)u * CHUNKS + tid];
+  if (tid < L) lds.seq[tid] = tid < M ? mine[tid] : incoming[t * h + (tid - M)];
+  __syncthreads();
+  if (wave == 0) {
+    const bool k0 = g_first_edge(lds.seq, lane, L, u, n_total), k1 = g_first_edge(lds.seq, lane + 64, L, u, n_total);
+    const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const int n0 = __popcll(m0);
+    if (k0) lds.kept[__popcll(m0 & lt)] = lds.seq[lane];
+    if (k1) lds.kept[n0 + __popcll(m1 & lt)] = lds.seq[lane + 64];
+    if (lane == 0) {
+      const int n_adj = __popcll(M == 64 ? m0 : m0 & ((1ull << M) - 1ull));   // entries kept out of graph[u]: M <= 64
+      lds.n_kept = n0 + __popcll(m1);
+      lds.n_head = min(h, n_adj);
+    }
+  }
+  __syncthreads();
+  const int n_head = lds.n_head, P = lds.n_kept - n_head;   // (uniform) P <= M: at most M - h of graph[u] and h incoming
+  const int* pool = lds.kept + n_head;
+
+  RowStage stage;
+  auto load_chunk = [&](int ch) {
+    const int* ids = pool + ch * STAGE_ROWS;
+    const int left = P - ch * STAGE_ROWS;
+    stage.load(rows4, tid, [&](int row) { return row < left ? ids[row] : -1; });
+  };
+  const int n_chunks = (P + STAGE_ROWS - 1) / STAGE_ROWS;
+  if (n_chunks > 0) {   // (uniform)
+    load_chunk(0);
+    stage.store(lds.rows, tid);
+  }
+  __syncthreads();
+  for (int ch = 0; ch < n_chunks; ++ch) {
+    const bool more = ch + 1 < n_chunks;
+    if (more) load_chunk(ch + 1);   // in flight while wave 0 scores
+    if (wave == 0 && lane < STAGE_ROWS) {
+      const int j = ch * STAGE_ROWS + lane;
+      if (j < P) lds.score[j] = stage_score(lds.rows, lane, lds.q);
+    }
+    __syncthreads();   // the chunk has been read
+    if (more) stage.store(lds.rows, tid);
+    __syncthreads();
+  }
+  // graph[u] was read whole before the barriers above; every element is written once below
+  const int n_out = min(M, n_head + P);
+  if (tid < n_head) mine[tid] = lds.kept[tid];
+  if (tid < P) {
+    const float s = lds.score[tid];
+    const int id = pool[tid];
+    int rank = 0;
+    for (int e = 0; e < P; ++e) rank += l_before(lds.score[e], pool[e], s, id);
+    if (n_head + rank < M) mine[n_head + rank] = id;
+  }
+  if (tid >= n_out && tid < M) mine[tid] = -1;
+}
+
 bool graph_degree_ok(int M) { return M >= 4 && M <= G_M_MAX && M % 2 == 0; }
 
 bool graph_shape_ok(int nq, int k, int ef, int width, int M, int n_seeds) {
   return nq >= 1 && k >= 1 && k <= ef && ef <= G_EF_MAX && width >= 1 && width <= G_WIDTH_MAX && graph_degree_ok(M) &&
          n_seeds >= 1 && n_seeds <= G_EF_MAX;
+}
+
+// sskd_graph_merge and sskd_graph_merge_rows: one set of checks, one launch
+int graph_merge_rows(const char* who, const int32_t* d_fwd, const int32_t* d_rev, int64_t n_rows, int64_t row_base,
+                     int64_t n_total, int M, int32_t* d_graph, void* stream) {
+  SSKD_REQUIRE(n_rows >= 0, "%s: n_rows < 0", who);
+  SSKD_REQUIRE(row_base >= 0, "%s: row_base < 0", who);
+  SSKD_REQUIRE(graph_degree_ok(M), "%s: M=%d must be even and in [4, %d]", who, M, G_M_MAX);
+  SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS && n_total < sskd::MAX_SHARD_ROWS, "%s: shard too large for int32 row ids", who);
+  SSKD_REQUIRE(row_base <= n_total && n_rows <= n_total - row_base, "%s: rows [row_base, row_base + n_rows) outside [0, n_total=%lld)",
+               who, (long long)n_total);
+  if (n_rows == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_fwd && d_rev && d_graph, "%s: null pointer", who);
+  const int per_block = G_MERGE_THREADS / 64;
+  hipLaunchKernelGGL(graph_merge_kernel, dim3((unsigned)sskd::ceil_div(n_rows, per_block)), dim3(G_MERGE_THREADS), 0,
+                     sskd::as_stream(stream), d_fwd, d_rev, n_rows, row_base, n_total, M, d_graph);
+  return sskd::check_launch("graph_merge_kernel");
 }
 
 }  // namespace
@@ -448,21 +592,49 @@ int sskd_graph_prune(const int32_t* d_knn, int64_t n_rows, int knn_k, int M, int
   SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS, "graph_prune: shard too large for int32 row ids");
   if (n_rows == 0) return SSKD_OK;
   SSKD_REQUIRE(d_knn && d_fwd, "graph_prune: null pointer");
-  hipLaunchKernelGGL(graph_prune_kernel, dim3((unsigned)n_rows), dim3(G_KNN_MAX), 0, sskd::as_stream(stream), d_knn, n_rows,
-                     knn_k, M, d_fwd);
+  hipLaunchKernelGGL(graph_prune_kernel<KnnLists>, dim3((unsigned)n_rows), dim3(G_KNN_MAX), 0, sskd::as_stream(stream),
+                     KnnLists{d_knn, knn_k}, d_knn, (int64_t)0, n_rows, knn_k, M, d_fwd);
   return sskd::check_launch("graph_prune_kernel");
 }
 
+int sskd_graph_insert_prune(const int32_t* d_graph_old, int64_t n_old, const int32_t* d_knn_new, int64_t n_new, int knn_k,
+                            int M, int32_t* d_fwd_new, void* stream) {
+  SSKD_REQUIRE(n_old >= 0, "graph_insert_prune: n_old < 0");
+  SSKD_REQUIRE(n_new >= 0, "graph_insert_prune: n_new < 0");
+  SSKD_REQUIRE(graph_degree_ok(M), "graph_insert_prune: M=%d must be even and in [4, %d]", M, G_M_MAX);
+  SSKD_REQUIRE(knn_k >= M && knn_k <= G_KNN_MAX, "graph_insert_prune: knn_k=%d outside [M=%d, %d]", knn_k, M, G_KNN_MAX);
+  SSKD_REQUIRE(n_old < sskd::MAX_SHARD_ROWS && n_new < sskd::MAX_SHARD_ROWS && n_old + n_new < sskd::MAX_SHARD_ROWS,
+               "graph_insert_prune: shard too large for int32 row ids");
+  if (n_new == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_knn_new && d_fwd_new && (n_old == 0 || d_graph_old), "graph_insert_prune: null pointer");
+  hipLaunchKernelGGL(graph_prune_kernel<InsertLists>, dim3((unsigned)n_new), dim3(G_KNN_MAX), 0, sskd::as_stream(stream),
+                     InsertLists{d_graph_old, d_knn_new, n_old, M, knn_k}, d_knn_new, n_old, n_old + n_new, knn_k, M, d_fwd_new);
+  return sskd::check_launch("graph_insert_prune_kernel");
+}
+
 int sskd_graph_merge(const int32_t* d_fwd, const int32_t* d_rev, int64_t n_rows, int M, int32_t* d_graph, void* stream) {
-  SSKD_REQUIRE(n_rows >= 0, "graph_merge: n_rows < 0");
-  SSKD_REQUIRE(graph_degree_ok(M), "graph_merge: M=%d must be even and in [4, %d]", M, G_M_MAX);
-  SSKD_REQUIRE(n_rows < sskd::MAX_SHARD_ROWS, "graph_merge: shard too large for int32 row ids");
-  if (n_rows == 0) return SSKD_OK;
-  SSKD_REQUIRE(d_fwd && d_rev && d_graph, "graph_merge: null pointer");
-  const int per_block = G_MERGE_THREADS / 64;
-  hipLaunchKernelGGL(graph_merge_kernel, dim3((unsigned)sskd::ceil_div(n_rows, per_block)), dim3(G_MERGE_THREADS), 0,
-                     sskd::as_stream(stream), d_fwd, d_rev, n_rows, M, d_graph);
-  return sskd::check_launch("graph_merge_kernel");
+  return graph_merge_rows("graph_merge", d_fwd, d_rev, n_rows, 0, n_rows, M, d_graph, stream);
+}
+
+int sskd_graph_merge_rows(const int32_t* d_fwd, const int32_t* d_incoming, int64_t n_rows, int64_t row_base, int64_t n_total,
+                          int M, int32_t* d_graph_rows, void* stream) {
+  return graph_merge_rows("graph_merge_rows", d_fwd, d_incoming, n_rows, row_base, n_total, M, d_graph_rows, stream);
+}
+
+int sskd_graph_link(const float* d_tiled, int32_t* d_graph, int64_t n_old, int64_t n_total, int M, const int32_t* d_touched,
+                    const int32_t* d_incoming, int64_t n_touched, void* stream) {
+  SSKD_REQUIRE(n_old >= 0, "graph_link: n_old < 0");
+  SSKD_REQUIRE(n_total >= n_old, "graph_link: n_total=%lld < n_old=%lld", (long long)n_total, (long long)n_old);
+  SSKD_REQUIRE(n_touched >= 0, "graph_link: n_touched < 0");
+  SSKD_REQUIRE(graph_degree_ok(M), "graph_link: M=%d must be even and in [4, %d]", M, G_M_MAX);
+  SSKD_REQUIRE(n_total < sskd::MAX_SHARD_ROWS, "graph_link: shard too large for int32 row ids");
+  SSKD_REQUIRE(n_touched < sskd::MAX_SHARD_ROWS, "graph_link: n_touched too large");
+  if (n_touched == 0) return SSKD_OK;
+  SSKD_REQUIRE(d_tiled && d_graph && d_touched && d_incoming, "graph_link: null pointer");
+  SSKD_REQUIRE(reinterpret_cast<uintptr_t>(d_tiled) % 16 == 0, "graph_link: the index must be 16-byte aligned");
+  hipLaunchKernelGGL(graph_link_kernel, dim3((unsigned)n_touched), dim3(G_THREADS), 0, sskd::as_stream(stream), d_tiled,
+                     d_graph, n_old, n_total, M, d_touched, d_incoming);
+  return sskd::check_launch("graph_link_kernel");
 }
 
 }  // extern "C"

@@ -13,7 +13,11 @@ force).  ``flat`` is ``FAISSIndexBuilder``, the inverted lists are ``ivf.IVFInde
   index"): a search returns, of the rows it scored, the top-k in the exact search's order with the exact search's bits.
 * The graph is built on the device and deterministically: the k-NN lists are the exact search of the index against
   itself, pruning (``sskd_graph_prune``), reverse edges (a stable sort) and the merge (``sskd_graph_merge``) are
-  integer-only.  There is no incremental insertion: ``add`` rebuilds the graph over all rows.
+  integer-only.
+* ``insert`` appends rows and links them into the graph it has, at a cost proportional to the new rows: their exact
+  k-NN lists, the same pruning over two kinds of lists (``sskd_graph_insert_prune``), reverse edges, the adjacency of
+  the new rows (``sskd_graph_merge_rows``) and, for every linked row a new row names, a re-selection of its
+  replaceable half by exact score (``sskd_graph_link``).  ``add`` rebuilds the graph over all rows.
 """
 from __future__ import annotations
 
@@ -60,6 +64,17 @@ def entry_rows_of(n: int, n_entry: int) -> np.ndarray:
     if n_entry < 0 or n_entry > n:
         raise ValueError(f"n_entry={n_entry} outside [0, {n}]")
     return ((np.arange(n_entry, dtype=np.int64) * int(n)) // max(int(n_entry), 1)).astype(np.int32)
+
+
+def n_entry_of_insert(b: int, n0: int, M: int, n_entry_requested: Optional[int]) -> int:
+    """Entry rows an insertion of ``b`` rows into ``n0`` adds: one in M (``default_n_entry``'s rule), or the share
+    ``b / n0`` of the count the caller fixed; at least one, at most ``b``."""
+    b, n0 = int(b), int(n0)
+    if n_entry_requested is None:
+        e = -(-b // int(M))
+    else:
+        e = -(-b * int(n_entry_requested) // max(n0, 1))
+    return min(b, max(1, e))
 
 
 def check_graph(graph: np.ndarray, n_rows: int) -> None:
@@ -136,6 +151,7 @@ class GraphIndex(FlatOverlay):
         self.graph: Optional[torch.Tensor] = None        # device int32 [ntotal, M]
         self.entry_rows: Optional[torch.Tensor] = None   # device int32 [n_entry]
         self._n_linked = 0
+        self.n_inserted = 0                              # rows linked by insert() since the last build_graph()
         self.last_search_path: Optional[str] = None
 
     # ------------------------------------------------------------------ properties
@@ -157,25 +173,26 @@ class GraphIndex(FlatOverlay):
         return self.entry_rows.cpu().numpy()
 
     # ------------------------------------------------------------------ building
-    def knn_device(self, knn_k: int, batch: int = 1 << 14) -> torch.Tensor:
-        """Device int32 ``[ntotal, knn_k]``: every row's nearest rows in the exact search's rank order without the row
-        itself, -1 where the index has fewer rows.  Batches of rows are searched for ``knn_k + 1`` results over ALL
+    def knn_device(self, knn_k: int, batch: int = 1 << 14, first: int = 0) -> torch.Tensor:
+        """Device int32 ``[ntotal - first, knn_k]``: the nearest rows of every row from ``first`` on (``insert`` asks
+        for the new rows only) in the exact search's rank order without the row itself, -1 where the index has fewer
+        rows.  Batches of rows are searched for ``knn_k + 1`` results over ALL
         rows; the entry equal to the row is dropped, or the last one when the row is not among its own results (more
         than ``knn_k`` copies of it rank first).  The search is the flat index's ``_search_device_masked`` - what
         ``flat.search_device`` runs - called directly with no mask and ``id_offset = 0``: ``search_device`` would hide
         removed rows, which must take part here, and return global ids where the graph needs local rows.  Dropping the
         entry is a boolean-mask gather in torch, which synchronises the host once per batch: harmless for a build,
         and the reason a build cannot be captured into a graph."""
-        n, K0 = self.flat.ntotal, int(knn_k)
+        n, K0, first = self.flat.ntotal, int(knn_k), int(first)
         rows = self._rows_view()
-        out = torch.empty((n, K0), dtype=torch.int32, device=self.device)
+        out = torch.empty((n - first, K0), dtype=torch.int32, device=self.device)
         cols = torch.arange(K0 + 1, device=self.device)
-        for lo in range(0, n, batch):
+        for lo in range(first, n, batch):
             part = rows[lo: lo + batch]
             _, ids = self.flat._search_device_masked(part, K0 + 1, False, None, None, None, id_offset=0)
             own = ids == torch.arange(lo, lo + part.shape[0], device=self.device)[:, None]
             drop = torch.where(own.any(dim=1), own.to(torch.int8).argmax(dim=1), torch.full_like(ids[:, 0], K0))
-            out[lo: lo + part.shape[0]] = ids[cols[None, :] != drop[:, None]].view(-1, K0).to(torch.int32)
+            out[lo - first: lo - first + part.shape[0]] = ids[cols[None, :] != drop[:, None]].view(-1, K0).to(torch.int32)
         return out
 
     def prune_device(self, knn: torch.Tensor, M: int) -> torch.Tensor:
@@ -214,6 +231,88 @@ class GraphIndex(FlatOverlay):
                                                       _native.current_stream_ptr(self.device)))
         return graph
 
+    # ------------------------------------------------------------------ incremental insertion
+    def insert_prune_device(self, graph_old: torch.Tensor, knn_new: torch.Tensor) -> torch.Tensor:
+        """``sskd_graph_insert_prune``: device int32 ``[b, M]`` for the ``b`` new rows behind the ``n0`` rows of
+        ``graph_old``; the list of a neighbour is its row of ``graph_old`` or of ``knn_new``."""
+        n0, M = graph_old.shape
+        b, K0 = knn_new.shape
+        fwd = torch.empty((b, M), dtype=torch.int32, device=self.device)
+        _native.check(_native.load().sskd_graph_insert_prune(graph_old.data_ptr(), n0, knn_new.data_ptr(), b, K0, M,
+                                                             fwd.data_ptr(), _native.current_stream_ptr(self.device)))
+        return fwd
+
+    def incoming_device(self, fwd_new: torch.Tensor, n0: int):
+        """The reverse edges of an insertion, ``(incoming_new [b, M / 2], touched [t], incoming_old [t, M / 2])``, all
+        device int32: the sources ``n0 + v`` that name a target among the first M / 2 entries of ``fwd_new[v]``, by
+        (position, source), the first M / 2 per target, -1 padded.  ``touched`` = the targets below ``n0``, ascending
+        and unique; row i of ``incoming_old`` belongs to ``touched[i]``.  One stable sort by target over the edges laid
+        out position-major, as ``reverse_device``."""
+        b, M = fwd_new.shape
+        h = M // 2
+        target = fwd_new[:, :h].t().reshape(-1).to(torch.int64)                   # (position, source) ascending
+        source = (n0 + torch.arange(b, dtype=torch.int32, device=self.device)).repeat(h)
+        real = target >= 0
+        target, source = target[real], source[real]
+        order = torch.sort(target, stable=True).indices
+        target, source = target[order], source[order]
+        named, group, counts = torch.unique_consecutive(target, return_inverse=True, return_counts=True)
+        first = torch.cumsum(counts, 0) - counts
+        place = torch.arange(target.numel(), device=self.device) - first[group]
+        fits = place < h
+        incoming = torch.full((named.numel(), h), -1, dtype=torch.int32, device=self.device)
+        incoming[group[fits], place[fits]] = source[fits]
+        n_touched = int((named < n0).sum().item())
+        incoming_new = torch.full((b, h), -1, dtype=torch.int32, device=self.device)
+        incoming_new[named[n_touched:] - n0] = incoming[n_touched:]
+        return incoming_new, named[:n_touched].to(torch.int32), incoming[:n_touched].contiguous()
+
+    def merge_rows_device(self, fwd_new: torch.Tensor, incoming_new: torch.Tensor, n0: int, out: torch.Tensor) -> None:
+        """``sskd_graph_merge_rows`` into ``out`` (device int32 ``[b, M]``, the rows ``[n0, n0 + b)`` of the adjacency)."""
+        b, M = fwd_new.shape
+        _native.check(_native.load().sskd_graph_merge_rows(fwd_new.data_ptr(), incoming_new.data_ptr(), b, n0, n0 + b, M,
+                                                           out.data_ptr(), _native.current_stream_ptr(self.device)))
+
+    def link_device(self, graph: torch.Tensor, n0: int, touched: torch.Tensor, incoming_old: torch.Tensor) -> None:
+        """``sskd_graph_link``: rewrites the rows ``touched`` (strictly ascending, below ``n0``) of ``graph`` (device
+        int32 ``[ntotal, M]``) in place."""
+        n1, M = graph.shape
+        _native.check(_native.load().sskd_graph_link(self.flat._tiled.data_ptr(), graph.data_ptr(), n0, n1, M,
+                                                     touched.data_ptr(), incoming_old.data_ptr(), touched.numel(),
+                                                     _native.current_stream_ptr(self.device)))
+
+    def insert(self, embeddings, groups: Optional[Sequence] = None) -> None:
+        """Append rows and link them into the graph the index has ("Incremental insertion"): the
+        cost follows the new rows, not the corpus.  The new rows get their exact k-NN lists over ALL rows, pruned like
+        a build's; every linked row a new row names re-selects, by exact score, the half of its adjacency that the
+        build's forward edges do not protect.  Deterministic.  ``groups`` passes to the flat add.  ``n_inserted`` counts
+        the rows linked this way since the last ``build_graph()``: the graph of a corpus that has grown severalfold is
+        worth rebuilding."""
+        self._require_graph()
+        n0 = self.flat.ntotal
+        self.flat.add(embeddings, groups=groups)
+        n1 = self.flat.ntotal
+        b = n1 - n0
+        if b == 0:
+            return
+        M = self.M
+        K0 = self.knn_k if self.knn_k is not None else min(2 * M, GRAPH_KNN_MAX)
+        e = n_entry_of_insert(b, n0, M, self.n_entry_requested)
+        with torch.cuda.device(self.device):
+            knn_new = self.knn_device(K0, first=n0)
+            fwd_new = self.insert_prune_device(self.graph, knn_new)
+            incoming_new, touched, incoming_old = self.incoming_device(fwd_new, n0)
+            graph = torch.empty((n1, M), dtype=torch.int32, device=self.device)
+            graph[:n0].copy_(self.graph)
+            self.merge_rows_device(fwd_new, incoming_new, n0, graph[n0:])
+            self.link_device(graph, n0, touched, incoming_old)
+            new_entry = torch.from_numpy((n0 + entry_rows_of(b, e).astype(np.int64)).astype(np.int32)).to(self.device)
+            self.entry.add(self._rows_view()[new_entry.to(torch.int64)].contiguous())
+            self.entry_rows = torch.cat([self.entry_rows, new_entry])
+            self.graph = graph
+        self._n_linked = n1
+        self.n_inserted += b
+
     def build_graph(self, M: Optional[int] = None, knn_k: Optional[int] = None) -> None:
         """k-NN lists (the exact search of the index against itself), detour pruning, reverse edges, merge; then the
         entry rows.  ``knn_k`` defaults to ``2 M``.  Deterministic."""
@@ -229,6 +328,7 @@ class GraphIndex(FlatOverlay):
             graph = self.merge_device(fwd, self.reverse_device(fwd))
         self.M, self.knn_k = M, K0
         self._install(graph, None)
+        self.n_inserted = 0
 
     def _install(self, graph: torch.Tensor, entry_rows: Optional[np.ndarray]) -> None:
         """Adopts a device adjacency over all rows held and (re)builds the entry index (None: the default rows)."""
@@ -273,8 +373,8 @@ class GraphIndex(FlatOverlay):
         return handle
 
     def add(self, embeddings, groups: Optional[Sequence] = None) -> None:
-        """Flat add, then ``build_graph()`` over ALL rows: there is no incremental insertion (DESIGN section 20 has the
-        rebuild time)."""
+        """Flat add, then ``build_graph()`` over ALL rows (DESIGN section 20 has the rebuild time); ``insert`` appends
+        without rebuilding."""
         first = self.flat.ntotal
         self.flat.add(embeddings, groups=groups)
         if self.flat.ntotal != first or self.graph is None:
@@ -287,6 +387,7 @@ class GraphIndex(FlatOverlay):
         graph = self.graph_numpy()
         kept = self.flat.compact()
         self._from_host(remap_graph(graph, kept - self.flat.id_offset), None)
+        self.n_inserted = min(self.n_inserted, self.flat.ntotal)
         return kept
 
     # ------------------------------------------------------------------ search
@@ -363,8 +464,10 @@ class GraphIndex(FlatOverlay):
         ``graph_entry_rows.npy`` and ``graph.json``."""
         self._require_graph()
         self.flat.save(output_dir)
-        save_graph(output_dir, self.graph_numpy(), self.entry_rows_numpy(),
-                   {"knn_k": self.knn_k, "ef": self.ef, "width": self.width})
+        meta = {"knn_k": self.knn_k, "ef": self.ef, "width": self.width}
+        if self.n_inserted:
+            meta["n_inserted"] = int(self.n_inserted)   # an optional key: absent = 0
+        save_graph(output_dir, self.graph_numpy(), self.entry_rows_numpy(), meta)
 
     def load(self, index_dir: Union[str, Path]) -> None:
         """Restore a saved graph index: its searches return the bits they returned before the save."""
@@ -380,9 +483,10 @@ class GraphIndex(FlatOverlay):
         self.knn_k = meta.get("knn_k")
         self.ef = int(meta.get("ef", self.ef))
         self.width = int(meta.get("width", self.width))
+        self.n_inserted = int(meta.get("n_inserted", 0))
 
     def cleanup(self) -> None:
         self.flat.cleanup()
         self.entry.cleanup()
         self.graph = self.entry_rows = None
-        self._n_linked = 0
+        self._n_linked = self.n_inserted = 0
