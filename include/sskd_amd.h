@@ -554,6 +554,41 @@ int sskd_prf_rm3(const int64_t* d_fwd_lims, const int32_t* d_fwd_terms, const do
                  int32_t* d_out_fb, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Diversified search: Maximal Marginal Relevance over a first stage's candidates, with a near-duplicate cut-off
+ *   Carbonell & Goldstein 1998.  The reference has no such step; the rule below is this library's definition.
+ * Inputs per query q: the ranking d_rank_scores fp32 / d_rank_ids int64 [nq, fetch_k] as any dense search above writes it
+ * with id_offset 0 (LOCAL rows, padded with id -1).
+ *   - candidates: the entries up to the first id -1, ids outside [0, n_rows) skipped, in list order: c_0 .. c_{m-1} with
+ *     relevance s_i = the list's score taken as given (not recomputed).  The caller promises that a row occurs at most
+ *     once; the call is safe if it does not.
+ *   - similarity: sim(i, j) = the fp32 fma chain of the exact scan with row c_i as the row and row c_j as the query
+ *     vector - the bits a search for row c_j would return for row c_i, symmetric bit for bit (products commute, the
+ *     column order is fixed).  It reads the stored rows (unit rows under the cosine metric), never the query.
+ *   - redundancy: every candidate carries red_i, unset at the start.  After a candidate p is selected, every still-alive
+ *     i gets red_i = sim(i, p) if red_i is unset or sim(i, p) > red_i (fp32, strict); then, if red_i >= dup_threshold,
+ *     the candidate dies: it can never be selected.  dup_threshold = +inf turns the cut-off off.
+ *   - value, fp64, every product and the subtraction rounded once (no fma): value_i = a * (double)s_i - b * (double)r_i
+ *     with a = lambda, b = 1.0 - lambda, r_i = red_i, or +0.0 while red_i is unset.
+ *   - selection: up to k times while a candidate is alive, the alive candidate with the largest value, ties to the
+ *     earlier list position, is selected and marked dead; then the redundancy state is updated as above.  (With
+ *     lambda > 0 the first selection is therefore candidate c_0.)
+ *   - output, in selection order: d_out_scores fp32 [nq, k] = s (padded with -FLT_MAX), d_out_ids int64 [nq, k] = row +
+ *     id_offset (padded with -1), d_out_mmr fp64 [nq, k] = the value at selection (padded with -inf; may be NULL),
+ *     d_out_red fp32 [nq, k] = r at selection (padded with a quiet NaN; may be NULL), d_out_counts int32 [nq] = how
+ *     many were selected.
+ * One workgroup of 256 threads per query; candidates, relevance, red and an alive bitmap live in LDS, and a selection
+ * costs only the similarities of the selected row to the alive candidates (k * m chains per query, not m * m).  With
+ * fetch_k <= 100 every candidate row is held in LDS for the whole call; longer lists go through a 32-row stage.
+ * Limits: 1 <= k <= fetch_k <= SSKD_K_MAX; lambda finite and in [0, 1]; dup_threshold not NaN; n_rows < 2^31 - 64;
+ * d_tiled 16-byte aligned.  Scores and rows are finite: the call does not check that.  Stream-ordered, no host sync
+ * (graph-capturable), no workspace, allocates nothing; arguments are checked before the launch (SSKD_ERR_INVALID);
+ * nq = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_mmr_select(const float* d_tiled, int64_t n_rows, const float* d_rank_scores, const int64_t* d_rank_ids, int nq,
+                    int fetch_k, double lambda, float dup_threshold, int k, int64_t id_offset, float* d_out_scores,
+                    int64_t* d_out_ids, double* d_out_mmr, float* d_out_red, int32_t* d_out_counts, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Retrieval evaluation: nDCG / MRR / recall / precision per cutoff, and the discordant pairs behind Kendall's tau
  *   reference: ndcg_at_k / mrr_at_k / recall_at_k / precision_at_k / kendall_tau, src/utils/metrics.py:11-157;
  *   KDEvaluator.evaluate_retrieval / _evaluate_model / evaluate_ranking_quality, src/kd/eval.py:42-265

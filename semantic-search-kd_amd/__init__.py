@@ -16,6 +16,7 @@ from .losses import CombinedKDLoss, ContrastiveLoss, ListwiseKDLoss, MarginMSELo
 from .bm25 import BM25Index, build_bm25_index  # noqa: F401
 from .hybrid import HybridIndex  # noqa: F401
 from .expand import ExpandedIndex, QueryExpansion  # noqa: F401
+from .diversify import DiverseIndex, Diversity  # noqa: F401
 from .graph import GraphIndex  # noqa: F401
 from .ivf import IVFIndex  # noqa: F401
 from .pq import IVFPQIndex  # noqa: F401
@@ -47,6 +48,8 @@ __all__ = [
     "HybridIndex",
     "ExpandedIndex",
     "QueryExpansion",
+    "DiverseIndex",
+    "Diversity",
     "GraphIndex",
     "IVFIndex",
     "IVFPQIndex",

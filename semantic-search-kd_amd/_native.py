@@ -193,6 +193,9 @@ SIGNATURES = {
         _i, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i64, _vp, _vp,
              _vp, _vp, _vp, _vp, _vp, _vp]
     ),
+    "sskd_mmr_select": (
+        _i, [_vp, _i64, _vp, _vp, _i, _i, C.c_double, _f, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_eval_judge": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp]),
     "sskd_eval_lists": (
         _i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]

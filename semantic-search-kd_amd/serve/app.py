@@ -92,6 +92,25 @@ class ServeSettings:
     expansion_beta: float = 0.75
     expansion_orig_repeat: int = 2
     expansion_max_df_fraction: float = 0.25
+    # diversified results (diversify.DiverseIndex; the reference has no such step): /search fetches diversity_fetch_k
+    # candidates from the dense first stage and picks k of them by Maximal Marginal Relevance, dropping candidates whose
+    # cosine to a picked row reaches diversity_dup_threshold (unset: no cut-off).  It wraps the dense stage outermost,
+    # around the optional query expansion; with hybrid retrieval it is skipped (fused scores are not cosine relevance).
+    # A late-interaction or teacher rerank that follows RE-ORDERS the diversified set by its own scores: the set is
+    # MMR's, the order is the reranker's.
+    diversity_enabled: bool = False
+    diversity_lambda: float = 0.5
+    diversity_fetch_k: int = 50
+    diversity_dup_threshold: Optional[float] = None
+
+    def diversity(self):
+        """The ``Diversity`` /search applies, or None (the flag is off)."""
+        if not self.diversity_enabled:
+            return None
+        from ..diversify import Diversity
+
+        return Diversity(lambda_mult=self.diversity_lambda, fetch_k=self.diversity_fetch_k,
+                         dup_threshold=self.diversity_dup_threshold)
 
     def query_expansion(self):
         """The ``QueryExpansion`` /search applies, or None (the flag is off)."""
@@ -131,6 +150,11 @@ class ServeSettings:
             expansion_orig_repeat=int(e.get("SEMANTIC_KD_EXPANSION__ORIG_REPEAT") or ServeSettings.expansion_orig_repeat),
             expansion_max_df_fraction=float(e.get("SEMANTIC_KD_EXPANSION__MAX_DF_FRACTION")
                                             or ServeSettings.expansion_max_df_fraction),
+            diversity_enabled=_env_bool(e.get("SEMANTIC_KD_FEATURES__ENABLE_DIVERSITY"), ServeSettings.diversity_enabled),
+            diversity_lambda=float(e.get("SEMANTIC_KD_DIVERSITY__LAMBDA") or ServeSettings.diversity_lambda),
+            diversity_fetch_k=int(e.get("SEMANTIC_KD_DIVERSITY__FETCH_K") or ServeSettings.diversity_fetch_k),
+            diversity_dup_threshold=(float(e["SEMANTIC_KD_DIVERSITY__DUP_THRESHOLD"])
+                                     if (e.get("SEMANTIC_KD_DIVERSITY__DUP_THRESHOLD") or "").strip() else None),
         )
 
     def is_production(self) -> bool:
@@ -195,8 +219,12 @@ def _load_hybrid(builder, settings: Optional["ServeSettings"]):
 
         bm25 = BM25Index(settings.bm25_index_path, device=str(builder.device))
         bm25.load()
-        return HybridIndex(builder, bm25, semantic_weight=settings.semantic_weight, bm25_weight=settings.bm25_weight,
-                           fusion_method=settings.fusion_method)
+        hybrid = HybridIndex(builder, bm25, semantic_weight=settings.semantic_weight, bm25_weight=settings.bm25_weight,
+                             fusion_method=settings.fusion_method)
+        if settings.diversity_enabled:
+            logger.warning("Diversity is enabled but retrieval is hybrid: fused scores are not cosine relevance, "
+                           "serving without the MMR step")
+        return hybrid
     except Exception as exc:  # noqa: BLE001
         logger.warning("Failed to load the BM25 index (hybrid retrieval disabled, serving dense-only): %s", exc)
         return None
@@ -378,17 +406,32 @@ def register_routes(app: FastAPI, settings: ServeSettings) -> None:
 
                 return ExpandedIndex(stage, expansion)
 
+            diversity = (app_state.settings or settings).diversity()
+            if diversity is not None and not isinstance(app_state.index_builder, FAISSIndexBuilder):
+                diversity = None   # (a row-sharded index: the candidates' rows live on other ranks)
+
+            def diverse(stage):
+                # diversity wraps the dense stage outermost: MMR over the (expanded) stage's own candidates; a late or
+                # teacher rerank below re-orders the set it returns
+                if diversity is None:
+                    return stage
+                from ..diversify import DiverseIndex
+
+                return DiverseIndex(stage, diversity)
+
             def first_stage(k_first: int):
                 if hybrid is not None and hybrid.dense is app_state.index_builder:
-                    # both sides contribute at least k rows; the fused score is the result's score
+                    # both sides contribute at least k rows; the fused score is the result's score (no MMR step: warned
+                    # about when the BM25 index was loaded)
                     depth = hybrid.clip_depth(max(hybrid.depth, k_first))
                     return expanded(hybrid).search([request.query], query_emb, k=min(k_first, 2 * depth), depth=depth)
-                if app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_first <= 256:
-                    return expanded(app_state.ivf).search(query_emb, k=k_first)
+                k_stage = k_first if diversity is None else diversity.depth(k_first)   # what the stage itself is asked for
+                if app_state.ivf is not None and app_state.ivf.flat is app_state.index_builder and k_stage <= 256:
+                    return diverse(expanded(app_state.ivf)).search(query_emb, k=k_first)
                 if (app_state.graph is not None and app_state.graph.flat is app_state.index_builder
-                        and k_first <= app_state.graph.ef):
-                    return expanded(app_state.graph).search(query_emb, k=k_first)
-                return expanded(app_state.index_builder).search(query_emb, k=k_first)
+                        and k_stage <= app_state.graph.ef):
+                    return diverse(expanded(app_state.graph)).search(query_emb, k=k_first)
+                return diverse(expanded(app_state.index_builder)).search(query_emb, k=k_first)
 
             late = app_state.late
             if late is not None and late.flat is app_state.index_builder and k_retrieve <= LATE_R_MAX:
