@@ -96,9 +96,9 @@ def bert_hidden_states_torch(t, input_ids, attention_mask, num_layers, num_heads
     return outs
 
 
-def embeddings_torch(t, input_ids, attention_mask, num_layers, num_heads=12, eps=1e-12, normalize=True):
+def embeddings_torch(t, input_ids, attention_mask, num_layers, num_heads=12, eps=1e-12, normalize=True, pos_offset: int = 0):
     """Differentiable masked mean-pool (+ L2 normalise) of ``bert_hidden_states_torch``."""
-    h = bert_hidden_states_torch(t, input_ids, attention_mask, num_layers, num_heads, eps)[-1]
+    h = bert_hidden_states_torch(t, input_ids, attention_mask, num_layers, num_heads, eps, pos_offset=pos_offset)[-1]
     m = torch.from_numpy(np.asarray(attention_mask)).to(h.dtype)[..., None]
     e = (h * m).sum(1) / torch.clamp(m.sum(1), min=1e-9)
     if normalize:

@@ -10,6 +10,14 @@ tests/test_generic_kernels_gpu.py stay tight:
   * ``gelu_bwd_colsum``: the column sum adds du AS STORED (bf16);
   * ``ln_bwd``: ``dz_colsum`` adds dz AS STORED (bf16).
 
+Two further roundings happen in REGISTERS of the fused attention kernels (the bf16 operand of an MFMA).  The per-kernel
+tests cover them with a 2^-8 term in the bound; the chained reference of the whole step (oracle/generic_step.py) asks for
+them, because it is compared with a gate that has no such term:
+
+  * ``attention_fwd(round_p="running")``: P of key tile kt (32 keys) is rounded relative to the row's maximum over
+    tiles 0 .. kt, as the online softmax does, not relative to the final maximum;
+  * ``attention_bwd(round_ps=True)``: P is rounded before P^T dO and dS before dS K and dS^T Q.
+
 Besides the value, most functions return ``mag``: per output element, the sum of the absolute values of the terms that
 make it (sum_k |a_ik| |b_jk| for a product, sum |x| for a column sum ...).  An fp32 accumulation of n such terms is off by
 at most n * 2^-24 * mag; the tests build their bounds from it.
@@ -99,11 +107,13 @@ def attention_scores(qkv, mask, B, S, heads, DH, scale):
     return s.masked_fill(~keep, float("-inf")), keep
 
 
-def attention_fwd(qkv, mask, B, S, heads, DH, scale, round_p: bool = True):
+def attention_fwd(qkv, mask, B, S, heads, DH, scale, round_p=True):
     """ctx [B*S, H] and lse [B, heads, S] (log2 domain) of softmax(scale Q K^T + mask) V.
 
     The kernel multiplies bf16(P) (relative to its running row maximum) by V and divides by the fp32 sum of the UNROUNDED
-    exponentials; with ``round_p`` the reference does the same with P relative to the row's final maximum.  A row
+    exponentials; with ``round_p`` the reference does the same with P relative to the row's final maximum, and with
+    ``round_p="running"`` relative to the maximum over the valid keys of the 32-key tiles up to and including the key's
+    own (what the kernel's online softmax holds when it rounds that tile; later tiles rescale the sum exactly).  A row
     without any valid key: ctx = 0 and lse = -inf (the project's contract, csrc/generic.h).
     Also returns mag [B*S, H] = sum_j P_ij |V_jd| (what the bf16 rounding of P is relative to)."""
     s, keep = attention_scores(qkv, mask, B, S, heads, DH, scale)
@@ -113,7 +123,16 @@ def attention_fwd(qkv, mask, B, S, heads, DH, scale, round_p: bool = True):
     e = torch.exp2(s - torch.where(empty, torch.zeros_like(m), m))
     e = torch.where(empty, torch.zeros_like(e), e)
     l = e.sum(-1, keepdim=True)
-    pe = round_bf16(e) if round_p else e
+    if isinstance(round_p, str):
+        if round_p != "running":
+            raise ValueError(round_p)
+        mt = s.view(B, heads, S, S // 32, 32).amax(-1).cummax(-1).values.repeat_interleave(32, -1)   # [B, heads, S, S]
+        none = torch.isinf(mt)
+        er = torch.exp2(s - torch.where(none, torch.zeros_like(mt), mt))
+        er = torch.where(none, torch.zeros_like(er), er)
+        pe = round_bf16(er) * torch.exp2(torch.where(none, torch.zeros_like(mt), mt - m))
+    else:
+        pe = round_bf16(e) if round_p else e
     inv = torch.where(l > 0, 1.0 / l.clamp_min(1e-300), torch.zeros_like(l))
     ctx = (pe @ v) * inv
     mag = (e @ v.abs()) * inv
@@ -121,11 +140,12 @@ def attention_fwd(qkv, mask, B, S, heads, DH, scale, round_p: bool = True):
     return _merge_heads(ctx), lse, _merge_heads(mag)
 
 
-def attention_bwd(qkv, mask, ctx, dctx, B, S, heads, DH, scale, lse=None):
+def attention_bwd(qkv, mask, ctx, dctx, B, S, heads, DH, scale, lse=None, round_ps: bool = False):
     """dqkv [B*S, 3H] of the fused backward:
         P  = exp2(s - lse)   (lse: the forward's saved log-sum-exp when given, else the exact one)
         D  = rowsum(dO o O)  with O = the GIVEN ctx (the kernel reads the forward's bf16 output)
         dS = P o (dO V^T - D) * scale,   dQ = dS K,   dK = dS^T Q,   dV = P^T dO.
+    ``round_ps``: P and dS are rounded to bf16 before these three products, as the kernel packs them.
     Rows without a valid key contribute nothing.  Also returns mag [B*S, 3H]: sum_j |dS_ij| |K_jd| for dQ,
     sum_i |dS_ij| |Q_id| for dK, sum_i P_ij |dO_id| for dV; and mag_d: the same sums with |dS_ij| replaced by
     P_ij scale (sum_d |dO_id| (|V_jd| + |O_id|)), what the fp32 error of dP - D is relative to."""
@@ -141,7 +161,8 @@ def attention_bwd(qkv, mask, ctx, dctx, B, S, heads, DH, scale, lse=None):
     dp = do @ v.transpose(-1, -2)
     D = (do * o).sum(-1, keepdim=True)
     ds = p * (dp - D) * scale
-    dq, dk, dv = ds @ k, ds.transpose(-1, -2) @ q, p.transpose(-1, -2) @ do
+    pr, dsr = (round_bf16(p), round_bf16(ds)) if round_ps else (p, ds)
+    dq, dk, dv = dsr @ k, dsr.transpose(-1, -2) @ q, pr.transpose(-1, -2) @ do
     mq, mk, mv = ds.abs() @ k.abs(), ds.abs().transpose(-1, -2) @ q.abs(), p.transpose(-1, -2) @ do.abs()
     out = torch.cat([_merge_heads(dq), _merge_heads(dk), _merge_heads(dv)], 1)
     mag = torch.cat([_merge_heads(mq), _merge_heads(mk), _merge_heads(mv)], 1)

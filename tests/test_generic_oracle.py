@@ -154,3 +154,50 @@ def test_embedding_references():
     assert torch.all(dpos[:2] == 0) and torch.all(dpos[6:] == 0)
     _close(dpos[2:6], dz[:4] + dz[4:] * mask[1].to(F64)[:, None], "dpos")
     _close(dtype0, (dz * mask.reshape(-1, 1)).sum(0), "dtype0")
+
+
+def test_attention_register_roundings_mirror_the_online_softmax():
+    """``attention_fwd(round_p="running")`` against a plain loop over 32-key tiles that keeps a running maximum, rounds the
+    tile's exponentials to bf16 relative to it and rescales the sums when it moves (what the kernel does); with one tile it
+    is ``round_p=True``.  ``attention_bwd(round_ps=True)`` against the three products written out with rounded P and dS; both
+    stay within one rounding (2^-8 of the terms' magnitude) of the unrounded formulas that autograd pins above."""
+    g = torch.Generator().manual_seed(17)
+    B, S, heads, DH = 2, 96, 2, 32
+    H = heads * DH
+    qkv = go.round_bf16(torch.randn(B * S, 3 * H, generator=g, dtype=F64) * 1.5)
+    mask = torch.ones(B, S, dtype=torch.int32)
+    mask[1, 41:] = 0
+    scale = 1.0 / DH ** 0.5
+    ctx, lse, mag = go.attention_fwd(qkv, mask, B, S, heads, DH, scale, round_p="running")
+    plain, lse0, _ = go.attention_fwd(qkv, mask, B, S, heads, DH, scale, round_p=False)
+    assert torch.equal(lse, lse0)
+    assert bool(((ctx - plain).abs() <= 2.0 ** -8 * mag).all()) and not torch.equal(ctx, plain)
+    s, _ = go.attention_scores(qkv, mask, B, S, heads, DH, scale)
+    _, _, v = go._split_heads(qkv, B, S, heads, DH)
+    m = torch.full((B, heads, S, 1), float("-inf"), dtype=F64)
+    l = torch.zeros(B, heads, S, 1, dtype=F64)
+    o = torch.zeros(B, heads, S, DH, dtype=F64)
+    for kt in range(S // 32):
+        st = s[..., 32 * kt:32 * kt + 32]
+        if not torch.isfinite(st).any():
+            continue
+        m_new = torch.maximum(m, st.amax(-1, keepdim=True))
+        alpha = torch.where(torch.isinf(m), torch.zeros_like(m), torch.exp2(m - m_new))
+        e = torch.exp2(st - m_new)
+        l, o, m = l * alpha + e.sum(-1, keepdim=True), o * alpha + go.round_bf16(e) @ v[:, :, 32 * kt:32 * kt + 32], m_new
+    _close(ctx, go._merge_heads(o / l), "ctx with P rounded against the running maximum")
+    one_tile = [go.attention_fwd(qkv[:64], mask[:, :32], 2, 32, heads, DH, scale, round_p=r)[0] for r in ("running", True)]
+    assert torch.equal(one_tile[0], one_tile[1])      # two sequences of 32 keys: the running maximum is the final one
+
+    dctx = go.round_bf16(torch.randn(B * S, H, generator=g, dtype=F64))
+    ctx_b = go.round_bf16(plain)
+    got, _, _ = go.attention_bwd(qkv, mask, ctx_b, dctx, B, S, heads, DH, scale, lse=lse, round_ps=True)
+    ref, mag_b, _ = go.attention_bwd(qkv, mask, ctx_b, dctx, B, S, heads, DH, scale, lse=lse)
+    assert bool(((got - ref).abs() <= 2.0 ** -8 * mag_b).all()) and not torch.equal(got, ref)
+    q, k, _ = go._split_heads(qkv, B, S, heads, DH)
+    p = torch.where(torch.isinf(s), torch.zeros_like(s), torch.exp2(s - lse[..., None]))
+    do = dctx.view(B, S, heads, DH).permute(0, 2, 1, 3)
+    D = (do * ctx_b.view(B, S, heads, DH).permute(0, 2, 1, 3)).sum(-1, keepdim=True)
+    ds = go.round_bf16(p * (do @ v.transpose(-1, -2) - D) * scale)
+    want = torch.cat([go._merge_heads(t) for t in (ds @ k, ds.transpose(-1, -2) @ q, go.round_bf16(p).transpose(-1, -2) @ do)], 1)
+    _close(got, want, "dqkv with P and dS rounded")

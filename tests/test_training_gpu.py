@@ -254,8 +254,11 @@ def test_kd_training_step_matches_oracle_and_learns(gpu):
         refg = t[name].grad.numpy()
         if "key.bias" in name or np.linalg.norm(refg) < 1e-10:
             continue
-        c = _cos(model.p(name).grad.cpu().numpy(), refg)
+        got = model.p(name).grad.cpu().numpy()
+        c = _cos(got, refg)
         assert c >= 0.999, (name, c)   # the per-tensor gate of the encoder-only test holds for the whole step too
+        # ... with its norm rule: a cosine is blind to scale (any positive factor on every gradient would pass it)
+        assert abs(np.linalg.norm(got) / np.linalg.norm(refg) - 1.0) < 0.03, (name, np.linalg.norm(got) / np.linalg.norm(refg))
         checked += 1
     assert checked >= 30
     # optimisation: the same batch, a few AdamW steps
@@ -310,7 +313,7 @@ def test_kd_step_at_bench_depth_and_geometry_vs_oracle(gpu):
     so.backward(gradient=torch.from_numpy(ref_ds.astype(np.float32)))
     assert np.abs(scores.detach().cpu().numpy() - so.detach().numpy()).max() < 1e-2
     assert abs(float(out["loss"].detach()) - ref["loss"]) < 2e-2 * max(1.0, abs(ref["loss"]))
-    worst, checked = 1.0, 0
+    worst, worst_norm, checked = 1.0, 0.0, 0
     for name in model.names:
         refg = t[name].grad.numpy()
         if "key.bias" in name or np.linalg.norm(refg) < 1e-10:
@@ -318,8 +321,12 @@ def test_kd_step_at_bench_depth_and_geometry_vs_oracle(gpu):
         c = _cos(grads[name], refg)
         worst = min(worst, c)
         assert c >= 0.999, (name, c)   # measured worst 0.99954 over 185 tensors (gpurun_out/r03_prof: 12 layers)
+        # the encoder test's norm rule: a cosine is blind to scale (any positive factor on every gradient would pass it)
+        ratio = float(np.linalg.norm(grads[name]) / np.linalg.norm(refg))
+        worst_norm = max(worst_norm, abs(ratio - 1.0))
+        assert abs(ratio - 1.0) < 0.03, (name, ratio)
         checked += 1
-    print(f"12-layer KD step: {checked} parameter tensors, worst gradient cosine {worst:.5f}")
+    print(f"12-layer KD step: {checked} parameter tensors, worst gradient cosine {worst:.5f}, worst |norm ratio - 1| {worst_norm:.4f}")
     assert checked >= 150
     # a second step after zero_grad(set_to_none=True) starts from a zeroed buffer again (no stale accumulation)
     opt = torch.optim.AdamW(model.parameters(), lr=1e-5)
