@@ -409,6 +409,55 @@ int sskd_index_mine_select(const float* d_tiled, int64_t n_rows, const float* d_
                            int32_t* d_out_counts, float* d_out_max_pos, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Denoising of a ranking: drop the mined candidates that are false negatives (text overlap, teacher score)
+ *   reference: configs/kd.yaml `denoising:` (teacher_score_threshold 0.7, text_overlap_threshold 0.8),
+ *   docs/guides/hyperparameter-tuning.md:107 (the rule), compute_text_overlap, src/utils/chunk.py:150-182 (the measure)
+ * The trigram store is built on the host (semantic-search-kd_amd/denoise.py) and uploaded once: a CSR over set numbers
+ * (= corpus rows), d_gram_lims int64 [n_sets + 1] non-decreasing from 0, d_grams uint64 the sets' keys, STRICTLY
+ * ascending within a set.  A key is the three code points of one character 3-gram of the lowered, stripped text,
+ * (c0 << 42) | (c1 << 21) | c2.  The entry points trust a validated store (as the BM25 postings are trusted); a set
+ * holds fewer than 2^31 keys.
+ *   jaccard(a, b): inter = |A n B|, uni = |A| + |B| - inter, value = (double)inter / (double)uni - ONE correctly rounded
+ *   fp64 division, the bits of Python's `int / int`; exactly 0.0 when either set is empty.  A set number outside
+ *   [0, n_sets) is the empty set and never becomes an address.
+ *
+ * sskd_overlap_pairs: pair i = sets (d_a[i], d_b[i]), DEVICE int32 [n_pairs]; writes d_inter / d_union int32 and
+ * d_jaccard fp64 [n_pairs] (union = |A| + |B| for disjoint or empty sets).  One wave per pair, the shorter list
+ * searched in the longer.  n_pairs = 0 is a successful no-op.
+ *
+ * sskd_rank_denoise: the ranking d_rank_scores / d_rank_ids [nq, search_k] has the layout every search writes with
+ * id_offset 0 (LOCAL rows = set numbers, padded with id -1); the positives are the CSR sskd_index_mine_select takes
+ * (d_pos_rows == NULL: no query has positives); d_aux fp32 [nq, search_k] is aligned with the ranking (the teacher's
+ * confidence of each candidate).  Whether a rule is on is decided by its pointer, never by its threshold: d_gram_lims
+ * and d_grams both NULL = overlap rule off (giving one of the two is an error), d_aux NULL = teacher rule off; with
+ * both off the call copies the window.  Per query, in rank order; the walk stops at the first id -1:
+ *   - overlap(rank) = the maximum over the query's positives of jaccard(row, positive); 0.0 without positives or without
+ *     a store.  A candidate that is itself a positive has overlap 1.0 (its set is not empty) and goes whenever the
+ *     threshold is below 1.
+ *   - a rank is DROPPED FOR OVERLAP when overlap > overlap_threshold (strict, in fp64), and DROPPED FOR THE TEACHER
+ *     when (double)aux >= aux_threshold (a NaN aux is therefore kept).
+ *   - the surviving ranks go to d_out_scores fp32 / d_out_ids int64 [nq, search_k] in their input order, score bits and
+ *     ids untouched, the tail padded with (-FLT_MAX, -1): the shape sskd_index_mine_select, sskd_hybrid_fuse and the
+ *     re-rankers take.  d_out_aux fp32 [nq, search_k] (NULL ok) carries the survivors' aux values, the tail (and every
+ *     entry when d_aux is NULL) NaN.  d_out_counts int32 [nq] = the number of survivors.
+ *   - d_out_overlap fp64 / d_out_reason uint8 [nq, search_k] (NULL ok) are aligned with the INPUT ranks: the overlap and
+ *     a bit set (1 = overlap, 2 = teacher); past the walk's end they hold 0.0 and 0.
+ * One workgroup of 256 threads per query (40 KiB of LDS).  Limits: 1 <= search_k <= SSKD_K_MAX; a threshold whose rule is
+ * on must not be NaN; the outputs must not overlap the inputs.  Stream-ordered, no host sync, no workspace, allocates
+ * nothing; arguments are checked before the launch (SSKD_ERR_INVALID); nq = 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+int sskd_overlap_pairs(const int64_t* d_gram_lims, const uint64_t* d_grams, int64_t n_sets,
+                       const int32_t* d_a, const int32_t* d_b, int64_t n_pairs,
+                       int32_t* d_inter, int32_t* d_union, double* d_jaccard, void* stream);
+
+int sskd_rank_denoise(const int64_t* d_gram_lims, const uint64_t* d_grams, int64_t n_sets,
+                      const float* d_rank_scores, const int64_t* d_rank_ids, int nq, int search_k,
+                      const int64_t* d_pos_lims, const int32_t* d_pos_rows,
+                      const float* d_aux, double aux_threshold, double overlap_threshold,
+                      float* d_out_scores, int64_t* d_out_ids, float* d_out_aux, int32_t* d_out_counts,
+                      double* d_out_overlap, uint8_t* d_out_reason, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * BM25 search over an inverted index in HBM (stage 1 of the mining curriculum)
  *   reference: BM25Index.search, src/data/bm25.py:162-192, over rank_bm25.BM25Okapi.get_scores
  * The index is built on the host (semantic-search-kd_amd/bm25.py) and uploaded once: postings in CSR by term id,

@@ -35,6 +35,7 @@ from .evaluation import (  # noqa: F401
     recall_at_k,
 )
 from .mining import ANCEMiner, BM25Miner, TeacherMiner, build_mining_curriculum  # noqa: F401
+from .denoise import Denoising, TrigramStore, compute_text_overlap, text_overlap  # noqa: F401
 from .teacher import TeacherConfig, TeacherModel  # noqa: F401
 from .bench_support import bench_encode  # noqa: F401
 
@@ -69,6 +70,10 @@ __all__ = [
     "precision_at_k",
     "recall_at_k",
     "build_mining_curriculum",
+    "Denoising",
+    "TrigramStore",
+    "compute_text_overlap",
+    "text_overlap",
     "TeacherMiner",
     "TeacherConfig",
     "TeacherModel",

@@ -181,6 +181,10 @@ SIGNATURES = {
     "sskd_index_mine_select": (
         _i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, C.c_double, _i, _i64, _vp, _vp, _vp, _vp, _vp]
     ),
+    "sskd_overlap_pairs": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sskd_rank_denoise": (
+        _i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    ),
     "sskd_bm25_search_workspace_bytes": (_sz, [_i64, _i, _i]),
     "sskd_bm25_search_plan": (_i, [_i64, _i, _i, _ip, _ip, _ip]),
     "sskd_bm25_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -765,6 +765,8 @@ class FAISSIndexBuilder:
         allow=None,
         by_group: bool = False,
         normalize_queries: Optional[bool] = None,
+        denoising=None,
+        trigrams=None,
     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
         """The ANCE rule on the device (``include/sskd_amd.h``, hard-negative mining): the ``search_k`` best rows of
         every query are its candidates, its positives ``pos_rows[pos_lims[q]:pos_lims[q + 1]]`` (device int64 / int32,
@@ -777,8 +779,25 @@ class FAISSIndexBuilder:
         ``max_pos``.  ``by_group=True`` also leaves out every row that shares a group with a positive (the other
         chunks of a positive document).  No host synchronisation (``allow`` should then be a prepared ``RowFilter``):
         the caller guarantees that ``pos_lims`` is non-decreasing and ends inside ``pos_rows``; ``mine_negatives``
-        checks all of that on the host."""
-        lib = _native.load()
+        checks all of that on the host.
+
+        ``denoising`` (a ``denoise.Denoising``; None: today's path, untouched) with ``trigrams`` (the ``TrigramStore``
+        of the index's rows) puts ``sskd_rank_denoise`` between the search and the selection: a candidate whose text
+        overlap with a positive exceeds ``text_overlap_threshold`` leaves the window first, and ``counts`` then counts
+        the survivors of both steps.  Still nothing synchronises and the call stays graph-capturable.  Only the overlap
+        rule runs here: the teacher rule needs texts to score, so a ``denoising`` with a teacher threshold is refused
+        (``ANCEMiner.mine_from_index`` has the texts and a teacher)."""
+        self._check_mining_denoising(denoising, trigrams)
+        q, lims, rows, rank_scores, rank_rows = self._mine_rank(queries, pos_lims, pos_rows, top_k, search_k, allow,
+                                                                normalize_queries)
+        if denoising is not None and q.shape[0]:
+            rank_scores, rank_rows, _, _ = self.denoise_ranking_device(rank_scores, rank_rows, lims, rows, denoising,
+                                                                       trigrams=trigrams)
+        return self._mine_select(q, rank_scores, rank_rows, lims, rows, top_k, margin, by_group)
+
+    def _mine_rank(self, queries, pos_lims, pos_rows, top_k, search_k, allow, normalize_queries):
+        """The checks and the search of ``mine_negatives_device``: ``(q, pos_lims, pos_rows, rank_scores, rank_rows)``,
+        the ranking in LOCAL rows."""
         top_k, search_k = int(top_k), int(search_k)
         if top_k < 1 or top_k > search_k:
             raise ValueError(f"top_k={top_k} outside [1, search_k={search_k}]")
@@ -796,13 +815,19 @@ class FAISSIndexBuilder:
         mask = self._effective_mask(allow)
         # the ranking in LOCAL rows: the kernel compares them with the positives and looks their groups up
         rank_scores, rank_rows = self._search_device_masked(q, search_k, False, None, None, mask, id_offset=0)
+        return q, pos_lims.contiguous(), pos_rows.contiguous(), rank_scores, rank_rows
+
+    def _mine_select(self, q, rank_scores, rank_rows, lims, rows, top_k, margin, by_group):
+        """``sskd_index_mine_select`` over a ranking in LOCAL rows (the search's, or a denoised one)."""
+        lib = _native.load()
+        nq, search_k = rank_scores.shape
+        top_k = int(top_k)
         scores = torch.empty((nq, top_k), dtype=torch.float32, device=self.device)
         ids = torch.empty((nq, top_k), dtype=torch.int64, device=self.device)
         counts = torch.empty(nq, dtype=torch.int32, device=self.device)
         max_pos = torch.empty(nq, dtype=torch.float32, device=self.device)
         if nq == 0:
             return scores, ids, counts, max_pos
-        lims, rows = pos_lims.contiguous(), pos_rows.contiguous()
         groups = self._row_group_device() if by_group and self.group_keys is not None else None   # no groups: rows
         _native.check(
             lib.sskd_index_mine_select(
@@ -816,11 +841,13 @@ class FAISSIndexBuilder:
         return scores, ids, counts, max_pos
 
     def mine_negatives(self, query_emb: np.ndarray, positives, *, top_k: int = 5, search_k: int = 100,
-                       margin: float = 0.1, allow=None, by_group: bool = False):
+                       margin: float = 0.1, allow=None, by_group: bool = False, denoising=None, trigrams=None):
         """``mine_negatives_device`` for host queries: NumPy ``(D, I, counts, max_pos)``.  ``positives``: one list of
         LOCAL rows per query, or a ``(lims, rows)`` tuple (query ``q`` owns ``rows[lims[q]:lims[q + 1]]``); rows are
         sorted and de-duplicated per query, rows outside the index raise ``ValueError``.  ``by_group=True`` on an index
-        without groups means every row is its own group, as in ``search_grouped``."""
+        without groups means every row is its own group, as in ``search_grouped``.  ``denoising`` / ``trigrams``: as
+        in ``mine_negatives_device``."""
+        self._check_mining_denoising(denoising, trigrams)
         if top_k < 1 or top_k > search_k:
             raise ValueError(f"top_k={top_k} outside [1, search_k={search_k}]")
         if search_k > _native.SSKD_K_MAX:
@@ -830,11 +857,66 @@ class FAISSIndexBuilder:
             q = q[None, :]
         lims, rows = normalize_positives(positives, q.shape[0], self._n)
         qd = _host_queries_to_device(q, self.device)
+        extra = {} if denoising is None else {"denoising": denoising, "trigrams": trigrams}
         with torch.cuda.device(self.device):
             out = self.mine_negatives_device(
                 qd, torch.from_numpy(lims).to(self.device), torch.from_numpy(rows).to(self.device), top_k=top_k,
-                search_k=search_k, margin=margin, allow=allow, by_group=by_group)
+                search_k=search_k, margin=margin, allow=allow, by_group=by_group, **extra)
             return tuple(t.cpu().numpy() for t in out)
+
+    # ------------------------------------------------------------------ denoising
+    def _check_mining_denoising(self, denoising, trigrams) -> None:
+        """What ``mine_negatives`` can do of a ``Denoising``: the overlap rule, given the store of this index's rows."""
+        if denoising is None:
+            if trigrams is not None:
+                raise ValueError("trigrams given without denoising")
+            return
+        from .denoise import Denoising
+
+        if not isinstance(denoising, Denoising):
+            raise TypeError("denoising must be a Denoising (or None)")
+        if denoising.teacher_score_threshold is not None:
+            raise ValueError("mine_negatives cannot apply teacher_score_threshold: the teacher rule needs texts to score "
+                             "(pass Denoising(teacher_score_threshold=None) here, or mine through ANCEMiner with a teacher)")
+        if denoising.text_overlap_threshold is not None and trigrams is None:
+            raise ValueError("denoising with a text_overlap_threshold needs trigrams (the TrigramStore of the index's rows)")
+        if trigrams is not None and trigrams.n_sets != self._n:
+            raise ValueError(f"trigrams holds {trigrams.n_sets} sets for an index of {self._n} rows")
+
+    def denoise_ranking_device(self, rank_scores: torch.Tensor, rank_rows: torch.Tensor, pos_lims: torch.Tensor,
+                               pos_rows: torch.Tensor, denoising, trigrams=None, aux: Optional[torch.Tensor] = None,
+                               diagnostics: bool = False):
+        """Drop the false negatives of a ranking in LOCAL rows (``include/sskd_amd.h``, denoising of a ranking): ONE
+        ``sskd_rank_denoise`` on the current stream, no host synchronisation.  A rank goes when its text overlap with
+        one of the query's positives is ``> denoising.text_overlap_threshold`` (needs ``trigrams``, the
+        ``TrigramStore`` of this index's rows) or when ``aux`` (float32 ``[nq, search_k]``, e.g. the teacher's
+        confidence) is ``>= denoising.teacher_score_threshold``; a rule whose threshold is None or whose input is
+        missing is off, and with both off the window is copied.  Returns ``(scores, rows, aux, counts)`` - the
+        survivors in rank order, ``(-FLT_MAX, -1, NaN)`` padded, the shape ``sskd_index_mine_select`` and the re-rankers
+        take - and with ``diagnostics`` also ``(overlap float64, reason uint8)`` aligned with the input ranks."""
+        from . import denoise
+
+        if trigrams is not None and trigrams.n_sets != self._n:
+            raise ValueError(f"trigrams holds {trigrams.n_sets} sets for an index of {self._n} rows")
+        return denoise.rank_denoise_device(rank_scores, rank_rows, pos_lims, pos_rows, denoising, trigrams=trigrams,
+                                           aux=aux, diagnostics=diagnostics)
+
+    def denoise_ranking(self, rank_scores, rank_rows, positives, denoising, trigrams=None, aux=None,
+                        diagnostics: bool = False):
+        """``denoise_ranking_device`` for host arrays: NumPy in (``positives`` as in ``mine_negatives``), NumPy out
+        (``None`` stays ``None``)."""
+        s = np.ascontiguousarray(np.asarray(rank_scores, dtype=np.float32))
+        r = np.ascontiguousarray(np.asarray(rank_rows, dtype=np.int64))
+        if s.ndim != 2 or s.shape != r.shape:
+            raise ValueError("rank_scores and rank_rows must be 2-d arrays of one shape")
+        lims, rows = normalize_positives(positives, s.shape[0], self._n)
+        to = lambda a: torch.from_numpy(a).to(self.device)
+        with torch.cuda.device(self.device):
+            out = self.denoise_ranking_device(
+                to(s), to(r), to(lims), to(rows), denoising, trigrams=trigrams,
+                aux=None if aux is None else to(np.ascontiguousarray(np.asarray(aux, dtype=np.float32))),
+                diagnostics=diagnostics)
+            return tuple(None if t is None else t.cpu().numpy() for t in out)
 
     # ----------------------------------------------------------- grouped search
     def _default_k_rows(self, k: int) -> int:
