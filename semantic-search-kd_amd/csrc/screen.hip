@@ -296,13 +296,24 @@ typedef __attribute__((address_space(3))) const sbf16x8 screen_lds_frag;
 constexpr int SCREEN_FRAGS_PER_BASE = 64;
 template <int QB>
 constexpr int screen_frag_bases() { return (2 * QB * BSTEPS + SCREEN_FRAGS_PER_BASE - 1) / SCREEN_FRAGS_PER_BASE; }
-// Fragment ring of a wave: the LDS read of fragment i + SCREEN_FRAG_DEPTH - 1 is issued in front of the two MFMAs of
-// fragment i.  The register budget of three waves per SIMD (168) decides the depth (per instantiation: DESIGN.md 3.1b)
-#ifndef SSKD_SCREEN_FRAG_DEPTH
-#define SSKD_SCREEN_FRAG_DEPTH 2
+// Fragment ring of a wave: the LDS read of fragment i + D - 1 is issued in front of the two MFMAs of fragment i.  The depth
+// D is chosen per workgroup size, beside the tile ring above ("Fragment read-ahead and the first test";
+// profiles/readahead/README.md).  One read ahead (D = 2) covers the two MFMAs of a fragment, 32 cycles of the matrix
+// pipe, which is less than an LDS round trip: a wave stalled on every fragment unless its partners on the SIMD were
+// multiplying too.  Two ahead (D = 3) took 0.09 ms off the bench kernel; a third (D = 4) added nothing, costs four more
+// registers, and would take 64-query blocks from four waves per SIMD to three (134 registers).  At D = 3 no
+// instantiation spills or loses a wave.  -DSSKD_SCREEN_FRAG_DEPTH=d sets all three for an A/B build (tools/ab_build.py).
+#ifdef SSKD_SCREEN_FRAG_DEPTH
+constexpr int SCREEN_FRAG_DEPTH_Q2 = SSKD_SCREEN_FRAG_DEPTH, SCREEN_FRAG_DEPTH_Q4 = SSKD_SCREEN_FRAG_DEPTH,
+              SCREEN_FRAG_DEPTH_Q5 = SSKD_SCREEN_FRAG_DEPTH;
+#else
+constexpr int SCREEN_FRAG_DEPTH_Q2 = 3, SCREEN_FRAG_DEPTH_Q4 = 3, SCREEN_FRAG_DEPTH_Q5 = 3;
 #endif
-constexpr int SCREEN_FRAG_DEPTH = SSKD_SCREEN_FRAG_DEPTH;
-static_assert(SCREEN_FRAG_DEPTH >= 2, "the fragment ring holds the MFMAs' own operand and at least one read ahead");
+// the depth of the instantiations with QB x 32 queries per workgroup
+template <int QB>
+constexpr int screen_frag_depth() { return QB == 2 ? SCREEN_FRAG_DEPTH_Q2 : QB == 4 ? SCREEN_FRAG_DEPTH_Q4 : SCREEN_FRAG_DEPTH_Q5; }
+static_assert(SCREEN_FRAG_DEPTH_Q2 >= 2 && SCREEN_FRAG_DEPTH_Q4 >= 2 && SCREEN_FRAG_DEPTH_Q5 >= 2,
+              "the fragment ring holds the MFMAs' own operand and at least one read ahead");
 
 // the tile's I-th fragment: fragments run k-step major, query block minor (I = kstep * 2 QB + nb)
 template <int QB, int NB>
@@ -316,7 +327,8 @@ __device__ __forceinline__ sbf16x8 read_qfrag(screen_lds_frag* const (&qbase)[NB
 // through a register ring D deep that runs D - 1 LDS reads ahead of the MFMAs that consume them, across the groups of a
 // tile (the fragments do not depend on the tile): the first MFMA of a fragment waits with a counted lgkmcnt(D - 2) for
 // it while the next reads are in flight, so ONE ready wave keeps the matrix pipe of its SIMD fed when its partners are
-// parked on their tile ring or in their epilogue.  A scheduling barrier on both sides of each MFMA pins that order -
+// parked on their tile ring or in their epilogue - with D - 1 = 2 reads (64 cycles of MFMAs) ahead; one read ahead was
+// short of an LDS round trip (screen_frag_depth above).  A scheduling barrier on both sides of each MFMA pins that order -
 // left to itself the machine scheduler sinks every read to "read, lgkmcnt(0), MFMA", a full LDS round trip in front of
 // the MFMAs.  The tile ring's global loads are issued by the caller ahead of the group and stay there.
 template <int QB, int G, int BG, int D, int NB>
@@ -534,7 +546,8 @@ __global__ __launch_bounds__(64) void screen_scores_probe_kernel(const sbf16x8* 
   screen_lds_frag* qbase[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) qbase[nb] = (screen_lds_frag*)(qs + lane) + nb * SCREEN_FRAGS_PER_BASE * 64;
-  sbf16x8 buf[RG][BG][2], qfrag[SCREEN_FRAG_DEPTH];
+  constexpr int D = screen_frag_depth<QB>();
+  sbf16x8 buf[RG][BG][2], qfrag[D];
   const unsigned lane_off = (unsigned)(n + 32 * g) * 16u;
 #pragma unroll
   for (int gr = 0; gr + 1 < RG; ++gr) load_bgroup<BG>(buf[gr], tiled + gr * BG * 128, lane_off);
@@ -546,8 +559,8 @@ __global__ __launch_bounds__(64) void screen_scores_probe_kernel(const sbf16x8* 
       for (int nb = 0; nb < 2 * QB; ++nb)
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[mb][nb][i] = 0.f;
-    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tiled + (int64_t)t * BTILE_VEC, qbase, qfrag, acc,
-                                                             t + 1 < n_tiles, (int64_t)BTILE_VEC, lane_off);
+    screen_tile_groups<QB, 0, BG, RG, D, NB>(buf, tiled + (int64_t)t * BTILE_VEC, qbase, qfrag, acc, t + 1 < n_tiles,
+                                             (int64_t)BTILE_VEC, lane_off);
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -667,7 +680,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
                                              int wave, int n, int g, int q0,
                                              const sbf16x8* __restrict__ qlane, int* pool, int list0,
                                              bool ragged, unsigned (&gthr)[QB]) {
-  constexpr int NQ = 2 * QB;
+  constexpr int NQ = 2 * QB, D = screen_frag_depth<QB>();
   // (wave-uniform LDS addresses; every per-lane address below is formed where it is used, from a lane number the
   // optimiser cannot follow - a laundered copy of n in the sample phase, screen_lane_now() in the slice phase, where
   // n and g themselves are then dead: hoisted out of the tile loop, the forty addresses of ten queries' pool, bound,
@@ -683,7 +696,7 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
     qbase[nb] = (screen_lds_frag*)qlane + nb * SCREEN_FRAGS_PER_BASE * 64;
     asm volatile("" : "+v"(qbase[nb]));   // one register each, not re-derived per read
   }
-  sbf16x8 qfrag[SCREEN_FRAG_DEPTH];
+  sbf16x8 qfrag[D];
 #ifdef SSKD_SCREEN_ABL_CONTIG
   const unsigned lane_off = (unsigned)(n + 16 * g) * 16u;
 #else
@@ -804,9 +817,9 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[mb][nb][i] = 0.f;
 
-    screen_tile_groups<QB, 0, BG, RG, SCREEN_FRAG_DEPTH, NB>(buf, tile, qbase, qfrag, acc, next_t >= 0,
-                                                             BOUND_ONLY ? (int64_t)WAVES * BTILE_VEC
-                                                                        : (int64_t)(next_t - t) * BTILE_VEC, lane_off);
+    screen_tile_groups<QB, 0, BG, RG, D, NB>(buf, tile, qbase, qfrag, acc, next_t >= 0,
+                                             BOUND_ONLY ? (int64_t)WAVES * BTILE_VEC
+                                                        : (int64_t)(next_t - t) * BTILE_VEC, lane_off);
 
     // acc[mb][nb][i]: row rowbase + 16 mb + i, query 16 nb + n of the block
     const int rowbase = t * TILE_ROWS + 4 * (BOUND_ONLY ? g : screen_lane_now() >> 4);

@@ -2,7 +2,8 @@
 library in ONE process and times the screening kernel (HIP events around it) alternately at the bench shape.
 AB_STAMPS=1: every library listed was built with -DSSKD_SCREEN_STAMPS (tools/ab_build.py); the finish-time stamps of
 its last call are read back from the tail of the workspace and summarised (use with AB_NOCHECK-style care: the stamp
-stores are part of the timed kernel)."""
+stores are part of the timed kernel).  AB_CALLS=1 also prints every timed call of every library (block means against a
+spread: profiles/readahead/README.md)."""
 import ctypes as C
 import os
 import sys
@@ -75,8 +76,11 @@ for r in range(ROUNDS):
         if not os.environ.get('AB_NOCHECK'):
             assert torch.equal(out_i, ref[1]) and torch.equal(out_s, ref[0]) and int(status[0]) == 0, n
 for n in times:
-    print(f"{n}: screen kernel median {np.median(times[n][1:]):.3f} ms (min {np.min(times[n][1:]):.3f}); whole call {np.median(wall[n][1:]):.3f} ms"
+    print(f"{n}: screen kernel median {np.median(times[n][1:]):.3f} ms (min {np.min(times[n][1:]):.3f}, max {np.max(times[n][1:]):.3f}, mean {np.mean(times[n][1:]):.3f}); whole call {np.median(wall[n][1:]):.3f} ms"
           + ("" if EXACT else f"; exact-fallback queries {fallbacks[n]}"), flush=True)
+if os.environ.get("AB_CALLS"):   # AB_CALLS=1: every timed call, for block means (the first call of a library is left out above)
+    for n in times:
+        print(f"{n}: calls " + " ".join(f"{t:.3f}" for t in times[n][1:]), flush=True)
 
 
 def stamp_report(name, lib, ws, waves=12):
