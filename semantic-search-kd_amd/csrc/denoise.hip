@@ -18,6 +18,7 @@
 // Every loop bound and every branch around a barrier depends on the query alone (workgroup-uniform).  A set number is
 // range-checked before it becomes an address; the store itself (limits, ascending keys) is trusted, as the BM25
 // postings are.
+#include "ranking_walk.h"
 #include "search_host.h"
 
 #include <cfloat>
@@ -158,18 +159,9 @@ __global__ __launch_bounds__(DN_THREADS) void rank_denoise_kernel(DenoiseParams 
       }
     }
     const bool keep = walked && reason == 0;
-    const unsigned long long surv = __ballot(keep);
-    if (lane == 0) s_kept[wave] = __popcll(surv);
-    __syncthreads();
-    int before = count, total = 0;
-#pragma unroll
-    for (int w = 0; w < DN_WAVES; ++w) {
-      const int c = s_kept[w];
-      if (w < wave) before += c;
-      total += c;
-    }
+    int total;
+    const int at = count + block_walk_pack<DN_WAVES>(keep, lane, wave, s_kept, total);   // <= r
     if (keep) {
-      const int at = before + __popcll(surv & ((1ull << lane) - 1ull));   // <= r
       os[at] = s;
       oi[at] = id;
       if (oa) oa[at] = a;

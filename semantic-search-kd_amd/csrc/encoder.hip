@@ -27,6 +27,7 @@
 //   fused_mlp_ln_kernel     X1 = LN(X  + ctx Wo^T + bo)                      (prologue; X1 stays on chip)
 //                           X2 = LN(X1 + gelu(X1 W1^T + b1) W2^T + b2)       (hidden 1536 stays on chip)
 #include "common.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -207,12 +208,6 @@ struct GemmN384Params {
   const float* beta;
   float eps;
 };
-
-// LDS-DMA: 16 B per lane, global -> LDS, no registers (LDS address = wave-uniform base + 16 lane)
-__device__ inline void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // 16 B per lane through a buffer resource: wave-uniform fragment offset in an SGPR, one 32-bit lane offset - no 64-bit
 // address arithmetic and no address registers inside the MFMA bursts

@@ -3,8 +3,8 @@
 // Implements the step the reference's service contract names and its code never had (reference: configs/service.yaml
 // 108-113, features.enable_query_expansion): between a first search and a second one, "the best rows of this query"
 // become "a better query", on the device, with no host synchronisation.
-//   prf_rocchio_kernel  dense side.  One wave per query: it walks the first fb_docs ranks (ballot + prefix popcount, as
-//                       the miner does), puts the feedback rows and their weights into LDS, then every lane owns float4
+//   prf_rocchio_kernel  dense side.  One wave per query: it walks the first fb_docs ranks (the common walk of
+//                       ranking_walk.h), puts the feedback rows and their weights into LDS, then every lane owns float4
 //                       chunks of the 1 536-byte row and adds the rows in rank order: out = alpha q + sum b_i row_i,
 //                       every product and every sum rounded once.
 //   prf_rm3_kernel      lexical side.  One workgroup per query: wave 0 walks the BM25 ranking under the candidate rule of
@@ -14,6 +14,7 @@
 //                       fb_terms under (weight descending, term ascending) come from the radix select of the BM25
 //                       search; the expanded query CSR is written behind the repeated original tokens.
 #include "radix_select.h"
+#include "ranking_walk.h"
 #include "search_device.h"
 #include "search_host.h"
 
@@ -63,20 +64,13 @@ __global__ __launch_bounds__(RC_WAVES * 64) void prf_rocchio_kernel(RocchioParam
     const int at = base + lane;
     const bool inside = at < p.fb_docs;
     const int64_t row = inside ? ri[at] : -1;
-    const unsigned long long pad = __ballot(inside && row == -1);
-    bool alive = inside && row >= 0 && row < p.n_rows;
-    if (pad) {
-      ended = true;
-      if (lane > __ffsll((long long)pad) - 1) alive = false;
-    }
-    const unsigned long long surv = __ballot(alive);
+    const bool alive = walk_step(inside, row, p.n_rows, lane, ended);
+    const int pos = walk_pack(alive, lane, m);   // < fb_docs <= SSKD_K_MAX
     if (alive) {
-      const int pos = m + __popcll(surv & ((1ull << lane) - 1ull));   // < fb_docs <= SSKD_K_MAX
       const float s = rs[at];
       fb_row[pos] = (int32_t)row;
       fb_b[pos] = s > 0.f ? s : 0.f;
     }
-    m += __popcll(surv);
   }
   wave_lds_sync();
 
@@ -193,25 +187,18 @@ __global__ __launch_bounds__(RM3_THREADS) void prf_rm3_kernel(Rm3Params p) {
     for (int base = 0; base < p.kb && !ended && count < p.fb_docs; base += 64) {
       const int at = base + lane;
       const int64_t row = at < p.kb ? ri[at] : -1;
-      const unsigned long long pad = __ballot(at < p.kb && row == -1);
-      bool alive = at < p.kb && row >= 0 && row < p.n_rows;
-      if (pad) {
-        ended = true;
-        if (lane > __ffsll((long long)pad) - 1) alive = false;
-      }
+      bool alive = walk_step(at < p.kb, row, p.n_rows, lane, ended);
       double s = 0.0;
       if (alive) {
         s = rs[at];
         if (s == 0.0) alive = false;   // +0.0 or -0.0: the row matched no query word
         if (!row_allowed(p.mask, row)) alive = false;
       }
-      const unsigned long long surv = __ballot(alive);
-      const int pos = count + __popcll(surv & ((1ull << lane) - 1ull));
+      const int pos = walk_pack(alive, lane, count);
       if (alive && pos < p.fb_docs) {   // fb_docs <= RM3_FB_DOCS_MAX
         fb_row[pos] = (int32_t)row;
         fb_s[pos] = s;
       }
-      count += __popcll(surv);
     }
     if (lane == 0) n_fb_sh = min(count, p.fb_docs);
   }

@@ -1,6 +1,7 @@
 // Dimension-generic bf16 kernels (row-major activations): NT GEMM on v_mfma_f32_32x32x16_bf16,
 // transpose, LayerNorm / softmax / GELU forward + backward, embeddings, mean-pool.  See generic.h.
 #include "generic.h"
+#include "wave_ops.h"
 
 namespace sskd_generic {
 
@@ -19,17 +20,6 @@ __device__ inline float epilogue_gelu(float x) {
 #else
   return sskd::gelu_erf(x);
 #endif
-}
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
 }
 
 // ------------------------------------------------------------------------- //
@@ -195,11 +185,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs p) {
 // ------------------------------------------------------------------------- //
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int GEMM256_CUS = 256;  // persistent grid: one workgroup per CU of an MI355X
-
-__device__ inline void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 template <int BN>   // 256; 192 for the 384-wide student's outputs (384, 1152: 128 x 48 per wave); 128 for other multiples of 128
 __global__ __launch_bounds__(512) void gemm_nt256_kernel(GemmArgs p) {

@@ -42,6 +42,7 @@
 // pool follow the head in rank order - each pool row counts the pool rows that rank before it (l_before: NaN after every
 // number, then lower id, so the order is total and the places distinct).  A workgroup reads and writes its own row only,
 // reads it whole before the barrier that precedes the first write, and writes every element of it once.
+#include "ranking_walk.h"
 #include "row_stage.h"
 #include "search_host.h"
 
@@ -275,17 +276,9 @@ __global__ __launch_bounds__(G_THREADS) void graph_search_kernel(GraphParams p) 
     }
     // the first `width` unexpanded entries of T become the parents
     const bool open = tid < T.count && (T.i(tid) & G_EXPANDED) == 0;
-    const unsigned long long m = __ballot(open);
-    if (lane == 0) wcount_s[wave] = __popcll(m);
-    __syncthreads();
-    int ahead = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < G_THREADS / 64; ++w) {
-      if (w < wave) ahead += wcount_s[w];
-      total += wcount_s[w];
-    }
+    int total;
+    const int mine = block_walk_pack<G_THREADS / 64>(open, lane, wave, wcount_s, total);
     if (total == 0) break;   // (uniform)
-    const int mine = ahead + __popcll(m & ((1ull << lane) - 1ull));
     if (open && mine < p.width) {
       parent_s[mine] = T.i(tid);
       T.i(tid) |= G_EXPANDED;

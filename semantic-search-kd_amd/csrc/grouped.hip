@@ -7,6 +7,7 @@
 // proven when k groups were found or the ranking ran out of rows, and otherwise the `count` groups written are still
 // the exact top-count groups (the caller asks again with a larger k_rows).
 // ------------------------------------------------------------------------- //
+#include "ranking_walk.h"
 #include "search_device.h"
 #include "search_host.h"
 
@@ -36,7 +37,7 @@ struct CollapseParams {
 
 constexpr int COLLAPSE_WAVES = 4;
 
-// One wave per query, 64 ranks per step.  kept[] (LDS, k entries per wave) holds the groups written so far.
+// One wave per query, 64 ranks per step (ranking_walk.h).  kept[] (LDS, k entries per wave) holds the groups written so far.
 __global__ __launch_bounds__(COLLAPSE_WAVES * 64) void group_collapse_kernel(CollapseParams p) {
   extern __shared__ int32_t kept_all[];  // [COLLAPSE_WAVES][k]
   const int lane = threadIdx.x & 63;
@@ -61,8 +62,7 @@ __global__ __launch_bounds__(COLLAPSE_WAVES * 64) void group_collapse_kernel(Col
       s = rs[rank];
     }
     // a -1 record inside the ranking: the allowed rows ran out (the padding is a suffix)
-    if (__any(rank < p.k_rows && row < 0)) exhausted = true;
-    bool alive = row >= 0 && row < p.n_rows;
+    bool alive = walk_step<WalkEnd::AnyNegative, false>(rank < p.k_rows, row, p.n_rows, lane, exhausted);
     const int32_t g = alive ? p.row_group[row] : -1;
     // groups kept by earlier steps (every lane reads the same word: an LDS broadcast)
     for (int i = 0; i < count; ++i)
@@ -78,15 +78,14 @@ __global__ __launch_bounds__(COLLAPSE_WAVES * 64) void group_collapse_kernel(Col
       rest &= rest - 1;
       rest &= ~__ballot(dup);
     }
-    const unsigned long long surv = __ballot(alive);
-    const int pos = count + __popcll(surv & ((1ull << lane) - 1ull));
+    const int pos = walk_pack(alive, lane, count);
     if (alive && pos < p.k) {
       os[pos] = s;
       oi[pos] = row + p.id_offset;
       og[pos] = g;
       kept[pos] = g;
     }
-    count = min(p.k, count + __popcll(surv));
+    count = min(p.k, count);
     wave_lds_sync();   // the next step's lanes read what this step's lanes wrote to kept[]
   }
   for (int i = count + lane; i < p.k; i += 64) {

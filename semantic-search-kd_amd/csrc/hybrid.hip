@@ -5,12 +5,13 @@
 // 43-49, hybrid.fusion_method "rrf" / "linear" with semantic_weight / bm25_weight).  One workgroup per query, the union
 // of both lists (at most 512 rows) in LDS:
 //   walk      wave 0 walks the dense list, wave 1 the BM25 list, 64 entries per round: candidates get their 1-based
-//             rank among the survivors (ballot + prefix popcount); waves 2 and 3 bring the query into LDS meanwhile
+//             rank among the survivors (ranking_walk.h); waves 2 and 3 bring the query into LDS meanwhile
 //   union     a BM25 candidate whose row the dense list holds hands its score and rank to that slot and leaves
 //   complete  (linear only) one lane per row: a row without a dense score is scored with the fma chain of the exact
 //             scan, a row without a BM25 score with the search's own sum (binary search per query token)
 //   fuse      fp64, every operation rounded once: this translation unit is compiled without contraction
 //   order     every row counts the rows that beat it under (fused descending, row ascending) and writes itself there
+#include "ranking_walk.h"
 #include "search_device.h"
 #include "search_host.h"
 
@@ -119,12 +120,7 @@ __global__ __launch_bounds__(THREADS) void hybrid_fuse_kernel(FuseParams p) {
     for (int base = 0; base < len && !ended; base += 64) {
       const int at = base + lane;
       const int64_t row = at < len ? ids[at] : -1;
-      const unsigned long long pad = __ballot(at < len && row == -1);
-      bool alive = at < len && row >= 0 && row < p.n_rows;
-      if (pad) {
-        ended = true;
-        if (lane > __ffsll((long long)pad) - 1) alive = false;
-      }
+      bool alive = walk_step(at < len, row, p.n_rows, lane, ended);
       float s = 0.f;
       double b = 0.0;
       if (alive) {
@@ -136,9 +132,8 @@ __global__ __launch_bounds__(THREADS) void hybrid_fuse_kernel(FuseParams p) {
           if (!row_allowed(p.mask, row)) alive = false;
         }
       }
-      const unsigned long long surv = __ballot(alive);
+      const int rank = walk_pack(alive, lane, count) + 1;
       if (alive) {
-        const int rank = count + __popcll(surv & ((1ull << lane) - 1ull)) + 1;
         const int slot = dense ? at : kd + at;
         u_row[slot] = (int32_t)row;
         if (dense) {
@@ -149,7 +144,6 @@ __global__ __launch_bounds__(THREADS) void hybrid_fuse_kernel(FuseParams p) {
           u_rank_b[slot] = rank;
         }
       }
-      count += __popcll(surv);
     }
   } else if (p.method == 1) {
     const float4* src = reinterpret_cast<const float4*>(p.queries) + (int64_t)q * CHUNKS;

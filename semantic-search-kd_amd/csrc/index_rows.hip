@@ -341,12 +341,6 @@ constexpr int COMPACT_ROWS = 4;                               // live rows moved
 constexpr int COMPACT_LOADS = COMPACT_ROWS * CHUNKS / 64;     // 6 wave-wide 16-byte loads in flight, then 6 stores
 static_assert(COMPACT_ROWS * CHUNKS % 64 == 0, "a step is a whole number of wave-wide accesses");
 
-__device__ inline int64_t wave_uniform(int64_t v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // One wave per SOURCE tile t (= mask word t); wave n_tiles zero-fills the tail of the last destination tile.  Everything
 // that steers the wave (word, prefix, the rows of a step) is wave-uniform; lanes differ only in the 16-byte chunk they
 // move.  The live rows of a tile are consecutive in the destination, so chunk c of a step goes to out + c: a step of four

@@ -9,6 +9,7 @@
 //   contrastive  :127-149  - 1/B sum_b log_softmax(s / tau)[b, 0]
 //   combined     :219-252  w_mm * MM + w_lk * LK + w_c * C
 #include "common.h"
+#include "wave_ops.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,17 +32,6 @@ struct KdParams {
   float* losses;  // [4]: total, margin-MSE, listwise, contrastive
   float* grad;    // [B][D] d total / d s, or null
 };
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 __global__ __launch_bounds__(256) void kd_loss_rows_kernel(KdParams p) {
   const int lane = threadIdx.x & 63;

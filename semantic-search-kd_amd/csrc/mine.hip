@@ -6,7 +6,8 @@
 //     negatives   = the first top_k adversarial ranks (the ranking is already the stable descending order)
 // One wave per query: it scores the query's positive rows with the fma chain of the screened search's exact re-scoring
 // (screen.hip, "exact scores, 64 candidates per round"), so a positive scores with the bits a search returns for that
-// row, then walks the ranking 64 ranks per round and compacts the survivors in rank order (ballot + prefix popcount).
+// row, then walks the ranking 64 ranks per round and packs the survivors in rank order (ranking_walk.h: ANY id < 0 ends it).
+#include "ranking_walk.h"
 #include "search_device.h"
 #include "search_host.h"
 
@@ -71,8 +72,7 @@ __global__ __launch_bounds__(MINE_WAVES * 64) void mine_select_kernel(MineParams
     }
     n_pos += __popcll(__ballot(valid));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o));
+  best = wave_max(best);
   // a NaN positive makes the maximum NaN, and every comparison below false (as ndarray.max() does)
   const float max_pos = n_pos == 0 ? 0.0f : (__any(any_nan) ? __builtin_nanf("") : best);
   const double threshold = (double)max_pos - p.margin;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(MINE_WAVES * 64) void mine_select_kernel(MineParams
   float* os = p.out_scores + (int64_t)q * p.top_k;
   int64_t* oi = p.out_ids + (int64_t)q * p.top_k;
   int count = 0;      // (wave-uniform) ranks kept so far
-  bool ended = false; // a -1 record was met: nothing behind it counts
+  bool ended = false; // a negative id was met: nothing behind it counts
   for (int base = 0; base < p.search_k && !ended; base += 64) {
     const int rank = base + lane;
     int64_t row = -1;
@@ -92,12 +92,7 @@ __global__ __launch_bounds__(MINE_WAVES * 64) void mine_select_kernel(MineParams
       row = ri[rank];
       s = rs[rank];
     }
-    const unsigned long long pad = __ballot(rank < p.search_k && row < 0);
-    bool alive = row >= 0 && row < p.n_rows;
-    if (pad) {
-      ended = true;
-      if (lane > __ffsll((long long)pad) - 1) alive = false;
-    }
+    bool alive = walk_step<WalkEnd::AnyNegative>(rank < p.search_k, row, p.n_rows, lane, ended);
     const int32_t g = (alive && p.row_group) ? p.row_group[row] : -1;
     // (every lane reads the same positive: wave-uniform loads)
     for (int64_t j = lo; j < hi; ++j) {
@@ -107,13 +102,11 @@ __global__ __launch_bounds__(MINE_WAVES * 64) void mine_select_kernel(MineParams
       if (p.row_group && g == p.row_group[pr]) alive = false;
     }
     const bool keep = alive && (double)s >= threshold;
-    const unsigned long long surv = __ballot(keep);
-    const int pos = count + __popcll(surv & ((1ull << lane) - 1ull));
+    const int pos = walk_pack(keep, lane, count);
     if (keep && pos < p.top_k) {
       os[pos] = s;
       oi[pos] = row + p.id_offset;
     }
-    count += __popcll(surv);
   }
   for (int i = min(count, p.top_k) + lane; i < p.top_k; i += 64) {
     os[i] = -FLT_MAX;

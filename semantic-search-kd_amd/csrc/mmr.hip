@@ -3,7 +3,7 @@
 //
 // One workgroup of 256 threads per query, the candidate list (at most 1 024 rows) in LDS.  The work is lazy: a selection
 // costs the similarities of the selected row to the candidates that are still alive, never a Gram matrix.
-//   compact   wave 0 walks the ranking, 64 entries per round (ballot + prefix popcount, as the expansion kernels do):
+//   compact   wave 0 walks the ranking, 64 entries per round (the common walk of ranking_walk.h):
 //             row, relevance and an alive bitmap (one word per 32 candidates) in list order
 //   argmax    every thread values its candidates in fp64, every operation rounded once (this translation unit is compiled
 //             without contraction); the pair (value, position) is reduced over the wave, then over the four waves
@@ -20,6 +20,7 @@
 //                           lane each, on waves 0 and 1 - no row is read from HBM twice.  R = 50 is 80 KiB (two
 //                           workgroups per CU), R = 100 is 155 KiB (one).
 //   mmr_select_kernel       any fetch_k: the 32-row stage described above, 62 KiB.
+#include "ranking_walk.h"
 #include "row_stage.h"
 #include "search_host.h"
 
@@ -67,19 +68,12 @@ __device__ inline int compact_candidates(const MmrParams& p, int q, int32_t* c_r
     const int at = base + lane;
     const bool inside = at < p.fetch_k;
     const int64_t row = inside ? ri[at] : -1;
-    const unsigned long long pad = __ballot(inside && row == -1);
-    bool cand = inside && row >= 0 && row < p.n_rows;
-    if (pad) {
-      ended = true;
-      if (lane > __ffsll((long long)pad) - 1) cand = false;
-    }
-    const unsigned long long surv = __ballot(cand);
+    const bool cand = walk_step(inside, row, p.n_rows, lane, ended);
+    const int pos = walk_pack(cand, lane, m);   // < fetch_k
     if (cand) {
-      const int pos = m + __popcll(surv & ((1ull << lane) - 1ull));   // < fetch_k
       c_row[pos] = (int32_t)row;
       c_s[pos] = rs[at];
     }
-    m += __popcll(surv);
   }
   return m;
 }

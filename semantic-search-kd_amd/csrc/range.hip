@@ -195,13 +195,15 @@ __device__ inline int64_t block_exclusive_scan_256(int64_t v, int64_t* s_wave, i
   return before + x - v;
 }
 
-__global__ __launch_bounds__(256) void range_count_blocks_kernel(const int* __restrict__ counts, int nq,
-                                                                 int64_t* __restrict__ block_sums) {
+// The counts come from a source `C` (`C::count_t operator()(int64_t q) const`): CountArray for the range search,
+// MergeCounts for the sharded merge.  One workgroup takes RANGE_SCAN_BLOCK queries, 16 per thread.
+template <typename C>
+__global__ __launch_bounds__(256) void range_count_blocks_kernel(C count, int nq, int64_t* __restrict__ block_sums) {
   __shared__ int64_t s_wave[4];
   const int64_t base = (int64_t)blockIdx.x * RANGE_SCAN_BLOCK + threadIdx.x * 16;
   int64_t v = 0;
   for (int i = 0; i < 16; ++i)
-    if (base + i < nq) v += counts[base + i];
+    if (base + i < nq) v += count(base + i);
   int64_t total;
   (void)block_exclusive_scan_256(v, s_wave, &total);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
@@ -223,26 +225,40 @@ __global__ __launch_bounds__(256) void range_scan_blocks_kernel(int64_t* __restr
   if (threadIdx.x == 0) lims[nq] = carry;
 }
 
-__global__ __launch_bounds__(256) void range_lims_kernel(const int* __restrict__ counts, int nq,
-                                                         const int64_t* __restrict__ block_offsets,
+template <typename C>
+__global__ __launch_bounds__(256) void range_lims_kernel(C count, int nq, const int64_t* __restrict__ block_offsets,
                                                          int64_t* __restrict__ lims) {
   __shared__ int64_t s_wave[4];
   const int64_t base = (int64_t)blockIdx.x * RANGE_SCAN_BLOCK + threadIdx.x * 16;
-  int c[16];
+  typename C::count_t c[16];
   int64_t v = 0;
-#pragma unroll
   for (int i = 0; i < 16; ++i) {
-    c[i] = base + i < nq ? counts[base + i] : 0;
+    c[i] = base + i < nq ? count(base + i) : 0;
     v += c[i];
   }
   int64_t total;
   int64_t run = block_offsets[blockIdx.x] + block_exclusive_scan_256(v, s_wave, &total);
-#pragma unroll
   for (int i = 0; i < 16; ++i) {
     if (base + i < nq) lims[base + i] = run;
     run += c[i];
   }
 }
+
+// lims[0 .. nq] = exclusive scan of count(q), lims[nq] = the total: the three launches of both entry points
+template <typename C>
+int enqueue_lims_scan(C count, int nq, int64_t* block_sums, int64_t* lims, hipStream_t st) {
+  const int n_blocks = (int)sskd::ceil_div(nq, RANGE_SCAN_BLOCK);
+  hipLaunchKernelGGL(range_count_blocks_kernel<C>, dim3(n_blocks), dim3(256), 0, st, count, nq, block_sums);
+  hipLaunchKernelGGL(range_scan_blocks_kernel, dim3(1), dim3(256), 0, st, block_sums, n_blocks, lims, nq);
+  hipLaunchKernelGGL(range_lims_kernel<C>, dim3(n_blocks), dim3(256), 0, st, count, nq, block_sums, lims);
+  return sskd::check_launch("range_lims_kernel");
+}
+
+struct CountArray {
+  typedef int count_t;
+  const int* __restrict__ counts;
+  __device__ int operator()(int64_t q) const { return counts[q]; }
+};
 
 // ---- scatter: pool records -> their query's segment of the key buffer (d_out_ids), any order ----
 __global__ __launch_bounds__(256) void range_scatter_kernel(const int* __restrict__ rec_q,
@@ -462,45 +478,20 @@ __device__ inline void merge_run_segment(const RangeMergeParams& p, const int64_
   b = min(max(lr[q + 1], a), p.cap);
 }
 
-__device__ inline int64_t merge_query_count(const RangeMergeParams& p, int n_runs, int q) {
-  int64_t c = 0;
-  for (int r = 0; r < n_runs; ++r) {
-    int64_t a, b;
-    merge_run_segment(p, merge_run_lims(p, r), q, a, b);
-    c += b - a;
+struct MergeCounts {
+  typedef int64_t count_t;
+  RangeMergeParams p;
+  int n_runs;
+  __device__ int64_t operator()(int64_t q) const {
+    int64_t c = 0;
+    for (int r = 0; r < n_runs; ++r) {
+      int64_t a, b;
+      merge_run_segment(p, merge_run_lims(p, r), (int)q, a, b);
+      c += b - a;
+    }
+    return c;
   }
-  return c;
-}
-
-__global__ __launch_bounds__(256) void range_merge_count_blocks_kernel(RangeMergeParams p, int n_runs,
-                                                                       int64_t* __restrict__ block_sums) {
-  __shared__ int64_t s_wave[4];
-  const int64_t base = (int64_t)blockIdx.x * RANGE_SCAN_BLOCK + threadIdx.x * 16;
-  int64_t v = 0;
-  for (int i = 0; i < 16; ++i)
-    if (base + i < p.nq) v += merge_query_count(p, n_runs, (int)(base + i));
-  int64_t total;
-  (void)block_exclusive_scan_256(v, s_wave, &total);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void range_merge_lims_kernel(RangeMergeParams p, int n_runs,
-                                                               const int64_t* __restrict__ block_offsets) {
-  __shared__ int64_t s_wave[4];
-  const int64_t base = (int64_t)blockIdx.x * RANGE_SCAN_BLOCK + threadIdx.x * 16;
-  int64_t c[16];
-  int64_t v = 0;
-  for (int i = 0; i < 16; ++i) {
-    c[i] = base + i < p.nq ? merge_query_count(p, n_runs, (int)(base + i)) : 0;
-    v += c[i];
-  }
-  int64_t total;
-  int64_t run = block_offsets[blockIdx.x] + block_exclusive_scan_256(v, s_wave, &total);
-  for (int i = 0; i < 16; ++i) {
-    if (base + i < p.nq) p.lims[base + i] = run;
-    run += c[i];
-  }
-}
+};
 
 // grid (x: records of a run, grid-stride; y: the run)
 __global__ __launch_bounds__(256) void range_merge_place_kernel(RangeMergeParams p) {
@@ -624,11 +615,7 @@ int sskd_index_range_search(const float* d_tiled, int64_t n_rows, const float* d
   rc = sskd::check_launch("range_scan_kernel");
   if (rc != SSKD_OK) return rc;
 
-  const int n_blocks = (int)sskd::ceil_div(nq, RANGE_SCAN_BLOCK);
-  hipLaunchKernelGGL(range_count_blocks_kernel, dim3(n_blocks), dim3(256), 0, st, w.counts, nq, w.block_sums);
-  hipLaunchKernelGGL(range_scan_blocks_kernel, dim3(1), dim3(256), 0, st, w.block_sums, n_blocks, d_lims, nq);
-  hipLaunchKernelGGL(range_lims_kernel, dim3(n_blocks), dim3(256), 0, st, w.counts, nq, w.block_sums, d_lims);
-  if ((rc = sskd::check_launch("range_lims_kernel")) != SSKD_OK) return rc;
+  if ((rc = enqueue_lims_scan(CountArray{w.counts}, nq, w.block_sums, d_lims, st)) != SSKD_OK) return rc;
   if (max_results == 0) return SSKD_OK;   // count-only
 
   uint64_t* keys = reinterpret_cast<uint64_t*>(d_out_ids);
@@ -695,11 +682,7 @@ int sskd_range_merge_packed(const void* d_records, int n_runs, int nq, int64_t c
   p.out_scores = d_out_scores;
   p.out_ids = d_out_ids;
   p.max_results = max_results;
-  const int n_blocks = (int)sskd::ceil_div(nq, RANGE_SCAN_BLOCK);
-  hipLaunchKernelGGL(range_merge_count_blocks_kernel, dim3(n_blocks), dim3(256), 0, st, p, n_runs, w.block_sums);
-  hipLaunchKernelGGL(range_scan_blocks_kernel, dim3(1), dim3(256), 0, st, w.block_sums, n_blocks, d_lims, nq);
-  hipLaunchKernelGGL(range_merge_lims_kernel, dim3(n_blocks), dim3(256), 0, st, p, n_runs, w.block_sums);
-  if ((rc = sskd::check_launch("range_merge_lims_kernel")) != SSKD_OK) return rc;
+  if ((rc = enqueue_lims_scan(MergeCounts{p, n_runs}, nq, w.block_sums, d_lims, st)) != SSKD_OK) return rc;
   if (max_results == 0 || cap == 0) return SSKD_OK;   // count-only, or nothing to place
   const int64_t blocks = std::min<int64_t>(sskd::ceil_div(cap, 256), 2048);
   hipLaunchKernelGGL(range_merge_place_kernel, dim3((unsigned)blocks, (unsigned)n_runs), dim3(256), 0, st, p);

@@ -2,6 +2,7 @@
 // What only one of them uses stays there.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -61,20 +62,6 @@ __device__ inline float row_score_fma(const float4* src, const float* qv, int st
     acc = fmaf(a.w, qa.w, acc); acc = fmaf(c.w, qc.w, acc);
   }
   return acc;
-}
-
-// sum over the lanes of one wave
-template <typename T>
-__device__ inline T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// what lanes of a wave wrote to LDS is read by the other lanes of that wave (no workgroup barrier needed)
-__device__ inline void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 // bit r of a row allow-mask given as words (the per-row test; the tile scans test a whole word, below); null = all allowed.

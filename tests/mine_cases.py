@@ -50,9 +50,11 @@ def oracle_query(rank_scores, rank_rows, pos_rows, pos_scores, margin, top_k, gr
     return D, I, len(kept), max_pos
 
 
-def walk(rank_scores, rank_rows, pos_rows, max_pos, margin, top_k, groups=None, id_offset=0):
-    """The kernel's walk for one query, in NumPy: stop at the first -1, drop the positives (and their groups), keep a
-    rank when ``float64(score) >= float64(max_pos) - margin``, write the first ``top_k`` survivors in rank order."""
+def walk(rank_scores, rank_rows, pos_rows, max_pos, margin, top_k, groups=None, id_offset=0, n_rows=None):
+    """The kernel's walk for one query, in NumPy: stop at the first NEGATIVE id (-1 or any other: this kernel's own
+    rule, ``csrc/ranking_walk.h``), skip an id at or above ``n_rows`` (when given), drop the positives (and their
+    groups), keep a rank when ``float64(score) >= float64(max_pos) - margin``, write the first ``top_k`` survivors in
+    rank order."""
     pos = set(int(r) for r in pos_rows)
     pos_groups = set() if groups is None else set(int(groups[r]) for r in pos)
     threshold = np.float64(np.float32(max_pos)) - np.float64(margin)
@@ -62,6 +64,8 @@ def walk(rank_scores, rank_rows, pos_rows, max_pos, margin, top_k, groups=None, 
     for s, r in zip(np.asarray(rank_scores, np.float32), rank_rows):
         if r < 0:
             break
+        if n_rows is not None and r >= n_rows:
+            continue
         if _dropped(int(r), pos, groups, pos_groups):
             continue
         if np.float64(s) >= threshold:

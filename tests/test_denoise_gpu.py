@@ -12,6 +12,7 @@ import torch
 
 import denoise_cases as dc
 import mine_cases as mc
+import ranking_walk_cases as rw
 from capi_helpers import stream
 from semantic_search_kd_amd import _native
 
@@ -149,6 +150,32 @@ def test_rank_denoise_equals_the_restatement(gpu, native_lib, nq, search_k, n_po
         assert (ids == len(sets) + 11).any() and (ids == -7).any() and len(set(ref[3].tolist())) > 10
         assert ref[3][2 + 4] == 0 and 0 < ref[3][1] <= (search_k * 2) // 3, "an all -1 window, an early -1"
         assert (ref[4] == 1.0).any(), "a candidate equal to a positive"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", rw.WIDTHS)
+def test_rank_denoise_walk_at_the_round_boundaries(gpu, native_lib, width):
+    """The shared hand-made rankings over the first 200 sets of the family.  This kernel's own row of the table in
+    ``csrc/ranking_walk.h``: the first -1 ends the window and nothing behind it is kept, but every other id - outside
+    the store, or negative like -9 - is the empty set and STAYS in the output (the select that follows drops it)."""
+    sets, _ = dc.family()
+    n = 200
+    g_lims, g_keys, _ = _device_store("family", sets)
+    jac = dc.Pairs(sets[:n])
+    ids = rw.ids(n, width)
+    scores = rw.descending_scores(width, low=0.0, high=1.0)
+    lims = np.arange(0, 2 * rw.NQ + 1, 2, dtype=np.int64)
+    rows = np.array([r for q in range(rw.NQ) for r in (q + 3, q + 43)], np.int32)
+    aux = np.random.default_rng(width).random((rw.NQ, width)).astype(np.float32)
+    end = rw.first_pad(ids)
+    for use_store, use_aux in ((True, True), (False, False)):
+        ref = dc.denoise_ref(jac if use_store else None, scores, ids, lims, rows, aux if use_aux else None, 0.7, 0.5)
+        got = _rank_denoise(native_lib, (g_lims, g_keys, n) if use_store else None, scores, ids, lims, rows,
+                            aux if use_aux else None, 0.7, 0.5)
+        dc.same(got, ref, (width, use_store, use_aux))
+    assert ref[3].tolist() == end.tolist(), "no rule: a copy of the window up to the first -1, -9 and all"
+    if width >= 63:
+        assert (ref[1][4, :end[4]] == ids[4]).all() and ref[1][4, 2] == -9
 
 
 @pytest.mark.gpu

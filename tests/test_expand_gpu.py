@@ -12,6 +12,7 @@ import torch
 
 import bm25_cases as bc
 import expand_cases as ec
+import ranking_walk_cases as rw
 from capi_helpers import capi_search, stream, tile_corpus
 from oracle import search as oracle
 from semantic_search_kd_amd import BM25Index, _native
@@ -112,6 +113,27 @@ def test_rocchio_on_hand_made_rankings(native_lib, dense_worlds):
     out, counts = capi_rocchio(native_lib, w.tiled, n, Q[:0], S[:0], I[:0], fb_docs=5, alpha=1.0, beta=0.75,
                                weighting="uniform")
     assert out.shape == (0, 384) and counts.shape == (0,)
+
+
+@pytest.mark.parametrize("width", rw.WIDTHS)
+def test_rocchio_walk_at_the_round_boundaries(native_lib, dense_worlds, width):
+    """The shared hand-made rankings over the first 200 rows: the first -1 at rank 0, 63, 64 and absent, rows behind
+    it, ids outside the index and -9 before it (skipped: the walk goes on); ``fb_docs`` on both sides of the round."""
+    w, n = dense_worlds[1003], 200
+    I = rw.ids(n, width)
+    S = rw.descending_scores(width, low=-0.2, high=0.9)
+    Q = w.queries[:rw.NQ]
+    end = rw.first_pad(I)
+    for fb_docs in sorted({1, min(63, width), min(64, width), min(65, width), width}):
+        for weighting in ("uniform", "score"):
+            kw = dict(fb_docs=fb_docs, alpha=1.0, beta=0.75, weighting=weighting)
+            got = capi_rocchio(native_lib, w.tiled, n, Q, S, I, **kw)
+            want = ec.rocchio_batch(Q, S, I, w.rows[:n], **kw)
+            _same_rocchio(got, want, f"walk width={width} fb_docs={fb_docs} {weighting}")
+        kept = [int(((I[q, :min(end[q], fb_docs)] >= 0) & (I[q, :min(end[q], fb_docs)] < n)).sum()) for q in range(rw.NQ)]
+        assert want[1].tolist() == kept
+    if width >= 63:
+        assert kept[4] == width - 1 and kept[0] == 0, "-9 is skipped and the walk goes on; a -1 at rank 0 ends it"
 
 
 # ---------------------------------------------------------------------------------------------------- RM3
@@ -263,6 +285,35 @@ def test_rm3_max_df_and_masks(native_lib, zipf):
     J2[3, :] = -1
     B2[3, :] = -np.inf
     zipf.check(native_lib, queries, kb=kb, fb_docs=5, fb_terms=10, orig_repeat=2, ranking=(B2, J2), what="hand-made")
+
+
+@pytest.fixture(scope="module")
+def zipf200(gpu):
+    return LexWorld(bc.zipf_corpus(200, 300, 5), gpu)
+
+
+@pytest.mark.parametrize("width", rw.WIDTHS)
+def test_rm3_walk_at_the_round_boundaries(native_lib, zipf200, width):
+    """The shared hand-made rankings as BM25 rankings over 200 rows.  Ranks 3 .. 59 score 0.0 (no feedback), so round one
+    leaves fewer than ``fb_docs`` = 16 survivors and the walk enters round two; it stops once 16 are found."""
+    world, n = zipf200, 200
+    queries = [bc.zipf_query(300, 1 + q, 120 + q) for q in range(rw.NQ)]
+    J = rw.ids(n, width)
+    B = rw.descending_scores(width, np.float64).copy()
+    B[:, 3:60] = 0.0
+    B[4, min(1, width - 1)] = -0.0
+    allowed = np.ones(n, bool)
+    allowed[::7] = False
+    fb_docs = min(16, width)
+    end = rw.first_pad(J)
+    for a in (None, allowed.tolist()):
+        world.check(native_lib, queries, kb=width, fb_docs=fb_docs, fb_terms=10, orig_repeat=2, ranking=(B, J),
+                    allowed=a, what=f"walk width={width} mask={a is not None}")
+    kept = [int(((J[q, :end[q]] >= 0) & (J[q, :end[q]] < n) & (B[q, :end[q]] != 0.0)).sum()) for q in range(rw.NQ)]
+    fb = [len(world.lex.feedback(B[q], J[q], fb_docs)) for q in range(rw.NQ)]
+    assert fb == [min(c, fb_docs) for c in kept]
+    if width == 130:
+        assert kept[:3] == [0, 4, 5] and fb[3] == 16 and kept[3] > 64, (kept, fb)
 
 
 def _worst_case_texts():

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import grouped_cases as gc
+import ranking_walk_cases as rw
 from capi_helpers import stream, tile_corpus
 from oracle import search as oracle
 from semantic_search_kd_amd import _native
@@ -133,6 +134,36 @@ def test_capi_id_offset_shifts_ids_not_groups(gpu, native_lib):
     ref = gc.expected(scores[:5], groups, 10, id_offset=1_000_000_007, k_rows=32)
     _check_against(got, ref)
     assert np.array_equal(got[1], base[1] + 1_000_000_007) and np.array_equal(got[2], base[2])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k_rows", rw.WIDTHS)
+def test_capi_walk_with_the_first_pad_on_both_sides_of_the_step(gpu, native_lib, k_rows):
+    """The row ranking this kernel walks is written by the exact search inside the same call, so its padding is always
+    a suffix of -1: the first -1 stands at rank 0, 63 (last lane of step one), 64 (first lane of step two) or nowhere
+    by allowing 0, 63, 64 or all of the 200 rows.  (A negative id other than -1, an id outside the index or a row behind
+    the padding cannot reach this kernel through the C-ABI: see the table in ``csrc/ranking_walk.h``.)"""
+    n, nq = 200, rw.NQ
+    corpus = oracle.seeded_unit_rows(n, DIM, 441)
+    queries = oracle.seeded_unit_rows(nq, DIM, 442)
+    scores = oracle.scores_fma(queries, corpus)
+    groups = (np.arange(n) // 3).astype(np.int32)
+    tiled = tile_corpus(native_lib, corpus)
+    rng = np.random.default_rng(443)
+    for n_allowed in (0, 63, 64, n):
+        allowed = np.zeros(n, bool)
+        allowed[rng.permutation(n)[:n_allowed]] = True
+        # k = k_rows too, except where the ranking is full to its last rank with nothing behind it: the kernel meets no
+        # -1 there and reports such a query as unproved (the safe answer), the oracle knows that no row is left
+        for k in sorted({min(10, k_rows)} | ({k_rows} if n_allowed != k_rows else set())):
+            got = _capi(native_lib, tiled, n, queries, k, k_rows, groups, id_offset=1000,
+                        allowed=None if n_allowed == n else allowed)
+            ref = gc.expected(scores, groups, k, allowed, 1000, k_rows)
+            _check_against(got, ref)
+            if n_allowed < k_rows:
+                assert not got[4].any(), "a -1 inside the ranking proves the answer"
+            if n_allowed == 0:
+                assert (got[3] == 0).all() and (got[1] == -1).all()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ import torch
 
 import bm25_cases as bc
 import hybrid_cases as hc
+import ranking_walk_cases as rw
 from oracle import search as oracle
 from semantic_search_kd_amd import BM25Index, FAISSIndexBuilder, HybridIndex, _native
 
@@ -198,6 +199,43 @@ def test_c_abi_on_hand_made_rankings(native_lib, corpus_a):
                     method="rrf", ws=0.3, wb=0.7, rrf_k=1.5)
     hc.assert_same(got, hc.fuse_batch(B[:, :5].astype(np.float32), J[:, :5], S.astype(np.float64) + 4.0, I, n_rows=n_rows,
                                       k=30, method="rrf", ws=0.3, wb=0.7, rrf_k=1.5), "hand-made rrf, kb = 256")
+
+
+@pytest.mark.parametrize("width", rw.WIDTHS)
+def test_c_abi_walk_at_the_round_boundaries(native_lib, width):
+    """Both walks (wave 0 the dense list, wave 1 the BM25 list) on the shared hand-made rankings: the first -1 at rank
+    0, 63, 64 and absent, rows behind it, ids outside the index and -9 before it (skipped: the walk goes on)."""
+    from semantic_search_kd_amd.index import mask_words
+
+    n = 200
+    I, J = rw.ids(n, width), rw.ids(n, width, seed=1)
+    S = rw.descending_scores(width)
+    B = rw.descending_scores(width, np.float64, seed=1).copy()
+    B[3, width // 2] = 0.0                       # a row that matched no query word, between survivors
+    B[4, width - 1] = -0.0
+    allowed = np.ones(n, bool)
+    allowed[::7] = False
+    mask = torch.from_numpy(mask_words(allowed, n).view(np.int32)).cuda()
+    for k in sorted({1, min(20, 2 * width), 2 * width}):
+        for ws, wb in ((0.7, 0.3), (1.0, 1.0)):
+            for m, a in ((None, None), (mask, allowed)):
+                got = capi_fuse(native_lib, S, I, B, J, n_rows=n, k=k, method="rrf", ws=ws, wb=wb, id_offset=10_000, mask=m)
+                want = hc.fuse_batch(S, I, B, J, n_rows=n, k=k, method="rrf", ws=ws, wb=wb, id_offset=10_000, allowed=a)
+                hc.assert_same(got, want, f"walk width={width} k={k} mask={m is not None}")
+    # each side alone (the other list all padding): the union is what that walk kept, counted here by hand
+    pad_i, pad_s, pad_b = np.full((rw.NQ, width), -1, np.int64), np.zeros((rw.NQ, width), np.float32), np.zeros((rw.NQ, width))
+    end = rw.first_pad(I)
+    kept = [int(((I[q, :end[q]] >= 0) & (I[q, :end[q]] < n)).sum()) for q in range(rw.NQ)]
+    got = capi_fuse(native_lib, S, I, pad_b, pad_i, n_rows=n, k=width, method="rrf", ws=1.0, wb=1.0)
+    hc.assert_same(got, hc.fuse_batch(S, I, pad_b, pad_i, n_rows=n, k=width, method="rrf", ws=1.0, wb=1.0), "dense alone")
+    assert got[4].tolist() == kept
+    end = rw.first_pad(J)
+    kept = [int(((J[q, :end[q]] >= 0) & (J[q, :end[q]] < n) & (B[q, :end[q]] != 0.0)).sum()) for q in range(rw.NQ)]
+    got = capi_fuse(native_lib, pad_s, pad_i, B, J, n_rows=n, k=width, method="rrf", ws=1.0, wb=1.0)
+    hc.assert_same(got, hc.fuse_batch(pad_s, pad_i, B, J, n_rows=n, k=width, method="rrf", ws=1.0, wb=1.0), "BM25 alone")
+    assert got[4].tolist() == kept
+    if width >= 63:
+        assert kept[4] == width - 2 and kept[0] == 0, "-9 is skipped and the walk goes on; a -1 at rank 0 ends it"
 
 
 def test_c_abi_mirrored_ranks_tie_and_the_row_decides(native_lib):

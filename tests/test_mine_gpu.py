@@ -14,7 +14,9 @@ import pytest
 import torch
 
 import mine_cases as mc
-from capi_helpers import stream
+import ranking_walk_cases as rw
+from capi_helpers import stream, tile_corpus
+from oracle import search as oracle
 from semantic_search_kd_amd import _native
 
 DIM = mc.DIM
@@ -127,6 +129,58 @@ def test_id_offset_shifts_the_ids_out_not_the_positives_in(gpu, native_lib):
     mc.same(got, ref, "offset")
     plain = base.mine_negatives(np.array(queries), (lims, rows), top_k=5, search_k=100, margin=0.1)
     assert np.array_equal(got[1], np.where(plain[1] >= 0, plain[1] + OFFSET, -1)) and np.array_equal(got[2], plain[2])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the walk itself, on hand-made rankings
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", rw.WIDTHS)
+def test_capi_walk_ends_on_any_negative_id_and_cuts_the_lanes_behind_it(gpu, native_lib, width):
+    """This kernel's row of the table in ``csrc/ranking_walk.h``: ANY negative id ends the ranking (the other walks
+    skip -9 and end on -1 alone), ids at or above ``n_rows`` are skipped, nothing behind the end is kept."""
+    n, nq = 200, rw.NQ
+    corpus = oracle.seeded_unit_rows(n, DIM, 661)
+    queries = oracle.seeded_unit_rows(nq, DIM, 662)
+    S = oracle.scores_fma(queries, corpus)
+    I = rw.ids(n, width)
+    D = rw.descending_scores(width, low=-0.5, high=0.9)
+    # one positive per query: the row at rank 1 (rank 0 of a one-wide ranking) where that is a row, else row 7
+    pos = [int(I[q, min(1, width - 1)]) for q in range(nq)]
+    pos = [r if 0 <= r < n else 7 for r in pos]
+    lims, rows = mc.csr([[r] for r in pos])
+    groups = (np.arange(n) // 3).astype(np.int32)
+    tiled = tile_corpus(native_lib, corpus)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dq, ds, di, dl, dr, dg = d(queries), d(D), d(I), d(lims), d(rows), d(groups)
+    for by_group in (False, True):
+        for margin in (10.0, 0.3):
+            for top_k in sorted({1, min(5, width), width}):
+                sc = torch.full((nq + 1, top_k), SENT_S, dtype=torch.float32, device="cuda")
+                ids = torch.full((nq + 1, top_k), SENT_I, dtype=torch.int64, device="cuda")
+                cnt = torch.full((nq + 1,), SENT_C, dtype=torch.int32, device="cuda")
+                mp = torch.full((nq + 1,), SENT_S, dtype=torch.float32, device="cuda")
+                _native.check(native_lib.sskd_index_mine_select(
+                    tiled.data_ptr(), n, dq.data_ptr(), nq, ds.data_ptr(), di.data_ptr(), width, dl.data_ptr(),
+                    dr.data_ptr(), dg.data_ptr() if by_group else None, margin, top_k, OFFSET, sc.data_ptr(),
+                    ids.data_ptr(), cnt.data_ptr(), mp.data_ptr(), stream()))
+                torch.cuda.synchronize()
+                sc, ids, cnt, mp = (t.cpu().numpy() for t in (sc, ids, cnt, mp))
+                assert (sc[nq] == np.float32(SENT_S)).all() and (ids[nq] == SENT_I).all()
+                assert cnt[nq] == SENT_C and mp[nq] == np.float32(SENT_S), "wrote past the last query"
+                ref = [mc.walk(D[q], I[q], [pos[q]], S[q, pos[q]], margin, top_k, groups if by_group else None, OFFSET,
+                               n_rows=n) for q in range(nq)]
+                ref = (np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref]),
+                       np.array([r[2] for r in ref], np.int32), np.array([r[3] for r in ref], np.float32))
+                mc.same((sc[:nq], ids[:nq], cnt[:nq], mp[:nq]), ref, (width, by_group, margin, top_k))
+                if margin == 10.0 and not by_group:
+                    # every walked row but the positive survives: the counts say where each walk ended
+                    ended = [int(np.flatnonzero(I[q] < 0)[0]) if (I[q] < 0).any() else width for q in range(nq)]
+                    walked = [sum(1 for r in I[q, :ended[q]] if r < n and r != pos[q]) for q in range(nq)]
+                    assert ref[2].tolist() == walked
+                    if width >= 63:
+                        assert ended[1] == 3 and ended[2] == 63 and ended[4] == 2, "-9 ends this walk"
+                        assert ref[2][4] == 1 and ref[2][0] == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

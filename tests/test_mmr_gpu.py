@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import mmr_cases as mc
+import ranking_walk_cases as rw
 from capi_helpers import stream, tile_corpus
 from oracle import search as oracle
 from semantic_search_kd_amd import _native
@@ -149,6 +150,28 @@ def test_hand_made_lists(native_lib, world, width):
     for off in (-5, (1 << 33) + 1):
         kw = dict(k=10, lam=0.5, id_offset=off)
         mc.same(capi_mmr(native_lib, w.tiled, n, S, I, **kw), w.want(S, I, **kw), f"id_offset={off}")
+
+
+@pytest.mark.parametrize("width", rw.WIDTHS)
+def test_walk_at_the_round_boundaries(native_lib, world, width):
+    """The shared hand-made rankings over the first 200 rows of the world: the first -1 at rank 0, 63, 64 and absent,
+    rows behind it, ids outside the index and -9 before it (skipped: the walk goes on).  Width 1 runs the kernel with
+    50 resident rows, 63 .. 65 the one with 100, 130 the staged one."""
+    w, n = world, 200
+    I = rw.ids(n, width)
+    S = rw.descending_scores(width, low=0.05, high=0.95)
+    rows, gram = w.rows[:n], w.gram[:n, :n]
+    for k in sorted({1, min(10, width), width}):
+        for lam, thr in ((0.5, INF), (0.3, 0.8), (1.0, INF)):
+            kw = dict(k=k, lam=lam, dup_threshold=thr, id_offset=7000)
+            want = mc.mmr_batch(S, I, rows, gram=gram, **kw)
+            mc.same(capi_mmr(native_lib, w.tiled, n, S, I, **kw), want, f"walk width={width} k={k} lambda={lam} thr={thr}")
+    # lambda = 1 without a threshold selects every candidate in list order: the counts are what the walk kept
+    end = rw.first_pad(I)
+    kept = [int(((I[q, :end[q]] >= 0) & (I[q, :end[q]] < n)).sum()) for q in range(rw.NQ)]
+    assert want[4].tolist() == kept
+    if width >= 63:
+        assert kept[4] == width - 1 and kept[0] == 0, "-9 is skipped and the walk goes on; a -1 at rank 0 ends it"
 
 
 def test_one_query_alone_and_many_queries(native_lib, world):

@@ -12,6 +12,7 @@ from capi_helpers import stream, tile_corpus
 from oracle import search as oracle
 from semantic_search_kd_amd import _native
 from semantic_search_kd_amd.dist import range_record_bytes, range_record_views
+from test_range_search_gpu import _past_one_scan_block, _ref_from_scores
 
 DIM = 384
 OFFSET = 11   # global id of the corpus' row 0: every shard's id_offset is OFFSET + its first row
@@ -155,6 +156,64 @@ def test_range_merge_equals_one_range_search(gpu, native_lib, w):
     lims, D, I = _merge(lib, buf, len(cuts) - 1, len(queries), cap, total - 1)
     assert np.array_equal(lims, ref[0])
     assert (I == SENTINEL_ID).all() and (D.view(np.uint32) == SENTINEL_BITS).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cuts", [[0, 30, 64], [0, 20, 20, 64]])
+@pytest.mark.parametrize("nq", [4095, 4096, 4097, 8193])
+def test_range_merge_lims_past_one_scan_block(gpu, native_lib, nq, cuts):
+    """The merged lims come from a scan of 4 096 queries per workgroup: one block not full, one exactly full, one query
+    into a second block, one into a third, with 2 and 3 runs of small capacity.  The reference is the host's range
+    search of the whole 64-row corpus (``test_range_search_gpu._ref_from_scores`` over its 8 193 x 64 score matrix)."""
+    c = _past_one_scan_block()
+    thr = c["thr"][:nq]
+    ref = _ref_from_scores(c["s"][:nq], thr, OFFSET)
+    counts = np.diff(ref[0])
+    assert (counts == 0).any() and (counts == 64).any() and len(set(counts.tolist())) >= 6
+    q = torch.from_numpy(c["queries"][:nq]).cuda()
+    t = torch.from_numpy(thr).cuda()
+    runs = [_range(native_lib, c["corpus"], a, b, q, t) for a, b in zip(cuts, cuts[1:])]
+    cap = max(int(r[0][-1].item()) for r in runs) + 3
+    buf = _pack(native_lib, runs, nq, cap)
+    total = int(ref[0][-1])
+    _same(_merge(native_lib, buf, len(runs), nq, cap, total), ref, total, (nq, cuts))
+    lims, _, _ = _merge(native_lib, buf, len(runs), nq, cap, 0, room=1, outputs=False)
+    assert np.array_equal(lims, ref[0])
+
+
+@pytest.mark.gpu
+def test_range_merge_lims_past_256_scan_blocks(gpu, native_lib):
+    """256 x 4 096 + 1 queries: the one workgroup that scans the block sums takes 256 of them per trip, so the last
+    query's block is the first of its SECOND trip and its offset is the carry of the first.  Two runs of 8.4 MB of
+    lims and six records: three queries (the first block, block 200, the last query) hold them."""
+    nq, cap = 256 * 4096 + 1, 4
+    at = [5, 200 * 4096 + 17, nq - 1]
+    # run -> query -> [(score, id)], each list in rank order
+    held = [{at[0]: [(0.5, 9), (0.25, 4)], at[2]: [(1.0, 70)]},
+            {at[0]: [(0.5, 3)], at[1]: [(2.0, 8)], at[2]: [(1.5, 6)]}]
+    rec = range_record_bytes(nq, cap)
+    buf = torch.zeros(2 * rec, dtype=torch.uint8, device="cuda")
+    for r, per_query in enumerate(held):
+        lv, sv, iv = range_record_views(buf[r * rec : (r + 1) * rec], nq, cap)
+        counts = torch.zeros(nq, dtype=torch.int64)
+        flat = []
+        for qq in sorted(per_query):
+            counts[qq] = len(per_query[qq])
+            flat += per_query[qq]
+        lims = torch.zeros(nq + 1, dtype=torch.int64)
+        lims[1:] = torch.cumsum(counts, 0)
+        lv.copy_(lims)
+        sv[: len(flat)].copy_(torch.tensor([x[0] for x in flat], dtype=torch.float32))
+        iv[: len(flat)].copy_(torch.tensor([x[1] for x in flat], dtype=torch.int64))
+    lims, D, I = _merge(native_lib, buf, 2, nq, cap, 6)
+    want = np.zeros(nq + 1, np.int64)
+    want[at[0] + 1:] += 3
+    want[at[1] + 1:] += 1
+    want[at[2] + 1:] += 2
+    assert np.array_equal(lims, want), np.flatnonzero(lims != want)[:5]
+    assert lims[nq - 1] == 4 and lims[nq] == 6
+    assert I[:6].tolist() == [3, 9, 4, 8, 6, 70] and D[:6].tolist() == [0.5, 0.5, 0.25, 2.0, 1.5, 1.0]
+    assert (I[6:] == SENTINEL_ID).all()
 
 
 @pytest.mark.gpu

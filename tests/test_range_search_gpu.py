@@ -132,6 +132,42 @@ def _capi(lib, tiled, n, queries, thr, max_results, id_offset=0, buf=None, null_
     return L, sc.cpu().numpy()[:keep], ids.cpu().numpy()[:keep], sc.cpu().numpy(), ids.cpu().numpy()
 
 
+_PAST_ONE_SCAN_BLOCK = {}
+
+
+def _past_one_scan_block():
+    """64 rows x 8 193 queries, computed once: the scores and thresholds that return 0, 1, 5, all 64, 2, 0 and 17 rows
+    in turn, so the counts the lims scan adds up differ from query to query"""
+    if not _PAST_ONE_SCAN_BLOCK:
+        corpus = oracle.seeded_unit_rows(64, DIM, 71)
+        queries = oracle.seeded_unit_rows(8193, DIM, 72)
+        s = oracle.scores_fma(queries, corpus)
+        desc = -np.sort(-s, axis=1)
+        want = np.array([0, 1, 5, 64, 2, 0, 17])[np.arange(8193) % 7]
+        thr = np.where(want >= 64, -np.inf, desc[np.arange(8193), np.minimum(want, 63)]).astype(np.float32)
+        _PAST_ONE_SCAN_BLOCK.update(corpus=corpus, queries=queries, s=s, thr=thr)
+    return _PAST_ONE_SCAN_BLOCK
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nq", [4095, 4096, 4097, 8193])
+def test_range_search_lims_past_one_scan_block(gpu, native_lib, nq):
+    """The CSR build scans 4 096 queries per workgroup: one block not full, one exactly full, one query into a second
+    block, one into a third - the block offsets, the carry over the block sums and the total in ``lims[nq]``."""
+    c = _past_one_scan_block()
+    s, thr = c["s"][:nq], c["thr"][:nq]
+    ref = _ref_from_scores(s, thr, 500)
+    counts = np.diff(ref[0])
+    assert (counts == 0).any() and (counts == 64).any() and len(set(counts.tolist())) >= 6
+    tiled = tile_corpus(native_lib, c["corpus"])
+    total = int(ref[0][-1])
+    got = _capi(native_lib, tiled, 64, c["queries"][:nq], thr, max_results=total, id_offset=500)
+    _same(got[:3], ref, nq)
+    # count-only: the same lims
+    got = _capi(native_lib, tiled, 64, c["queries"][:nq], thr, max_results=0, null_outputs=True)
+    assert np.array_equal(got[0], ref[0])
+
+
 @pytest.mark.gpu
 def test_range_search_masks_and_removed_rows(gpu):
     n, nq = 3001, 37
