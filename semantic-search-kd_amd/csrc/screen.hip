@@ -270,20 +270,47 @@ __global__ __launch_bounds__(256) void screen_setup_kernel(const float* __restri
 }
 
 // k-steps [0, BG) at the wave-uniform address `base` (the tile's vector 128 S of its first k-step S): both row blocks of
-// every step; lane l reads the 16 bytes at lane_off = 16 (32 (l >> 4) + (l & 15)).  Uniform base + 32-bit lane offset is
-// the scalar-base form of global_load: tile addresses cost scalar adds, no 64-bit vector pointers held (and spilled)
-// across the tile loop.
+// every step; lane l reads the 16 bytes at lane_off = 16 (32 (l >> 4) + (l & 15)).  Every load is the scalar-base form
+// of global_load - `global_load_dwordx4 v[..], vOff, s[b:b+1]` with the row block as the immediate (offset:0 / 256) -
+// and the k-step's base is formed on the scalar unit.  That form has to be asked for.  Written as pointer arithmetic
+// the compiler keeps it only where the uniform part is a run-time value (the next tile's groups); a compile-time
+// k-step offset it adds AFTER the lane offset, as 64-bit vector adds (v_lshl_add_u64, v_add_co / v_addc_co and their
+// hazard s_nops between the MFMAs: 51 vector instructions per tile in the bench kernel's loop).  So
+//  - the uniform byte address, k-step offset included, goes through a scalar register pair the optimiser cannot see
+//    into: nothing of it can be re-associated to the lane's side;
+//  - it comes back as a GLOBAL (address_space(1)) pointer - a laundered generic one is loaded through FLAT, and a FLAT
+//    load in flight turns the ring's counted vmcnt waits into vmcnt(0);
+//  - the lane offset is added last, zero-extended from a register that is laundered too: left visible it is widened
+//    once per kernel into a 64-bit pair, and every group is back to a v_lshl_add_u64.  The launder is chained through
+//    the caller's variable (the laundered value is the next call's input), so it costs no copy.
+// -DSSKD_SCREEN_VADDR_LOADS: the addressing as it was written before (64-bit vector addresses), for A/B builds.
+typedef __attribute__((address_space(1))) const char screen_global_bytes;
+typedef __attribute__((address_space(1))) const sbf16x8 screen_global_vec;
 template <int BG>
-__device__ __forceinline__ void load_bgroup(sbf16x8 (&buf)[BG][2], const sbf16x8* __restrict__ base, unsigned lane_off) {
-  asm volatile("" : "+v"(lane_off));   // widened next to its loads, not once per kernel into a 64-bit pair that spills
+__device__ __forceinline__ void load_bgroup(sbf16x8 (&buf)[BG][2], const sbf16x8* __restrict__ base, unsigned& lane_off) {
+#ifdef SSKD_SCREEN_ABL_CONTIG   // timing ablation (wrong operands): every load one contiguous KiB, as a re-ordered sidecar would give
+  constexpr int MB_BYTES = 1024;
+#else
+  constexpr int MB_BYTES = 256;
+#endif
+#ifdef SSKD_SCREEN_VADDR_LOADS
+  unsigned off = lane_off;
+  asm volatile("" : "+v"(off));
 #pragma unroll
   for (int s = 0; s < BG; ++s)
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
-#ifdef SSKD_SCREEN_ABL_CONTIG   // timing ablation (wrong operands): every load one contiguous KiB, as a re-ordered sidecar would give
-      buf[s][mb] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 128 + mb * 64) + lane_off);
+      buf[s][mb] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 128) + mb * MB_BYTES + off);
 #else
-      buf[s][mb] = *reinterpret_cast<const sbf16x8*>(reinterpret_cast<const char*>(base + s * 128 + mb * 16) + lane_off);
+  asm volatile("" : "+v"(lane_off));
+#pragma unroll
+  for (int s = 0; s < BG; ++s) {
+    uint64_t b = reinterpret_cast<uint64_t>(base + s * 128);   // sign-extended 64-bit scalar arithmetic up to here
+    asm volatile("" : "+s"(b));
+    screen_global_bytes* const g = reinterpret_cast<screen_global_bytes*>(b) + lane_off;
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) buf[s][mb] = *reinterpret_cast<screen_global_vec*>(g + mb * MB_BYTES);
+  }
 #endif
 }
 
@@ -364,7 +391,7 @@ __device__ __forceinline__ void compute_bgroup(const sbf16x8 (&a)[BG][2], screen
 template <int QB, int G, int BG, int RG, int D, int NB>
 __device__ __forceinline__ void screen_tile_groups(sbf16x8 (&buf)[RG][BG][2], const sbf16x8* __restrict__ tile,
                                                    screen_lds_frag* const (&qbase)[NB], sbf16x8 (&b)[D],
-                                                   f32x4 (&acc)[2][2 * QB], bool more, int64_t next_tile, unsigned lane_off) {
+                                                   f32x4 (&acc)[2][2 * QB], bool more, int64_t next_tile, unsigned& lane_off) {
   constexpr int NG = BSTEPS / BG;
   if constexpr (G < NG) {
     constexpr int PG = G + RG - 1;  // group to prefetch now
@@ -548,7 +575,7 @@ __global__ __launch_bounds__(64) void screen_scores_probe_kernel(const sbf16x8* 
   for (int nb = 0; nb < NB; ++nb) qbase[nb] = (screen_lds_frag*)(qs + lane) + nb * SCREEN_FRAGS_PER_BASE * 64;
   constexpr int D = screen_frag_depth<QB>();
   sbf16x8 buf[RG][BG][2], qfrag[D];
-  const unsigned lane_off = (unsigned)(n + 32 * g) * 16u;
+  unsigned lane_off = (unsigned)(n + 32 * g) * 16u;   // (not const: load_bgroup launders it in place)
 #pragma unroll
   for (int gr = 0; gr + 1 < RG; ++gr) load_bgroup<BG>(buf[gr], tiled + gr * BG * 128, lane_off);
   for (int t = 0; t < n_tiles; ++t) {
@@ -698,9 +725,9 @@ __device__ __forceinline__ void screen_tiles(const ScreenAppendParams& p, int t_
   }
   sbf16x8 qfrag[D];
 #ifdef SSKD_SCREEN_ABL_CONTIG
-  const unsigned lane_off = (unsigned)(n + 16 * g) * 16u;
+  unsigned lane_off = (unsigned)(n + 16 * g) * 16u;
 #else
-  const unsigned lane_off = (unsigned)(n + 32 * g) * 16u;
+  unsigned lane_off = (unsigned)(n + 32 * g) * 16u;   // (not const: load_bgroup launders it in place)
 #endif
   // (a padding query of the last block - zero fragments, every score 0 - carries the bound +inf from the kernel's head:
   // it passes no first test, and the tile loop holds no "real query" flags)
