@@ -379,6 +379,47 @@ int sskd_index_compact_rows(const float* d_src_tiled, int64_t n_rows, const uint
                             const int64_t* d_word_prefix, float* d_dst_tiled, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Near-duplicate clusters: the connected components of the self-join's pairs (single linkage), never leaving HBM
+ *   (the step between near_duplicates and remove_ids: one row kept per cluster)
+ * State, both DEVICE int32 [n_rows]: d_parent (a union-find forest; -1 = the row takes no part) and d_degree (edges per
+ * row).  The edges arrive as sskd_index_range_search outputs of a self-join (the queries are stored rows), call by
+ * call, in stream order.
+ *
+ * sskd_dup_init: parent[r] = r for a row that takes part (its bit of d_row_mask is set - the format of "Filtered
+ * search" - or d_row_mask is NULL), -1 otherwise; degree[r] = 0.
+ *
+ * sskd_dup_link: d_lims int64 [nq + 1] / d_ids int64 are one range search's CSR; query q is LOCAL row query_row0 + q.
+ * An entry (i, id) is an edge when j = id - id_offset lies in [0, n_rows), j > i (the self-join is symmetric bit for bit:
+ * the upper triangle holds every pair once), both rows take part, and the scope rule over d_row_group (DEVICE int32
+ * [n_rows], the grouped search's array) holds: scope 0 = every pair, 1 = only pairs of different groups, 2 = only pairs of
+ * one group.  Every edge unites the two components and adds 1 to degree[i] and degree[j] (integer atomics: the sums do
+ * not depend on the order).  Linking an edge twice leaves the components as they are and counts it twice.
+ * Overflow: the kernel reads lims[nq] on the device; when it exceeds max_results (the capacity d_ids was given to the
+ * range search with) the arrays are not valid: nothing is linked, nothing is added and *d_overflow (DEVICE int32) is set
+ * to 1.  Otherwise *d_overflow is left alone, so one zeroed word per call, read once after the last call, tells which
+ * calls must be repeated with more room.  The lims are trusted to be a range search's (ascending from 0); whatever they
+ * hold, no entry at or past min(lims[nq], max_results) is read.
+ *
+ * sskd_dup_labels, after the last link: flattens d_parent so that parent[r] is the SMALLEST row of r's component (-1
+ * stays), and writes d_rep int32 [n_rows] = the representative row of r's component (-1 for a row that takes no part):
+ * keep 0 ("first") the smallest row, keep 1 ("densest") the row with the largest degree, ties to the smallest row;
+ * d_size int32 [n_rows] = the component's size at its smallest row, 0 elsewhere; d_counts int32 [2] = { components, rows
+ * taking part }.
+ *
+ * The larger root is always linked under the smaller one, so every component's final root is its smallest row whatever
+ * order the hardware takes the edges in: every output is a pure function of the edge set.  All three: stream-ordered, no
+ * host sync, no workspace, allocate nothing; arguments are checked before any launch (negative sizes, a shard of 2^31 - 64
+ * rows or more, NULL pointers, query rows outside [0, n_rows), an unknown scope or keep, scope 1 or 2 without groups:
+ * SSKD_ERR_INVALID); nq = 0 and n_rows = 0 are successful no-ops (labels then only zeroes d_counts).
+ * ------------------------------------------------------------------------- */
+int sskd_dup_init(int64_t n_rows, const uint32_t* d_row_mask, int32_t* d_parent, int32_t* d_degree, void* stream);
+int sskd_dup_link(const int64_t* d_lims, const int64_t* d_ids, int nq, int64_t max_results, int64_t query_row0,
+                  int64_t id_offset, int64_t n_rows, const int32_t* d_row_group, int scope, int32_t* d_parent,
+                  int32_t* d_degree, int32_t* d_overflow, void* stream);
+int sskd_dup_labels(int64_t n_rows, int32_t* d_parent, const int32_t* d_degree, int keep, int32_t* d_rep, int32_t* d_size,
+                    int32_t* d_counts, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Hard-negative mining over a row ranking (ANCE refresh): the rows that fool the student
  *   reference: ANCEMiner.mine, src/mining/miners.py:232-247 (max positive score, margin rule, stable descending sort,
  *   the first top_k)

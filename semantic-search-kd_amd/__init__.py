@@ -36,6 +36,7 @@ from .evaluation import (  # noqa: F401
 )
 from .mining import ANCEMiner, BM25Miner, TeacherMiner, build_mining_curriculum  # noqa: F401
 from .denoise import Denoising, TrigramStore, compute_text_overlap, text_overlap  # noqa: F401
+from .dedup import DuplicateClusters, cluster_pairs  # noqa: F401
 from .teacher import TeacherConfig, TeacherModel  # noqa: F401
 from .bench_support import bench_encode  # noqa: F401
 
@@ -74,6 +75,8 @@ __all__ = [
     "TrigramStore",
     "compute_text_overlap",
     "text_overlap",
+    "DuplicateClusters",
+    "cluster_pairs",
     "TeacherMiner",
     "TeacherConfig",
     "TeacherModel",

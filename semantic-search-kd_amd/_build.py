@@ -20,7 +20,7 @@ OBJ_DIR = PKG_DIR / "build"
 LIB_PATH = PKG_DIR / "libsskd_amd.so"
 
 # search.hip and screen.hip first: they compile longest (the scan's and the screening kernel's instantiations)
-SOURCES = ["search.hip", "screen.hip", "capi_common.hip", "index_rows.hip", "range.hip", "grouped.hip", "mine.hip", "denoise.hip", "bm25.hip", "hybrid.hip", "expand.hip", "mmr.hip", "eval.hip", "ivf.hip", "pq.hip", "graph.hip", "late.hip", "late_train.hip", "plaid.hip", "pool.hip", "encoder.hip", "kd_loss.hip", "tokenizer.hip", "generic.hip", "train.hip", "blaslt.hip", "testhooks.hip"]
+SOURCES = ["search.hip", "screen.hip", "capi_common.hip", "index_rows.hip", "range.hip", "grouped.hip", "dedup.hip", "mine.hip", "denoise.hip", "bm25.hip", "hybrid.hip", "expand.hip", "mmr.hip", "eval.hip", "ivf.hip", "pq.hip", "graph.hip", "late.hip", "late_train.hip", "plaid.hip", "pool.hip", "encoder.hip", "kd_loss.hip", "tokenizer.hip", "generic.hip", "train.hip", "blaslt.hip", "testhooks.hip"]
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

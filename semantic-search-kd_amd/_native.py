@@ -178,6 +178,9 @@ SIGNATURES = {
     ),
     "sskd_row_mask_rank": (_i, [_vp, _i64, _vp, _vp]),
     "sskd_index_compact_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "sskd_dup_init": (_i, [_i64, _vp, _vp, _vp, _vp]),
+    "sskd_dup_link": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sskd_dup_labels": (_i, [_i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sskd_index_mine_select": (
         _i, [_vp, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, C.c_double, _i, _i64, _vp, _vp, _vp, _vp, _vp]
     ),

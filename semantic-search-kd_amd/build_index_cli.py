@@ -89,7 +89,16 @@ def main(argv=None) -> int:
     ap.add_argument("--late-centroid-lists", action="store_true",
                     help="late interaction: also write the centroid lists of the compressed store (late_list_lims.npy, "
                          "late_list_rows.npy), so that the store retrieves by itself (LateInteractionIndex.search_tokens)")
+    ap.add_argument("--dedup-threshold", type=float, default=None,
+                    help="after the build, drop near-duplicate rows: rows scoring above this cosine form clusters "
+                         "(single linkage), one row per cluster stays and the index is compacted; single-index builds only")
+    ap.add_argument("--dedup-keep", type=str, choices=("first", "densest"), default="first",
+                    help="the row a cluster keeps: its first row, or the one with the most near-duplicates")
+    ap.add_argument("--dedup-scope", type=str, choices=("all", "across_groups", "within_groups"), default="all",
+                    help="the pairs that count: all, or over --group-column only those across / within groups")
     args = ap.parse_args(argv)
+    if args.dedup_threshold is None and (args.dedup_keep != "first" or args.dedup_scope != "all"):
+        ap.error("--dedup-keep / --dedup-scope need --dedup-threshold")
     if args.late_compress and not args.late_interaction:
         ap.error("--late-compress needs --late-interaction")
     if args.late_centroid_lists and not args.late_compress:
@@ -107,6 +116,8 @@ def main(argv=None) -> int:
             ap.error(f"--index-type {args.index_type}: the row-sharded index has no {what} yet")
         if args.late_interaction:
             ap.error("--late-interaction: the row-sharded index has no token store yet")
+        if args.dedup_threshold is not None:
+            ap.error("--dedup-threshold: clusters span shards; the row-sharded index has no de-duplication yet")
         return _build_sharded(args, world)
 
     if args.late_interaction and args.late_max_doc_tokens < 2:
@@ -132,6 +143,12 @@ def main(argv=None) -> int:
         hnsw_ef_construction=args.hnsw_ef_construction,
         group_column=args.group_column,
     )
+    if args.dedup_threshold is not None:
+        # before anything is trained over the rows or saved: every later step sees the surviving rows only
+        before = index.ntotal
+        clusters = builder.deduplicate(args.dedup_threshold, keep=args.dedup_keep, scope=args.dedup_scope, compact=True)
+        print(f"De-duplication at {args.dedup_threshold}: {before} rows, {clusters.n_clusters} clusters, "
+              f"{clusters.removed.size} rows dropped")
     if args.index_type == "ivf":
         from .ivf import IVFIndex
 

@@ -154,6 +154,8 @@ class FAISSIndexBuilder:
         self.range_capacity = 1 << 16
         self._range_scores: Optional[torch.Tensor] = None
         self._range_ids: Optional[torch.Tensor] = None
+        # duplicate_clusters: result entries (12 B each) every batch of the self-join gets; a batch that needs more runs again
+        self.dedup_capacity = 1 << 20
         # row groups (grouped search: a document = the group of its chunks).  ``group_keys`` is None until groups are
         # set: every row is then its own group, numbered by its row.
         self.group_keys: Optional[List] = None              # group number -> key (None for a row added without one)
@@ -1163,6 +1165,114 @@ class FAISSIndexBuilder:
         if not pair_parts:
             return np.zeros((0, 2), dtype=np.int64), np.zeros(0, dtype=np.float32)
         return np.concatenate(pair_parts), np.concatenate(score_parts)
+
+    # ------------------------------------------------------- near-duplicate clusters
+    def _range_call_from(self, row0: int, q: torch.Tensor, thr: torch.Tensor, mask, lims, scores, ids, max_results: int):
+        """``sskd_index_range_search`` over the stored rows ``[row0, n)`` alone (``row0`` a multiple of 32, so the rows stay
+        tile-aligned and ``mask``, the words of ALL rows, is entered at word ``row0 / 32``); the ids written are those
+        of a scan over every row."""
+        lib = _native.load()
+        n_rows, nq = self._n - row0, q.shape[0]
+        ws = self._workspace_for(int(lib.sskd_index_range_search_workspace_bytes(n_rows, nq, max_results)))
+        tiled = 0 if self._tiled is None else self._tiled.data_ptr() + row0 * self.embedding_dim * 4
+        _native.check(
+            lib.sskd_index_range_search(
+                tiled, n_rows, q.data_ptr(), nq, thr.data_ptr(), self.id_offset + row0,
+                None if mask is None else mask.data_ptr() + (row0 // 32) * 4, lims.data_ptr(), scores.data_ptr(),
+                ids.data_ptr(), max_results, ws.data_ptr(), ws.numel(), _native.current_stream_ptr(self.device),
+            )
+        )
+
+    def duplicate_clusters(self, threshold: float, *, keep: str = "first", scope: str = "all", allow=None,
+                           batch_size: int = 4096):
+        """The clusters of near-duplicate rows: the connected components (single linkage) of the pairs
+        ``near_duplicates(threshold)`` returns, as a ``dedup.DuplicateClusters`` - one label per row, and per cluster the row
+        it keeps and its size.  ``keep``: ``"first"`` keeps a cluster's smallest row, ``"densest"`` the row with the most
+        pairs (ties to the smallest row).  ``scope``: ``"all"`` pairs, or over the row groups (``set_groups``) only the pairs
+        ``"across_groups"`` / ``"within_groups"``.  ``allow`` (as in ``search``) restricts the rows taking part; removed rows
+        never do.
+
+        The self-join is ``near_duplicates``' (stored rows as queries, not normalised again, strict ``>``), but every
+        batch's range result stays in HBM and goes straight into the union-find kernels (``include/sskd_amd.h``, near-
+        duplicate clusters): nothing proportional to the number of pairs reaches the host.  The batches are enqueued without
+        a synchronisation, each into ``dedup_capacity`` result entries; the per-batch overflow flags are read once at the
+        end, and only the batches that overflowed (they linked nothing) run again with exactly the room they need.  A batch
+        that starts at a multiple of 32 rows scans only the rows from its start on - the pairs ``i < j`` are all there -
+        so the self-join costs about half of ``near_duplicates``'."""
+        from . import dedup
+
+        keep_c, scope_c = dedup.keep_code(keep), dedup.scope_code(scope)
+        if batch_size < 1:
+            raise ValueError(f"batch_size={batch_size} < 1")
+        _native.require_gpu()
+        lib = _native.load()
+        n = self._n
+        with torch.cuda.device(self.device):
+            stream = _native.current_stream_ptr(self.device)
+            mask = self._effective_mask(allow)
+            groups = self._row_group_device() if scope_c else None
+            state = torch.empty((4, max(n, 1)), dtype=torch.int32, device=self.device)   # parent, degree, rep, size
+            parent, degree, rep, size = state[0], state[1], state[2], state[3]
+            counts = torch.empty(2, dtype=torch.int32, device=self.device)
+            _native.check(lib.sskd_dup_init(n, None if mask is None else mask.data_ptr(), parent.data_ptr(),
+                                            degree.data_ptr(), stream))
+            starts = list(range(0, n, batch_size))
+            overflow = torch.zeros(max(len(starts), 1), dtype=torch.int32, device=self.device)
+            totals = torch.zeros(max(len(starts), 1), dtype=torch.int64, device=self.device)
+
+            def run(b: int, cap: int, scores: torch.Tensor, ids: torch.Tensor) -> None:
+                lo = starts[b]
+                nq = min(batch_size, n - lo)
+                rows = torch.empty((nq, self.embedding_dim), dtype=torch.float32, device=self.device)
+                _native.check(lib.sskd_index_get_rows(self._tiled.data_ptr(), lo, nq, rows.data_ptr(), stream))
+                thr = torch.full((nq,), float(threshold), dtype=torch.float32, device=self.device)
+                lims = torch.empty(nq + 1, dtype=torch.int64, device=self.device)
+                self._range_call_from(lo if lo % _native.SSKD_TILE_ROWS == 0 else 0, rows, thr, mask, lims, scores, ids, cap)
+                totals[b : b + 1].copy_(lims[nq:])
+                _native.check(lib.sskd_dup_link(lims.data_ptr(), ids.data_ptr(), nq, cap, lo, self.id_offset, n,
+                                                None if groups is None else groups.data_ptr(), scope_c,
+                                                parent.data_ptr(), degree.data_ptr(), overflow[b:].data_ptr(), stream))
+
+            cap = max(int(self.dedup_capacity), 1)
+            scores = torch.empty(cap, dtype=torch.float32, device=self.device)
+            ids = torch.empty(cap, dtype=torch.int64, device=self.device)
+            for b in range(len(starts)):
+                run(b, cap, scores, ids)
+            again = np.flatnonzero(overflow.cpu().numpy()[: len(starts)])   # the one synchronisation of the join
+            if again.size:
+                need = totals.cpu().numpy()
+                overflow.zero_()
+                cap = int(need[again].max())   # lims[-1] is exact whatever the capacity was
+                scores = torch.empty(cap, dtype=torch.float32, device=self.device)
+                ids = torch.empty(cap, dtype=torch.int64, device=self.device)
+                for b in again.tolist():
+                    run(b, cap, scores, ids)
+            _native.check(lib.sskd_dup_labels(n, parent.data_ptr(), degree.data_ptr(), keep_c, rep.data_ptr(),
+                                              size.data_ptr(), counts.data_ptr(), stream))
+            host = state[:, :n].cpu().numpy()
+            if again.size and overflow.cpu().numpy().any():
+                raise RuntimeError("a range result overflowed the capacity its own count asked for")
+            n_clusters, n_rows = (int(x) for x in counts.cpu().numpy())
+        out = dedup.clusters_from_arrays(host[0], host[2], host[3], self.id_offset)
+        if (out.n_clusters, out.n_rows) != (n_clusters, n_rows):
+            raise RuntimeError("sskd_dup_labels' counts disagree with its labels")
+        return out
+
+    def deduplicate(self, threshold: float, *, keep: str = "first", scope: str = "all", allow=None,
+                    batch_size: int = 4096, compact: bool = False):
+        """``duplicate_clusters`` and then ``remove_ids`` of every row taking part that is not the row its cluster keeps:
+        afterwards ``near_duplicates(threshold)`` finds no pair among the rows that took part.  Returns the
+        ``DuplicateClusters`` with ``removed`` = the ids dropped (ascending); ``compact=True`` also runs ``compact()`` and
+        stores its ``kept`` array on the result (the labels and representatives stay in the OLD ids: ``kept`` maps them)."""
+        if compact and self.shard_info:
+            raise ValueError("deduplicate(compact=True): this index is one piece of a row-sharded build (see compact())")
+        out = self.duplicate_clusters(threshold, keep=keep, scope=scope, allow=allow, batch_size=batch_size)
+        out.removed = out.duplicates()
+        if out.removed.size:
+            self.remove_ids(out.removed)
+        if compact:
+            out.kept = self.compact()
+        return out
 
     # -------------------------------------------------------------- persistence
     def reconstruct(self, rows: Sequence[int]) -> np.ndarray:
